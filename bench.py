@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — particle-steps/s of the explicit P2G + stress + G2P step (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one fused explicit predictor-corrector particle step (search + LME Newton, P2G of mass
 and momentum, G2P gradient + F-update + Kirchhoff stress, P2G of the internal force, G2P kinematic
@@ -10,10 +10,15 @@ update) over the synthetic cloud.  N = 1 runs BASELINE configs[1]: 3-D elastic c
 N > 1 is WEAK scaling by default: every rank owns one such 1 M-particle block, stacked along z (the slab axis),
 ghost-node layers exchanged with the two z-neighbours over RCCL (the library's own ncclSend / ncclRecv path);
 `--scaling strong --particles-total 8000000` splits ONE cube (BASELINE configs[3], 100^3 cells x 8) into N z-slabs
-instead, so N = 1, 2, 4, 8 all run the same 8 M-particle job.  The line carries BOTH records (`weak`, `strong`; the
-headline fields are the one --scaling names), for N > 1 a partitioned-vs-whole check over the real communicator
-(`partition_check`), the rank count RCCL reports, the overlap form that survived the warm-up and per-rank kernel and
-exchange-wait times.
+instead, so N = 1, 2, 4, 8 all run the same 8 M-particle job.  A plain run measures the headline alone: set-up, W
+warm-up steps, K timed steps, the record --scaling names (and, for N > 1, the partitioned-vs-whole check over the real
+communicator that picks the exchange form, `partition_check`, the rank count RCCL reports and the overlap form that
+survived the warm-up).
+--full adds everything else: the other scaling record (the line then carries BOTH, `weak` and `strong`), per-kernel and
+per-rank exchange-wait times with the roofline figures, the stirred-cloud and 2-D `secondary` figures, the `implicit`
+record and the CPU baseline (each --no-* option still leaves its part out).
+--dump-outputs DIR writes what the last timed step left for a caller, rank 0's cloud (a fixed, seeded sample of the
+particles in the caller's order and of the active nodes in masked numbering), as DIR/<name>.npy in float64.
 Inputs are resident in HBM before the timed region; the timed region holds ONE physical re-sort of the particle
 arrays (the library's housekeeping, default cadence one per 50 steps: charged here at one per K steps).
 Rank 0 prints ONE JSON line.
@@ -74,7 +79,18 @@ def parse():
                     help="only the record --scaling asks for (default: the weak AND the strong record in the one line)")
     ap.add_argument("--no-partition-check", action="store_true", help="N > 1: skip the partitioned-vs-whole check")
     ap.add_argument("--no-secondary", action="store_true", help="skip the 2-D 1 M-particle secondary figure (N = 1 only)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other scaling record, per-kernel times and roofline, the stirred, "
+                         "secondary and implicit figures and the CPU baseline (the --no-* options leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--workload step: write the particle and nodal fields the last timed step left (rank 0, a "
+                         "fixed seeded sample) as DIR/<name>.npy, float64, at most 64 MB in all")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.workload != "step":
+        ap.error("--dump-outputs applies to --workload step (the headline) only")
+    return a
 
 
 def build_case(rank, world, cells, margin=5, cells_z=None):
@@ -707,7 +723,33 @@ def _partition_run(ctx, case, cells, margin, nsteps, dt, bcs, want, ref):
     return {"max_rel_err": res[0], "index_maps_equal": res[1] == 0.0, "status_flags": int(res[2]), "ref": ref}, info
 
 
-def run_config(ctx, scaling, with_kernels=True):
+DUMP_SAMPLE = 65536       # particles and active nodes written by --dump-outputs (fixed seed: the same rows every run)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(S, out_dir):
+    """What the last step left for its caller: particle fields in the caller's order (download_state) and the nodal
+    results of the step in masked numbering (explicit_nodal), a seeded sample of rows of each, float64 .npy files."""
+    st = S.download_state(fields=["x", "dis", "vel", "acc", "F_n", "Stress", "J_n", "I0"])
+    nodal = S.explicit_nodal()
+    d = S.ndim
+    arrays = {}
+    n = st["x"].shape[0]
+    rows = np.sort(np.random.default_rng(2024).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    for k in ("x", "dis", "vel", "acc", "F_n", "Stress", "J_n", "I0"):
+        arrays["particle_" + k] = np.asarray(st[k])[rows].astype(np.float64)
+    na = nodal["mass"].shape[0] // d
+    rows = np.sort(np.random.default_rng(2025).choice(na, size=min(na, DUMP_SAMPLE), replace=False))
+    for k in ("mass", "dU", "force", "accel", "reaction"):
+        arrays["node_" + k] = nodal[k].reshape(na, d)[rows]
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
+
+
+def run_config(ctx, scaling, with_kernels=True, dump_dir=None):
     """One timed configuration: `weak` (--cells^3 x 8 particles per rank, stacked along z) or `strong` (ONE cube of
     --particles-total particles in N z-slabs).  Barrier + synchronise on both sides of exactly K steps, max over ranks.
     -> (record for the JSON line, the solver's case, per-kernel ms of rank 0's further steps)"""
@@ -755,6 +797,8 @@ def run_config(ctx, scaling, with_kernels=True):
     flags = int(ctx.reduce(S.status_flags(), "max"))
     if flags:
         raise SystemExit("bench: particle failure flags 0x%x" % flags)
+    if dump_dir and rank == 0:
+        dump_outputs(S, dump_dir)
     npart = case["cloud"]["x"].shape[0]
     npart_total = int(ctx.reduce(npart, "sum"))
     rec = {"scaling": scaling, "n_gpus": world, "particles_total": npart_total, "particles_rank0": npart,
@@ -856,6 +900,63 @@ def secondary_2d(ctx):
                               "g2p_grad+stress+p2g_force": float(kms[2]), "g2p_update": float(kms[3]), "nodal": float(kms[4])}}
 
 
+def kernel_figures(npart, kms):
+    """--full: per-kernel times of rank 0 (HIP-event brackets of further steps, run_config) with the roofline figures"""
+    names = ["search+activate", "lists+newton+p2g_mass_mom", "g2p_grad+stress+p2g_force", "g2p_update", "nodal"]
+    kern = ["k_search", "k2_tile", "k3_tile", "k5_tile", None]
+    alg = [0, BYTES_3D["S1"] + BYTES_3D["S2"], BYTES_3D["S3"] + BYTES_3D["S4"], BYTES_3D["S5"], 0]
+    # PMC figures of the same command (rocprofv3 passes of tools/profile.sh, committed under profiles/): HBM bytes,
+    # VALU instructions and LDS-array cycles per launch at 1 M particles; scaled by the particle count
+    pmc = {}
+    for fn in ("hbm_traffic.json", "sq_counters.json"):
+        try:
+            pmc.update(json.load(open(os.path.join(ROOT, "profiles", fn))))
+        except Exception:
+            pass
+    per_kernel = {}
+    scale = npart / 1.0e6
+    for i in range(4):
+        t_s = kms[i] * 1e-3
+        if t_s <= 0:
+            continue
+        e = {"kernel_ms": float(kms[i]), "algorithmic_bytes_per_particle": alg[i],
+             "hbm_frac": npart * alg[i] / t_s / 1e9 / HBM_PEAK_GBS}
+        tr = pmc.get(names[i])
+        if tr is not None:  # counter bytes (FETCH_SIZE + WRITE_SIZE passes) / live kernel time / peak
+            e["traffic_bytes"] = tr * scale
+            e["traffic_frac"] = tr * scale / t_s / 1e9 / HBM_PEAK_GBS
+        sq = pmc.get(kern[i] or "", {}) if isinstance(pmc.get(kern[i] or ""), dict) else {}
+        if "valu_insts" in sq:  # SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x 2.4 GHz x kernel time)
+            e["fp64_issue_frac"] = sq["valu_insts"] * scale * 4.0 / (1024 * 2.4e9 * t_s)
+        if "lds_idx_active" in sq:  # SQ_LDS_IDX_ACTIVE (LDS-array cycles, summed over CUs) / (256 CUs x 2.4 GHz x time)
+            e["lds_busy_frac"] = sq["lds_idx_active"] * scale / (256 * 2.4e9 * t_s)
+        fr = {k: e[k] for k in ("hbm_frac", "fp64_issue_frac", "lds_busy_frac") if k in e}
+        e["bound"] = max(fr, key=fr.get).replace("_frac", "").replace("_busy", "")
+        per_kernel[names[i]] = e
+    dom = int(np.argmax(kms[:4]))
+    achieved = npart * alg[dom] / (kms[dom] * 1e-3) / 1e9 if kms[dom] > 0 else 0.0
+    domk = per_kernel.get(names[dom], {})
+    return {
+        "roofline": {"bound": "hbm", "limiter": domk.get("bound", "hbm"), "kernel": names[dom], "achieved": achieved,
+                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                     "traffic": domk.get("traffic_bytes"), "traffic_frac": domk.get("traffic_frac"),
+                     "algorithmic_bytes_per_particle": alg[dom], "kernel_ms": float(kms[dom]),
+                     "event_overhead_ms": float(kms[5]),
+                     "hbm_frac": domk.get("hbm_frac"), "fp64_issue_frac": domk.get("fp64_issue_frac"),
+                     "lds_busy_frac": domk.get("lds_busy_frac"),
+                     "note": "achieved/peak/frac are the HBM roofline of the dominant kernel (algorithmic bytes / "
+                             "live kernel time); traffic_frac is the same with the HBM bytes the counters saw "
+                             "(profiles/hbm_traffic.json); bound = hbm says which roofline achieved / peak are on; "
+                             "limiter names the LARGEST of the three fractions: hbm, "
+                             "fp64_issue (SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x 2.4 GHz x time)) and lds "
+                             "(SQ_LDS_IDX_ACTIVE / (256 CUs x 2.4 GHz x time)); the SQ counts come from "
+                             "profiles/sq_counters.json (rocprofv3 PMC passes of this command)"},
+        "kernel_ms_all": {names[i]: float(kms[i]) for i in range(5)},
+        "exchange_wait_ms": float(kms[6]),
+        "per_kernel": per_kernel,
+    }
+
+
 def main():
     a = parse()
     if a.workload == "tangent":
@@ -870,10 +971,10 @@ def main():
     check = partition_check(ctx) if world > 1 and not a.no_partition_check else None
     if check is not None and (check["max_rel_err"] > PARTITION_TOL or not check["index_maps_equal"] or check["status_flags"]):
         raise SystemExit("bench: the partitioned run does not reproduce the single-solver run: %r" % check)
-    rec, case, kms = run_config(ctx, a.scaling)
+    rec, case, kms = run_config(ctx, a.scaling, with_kernels=a.full, dump_dir=a.dump_outputs)
     other = "strong" if a.scaling == "weak" else "weak"
     rec_other, other_skipped = None, None
-    if not a.no_second_scaling:
+    if a.full and not a.no_second_scaling:
         if other == "strong" and int(round((a.particles_total / 8.0) ** (1.0 / 3.0))) < 8 * world:
             # (too few cell layers for this many ranks: the primary record stands, the second is left out and says why)
             other_skipped = "--particles-total %d gives fewer than 8 cell layers per rank at %d ranks" % (a.particles_total, world)
@@ -881,12 +982,12 @@ def main():
             rec_other, _, _ = run_config(ctx, other, with_kernels=world > 1)
     stirred = None
     second = None
-    if world == 1 and not a.no_stirred:
+    if a.full and world == 1 and not a.no_stirred:
         stirred = stirred_figure(ctx.nlps, ctx.synth, a, ctx.stream)
-    if world == 1 and not a.no_secondary:
+    if a.full and world == 1 and not a.no_secondary:
         second = secondary_2d(ctx)
     implicit = None
-    if world == 1 and not a.no_implicit:  # the maintained driver's hot call at the same size (Neo-Hookean), short form
+    if a.full and world == 1 and not a.no_implicit:  # the maintained driver's hot call at the same size (Neo-Hookean), short form
         r = bench_residual(a, stream=ctx.stream, laws=("nh",), cpu=False, emit=False)[0]
         implicit = {k: r[k] for k in ("metric", "value", "unit", "ms_per_step", "fused_ms", "separate_stages_ms",
                                       "fused_over_separate", "fused_vs_separate_max_rel_diff", "roofline", "status_flags",
@@ -894,40 +995,6 @@ def main():
         implicit["workload"] = r["config"]["workload"]
     if rank == 0:
         npart = rec["particles_rank0"]
-        names = ["search+activate", "lists+newton+p2g_mass_mom", "g2p_grad+stress+p2g_force", "g2p_update", "nodal"]
-        kern = ["k_search", "k2_tile", "k3_tile", "k5_tile", None]
-        alg = [0, BYTES_3D["S1"] + BYTES_3D["S2"], BYTES_3D["S3"] + BYTES_3D["S4"], BYTES_3D["S5"], 0]
-        # PMC figures of the same command (rocprofv3 passes of tools/profile.sh, committed under profiles/): HBM bytes,
-        # VALU instructions and LDS-array cycles per launch at 1 M particles; scaled by the particle count
-        pmc = {}
-        for fn in ("hbm_traffic.json", "sq_counters.json"):
-            try:
-                pmc.update(json.load(open(os.path.join(ROOT, "profiles", fn))))
-            except Exception:
-                pass
-        per_kernel = {}
-        scale = npart / 1.0e6
-        for i in range(4):
-            t_s = kms[i] * 1e-3
-            if t_s <= 0:
-                continue
-            e = {"kernel_ms": float(kms[i]), "algorithmic_bytes_per_particle": alg[i],
-                 "hbm_frac": npart * alg[i] / t_s / 1e9 / HBM_PEAK_GBS}
-            tr = pmc.get(names[i])
-            if tr is not None:  # counter bytes (FETCH_SIZE + WRITE_SIZE passes) / live kernel time / peak
-                e["traffic_bytes"] = tr * scale
-                e["traffic_frac"] = tr * scale / t_s / 1e9 / HBM_PEAK_GBS
-            sq = pmc.get(kern[i] or "", {}) if isinstance(pmc.get(kern[i] or ""), dict) else {}
-            if "valu_insts" in sq:  # SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x 2.4 GHz x kernel time)
-                e["fp64_issue_frac"] = sq["valu_insts"] * scale * 4.0 / (1024 * 2.4e9 * t_s)
-            if "lds_idx_active" in sq:  # SQ_LDS_IDX_ACTIVE (LDS-array cycles, summed over CUs) / (256 CUs x 2.4 GHz x time)
-                e["lds_busy_frac"] = sq["lds_idx_active"] * scale / (256 * 2.4e9 * t_s)
-            fr = {k: e[k] for k in ("hbm_frac", "fp64_issue_frac", "lds_busy_frac") if k in e}
-            e["bound"] = max(fr, key=fr.get).replace("_frac", "").replace("_busy", "")
-            per_kernel[names[i]] = e
-        dom = int(np.argmax(kms[:4]))
-        achieved = npart * alg[dom] / (kms[dom] * 1e-3) / 1e9 if kms[dom] > 0 else 0.0
-        domk = per_kernel.get(names[dom], {})
         cz = rec["cells"]
         out = {
             "metric": "particle-steps/sec (P2G+stress+G2P)", "value": rec["value"],
@@ -943,25 +1010,10 @@ def main():
                        "halo_overlap_mode": rec["halo_overlap_mode"], "rccl_nranks": rec["rccl_nranks"],
                        "overlap_forms_tried": rec["overlap_forms_tried"],
                        "resorts_in_timed_region": 1, "library_default_resort_interval": 50},
-            "roofline": {"bound": "hbm", "limiter": domk.get("bound", "hbm"), "kernel": names[dom], "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": domk.get("traffic_bytes"), "traffic_frac": domk.get("traffic_frac"),
-                         "algorithmic_bytes_per_particle": alg[dom], "kernel_ms": float(kms[dom]),
-                         "event_overhead_ms": float(kms[5]),
-                         "hbm_frac": domk.get("hbm_frac"), "fp64_issue_frac": domk.get("fp64_issue_frac"),
-                         "lds_busy_frac": domk.get("lds_busy_frac"),
-                         "note": "achieved/peak/frac are the HBM roofline of the dominant kernel (algorithmic bytes / "
-                                 "live kernel time); traffic_frac is the same with the HBM bytes the counters saw "
-                                 "(profiles/hbm_traffic.json); bound = hbm says which roofline achieved / peak are on; "
-                                 "limiter names the LARGEST of the three fractions: hbm, "
-                                 "fp64_issue (SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x 2.4 GHz x time)) and lds "
-                                 "(SQ_LDS_IDX_ACTIVE / (256 CUs x 2.4 GHz x time)); the SQ counts come from "
-                                 "profiles/sq_counters.json (rocprofv3 PMC passes of this command)"},
-            "kernel_ms_all": {names[i]: float(kms[i]) for i in range(5)},
-            "exchange_wait_ms": float(kms[6]),
-            "per_kernel": per_kernel,
-            a.scaling: {k: v for k, v in rec.items()},
         }
+        if kms is not None:
+            out.update(kernel_figures(npart, kms))
+        out[a.scaling] = {k: v for k, v in rec.items()}
         if rec_other is not None:
             out[other] = rec_other
         elif other_skipped:
@@ -975,7 +1027,7 @@ def main():
             out["stirred"] = stirred
         if second is not None:
             out["secondary"] = second
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.cpu_cells)
         print(json.dumps(out))
     if world > 1:

@@ -994,7 +994,7 @@ def test_bench_multi_rank_path_rehearsal(scaling):
     extra = ["--cells", "16", "--particles-total", str(8 * 17 ** 3)] + ([] if scaling == "weak" else ["--scaling", "strong"])
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4",
-           "--warmup", "2", "--no-cpu-baseline"] + extra
+           "--warmup", "2", "--full", "--no-cpu-baseline"] + extra
     env = dict(os.environ, NLPS_BENCH_BACKEND="gloo", NLPS_BENCH_DEVICE="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]

@@ -36,7 +36,7 @@ pmc_passes() {  # name, sq-group array name, program + arguments ...
 for PART in $PARTS; do
   case $PART in
   step)
-    B="--no-cpu-baseline --no-stirred --no-second-scaling --no-secondary --no-implicit"
+    B="--full --no-cpu-baseline --no-stirred --no-second-scaling --no-secondary --no-implicit"
     rocprofv3 --kernel-trace --stats --output-format csv -d $O/step_stats -- python3 bench.py --steps 20 --warmup 5 $B > $O.step.log 2>&1
     pmc_passes step SQ5 python3 bench.py --steps 3 --warmup 2 $B
     tail -1 $O.step.log | cut -c1-200 ;;
