@@ -356,6 +356,37 @@ int nlps_gpu_tangent_coo(nlps_gpu *h, double alpha_1, const double *lumped_mass,
 /* __create_sparsity_pattern (U-Newmark-beta.c:1568-1632): visited columns per dof row, nnz_per_row[N_A*d] */
 int nlps_gpu_sparsity_pattern(nlps_gpu *h, int *nnz_per_row);
 
+/* ------------------------------------------------------------------ matrix-free tangent (MatShell of __jacobian_evaluation)
+ * The same K as nlps_gpu_tangent_assemble + nlps_gpu_tangent_coo, never formed: every block is bilinear in the
+ * particle's two LME gradients, K_AB[i][j] = sum_mn gn_A[m] gn_B[n] Dh[m][n][i][j] with ONE fourth-order tensor per
+ * particle (Dh = V0 DF^-1 D DF^-T pulled into the reference frame; V0 -> V0 (1 - Damage_n1) with the damage hooks on),
+ * so y = K x is a gather of x over the particle's members, a d^4 contraction and a scatter: O(members) work and memory
+ * that grows with the particle count only.  Same laws as the assembly, per particle (mixed clouds included).
+ * nlps_gpu_tangent_operator linearises at the current particle state (what the residual call or the compatibility +
+ * constitutive stages left), same inputs as nlps_gpu_tangent_coo: lumped_mass (masked [N_A*d], host or device, may be
+ * NULL) adds alpha_1 M on the diagonal, apply_dirichlet != 0 makes the dofs fixed at the step of nlps_gpu_active_masks
+ * identity rows and columns.  It SNAPSHOTS the linearisation (Dh per particle, alpha_1 M, the Dirichlet choice): later
+ * residual evaluations (line-search trials) do not change it.  Particles whose J or DF does not invert raise the flags
+ * and the error of nlps_gpu_tangent_assemble.  *bytes (may be NULL) = device memory this linearisation needs, by the
+ *   formula 8 * (d^4 np + N_A d + d^2 nnodes)  -- 81 doubles per particle in 3-D, 16 in 2-D, plus a masked vector and
+ *   a d^2-field grid array (the assembled path: 8 d^2 (9^d nnodes + triplets) bytes and more).  The buffers are kept
+ *   and only grow, so after a larger earlier linearisation the handle may hold more.  nlps_gpu_tangent_block_diagonal
+ *   with a host destination also keeps a staging buffer of 8 N_A d^2 bytes on the handle (not in *bytes).
+ * A failed allocation returns 1 with the reason in nlps_gpu_last_error.
+ * nlps_gpu_tangent_apply: y = K x (MATOP_MULT), x and y masked [N_A*d], host or device pointers; y is overwritten, x is
+ * not touched.  nlps_gpu_tangent_block_diagonal: the N_A d x d diagonal blocks of K, row-major, in masked node order,
+ * blocks[N_A*d*d], host or device (MATOP_GET_DIAGONAL / point-block Jacobi).
+ * Both fail with a message naming the cause, never with a stale result, before any nlps_gpu_tangent_operator and after
+ * any call that moves, reorders or re-lists particles: nlps_gpu_local_search, nlps_gpu_active_masks, a re-sort
+ * (nlps_gpu_resort, periodic or adaptive), a migration, nlps_gpu_update_kinetics, nlps_gpu_roll_state and
+ * nlps_gpu_explicit_step.  Several ranks: the scattered K x (and the blocks) pass the halo exchange hook before the
+ * nodal epilogue, like the residual call; every rank's x must agree on the shared nodes, as its dU does.
+ * Sums use floating-point atomics in every mode (deterministic mode included, like the level-B stage calls): results
+ * agree with the assembled matrix times x up to summation order. */
+int nlps_gpu_tangent_operator(nlps_gpu *h, double alpha_1, const double *lumped_mass, int apply_dirichlet, size_t *bytes);
+int nlps_gpu_tangent_apply(nlps_gpu *h, const double *x, double *y);
+int nlps_gpu_tangent_block_diagonal(nlps_gpu *h, double *blocks);
+
 /* ------------------------------------------------------------------ multi-GPU hooks */
 
 /* Halo exchange callback, invoked by explicit_step / the P2G stages after a nodal scatter, on the

@@ -306,3 +306,36 @@ int nlps_glue_lagrangian_evaluation_static(const nlps_glue *G, Particle MPM_Mesh
   return nlps_glue_lagrangian_evaluation(G, MPM_Mesh, Lagrangian_ptr, dU_ptr, dU_ptr, dU_ptr, Lumped_Mass_ptr, alpha0, b, neumann,
                                          nneumann, TimeStep, 1);
 }
+
+/* __jacobian_evaluation (U-Newmark-beta.c:1646-1830) as a MatShell instead of an assembled MATAIJ: the matrix-free
+ * counterpart of nlps_gpu_tangent_assemble + nlps_gpu_tangent_coo.  Call it where the driver assembles the Jacobian
+ * (the SNES Jacobian callback): it linearises at the state the last residual evaluation left, with alpha_1 M on the
+ * diagonal (Lumped_Mass_ptr = VecGetArrayRead(ctx->Lumped_Mass)) and the Dirichlet dofs as identity rows / columns
+ * (MatZeroRowsColumnsIS, :1822).  The operator stays fixed through the line-search trials that follow. */
+int nlps_glue_tangent_operator(const nlps_glue *G, double alpha_1, const double *Lumped_Mass_ptr) {
+  const int STATUS = nlps_gpu_tangent_operator(G->gpu, alpha_1, Lumped_Mass_ptr, 1, NULL);
+  if (STATUS != EXIT_SUCCESS) fprintf(stderr, "" RED "%s" RESET "\n", nlps_gpu_last_error(G->gpu));
+  return STATUS;
+}
+
+/* The body of the MatShell's MATOP_MULT after VecGetArrayRead(x, &x_ptr) / VecGetArray(y, &y_ptr): y = K x. */
+int nlps_glue_tangent_mult(const nlps_glue *G, const double *x_ptr, double *y_ptr) {
+  const int STATUS = nlps_gpu_tangent_apply(G->gpu, x_ptr, y_ptr);
+  if (STATUS != EXIT_SUCCESS) fprintf(stderr, "" RED "%s" RESET "\n", nlps_gpu_last_error(G->gpu));
+  return STATUS;
+}
+
+/* MATOP_GET_DIAGONAL after VecGetArray(d, &d_ptr): the diagonal of K (nactive * NumberDimensions doubles), taken from
+ * the point blocks; blocks_ptr = caller's scratch of nactive * NumberDimensions^2 doubles, or NULL to skip the
+ * blocks (they are what a point-block Jacobi preconditioner, PCPBJACOBI, inverts). */
+int nlps_glue_tangent_diagonal(const nlps_glue *G, double *d_ptr, double *blocks_ptr, int nactive) {
+  const int d = NumberDimensions;
+  double *b = blocks_ptr ? blocks_ptr : (double *)malloc((size_t)(nactive > 0 ? nactive : 1) * d * d * sizeof(double));
+  if (b == NULL) return EXIT_FAILURE;
+  const int STATUS = nlps_gpu_tangent_block_diagonal(G->gpu, b);
+  if (STATUS != EXIT_SUCCESS) fprintf(stderr, "" RED "%s" RESET "\n", nlps_gpu_last_error(G->gpu));
+  for (int A = 0; A < nactive && STATUS == EXIT_SUCCESS && d_ptr; A++)
+    for (int i = 0; i < d; i++) d_ptr[A * d + i] = b[((size_t)A * d + i) * d + i];
+  if (b != blocks_ptr) free(b);
+  return STATUS;
+}

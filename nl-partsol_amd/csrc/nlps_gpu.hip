@@ -1270,6 +1270,7 @@ __global__ __launch_bounds__(BLK) void k_fill_orders(int np, const int* __restri
   order2[s0 + tb[r * NNW + w] + (int)__popcll(m & ((1ull << (l & 63)) - 1ull))] = p;
 }
 #include "nlps_tangent_kernels.hpp"
+#include "nlps_tangent_operator.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // physical re-sort of the particle SoA (maintenance, every few dozen steps): restores the
@@ -1615,6 +1616,19 @@ struct nlps_gpu {
   bool tangent_grouped = true;  // one workgroup per closest node (false: one wave per particle, kept for comparison)
   bool tangent_symmetric = true;  // Neo-Hookean clouds: only the upper half of every row is assembled (nlps_gpu_debug_option "tangent_symmetric")
   bool ktan_sym = false;          // how the last nlps_gpu_tangent_assemble filled the stencil array (nlps_gpu_tangent_coo mirrors the rest)
+  // matrix-free tangent (nlps_gpu_tangent_operator), allocated on first use.  tan_gen counts the calls that move, reorder
+  // or re-list particles (tan_stale); the operator is valid while top_gen == tan_gen.
+  double* top_d = nullptr;  // Dh [d^4][top_np]
+  size_t top_cap = 0;       // doubles
+  double* top_m = nullptr;  // alpha_1 M snapshot, masked [N_A d] (valid when top_mass)
+  size_t top_mcap = 0;
+  double* top_g = nullptr;  // grid scratch [nnodes][d^2]: x and K x (2 d fields) or the diagonal blocks (d^2)
+  double* top_b = nullptr;  // staging of nlps_gpu_tangent_block_diagonal for host destinations [N_A d^2]
+  size_t top_bcap = 0;
+  int top_np = 0;
+  bool top_mass = false, top_dir = false;
+  unsigned long long tan_gen = 1, top_gen = 0;  // top_gen 0: no operator yet
+  const char* tan_why = "";
   int* order_d;
   int* order2_d = nullptr;  // canonical tile lists (k_tile_order), allocated on first use
 
@@ -1645,6 +1659,11 @@ struct nlps_gpu {
   } while (0)
 
 static inline int nblk(int n, int b = BLK) { return n > 0 ? (n + b - 1) / b : 1; }
+// a call that moves, reorders or re-lists particles: the matrix-free tangent of nlps_gpu_tangent_operator goes stale
+static inline void tan_stale(nlps_gpu* h, const char* why) {
+  h->tan_gen++;
+  h->tan_why = why;
+}
 static int materialise_nodal(nlps_gpu* h);  // the nodal arrays the folded explicit step left unmade (defined with the step)
 
 static bool is_device_ptr(const void* p) {
@@ -2202,6 +2221,7 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
 // live_only: called at the head of an explicit step -- the fields that step rewrites in full before anything reads them
 // (d_dis, the n+1 slots of F and b_e, DF, tau, J_n+1, W, kappa_n+1, eps_n+1: 43 of the 89 components) are not moved.
 static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live_only = false) {
+  tan_stale(h, "a re-sort of the particle arrays");
   const int np = h->P.np;
   if (np == 0) return 0;
   // The tile lists of the last step in canonical order (k_tile_order: layer r = the r-th particle of every closest node,
@@ -2366,6 +2386,7 @@ extern "C" int nlps_gpu_migration_select(nlps_gpu* h, int keep_lo, int keep_hi, 
 // Migration, step 2: the selected particles leave, the immigrants (packed rows from the neighbours, host or device
 // pointers) join, the arrays are re-sorted and the next search re-bins everything.
 extern "C" int nlps_gpu_migration_commit(nlps_gpu* h, const void* rows_a, int n_a, const void* rows_b, int n_b) {
+  tan_stale(h, "a particle migration");
   if (!h->mig_selected) {
     h->err = "nlps_gpu_migration_commit: call nlps_gpu_migration_select() first";
     return 1;
@@ -2478,7 +2499,7 @@ extern "C" int nlps_gpu_destroy(nlps_gpu* h) {
                   h->N.dU, h->N.force, h->N.accel, h->N.reaction, h->N.fixed, h->h_avg_d, h->beta_t2_d, h->n2m_d, h->d2m_d, h->canon_d, h->mask_flags_d, h->mask_idx_d,
                   h->fixedm_d, h->bsum_d, h->total_d, h->gstatus_d, h->gridA, h->gridB, h->maskedA, h->mats_d,
                   h->rank1_d, h->P.tile, h->P.rank, h->order_d, h->order2_d, h->tile_count_d, h->tile_count2_d, h->tile_start_d, h->work1_d, h->work2_d, h->nwork_d, h->slab_d, h->dmg_first_d, h->dmg_last_d, h->dmg_first0_d, h->dmg_last0_d, h->dmg_sorted0_d, h->perm_d, h->skey_d, h->skey2_d, h->sval_d, h->sval2_d,
-                  h->gather_tmp, h->cub_tmp, h->gid_d, h->leaving_d, h->mig_slot_d, h->mig_cnt_d, h->mig_down_d, h->mig_up_d, h->kst_d, h->ktouched_d, h->kcnt_d, h->koffs_d, h->kscan_tmp, h->khead_d, h->kng_d, h->vec_d, h->bcmask_d, h->home_d, h->foreign_d, h->node_cnt_d, h->nrank_d, h->tabo_d, h->tabm_d, h->tile_cursor_d};
+                  h->gather_tmp, h->cub_tmp, h->gid_d, h->leaving_d, h->mig_slot_d, h->mig_cnt_d, h->mig_down_d, h->mig_up_d, h->kst_d, h->ktouched_d, h->kcnt_d, h->koffs_d, h->kscan_tmp, h->khead_d, h->kng_d, h->vec_d, h->bcmask_d, h->home_d, h->foreign_d, h->node_cnt_d, h->nrank_d, h->tabo_d, h->tabm_d, h->tile_cursor_d, h->top_d, h->top_m, h->top_g, h->top_b};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& b : h->bcs)
@@ -3557,6 +3578,7 @@ static int beps_snapshot(nlps_gpu* h) {
 }
 
 extern "C" int nlps_gpu_local_search(nlps_gpu* h) {
+  tan_stale(h, "nlps_gpu_local_search");
   if (beps_snapshot(h)) return 1;  // (before this search moves any closest node)
   if (search_and_lists(h, false, false, 0.0, 0.0)) return 1;
   if (compute_node_mask(h)) return 1;
@@ -3610,6 +3632,7 @@ static int dirbits_of(const nlps_bcc& b, int step, int nsteps) {
 
 extern "C" int nlps_gpu_active_masks(nlps_gpu* h, const nlps_bcc* bcc, int nbcc, int step, int* nactive,
                                      int* nfree_dofs, int* nodes2mask, int* dofs2mask) {
+  tan_stale(h, "nlps_gpu_active_masks");
   int ND = h->nd, nn = h->g.nnodes;
   if (nbcc > 0 && check_step(h, step, "nlps_gpu_active_masks")) return 1;
   if (compute_node_mask(h)) return 1;
@@ -3910,6 +3933,7 @@ extern "C" int nlps_gpu_nodal_traction_forces(nlps_gpu* h, double* R, const nlps
 }
 
 extern "C" int nlps_gpu_roll_state(nlps_gpu* h) {
+  tan_stale(h, "nlps_gpu_roll_state");
   if (materialise_roll(h)) return 1;
   LAUNCH_ND((k_roll<2>), (k_roll<3>), nblk(h->P.np), h->P);
   HIPCHK(hipGetLastError());
@@ -3918,6 +3942,7 @@ extern "C" int nlps_gpu_roll_state(nlps_gpu* h) {
 
 extern "C" int nlps_gpu_update_kinetics(nlps_gpu* h, double alpha_blend, const double* dU, const double* Un_dt,
                                         const double* dU_dt, const double* dU_dt2) {
+  tan_stale(h, "nlps_gpu_update_kinetics");
   if (need_masks(h, "nlps_gpu_update_kinetics")) return 1;
   h->searched = h->ahead = false;  // the particles move: the next search is a search
   int ND = h->nd;
@@ -3955,6 +3980,7 @@ __global__ void k_null_bracket(PView, GridD, NView, TileD, const MatD*, ParamsD,
 
 extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc, int step, double dt, double gamma_nm,
                                       const double* gravity) {
+  tan_stale(h, "nlps_gpu_explicit_step");
   int ND = h->nd;
   if (h->P.erosion) {
     h->err = "nlps_gpu_explicit_step: the eigenerosion hooks exist in the level-B stages only (the reference defines them in "
@@ -4855,3 +4881,158 @@ extern "C" int nlps_gpu_sparsity_pattern(nlps_gpu* h, int* nnz_per_row) {
   return st;
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// matrix-free tangent (nlps_tangent_operator.hpp): MatShell MATOP_MULT / MATOP_GET_DIAGONAL
+// ------------------------------------------------------------------------------------------------
+static int tanop_valid(nlps_gpu* h, const char* who) {
+  if (h->top_gen == 0) {
+    h->err = std::string(who) + ": call nlps_gpu_tangent_operator() first";
+    return 1;
+  }
+  if (h->top_gen != h->tan_gen) {
+    h->err = std::string(who) + ": the operator is stale: " + h->tan_why +
+             " moved, reordered or re-listed the particles after nlps_gpu_tangent_operator(); linearise again";
+    return 1;
+  }
+  return need_masks(h, who);
+}
+
+static int tanop_alloc(nlps_gpu* h, const char* who, void** p, size_t bytes, const char* what) {
+  if (hipMalloc(p, bytes) == hipSuccess) return 0;
+  (void)hipGetLastError();
+  *p = nullptr;
+  char buf[200];
+  snprintf(buf, sizeof buf, "%s: cannot allocate %zu bytes for %s", who, bytes, what);
+  h->err = buf;
+  return 1;
+}
+
+extern "C" int nlps_gpu_tangent_operator(nlps_gpu* h, double alpha_1, const double* lumped_mass, int apply_dirichlet,
+                                         size_t* bytes) {
+  if (need_masks(h, "nlps_gpu_tangent_operator")) return 1;
+  if (materialise_roll(h)) return 1;
+  h->top_gen = 0;  // (no operator until this call succeeds)
+  const int ND = h->nd, E = ND * ND, np = h->P.np;
+  const size_t nD = (size_t)E * E * std::max(np, 1), nm = (size_t)h->nactive * ND, ngr = (size_t)h->g.nnodes * E;
+  if (nD > h->top_cap) {
+    if (h->top_d) HIPCHK(hipFree(h->top_d));
+    h->top_d = nullptr;
+    h->top_cap = 0;
+    if (tanop_alloc(h, "nlps_gpu_tangent_operator", (void**)&h->top_d, nD * sizeof(double), ND == 3 ? "81 doubles per particle" : "16 doubles per particle"))
+      return 1;
+    h->top_cap = nD;
+  }
+  if (std::max<size_t>(nm, 1) > h->top_mcap) {
+    if (h->top_m) HIPCHK(hipFree(h->top_m));
+    h->top_m = nullptr;
+    h->top_mcap = 0;
+    if (tanop_alloc(h, "nlps_gpu_tangent_operator", (void**)&h->top_m, std::max<size_t>(nm, 1) * sizeof(double), "the mass term")) return 1;
+    h->top_mcap = std::max<size_t>(nm, 1);
+  }
+  if (!h->top_g) {  // (the grid does not change size)
+    if (tanop_alloc(h, "nlps_gpu_tangent_operator", (void**)&h->top_g, ngr * sizeof(double), "the grid scratch")) return 1;
+  }
+  h->top_np = np;
+  h->top_dir = apply_dirichlet != 0;
+  h->top_mass = lumped_mass != nullptr;
+  if (lumped_mass && nm > 0) {
+    HIPCHK(hipMemcpyAsync(h->top_m, lumped_mass, nm * sizeof(double), hipMemcpyDefault, h->stream));
+    hipLaunchKernelGGL(k_tanop_scale, dim3(nblk((int)nm)), dim3(BLK), 0, h->stream, nm, alpha_1, h->top_m);
+  }
+  if (np > 0) {
+    const int nb = (np + TANOP_SETUP_NT - 1) / TANOP_SETUP_NT;
+    if (ND == 2)
+      hipLaunchKernelGGL(k_tanop_setup<2>, dim3(nb), dim3(TANOP_SETUP_NT), 0, h->stream, h->P, h->g, h->mats_d, h->top_d, np, h->gstatus_d);
+    else
+      hipLaunchKernelGGL(k_tanop_setup<3>, dim3(nb), dim3(TANOP_SETUP_NT), 0, h->stream, h->P, h->g, h->mats_d, h->top_d, np, h->gstatus_d);
+  }
+  HIPCHK(hipGetLastError());
+  if (check_status(h, ST_NEWTON | ST_CONSTITUTIVE, "nlps_gpu_tangent_operator()")) return 1;  // (synchronises)
+  if (bytes) *bytes = (nD + nm + ngr) * sizeof(double);  // (the header's formula: what this linearisation needs)
+  h->top_gen = h->tan_gen;
+  return 0;
+}
+
+extern "C" int nlps_gpu_tangent_apply(nlps_gpu* h, const double* x, double* y) {
+  if (tanop_valid(h, "nlps_gpu_tangent_apply")) return 1;
+  if (!x || !y) {
+    h->err = "nlps_gpu_tangent_apply: x and y are required";
+    return 1;
+  }
+  const int ND = h->nd, nn = h->g.nnodes;
+  VecIO io;
+  if (vec_begin(h, "nlps_gpu_tangent_apply", io)) return 1;
+  if (io.n == 0) return 0;
+  const double* xd = io.in(x);
+  double* yd = io.out(y, false);
+  double *xg = h->top_g, *yg = h->top_g + (size_t)nn * ND;
+  const int* d2m = h->top_dir ? (const int*)h->d2m_d : nullptr;
+  LAUNCH_ND((k_tanop_expand<2>), (k_tanop_expand<3>), nblk(nn), nn, (const int*)h->n2m_d, d2m, xd, xg);
+  HIPCHK(hipMemsetAsync(yg, 0, (size_t)nn * ND * sizeof(double), h->stream));
+  if (h->top_np > 0) {
+    const TileD td = tile_view(h);
+    if (ND == 2)
+      hipLaunchKernelGGL(k_tanop_apply<2>, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, (const double*)h->top_d, h->top_np,
+                         (const double*)xg, yg);
+    else
+      hipLaunchKernelGGL(k_tanop_apply<3>, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, (const double*)h->top_d, h->top_np,
+                         (const double*)xg, yg);
+  }
+  HIPCHK(hipGetLastError());
+  if (halo(h, yg, ND, 8, 0)) return 1;
+  LAUNCH_ND((k_tanop_nodal<2>), (k_tanop_nodal<3>), nblk(nn), nn, (const int*)h->n2m_d, d2m, (const double*)yg, xd,
+            h->top_mass ? (const double*)h->top_m : (const double*)nullptr, yd);
+  HIPCHK(hipGetLastError());
+  if (io.finish()) {
+    h->err = "nlps_gpu_tangent_apply: HIP error";
+    return 1;
+  }
+  if (io.back.empty()) HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int nlps_gpu_tangent_block_diagonal(nlps_gpu* h, double* blocks) {
+  if (tanop_valid(h, "nlps_gpu_tangent_block_diagonal")) return 1;
+  if (!blocks) {
+    h->err = "nlps_gpu_tangent_block_diagonal: blocks is required";
+    return 1;
+  }
+  const int ND = h->nd, E = ND * ND, nn = h->g.nnodes;
+  const size_t nb = (size_t)h->nactive * E;
+  if (nb == 0) return 0;
+  double* out = blocks;
+  const bool host = !is_device_ptr(blocks);
+  if (host && nb > h->top_bcap) {  // staging of a host destination: kept on the handle (hipMalloc synchronises)
+    if (h->top_b) HIPCHK(hipFree(h->top_b));
+    h->top_b = nullptr;
+    h->top_bcap = 0;
+    if (tanop_alloc(h, "nlps_gpu_tangent_block_diagonal", (void**)&h->top_b, nb * sizeof(double), "the staging of the blocks"))
+      return 1;
+    h->top_bcap = nb;
+  }
+  if (host) out = h->top_b;
+  int st = hipMemsetAsync(h->top_g, 0, (size_t)nn * E * sizeof(double), h->stream) != hipSuccess;
+  if (!st && h->top_np > 0) {
+    const TileD td = tile_view(h);
+    if (ND == 2)
+      hipLaunchKernelGGL(k_tanop_bdiag<2>, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, (const double*)h->top_d, h->top_np,
+                         h->top_g);
+    else
+      hipLaunchKernelGGL(k_tanop_bdiag<3>, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, (const double*)h->top_d, h->top_np,
+                         h->top_g);
+    st = hipGetLastError() != hipSuccess;
+  }
+  if (!st) st = halo(h, h->top_g, E, 8, 0);
+  if (!st) {
+    LAUNCH_ND((k_tanop_bdiag_nodal<2>), (k_tanop_bdiag_nodal<3>), nblk(nn), nn, (const int*)h->n2m_d,
+              h->top_dir ? (const int*)h->d2m_d : (const int*)nullptr, (const double*)h->top_g,
+              h->top_mass ? (const double*)h->top_m : (const double*)nullptr, out);
+    st = hipGetLastError() != hipSuccess;
+  }
+  if (!st && host) st = hipMemcpyAsync(blocks, out, nb * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess;
+  if (hipStreamSynchronize(h->stream) != hipSuccess) st = 1;
+  if (st && h->err.find("nlps_gpu_tangent_block_diagonal") == std::string::npos)
+    h->err = "nlps_gpu_tangent_block_diagonal: HIP error (or halo exchange failure)";
+  return st;
+}

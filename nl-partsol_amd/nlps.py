@@ -76,7 +76,8 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_rccl_reduce", "nlps_gpu_rccl_info", "nlps_gpu_rccl_migrate", "nlps_gpu_rccl_selftest_migrate", "nlps_gpu_rccl_selftest_exchange", "nlps_gpu_touched_layers", "nlps_gpu_set_node_window", "nlps_gpu_set_ghost_bands",
            "nlps_gpu_form_initial_guess", "nlps_gpu_nodal_kinetic_increments", "nlps_gpu_nodal_inertial_forces",
            "nlps_gpu_tangent_assemble", "nlps_gpu_tangent_set_grouped", "nlps_gpu_tangent_coo",
-           "nlps_gpu_sparsity_pattern",
+           "nlps_gpu_sparsity_pattern", "nlps_gpu_tangent_operator", "nlps_gpu_tangent_apply",
+           "nlps_gpu_tangent_block_diagonal",
            "nlps_gpu_migration_select", "nlps_gpu_migration_commit", "nlps_gpu_num_particles",
            "nlps_gpu_set_particle_ids", "nlps_gpu_download_ids",
            "nlps_gpu_set_timing", "nlps_gpu_get_timing", "nlps_host_stencil_tables",
@@ -127,6 +128,9 @@ def lib():
         L.nlps_gpu_tangent_set_grouped.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_tangent_coo.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int, _ip, _ip, _dp]
         L.nlps_gpu_sparsity_pattern.argtypes = [C.c_void_p, _ip]
+        L.nlps_gpu_tangent_operator.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
+        L.nlps_gpu_tangent_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nlps_gpu_tangent_block_diagonal.argtypes = [C.c_void_p, C.c_void_p]
         L.nlps_gpu_migration_select.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_void_p)]
         L.nlps_gpu_migration_commit.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -568,6 +572,38 @@ class Solver:
         self._chk(self.L.nlps_gpu_tangent_coo(self.h, float(alpha_1), _vp(lumped_mass), 1 if apply_dirichlet else 0,
                                               _vp(rows), _vp(cols), _vp(vals)))
         return rows, cols, vals
+
+    def tangent_operator(self, alpha_1=0.0, lumped_mass=None, apply_dirichlet=False):  # __jacobian_evaluation as a MatShell
+        """Linearises at the current particle state without forming the matrix (nlps_gpu_tangent_operator): the operator of
+        tangent_apply / tangent_block_diagonal, the same K as jacobian_evaluation(alpha_1, lumped_mass, apply_dirichlet).
+        Returns the device bytes the operator holds."""
+        nb = C.c_size_t(0)
+        self._chk(self.L.nlps_gpu_tangent_operator(self.h, float(alpha_1), _vp(lumped_mass), 1 if apply_dirichlet else 0,
+                                                   C.byref(nb)))
+        return int(nb.value)
+
+    def tangent_apply(self, x, out=None):
+        """y = K x (MATOP_MULT).  x: numpy array (host) or torch tensor (device), masked [nactive*ndim]; y of the same kind
+        (out = the vector to overwrite)."""
+        if out is None:
+            if isinstance(x, np.ndarray):
+                out = np.empty(self.nactive * self.ndim)
+            else:
+                import torch
+                out = torch.empty(self.nactive * self.ndim, dtype=torch.float64, device=x.device)
+        self._chk(self.L.nlps_gpu_tangent_apply(self.h, _vp(x), _vp(out)))
+        return out
+
+    def tangent_block_diagonal(self, on_device=False):
+        """The nactive d x d diagonal blocks of K, shape (nactive, ndim, ndim), masked node order (MATOP_GET_DIAGONAL)."""
+        shape = (self.nactive, self.ndim, self.ndim)
+        if on_device:
+            import torch
+            out = torch.empty(shape, dtype=torch.float64, device="cuda")
+        else:
+            out = np.empty(shape)
+        self._chk(self.L.nlps_gpu_tangent_block_diagonal(self.h, _vp(out)))
+        return out
 
     def create_sparsity_pattern(self):                  # __create_sparsity_pattern (after jacobian_evaluation)
         pat = np.zeros(self.nactive * self.ndim, dtype=np.int32)
