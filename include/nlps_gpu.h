@@ -387,6 +387,52 @@ int nlps_gpu_tangent_operator(nlps_gpu *h, double alpha_1, const double *lumped_
 int nlps_gpu_tangent_apply(nlps_gpu *h, const double *x, double *y);
 int nlps_gpu_tangent_block_diagonal(nlps_gpu *h, double *blocks);
 
+/* nlps_gpu_tangent_solve: K x = b for the operator of the last nlps_gpu_tangent_operator, by restarted GMRES(restart) on
+ * the device -- the driver's KSPSolve (GMRES(30) + PCJACOBI, U-Newmark-beta.c:270-336) in one call.  b and x are masked
+ * [N_A*d], host or device pointers (a host vector crosses PCIe once per solve); b is not touched.
+ * Right preconditioning, K M^-1 u = b, x = M^-1 u: the stopping test sees the unpreconditioned residual ||b - K x||
+ * (PETSc's default is left preconditioning and the preconditioned norm).  Classical Gram-Schmidt with one more pass when
+ * the norm drops below 1/sqrt 2 of its value (DGKS, PETSc's refine_ifneeded).  Iterations are Arnoldi steps summed over
+ * the restarts.  Every cycle ends with the true residual b - K x (one product): it confirms a converged estimate or
+ * starts the next cycle.  history[0] = ||b - K x0||, history[k] = the estimate after step k.
+ * Preconditioners: NLPS_PC_JACOBI the reciprocal diagonal of K (PCJACOBI), NLPS_PC_PBJACOBI the inverted d x d diagonal
+ * blocks (PCPBJACOBI), built from nlps_gpu_tangent_block_diagonal's blocks once per successful
+ * nlps_gpu_tangent_operator and reused by the solves that follow on the same linearisation.  A block whose pivot (or a
+ * diagonal entry) is at or below 1e-14 of the block's Frobenius norm fails the call, naming the masked node.
+ * Returns 1 for misuse, a HIP failure, a preconditioner that does not invert, before any nlps_gpu_tangent_operator and
+ * after anything that makes the operator stale (as nlps_gpu_tangent_apply), and on a handle that exchanges halos (a halo
+ * callback or an RCCL world > 1: single rank only).  Returns 0 when the solve ran, converged or not (ksp->reason).
+ * bytes = 8 * ((restart + 3) n + (restart + 2) nb + 6 (restart + 2) + 8 + restart (restart + 1) + [pc] N_A d^2) with
+ *   n = N_A d, nb = ceil(n / 512): the basis, two work vectors, per-block partial sums, the Hessenberg state and the
+ *   preconditioner (pc != NLPS_PC_NONE).  Kept on the handle and only grown, like the operator's buffers. */
+enum { NLPS_PC_NONE = 0, NLPS_PC_JACOBI = 1, NLPS_PC_PBJACOBI = 2 };
+enum {
+  NLPS_KSP_CONVERGED_BZERO = 1,     /* b == 0: x = 0 */
+  NLPS_KSP_CONVERGED_RTOL = 2,      /* ||b - K x|| <= rtol ||b|| */
+  NLPS_KSP_CONVERGED_ATOL = 3,      /* ||b - K x|| <= atol */
+  NLPS_KSP_DIVERGED_ITS = -3,       /* max_it steps without convergence */
+  NLPS_KSP_DIVERGED_DTOL = -4,      /* ||b - K x|| > dtol ||b|| */
+  NLPS_KSP_DIVERGED_BREAKDOWN = -5, /* the Hessenberg matrix is singular (K M^-1 singular on the Krylov space) */
+  NLPS_KSP_DIVERGED_NANORINF = -9   /* a non-finite value: x is the one of the last finished cycle */
+};
+#define NLPS_KSP_MAX_RESTART 256
+typedef struct {
+  /* in */
+  int pc;         /* NLPS_PC_* */
+  int restart;    /* Krylov vectors per cycle, 1 .. NLPS_KSP_MAX_RESTART (the driver's default 30) */
+  int max_it;     /* Arnoldi steps over all cycles */
+  int x_is_guess; /* 0: x0 = 0 (x is only written), else x holds the initial guess */
+  double rtol, atol, dtol; /* converged: ||b - K x|| <= max(rtol ||b||, atol); diverged: > dtol ||b|| (at a cycle's end) */
+  double *history;         /* host array of max_it + 1 residual norms, or NULL (KSPSetResidualHistory) */
+  /* out */
+  int reason;     /* NLPS_KSP_*: > 0 converged, < 0 not */
+  int iterations; /* Arnoldi steps taken */
+  double rnorm;   /* ||b - K x|| of the returned x (the true residual, from one product) */
+  double bnorm;   /* ||b|| */
+  size_t bytes;   /* device workspace this solve holds, by the formula above */
+} nlps_ksp;
+int nlps_gpu_tangent_solve(nlps_gpu *h, const double *b, double *x, nlps_ksp *ksp);
+
 /* ------------------------------------------------------------------ multi-GPU hooks */
 
 /* Halo exchange callback, invoked by explicit_step / the P2G stages after a nodal scatter, on the

@@ -339,3 +339,37 @@ int nlps_glue_tangent_diagonal(const nlps_glue *G, double *d_ptr, double *blocks
   if (b != blocks_ptr) free(b);
   return STATUS;
 }
+
+/* The whole linear solve of the SNES iterate as one library call: the body of a PCShellSetApply after
+ * VecGetArrayRead(b, &b_ptr) / VecGetArray(x, &x_ptr), with KSPSetType(ksp, KSPPREONLY), so that SNES's
+ * KSPSolve (U-Newmark-beta.c:270-336; U-Static.c) hands its right-hand side straight to the device GMRES on the
+ * operator of nlps_glue_tangent_operator.  pc = NLPS_PC_JACOBI is the driver's PCJACOBI, NLPS_PC_PBJACOBI the point
+ * blocks; restart 30, rtol / atol / max_it as KSPGetTolerances returns them (dtol 1e5).  The stopping test sees the
+ * true residual ||b - K x||, not PETSc's left-preconditioned one.  *iterations (may be NULL) = the Arnoldi steps
+ * taken; a solve that ran without converging prints its reason and returns EXIT_FAILURE, as a failed KSPSolve makes
+ * SNES stop the step. */
+int nlps_glue_linear_solve(const nlps_glue *G, const double *b_ptr, double *x_ptr, int pc, double rtol, double atol,
+                           int max_it, int *iterations) {
+  nlps_ksp K;
+  memset(&K, 0, sizeof K);
+  K.pc = pc;
+  K.restart = 30;
+  K.max_it = max_it;
+  K.x_is_guess = 0;
+  K.rtol = rtol;
+  K.atol = atol;
+  K.dtol = 1e5;
+  K.history = NULL;
+  const int STATUS = nlps_gpu_tangent_solve(G->gpu, b_ptr, x_ptr, &K);
+  if (iterations) *iterations = K.iterations;
+  if (STATUS != EXIT_SUCCESS) {
+    fprintf(stderr, "" RED "%s" RESET "\n", nlps_gpu_last_error(G->gpu));
+    return STATUS;
+  }
+  if (K.reason < 0) {
+    fprintf(stderr, "" RED "nlps_gpu_tangent_solve: no convergence (reason %d) after %d iterations, ||r|| = %e of ||b|| = %e" RESET "\n",
+            K.reason, K.iterations, K.rnorm, K.bnorm);
+    return EXIT_FAILURE;
+  }
+  return EXIT_SUCCESS;
+}

@@ -1271,6 +1271,7 @@ __global__ __launch_bounds__(BLK) void k_fill_orders(int np, const int* __restri
 }
 #include "nlps_tangent_kernels.hpp"
 #include "nlps_tangent_operator.hpp"
+#include "nlps_krylov.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // physical re-sort of the particle SoA (maintenance, every few dozen steps): restores the
@@ -1629,6 +1630,24 @@ struct nlps_gpu {
   bool top_mass = false, top_dir = false;
   unsigned long long tan_gen = 1, top_gen = 0;  // top_gen 0: no operator yet
   const char* tan_why = "";
+  // device GMRES (nlps_gpu_tangent_solve, nlps_krylov.hpp), allocated on first use and kept (they only grow).  The
+  // preconditioner belongs to one linearisation: top_serial counts the successful nlps_gpu_tangent_operator calls
+  // (top_gen does not move when the caller re-linearises without moving particles), ksp_pc_serial says which one
+  // ksp_pc was built from.
+  unsigned long long top_serial = 0, ksp_pc_serial = 0;
+  int ksp_pc_kind = -1;
+  double* ksp_pc = nullptr;  // [N_A d^2]: the inverted blocks (PBJACOBI) or reciprocals on the block diagonals (JACOBI)
+  size_t ksp_pc_cap = 0;
+  double* ksp_v = nullptr;   // [(m + 3) n]: the basis V[0..m], z = M^-1 v, t = K x
+  size_t ksp_v_cap = 0;
+  double* ksp_part = nullptr;  // [(m + 2) nb]: per-block partial sums
+  size_t ksp_part_cap = 0;
+  double* ksp_s = nullptr;   // the cycle's small state (KspSmall)
+  size_t ksp_s_cap = 0;
+  int* ksp_bad_d = nullptr;  // first masked node whose PC block does not invert
+  KspHost* ksp_h = nullptr;  // pinned: what the host reads per step
+  KspHost* ksp_hd = nullptr; // its device alias (nullptr: the kernels write ksp_hdev and the host copies)
+  KspHost* ksp_hdev = nullptr;
   int* order_d;
   int* order2_d = nullptr;  // canonical tile lists (k_tile_order), allocated on first use
 
@@ -2499,7 +2518,8 @@ extern "C" int nlps_gpu_destroy(nlps_gpu* h) {
                   h->N.dU, h->N.force, h->N.accel, h->N.reaction, h->N.fixed, h->h_avg_d, h->beta_t2_d, h->n2m_d, h->d2m_d, h->canon_d, h->mask_flags_d, h->mask_idx_d,
                   h->fixedm_d, h->bsum_d, h->total_d, h->gstatus_d, h->gridA, h->gridB, h->maskedA, h->mats_d,
                   h->rank1_d, h->P.tile, h->P.rank, h->order_d, h->order2_d, h->tile_count_d, h->tile_count2_d, h->tile_start_d, h->work1_d, h->work2_d, h->nwork_d, h->slab_d, h->dmg_first_d, h->dmg_last_d, h->dmg_first0_d, h->dmg_last0_d, h->dmg_sorted0_d, h->perm_d, h->skey_d, h->skey2_d, h->sval_d, h->sval2_d,
-                  h->gather_tmp, h->cub_tmp, h->gid_d, h->leaving_d, h->mig_slot_d, h->mig_cnt_d, h->mig_down_d, h->mig_up_d, h->kst_d, h->ktouched_d, h->kcnt_d, h->koffs_d, h->kscan_tmp, h->khead_d, h->kng_d, h->vec_d, h->bcmask_d, h->home_d, h->foreign_d, h->node_cnt_d, h->nrank_d, h->tabo_d, h->tabm_d, h->tile_cursor_d, h->top_d, h->top_m, h->top_g, h->top_b};
+                  h->gather_tmp, h->cub_tmp, h->gid_d, h->leaving_d, h->mig_slot_d, h->mig_cnt_d, h->mig_down_d, h->mig_up_d, h->kst_d, h->ktouched_d, h->kcnt_d, h->koffs_d, h->kscan_tmp, h->khead_d, h->kng_d, h->vec_d, h->bcmask_d, h->home_d, h->foreign_d, h->node_cnt_d, h->nrank_d, h->tabo_d, h->tabm_d, h->tile_cursor_d, h->top_d, h->top_m, h->top_g, h->top_b,
+                  h->ksp_pc, h->ksp_v, h->ksp_part, h->ksp_s, h->ksp_bad_d, h->ksp_hdev};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& b : h->bcs)
@@ -2507,6 +2527,7 @@ extern "C" int nlps_gpu_destroy(nlps_gpu* h) {
   if (h->foreign_h) (void)hipHostFree(h->foreign_h);
   if (h->lagr_d) (void)hipFree(h->lagr_d);
   if (h->status_h) (void)hipHostFree(h->status_h);
+  if (h->ksp_h) (void)hipHostFree(h->ksp_h);
   for (int i = 0; i < 8; i++) (void)hipEventDestroy(h->ev[i]);
   for (hipEvent_t e : h->evw)
     if (e) (void)hipEventDestroy(e);
@@ -4951,25 +4972,31 @@ extern "C" int nlps_gpu_tangent_operator(nlps_gpu* h, double alpha_1, const doub
   if (check_status(h, ST_NEWTON | ST_CONSTITUTIVE, "nlps_gpu_tangent_operator()")) return 1;  // (synchronises)
   if (bytes) *bytes = (nD + nm + ngr) * sizeof(double);  // (the header's formula: what this linearisation needs)
   h->top_gen = h->tan_gen;
+  h->top_serial++;  // (a new linearisation: the preconditioner of nlps_gpu_tangent_solve is rebuilt)
   return 0;
 }
 
-extern "C" int nlps_gpu_tangent_apply(nlps_gpu* h, const double* x, double* y) {
-  if (tanop_valid(h, "nlps_gpu_tangent_apply")) return 1;
-  if (!x || !y) {
-    h->err = "nlps_gpu_tangent_apply: x and y are required";
-    return 1;
-  }
+// y = K M^-1 v on device masked vectors.  pc == nullptr: y = K v, the product of nlps_gpu_tangent_apply.  Otherwise the
+// solve's form: k_ksp_pc_expand folds z = M^-1 v (kind 0: z = v, not written) into the expansion and zeroes the
+// accumulator, and the nodal epilogue reads z.
+struct KspPc {
+  int kind;
+  const double* Minv;
+  double* z;
+};
+static int tanop_product(nlps_gpu* h, const double* v, double* y, const KspPc* pc) {
   const int ND = h->nd, nn = h->g.nnodes;
-  VecIO io;
-  if (vec_begin(h, "nlps_gpu_tangent_apply", io)) return 1;
-  if (io.n == 0) return 0;
-  const double* xd = io.in(x);
-  double* yd = io.out(y, false);
   double *xg = h->top_g, *yg = h->top_g + (size_t)nn * ND;
   const int* d2m = h->top_dir ? (const int*)h->d2m_d : nullptr;
-  LAUNCH_ND((k_tanop_expand<2>), (k_tanop_expand<3>), nblk(nn), nn, (const int*)h->n2m_d, d2m, xd, xg);
-  HIPCHK(hipMemsetAsync(yg, 0, (size_t)nn * ND * sizeof(double), h->stream));
+  const double* xin = v;
+  if (pc) {
+    LAUNCH_ND((k_ksp_pc_expand<2>), (k_ksp_pc_expand<3>), nblk(nn), nn, (const int*)h->n2m_d, d2m, pc->kind, pc->Minv, v,
+              pc->z, xg, yg);
+    if (pc->kind) xin = pc->z;
+  } else {
+    LAUNCH_ND((k_tanop_expand<2>), (k_tanop_expand<3>), nblk(nn), nn, (const int*)h->n2m_d, d2m, v, xg);
+    HIPCHK(hipMemsetAsync(yg, 0, (size_t)nn * ND * sizeof(double), h->stream));
+  }
   if (h->top_np > 0) {
     const TileD td = tile_view(h);
     if (ND == 2)
@@ -4981,9 +5008,24 @@ extern "C" int nlps_gpu_tangent_apply(nlps_gpu* h, const double* x, double* y) {
   }
   HIPCHK(hipGetLastError());
   if (halo(h, yg, ND, 8, 0)) return 1;
-  LAUNCH_ND((k_tanop_nodal<2>), (k_tanop_nodal<3>), nblk(nn), nn, (const int*)h->n2m_d, d2m, (const double*)yg, xd,
-            h->top_mass ? (const double*)h->top_m : (const double*)nullptr, yd);
+  LAUNCH_ND((k_tanop_nodal<2>), (k_tanop_nodal<3>), nblk(nn), nn, (const int*)h->n2m_d, d2m, (const double*)yg, xin,
+            h->top_mass ? (const double*)h->top_m : (const double*)nullptr, y);
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int nlps_gpu_tangent_apply(nlps_gpu* h, const double* x, double* y) {
+  if (tanop_valid(h, "nlps_gpu_tangent_apply")) return 1;
+  if (!x || !y) {
+    h->err = "nlps_gpu_tangent_apply: x and y are required";
+    return 1;
+  }
+  VecIO io;
+  if (vec_begin(h, "nlps_gpu_tangent_apply", io)) return 1;
+  if (io.n == 0) return 0;
+  const double* xd = io.in(x);
+  double* yd = io.out(y, false);
+  if (tanop_product(h, xd, yd, nullptr)) return 1;
   if (io.finish()) {
     h->err = "nlps_gpu_tangent_apply: HIP error";
     return 1;
@@ -4992,26 +5034,9 @@ extern "C" int nlps_gpu_tangent_apply(nlps_gpu* h, const double* x, double* y) {
   return 0;
 }
 
-extern "C" int nlps_gpu_tangent_block_diagonal(nlps_gpu* h, double* blocks) {
-  if (tanop_valid(h, "nlps_gpu_tangent_block_diagonal")) return 1;
-  if (!blocks) {
-    h->err = "nlps_gpu_tangent_block_diagonal: blocks is required";
-    return 1;
-  }
+// the N_A masked diagonal blocks into the device array out (stream order, no synchronisation); 0 or 1
+static int tanop_bdiag(nlps_gpu* h, double* out) {
   const int ND = h->nd, E = ND * ND, nn = h->g.nnodes;
-  const size_t nb = (size_t)h->nactive * E;
-  if (nb == 0) return 0;
-  double* out = blocks;
-  const bool host = !is_device_ptr(blocks);
-  if (host && nb > h->top_bcap) {  // staging of a host destination: kept on the handle (hipMalloc synchronises)
-    if (h->top_b) HIPCHK(hipFree(h->top_b));
-    h->top_b = nullptr;
-    h->top_bcap = 0;
-    if (tanop_alloc(h, "nlps_gpu_tangent_block_diagonal", (void**)&h->top_b, nb * sizeof(double), "the staging of the blocks"))
-      return 1;
-    h->top_bcap = nb;
-  }
-  if (host) out = h->top_b;
   int st = hipMemsetAsync(h->top_g, 0, (size_t)nn * E * sizeof(double), h->stream) != hipSuccess;
   if (!st && h->top_np > 0) {
     const TileD td = tile_view(h);
@@ -5030,9 +5055,267 @@ extern "C" int nlps_gpu_tangent_block_diagonal(nlps_gpu* h, double* blocks) {
               h->top_mass ? (const double*)h->top_m : (const double*)nullptr, out);
     st = hipGetLastError() != hipSuccess;
   }
+  return st;
+}
+
+extern "C" int nlps_gpu_tangent_block_diagonal(nlps_gpu* h, double* blocks) {
+  if (tanop_valid(h, "nlps_gpu_tangent_block_diagonal")) return 1;
+  if (!blocks) {
+    h->err = "nlps_gpu_tangent_block_diagonal: blocks is required";
+    return 1;
+  }
+  const int ND = h->nd, E = ND * ND;
+  const size_t nb = (size_t)h->nactive * E;
+  if (nb == 0) return 0;
+  double* out = blocks;
+  const bool host = !is_device_ptr(blocks);
+  if (host && nb > h->top_bcap) {  // staging of a host destination: kept on the handle (hipMalloc synchronises)
+    if (h->top_b) HIPCHK(hipFree(h->top_b));
+    h->top_b = nullptr;
+    h->top_bcap = 0;
+    if (tanop_alloc(h, "nlps_gpu_tangent_block_diagonal", (void**)&h->top_b, nb * sizeof(double), "the staging of the blocks"))
+      return 1;
+    h->top_bcap = nb;
+  }
+  if (host) out = h->top_b;
+  int st = tanop_bdiag(h, out);
   if (!st && host) st = hipMemcpyAsync(blocks, out, nb * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess;
   if (hipStreamSynchronize(h->stream) != hipSuccess) st = 1;
   if (st && h->err.find("nlps_gpu_tangent_block_diagonal") == std::string::npos)
     h->err = "nlps_gpu_tangent_block_diagonal: HIP error (or halo exchange failure)";
   return st;
+}
+
+// ------------------------------------------------------------------------------------------------
+// device GMRES on the matrix-free tangent (nlps_krylov.hpp): the driver's KSPSolve in one call
+// ------------------------------------------------------------------------------------------------
+static int ksp_grow(nlps_gpu* h, double** p, size_t* cap, size_t n, const char* what) {
+  if (n <= *cap) return 0;
+  if (*p) HIPCHK(hipFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  if (tanop_alloc(h, "nlps_gpu_tangent_solve", (void**)p, n * sizeof(double), what)) return 1;
+  *cap = n;
+  return 0;
+}
+
+// the values the kernels left in the host word (one synchronisation)
+static int ksp_wait(nlps_gpu* h) {
+  if (!h->ksp_hd) HIPCHK(hipMemcpyAsync(h->ksp_h, h->ksp_hdev, sizeof(KspHost), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// the preconditioner of the current linearisation: built from the diagonal blocks once per successful
+// nlps_gpu_tangent_operator (top_serial) and kind, reused by the solves that follow
+static int ksp_pc_build(nlps_gpu* h, int kind) {
+  if (kind == NLPS_PC_NONE || (h->ksp_pc_serial == h->top_serial && h->ksp_pc_kind == kind)) return 0;
+  const int ND = h->nd, nA = h->nactive;
+  h->ksp_pc_kind = -1;
+  if (ksp_grow(h, &h->ksp_pc, &h->ksp_pc_cap, (size_t)nA * ND * ND, "the preconditioner")) return 1;
+  if (!h->ksp_bad_d && tanop_alloc(h, "nlps_gpu_tangent_solve", (void**)&h->ksp_bad_d, sizeof(int), "the preconditioner check"))
+    return 1;
+  if (tanop_bdiag(h, h->ksp_pc)) {
+    if (h->err.find("nlps_gpu_tangent_solve") == std::string::npos)
+      h->err = "nlps_gpu_tangent_solve: HIP error in the diagonal blocks of the preconditioner";
+    return 1;
+  }
+  HIPCHK(hipMemsetAsync(h->ksp_bad_d, 0x7f, sizeof(int), h->stream));  // (0x7f7f7f7f: no node failed)
+  LAUNCH_ND((k_ksp_pc_build<2>), (k_ksp_pc_build<3>), nblk(nA), nA, kind, h->ksp_pc, h->ksp_bad_d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(&h->ksp_h->flags, h->ksp_bad_d, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const int bad = *(volatile int*)&h->ksp_h->flags;
+  if (bad < nA) {
+    char buf[240];
+    snprintf(buf, sizeof buf,
+             "nlps_gpu_tangent_solve: the %s of masked node %d does not invert (%s at or below 1e-14 of the block's norm): "
+             "no %s preconditioner for this operator",
+             kind == NLPS_PC_JACOBI ? "diagonal" : "diagonal block", bad, kind == NLPS_PC_JACOBI ? "an entry" : "a pivot",
+             kind == NLPS_PC_JACOBI ? "Jacobi" : "point-block Jacobi");
+    h->err = buf;
+    return 1;
+  }
+  h->ksp_pc_serial = h->top_serial;
+  h->ksp_pc_kind = kind;
+  return 0;
+}
+
+extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, nlps_ksp* ksp) {
+  const char* who = "nlps_gpu_tangent_solve";
+  if (!ksp) {
+    h->err = "nlps_gpu_tangent_solve: ksp is required";
+    return 1;
+  }
+  ksp->reason = 0;
+  ksp->iterations = 0;
+  ksp->rnorm = ksp->bnorm = 0.0;
+  ksp->bytes = 0;
+  if (tanop_valid(h, who)) return 1;
+  if (h->halo || (h->rccl && h->rccl->world > 1)) {
+    h->err = "nlps_gpu_tangent_solve: single rank only: this handle exchanges halos (a halo callback or an RCCL world > 1), "
+             "and dot products across ranks would need an owner mask and an allreduce";
+    return 1;
+  }
+  if (!b || !x) {
+    h->err = "nlps_gpu_tangent_solve: b and x are required";
+    return 1;
+  }
+  const int m = ksp->restart, kind = ksp->pc, max_it = ksp->max_it;
+  if (kind != NLPS_PC_NONE && kind != NLPS_PC_JACOBI && kind != NLPS_PC_PBJACOBI) {
+    h->err = "nlps_gpu_tangent_solve: pc must be NLPS_PC_NONE, NLPS_PC_JACOBI or NLPS_PC_PBJACOBI";
+    return 1;
+  }
+  if (m < 1 || m > NLPS_KSP_MAX_RESTART || max_it < 0) {
+    h->err = "nlps_gpu_tangent_solve: restart must be 1 .. NLPS_KSP_MAX_RESTART and max_it >= 0";
+    return 1;
+  }
+  if (!(ksp->rtol >= 0.0) || !(ksp->atol >= 0.0) || !(ksp->dtol > 0.0)) {
+    h->err = "nlps_gpu_tangent_solve: rtol and atol must be >= 0 and dtol > 0";
+    return 1;
+  }
+  VecIO io;
+  if (vec_begin(h, who, io)) return 1;
+  const size_t n = io.n;
+  const int ND = h->nd, nA = h->nactive, nb = (int)((n + KSP_TILE - 1) / KSP_TILE);
+  const KspSmall L{m};
+  ksp->bytes = sizeof(double) * ((size_t)(m + 3) * n + (size_t)(m + 2) * nb + L.size() +
+                                 (kind != NLPS_PC_NONE ? (size_t)nA * ND * ND : 0));
+  double* hist = ksp->history;
+  if (n == 0) {
+    ksp->reason = NLPS_KSP_CONVERGED_BZERO;
+    if (hist) hist[0] = 0.0;
+    return 0;
+  }
+  if (ksp_grow(h, &h->ksp_v, &h->ksp_v_cap, (size_t)(m + 3) * n, "the Krylov basis") ||
+      ksp_grow(h, &h->ksp_part, &h->ksp_part_cap, (size_t)(m + 2) * nb, "the partial sums") ||
+      ksp_grow(h, &h->ksp_s, &h->ksp_s_cap, L.size(), "the Hessenberg state"))
+    return 1;
+  if (!h->ksp_h) {
+    HIPCHK(hipHostMalloc((void**)&h->ksp_h, sizeof(KspHost), hipHostMallocDefault));
+    memset(h->ksp_h, 0, sizeof(KspHost));
+    if (hipHostGetDevicePointer((void**)&h->ksp_hd, h->ksp_h, 0) != hipSuccess) {
+      (void)hipGetLastError();
+      h->ksp_hd = nullptr;  // (then the kernels write a device copy and ksp_wait brings it over)
+      if (tanop_alloc(h, who, (void**)&h->ksp_hdev, sizeof(KspHost), "the step word")) return 1;
+    }
+  }
+  if (ksp_pc_build(h, kind)) return 1;
+  const double* bd = io.in(b);
+  double* xd = io.out(x, ksp->x_is_guess != 0);
+  double* const V = h->ksp_v;  // V[c] at V + c n
+  double* const z = V + (size_t)(m + 1) * n;
+  double* const t = z + n;
+  double* const part = h->ksp_part;
+  double* const s = h->ksp_s;
+  KspHost* const hw = h->ksp_hd ? h->ksp_hd : h->ksp_hdev;
+  const KspPc pcd{kind, h->ksp_pc, z};
+  const dim3 gs(nb), bs(KSP_NT);
+  // ||b|| and r0 = b - K x0 into V[0]
+  hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, (const double*)nullptr, (double*)nullptr, part);
+  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, (double*)nullptr, &hw->bn2,
+                     (const double*)nullptr, (double*)nullptr, (const double*)nullptr);
+  if (ksp->x_is_guess) {
+    if (tanop_product(h, xd, t, nullptr)) return 1;
+    hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, (const double*)t, V, part);
+  } else {
+    HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(double), h->stream));
+    hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, (const double*)nullptr, V, part);
+  }
+  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, (double*)nullptr, &hw->rn2,
+                     (const double*)nullptr, (double*)nullptr, (const double*)nullptr);
+  HIPCHK(hipGetLastError());
+  if (ksp_wait(h)) return 1;
+  const double bnorm = sqrt(h->ksp_h->bn2);
+  double rnorm = sqrt(h->ksp_h->rn2);
+  const double tol = std::max(ksp->rtol * bnorm, ksp->atol);
+  if (hist) hist[0] = rnorm;
+  int its = 0, reason = 0;
+  bool broke = false;
+  if (bnorm == 0.0) {  // x = 0 (also over a guess), as KSPSolve
+    HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(double), h->stream));
+    rnorm = 0.0;
+    if (hist) hist[0] = 0.0;
+    reason = NLPS_KSP_CONVERGED_BZERO;
+  }
+  while (!reason) {
+    if (!std::isfinite(rnorm) || !std::isfinite(bnorm)) reason = NLPS_KSP_DIVERGED_NANORINF;
+    else if (rnorm <= tol) reason = rnorm < ksp->atol ? NLPS_KSP_CONVERGED_ATOL : NLPS_KSP_CONVERGED_RTOL;
+    else if (rnorm > ksp->dtol * bnorm) reason = NLPS_KSP_DIVERGED_DTOL;
+    else if (its >= max_it) reason = NLPS_KSP_DIVERGED_ITS;
+    else if (broke) reason = NLPS_KSP_DIVERGED_BREAKDOWN;
+    if (reason) break;
+    // one cycle: V[0] = r / ||r||, Arnoldi steps on K M^-1 until the estimate converges, the cycle is full, max_it or
+    // a breakdown; one host synchronisation per step (the estimate and the flags)
+    hipLaunchKernelGGL(k_ksp_scale, gs, bs, 0, h->stream, (int)n, (const double*)V, V, 1.0 / rnorm, (const double*)nullptr);
+    int k = 0;
+    bool nonfinite = false;
+    for (int j = 0; j < m; j++) {
+      double* const w = V + (size_t)(j + 1) * n;
+      if (tanop_product(h, V + (size_t)j * n, w, &pcd)) return 1;
+      double* const refine = s + L.refine();
+      // classical Gram-Schmidt, pass 1 (with w.w for DGKS), then pass 2 when the refine word says so
+      hipLaunchKernelGGL(k_ksp_mdot, gs, bs, 0, h->stream, (int)n, (const double*)V, n, j + 1, 1, (const double*)w, part, nb,
+                         (const double*)nullptr);
+      hipLaunchKernelGGL(k_ksp_finish, dim3(j + 2), bs, 0, h->stream, (const double*)part, nb, s + L.h1(), (double*)nullptr,
+                         (const double*)nullptr, (double*)nullptr, (const double*)nullptr);
+      hipLaunchKernelGGL(k_ksp_maxpy, gs, bs, 0, h->stream, (int)n, (const double*)V, n, j + 1, (const double*)(s + L.h1()), w,
+                         part, (const double*)nullptr);
+      hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, s + L.wn2(), (double*)nullptr,
+                         (const double*)nullptr, refine, (const double*)(s + L.h1() + j + 1));
+      hipLaunchKernelGGL(k_ksp_mdot, gs, bs, 0, h->stream, (int)n, (const double*)V, n, j + 1, 0, (const double*)w, part, nb,
+                         (const double*)refine);
+      hipLaunchKernelGGL(k_ksp_finish, dim3(j + 1), bs, 0, h->stream, (const double*)part, nb, s + L.h2(), (double*)nullptr,
+                         (const double*)refine, (double*)nullptr, (const double*)nullptr);
+      hipLaunchKernelGGL(k_ksp_maxpy, gs, bs, 0, h->stream, (int)n, (const double*)V, n, j + 1, (const double*)(s + L.h2()), w,
+                         part, (const double*)refine);
+      hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, s + L.wn2(), (double*)nullptr,
+                         (const double*)refine, (double*)nullptr, (const double*)nullptr);
+      hipLaunchKernelGGL(k_ksp_arnoldi, dim3(1), dim3(64), 0, h->stream, L, s, j, rnorm, hw);
+      hipLaunchKernelGGL(k_ksp_scale, gs, bs, 0, h->stream, (int)n, (const double*)w, w, 1.0, (const double*)(s + L.wn2()));
+      HIPCHK(hipGetLastError());
+      if (ksp_wait(h)) return 1;
+      const double est = h->ksp_h->est;
+      const int flags = h->ksp_h->flags;
+      its++;
+      if (hist) hist[its] = est;
+      if ((flags & KSP_FLAG_NONFINITE) || !std::isfinite(est)) {
+        nonfinite = true;
+        break;
+      }
+      if (flags & KSP_FLAG_SINGULAR) {  // (column j does not enter the update)
+        broke = true;
+        break;
+      }
+      k = j + 1;
+      if (est <= tol || (flags & KSP_FLAG_HAPPY) || its >= max_it) break;
+    }
+    if (nonfinite) {
+      reason = NLPS_KSP_DIVERGED_NANORINF;
+      break;
+    }
+    if (k > 0) {  // x += M^-1 V y, R y = g
+      hipLaunchKernelGGL(k_ksp_hsolve, dim3(1), dim3(64), 0, h->stream, L, s, k);
+      LAUNCH_ND((k_ksp_update<2>), (k_ksp_update<3>), nblk(nA), nA, kind, (const double*)h->ksp_pc, (const double*)V, n, k,
+                (const double*)(s + L.y()), xd);
+    }
+    // the true residual of the new x: confirms the estimate, or starts the next cycle from V[0]
+    if (tanop_product(h, xd, t, nullptr)) return 1;
+    hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, (const double*)t, V, part);
+    hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, (double*)nullptr, &hw->rn2,
+                       (const double*)nullptr, (double*)nullptr, (const double*)nullptr);
+    HIPCHK(hipGetLastError());
+    if (ksp_wait(h)) return 1;
+    rnorm = sqrt(h->ksp_h->rn2);
+  }
+  ksp->reason = reason;
+  ksp->iterations = its;
+  ksp->rnorm = rnorm;
+  ksp->bnorm = bnorm;
+  if (io.finish()) {
+    h->err = "nlps_gpu_tangent_solve: HIP error";
+    return 1;
+  }
+  if (io.back.empty()) HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
 }

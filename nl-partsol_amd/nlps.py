@@ -55,6 +55,18 @@ class Particles(C.Structure):
                  ("Strain_f_n", _dp), ("Strain_f_n1", _dp)])
 
 
+class Ksp(C.Structure):  # nlps_ksp (include/nlps_gpu.h): nlps_gpu_tangent_solve's settings and results
+    _fields_ = [("pc", C.c_int), ("restart", C.c_int), ("max_it", C.c_int), ("x_is_guess", C.c_int),
+                ("rtol", C.c_double), ("atol", C.c_double), ("dtol", C.c_double), ("history", _dp),
+                ("reason", C.c_int), ("iterations", C.c_int), ("rnorm", C.c_double), ("bnorm", C.c_double),
+                ("bytes", C.c_size_t)]
+
+
+PC_KINDS = {"none": 0, "jacobi": 1, "pbjacobi": 2}  # NLPS_PC_NONE / _JACOBI / _PBJACOBI
+KSP_REASONS = {1: "converged_bzero", 2: "converged_rtol", 3: "converged_atol", -3: "diverged_its", -4: "diverged_dtol",
+               -5: "diverged_breakdown", -9: "diverged_nanorinf"}
+
+
 class Bcc(C.Structure):
     _fields_ = [("nnodes", C.c_int), ("nodes", _ip), ("dim", C.c_int), ("dir", _ip), ("value", _dp)]
 
@@ -77,7 +89,7 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_form_initial_guess", "nlps_gpu_nodal_kinetic_increments", "nlps_gpu_nodal_inertial_forces",
            "nlps_gpu_tangent_assemble", "nlps_gpu_tangent_set_grouped", "nlps_gpu_tangent_coo",
            "nlps_gpu_sparsity_pattern", "nlps_gpu_tangent_operator", "nlps_gpu_tangent_apply",
-           "nlps_gpu_tangent_block_diagonal",
+           "nlps_gpu_tangent_block_diagonal", "nlps_gpu_tangent_solve",
            "nlps_gpu_migration_select", "nlps_gpu_migration_commit", "nlps_gpu_num_particles",
            "nlps_gpu_set_particle_ids", "nlps_gpu_download_ids",
            "nlps_gpu_set_timing", "nlps_gpu_get_timing", "nlps_host_stencil_tables",
@@ -131,6 +143,7 @@ def lib():
         L.nlps_gpu_tangent_operator.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
         L.nlps_gpu_tangent_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.nlps_gpu_tangent_block_diagonal.argtypes = [C.c_void_p, C.c_void_p]
+        L.nlps_gpu_tangent_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Ksp)]
         L.nlps_gpu_migration_select.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_void_p)]
         L.nlps_gpu_migration_commit.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -604,6 +617,37 @@ class Solver:
             out = np.empty(shape)
         self._chk(self.L.nlps_gpu_tangent_block_diagonal(self.h, _vp(out)))
         return out
+
+    def tangent_solve(self, b, x=None, pc="pbjacobi", restart=30, max_it=10000, rtol=1e-5, atol=0.0, dtol=1e5,
+                      history=False, out=None):
+        """K x = b on the device by GMRES(restart), right-preconditioned (nlps_gpu_tangent_solve; the driver's KSPSolve).
+        b: numpy array (host) or torch tensor (device), masked [nactive*ndim]; the result is of the same kind.  x: an
+        initial guess (left as it is unless it is also out), None for x0 = 0.  out: the vector to write (default: a new
+        one).  pc: "none", "jacobi" or "pbjacobi".  Returns (x, info), info = dict(iterations, reason (an NLPS_KSP_*
+        value), reason_name, rnorm (the true residual of x), bnorm, bytes, history (iterations + 1 norms, or None))."""
+        if pc not in PC_KINDS:
+            raise ValueError(f"pc must be one of {sorted(PC_KINDS)}")
+        n = self.nactive * self.ndim
+        if out is None:
+            if isinstance(b, np.ndarray):
+                out = np.empty(n)
+            else:
+                import torch
+                out = torch.empty(n, dtype=torch.float64, device=b.device)
+        if x is not None and x is not out:
+            if isinstance(out, np.ndarray):
+                out[:] = x if isinstance(x, np.ndarray) else x.detach().cpu().numpy()
+            else:
+                import torch
+                out.copy_(torch.as_tensor(x, dtype=torch.float64))
+        hist = np.zeros(max_it + 1) if history else None
+        k = Ksp(pc=PC_KINDS[pc], restart=int(restart), max_it=int(max_it), x_is_guess=1 if x is not None else 0,
+                rtol=float(rtol), atol=float(atol), dtol=float(dtol), history=_d(hist) if hist is not None else None)
+        self._chk(self.L.nlps_gpu_tangent_solve(self.h, _vp(b), _vp(out), C.byref(k)))
+        info = dict(iterations=k.iterations, reason=k.reason, reason_name=KSP_REASONS.get(k.reason, str(k.reason)),
+                    rnorm=k.rnorm, bnorm=k.bnorm, bytes=int(k.bytes),
+                    history=hist[: k.iterations + 1].copy() if hist is not None else None)
+        return out, info
 
     def create_sparsity_pattern(self):                  # __create_sparsity_pattern (after jacobian_evaluation)
         pat = np.zeros(self.nactive * self.ndim, dtype=np.int32)
