@@ -29,19 +29,60 @@
 #include <numeric>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nlps_gpu.h"
 #include "nlps_device.hpp"
 #include "nlps_tables.hpp"
 
-#define LAUNCH_ND(kern2, kern3, grid, ...)                                                     \
-  do {                                                                                         \
-    if (h->nd == 2) hipLaunchKernelGGL(kern2, dim3(grid), dim3(BLK), 0, h->stream, __VA_ARGS__); \
-    else hipLaunchKernelGGL(kern3, dim3(grid), dim3(BLK), 0, h->stream, __VA_ARGS__);          \
+// one kernel name per dimension, the same arguments: the 2-D or the 3-D one on the handle's stream
+#define LAUNCH_ND_BLK(kern2, kern3, grid, block, ...)                                              \
+  do {                                                                                             \
+    if (h->nd == 2) { hipLaunchKernelGGL(kern2, dim3(grid), dim3(block), 0, h->stream, __VA_ARGS__); } \
+    else { hipLaunchKernelGGL(kern3, dim3(grid), dim3(block), 0, h->stream, __VA_ARGS__); }        \
   } while (0)
+#define LAUNCH_ND(kern2, kern3, grid, ...) LAUNCH_ND_BLK(kern2, kern3, grid, BLK, __VA_ARGS__)
 
 using namespace nlps;
+
+// Run-time values as template arguments: f is a generic lambda, called with a std::integral_constant, and names its
+// kernel through CT(arg).  Only the values a helper can pass are instantiated, so a kernel that exists for a part of
+// the laws is dispatched with with_law_in<LO, HI> over exactly that part.
+template <int V>
+using ic = std::integral_constant<int, V>;
+#define CT(x) (decltype(x)::value)
+template <class F>
+static void with_nd(int nd, F&& f) {
+  if (nd == 2) f(ic<2>{});
+  else f(ic<3>{});
+}
+template <class F>
+static void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+// law in LO .. HI; anything else goes to HI, as the last `else` of the ladders this replaces did (the handle only holds
+// kernel laws 0 .. NLPS_KLAW_FRICTIONAL, klaw_of): a law out of range launches the last kernel, never nothing
+template <int LO, int HI, class F>
+static void with_law_in(int law, F&& f) {
+  if constexpr (LO < HI) {
+    if (law == LO) f(ic<LO>{});
+    else with_law_in<LO + 1, HI>(law, f);
+  } else {
+    f(ic<HI>{});
+  }
+}
+template <class F>
+static void with_law(int law, F&& f) {
+  with_law_in<0, NLPS_KLAW_FRICTIONAL>(law, f);
+}
+// the laws of a cloud of several (law_present of the handle), ascending: f(law, is it the last one)
+template <class F>
+static void for_each_law_present(unsigned mask, F&& f) {
+  for (int l = 0; l <= NLPS_KLAW_FRICTIONAL; l++)
+    if (mask & (1u << l)) f(l, (mask >> (l + 1)) == 0);
+}
 
 // ------------------------------------------------------------------------------------------------
 // particle component table
@@ -137,6 +178,8 @@ struct TileCnt {
   // atomics whose result nobody waits for -- and leave the ranks (positions inside the tile list and inside the node) to
   // k_fill_orders of the next step, which takes them from cursors at full occupancy.  K5 runs three waves per SIMD: a
   // returning atomic there is a stall nothing covers (+20 us of K5's 110 at 1 M particles).
+  // (The host sets it for every riding search outside the deterministic mode; the field goes with a later change of
+  // the kernels that read it.)
   int defer;
 };
 template <int ND>
@@ -1519,7 +1562,6 @@ struct nlps_gpu {
   // update them a second time, LME.c:927-929); ahead: seeds, tile counters, per-particle tile / rank and per-node
   // counters of that search are in place, the next explicit step starts at the activation kernel.
   bool searched = false, ahead = false;
-  int fuse_search = 1;  // developer switch NLPS_FUSE_SEARCH
   int lazy_nodal = 1;  // the folded explicit step (k3_tile_lazy / k5_tile_lazy): 1 below 2 M particles, 2 always, 0 never (NLPS_LAZY_NODAL)
   int ncu = 256;
   bool nodal_stale = false;
@@ -1564,14 +1606,11 @@ struct nlps_gpu {
   int* tile_count2_d = nullptr;  // the counters the search ahead (k5_tile) fills while tile_count_d still sizes the lists in use
   int* tile_start_d;
   int2 *work1_d = nullptr, *work2_d = nullptr;  // compacted (tile, part) work lists, see TileD
-  int resort_from_lists = 1;     // developer switch NLPS_RESORT_FROM_LISTS (resort)
   // canonical lists from per-node counters (TileTab): node_cnt[nnodes], nrank[npad], layer tables [ntiles][LMAX]
   int *node_cnt_d = nullptr, *nrank_d = nullptr, *tabo_d = nullptr;
   int* tile_cursor_d = nullptr;  // [ntiles + 1] list cursors of the deferred ranks (TileCnt::defer, k_fill_orders)
-  int defer_ranks = 1;           // the search riding on K5 only counts; ranks come from k_fill_orders (debug option defer_ranks)
-  bool ranks_deferred = false;   // ... and did so in the step before: the lists of this step take their ranks from cursors
+  bool ranks_deferred = false;   // the search riding on K5 only counted in the step before: the lists of this step take their ranks from cursors
   unsigned long long* tabm_d = nullptr;
-  int node_lists_on = 1;         // developer switch NLPS_NODE_LISTS (0: the per-tile counting sort k_tile_order)
   // adaptive re-sort (nlps_gpu_set_adaptive_resort): see TileCnt::home.  The count of displaced particles of a step
   // reaches the pinned host word at the end of its search stage; explicit_step adds count / NumGP to `debt` every
   // step and re-sorts ahead of the interval when the debt since the last re-sort exceeds `adaptive_resort`
@@ -1589,12 +1628,6 @@ struct nlps_gpu {
   bool beps_snapshot = false;  // F_X0 / F_I00 hold the configuration of Initialize_Beps = true
   double* slab_d = nullptr; // P2G window slabs [ntiles][K2_SPLIT][1+ND][NW] (TileD::slab), deterministic mode only
   bool deterministic = false;
-  // canonical (layer, closest node) order of every tile list each step (k_tile_order) for the LDS-atomic-bound K2 and
-  // K3; the memory-bound K5 keeps the lists as binned.  13 us per step at 1 M particles.  A freshly sorted cloud has its
-  // lists in that order already (0.685 vs 0.677 ms/step), but once particles have changed closest node -- 45 steps into
-  // the bench cloud's fall -- K2 runs 0.231 instead of 0.300 ms and K3 0.260 instead of 0.304, and the stirred cloud of
-  // DESIGN.md 0.84 instead of 0.95 ms/step
-  int tile_ordering = 1;
   int band_lo = -(1 << 30), band_hi = 1 << 30;  // ghost bands: layers <= band_lo and >= band_hi are shared with neighbours
   int overlap = 0;          // halo exchanges: 0 blocking in place; 1 behind the interior tiles of the NEXT stage (split
                             // launches, two-phase callback); 2 behind the interior tiles of the SAME launch (library RCCL only)
@@ -1649,7 +1682,12 @@ struct nlps_gpu {
   KspHost* ksp_hd = nullptr; // its device alias (nullptr: the kernels write ksp_hdev and the host copies)
   KspHost* ksp_hdev = nullptr;
   int* order_d;
-  int* order2_d = nullptr;  // canonical tile lists (k_tile_order), allocated on first use
+  // canonical (layer, closest node) order of every tile list each step for the LDS-atomic-bound K2 and K3; the
+  // memory-bound K5 keeps the lists as binned.  13 us per step at 1 M particles.  A freshly sorted cloud has its lists in
+  // that order already (0.685 vs 0.677 ms/step), but once particles have changed closest node -- 45 steps into the bench
+  // cloud's fall -- K2 runs 0.231 instead of 0.300 ms and K3 0.260 instead of 0.304, and the stirred cloud of DESIGN.md
+  // 0.84 instead of 0.95 ms/step
+  int* order2_d = nullptr;  // canonical tile lists (k_fill_orders; k_tile_order in deterministic mode), allocated on first use
 
   nlps_halo_fn halo;
   void* halo_ctx;
@@ -1992,9 +2030,6 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
   h->P.erosion = prm->driver_eigenerosion != 0 || prm->driver_eigensoftening != 0;
   h->P.softening = prm->driver_eigensoftening != 0 && prm->driver_eigenerosion == 0;
 #if NLPS_DEV  // developer builds only (tools/build_variant.sh): the shipped library reads no environment variable
-  if (const char* e = getenv("NLPS_TILE_ORDERING")) h->tile_ordering = atoi(e);  // see k_tile_order
-  if (const char* e = getenv("NLPS_RESORT_FROM_LISTS")) h->resort_from_lists = atoi(e);
-  if (const char* e = getenv("NLPS_FUSE_SEARCH")) h->fuse_search = atoi(e);
   if (const char* e = getenv("NLPS_LAZY_NODAL")) h->lazy_nodal = atoi(e);
 #endif
   {
@@ -2144,7 +2179,6 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
   if (dev_alloc(h, &h->nwork_d, 16)) return 1;
 #if NLPS_DEV
   if (const char* e = getenv("NLPS_ADAPTIVE_RESORT")) h->adaptive_resort = atof(e);  // (0 = off)
-  if (const char* e = getenv("NLPS_NODE_LISTS")) h->node_lists_on = atoi(e);
 #endif
   if (dev_alloc(h, &h->node_cnt_d, (size_t)h->g.nnodes)) return 1;
   if (dev_alloc(h, &h->nrank_d, h->P.npad)) return 1;
@@ -2243,20 +2277,18 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
   tan_stale(h, "a re-sort of the particle arrays");
   const int np = h->P.np;
   if (np == 0) return 0;
-  // The tile lists of the last step in canonical order (k_tile_order: layer r = the r-th particle of every closest node,
+  // The tile lists of the last step in canonical order (order2_d: layer r = the r-th particle of every closest node,
   // nodes in lattice order) ARE the memory order the kernels want -- each wave then reads 64 consecutive slots that hit
   // 64 distinct window rows -- so the periodic re-sort of the fused step takes them as its permutation: no keys, no
   // radix sort.  Otherwise (first sort, migration, level-B callers): sort by (tile, corner type, node).
-  const bool from_lists = !leaving && live_only && h->binned && h->order2_d && (h->tile_ordering || h->deterministic) &&
-                          h->resort_from_lists && h->ntw > 0;
+  const bool from_lists = !leaving && live_only && h->binned && h->order2_d && h->ntw > 0;
   if (!from_lists) {
     TileCnt tc;
     for (int a = 0; a < 3; a++) tc.nt[a] = h->nt[a];
     tc.count = nullptr;
     tc.home = nullptr;
     tc.node_cnt = nullptr;
-    if (h->nd == 2) hipLaunchKernelGGL(k_sort_keys<2>, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->P, h->g, tc, h->skey_d, h->sval_d, leaving, h->mats_d);
-    else hipLaunchKernelGGL(k_sort_keys<3>, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->P, h->g, tc, h->skey_d, h->sval_d, leaving, h->mats_d);
+    LAUNCH_ND(k_sort_keys<2>, k_sort_keys<3>, nblk(np), h->P, h->g, tc, h->skey_d, h->sval_d, leaving, h->mats_d);
     HIPCHK(hipGetLastError());
     size_t bytes = h->cub_tmp_bytes;
     HIPCHK(hipcub::DeviceRadixSort::SortPairs(h->cub_tmp, bytes, h->skey_d, h->skey2_d, h->sval_d, h->sval2_d, np, 0, 64,
@@ -2444,21 +2476,11 @@ extern "C" int nlps_gpu_migration_commit(nlps_gpu* h, const void* rows_a, int n_
 }
 
 extern "C" int nlps_gpu_resort(nlps_gpu* h) { return resort(h); }
-extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_set_tile_ordering(nlps_gpu* h, int on) {
-  h->tile_ordering = on;  // developer switch (tools/kbench.py --no-order)
-  h->ahead = false;
-  return 0;
-}
 // Developer / test switches as an explicit call (never read from the environment in the shipped build): which of the
 // equivalent launch forms a handle uses.  Not part of include/nlps_gpu.h.  Results do not depend on any of them.
 extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_option(nlps_gpu* h, const char* name, double value) {
   const std::string k(name ? name : "");
   if (k == "lazy_nodal") h->lazy_nodal = (int)value;             // folded explicit step: 0 never, 1 below 2 M particles, 2 always
-  else if (k == "fuse_search") h->fuse_search = (int)value;      // the next step's search on K5: 0 off, 1 with binning, 2 without
-  else if (k == "resort_from_lists") h->resort_from_lists = (int)value;
-  else if (k == "node_lists") h->node_lists_on = (int)value;
-  else if (k == "tile_ordering") h->tile_ordering = (int)value;
-  else if (k == "defer_ranks") h->defer_ranks = (int)value;  // the riding search only counts, k_fill_orders hands out the ranks
   else if (k == "tangent_symmetric") h->tangent_symmetric = value != 0;  // Neo-Hookean clouds: half rows + mirror (1) or every pair (0)
   else {
     h->err = "nlps_gpu_debug_option: unknown option " + k;
@@ -2705,8 +2727,7 @@ extern "C" int nlps_gpu_shape_functions(nlps_gpu* h, int first, int count, doubl
   HIPCHK(hipMalloc((void**)&Ns_d, (size_t)count * NS * sizeof(double)));
   HIPCHK(hipMalloc((void**)&dNs_d, (size_t)count * NS * ND * sizeof(double)));
   HIPCHK(hipMemcpyAsync(slots_d, slots.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  if (ND == 2) hipLaunchKernelGGL(k_shape_slots<2>, dim3(nblk(count)), dim3(BLK), 0, h->stream, h->P, h->g, slots_d, count, Ns_d, dNs_d, h->gstatus_d);
-  else hipLaunchKernelGGL(k_shape_slots<3>, dim3(nblk(count)), dim3(BLK), 0, h->stream, h->P, h->g, slots_d, count, Ns_d, dNs_d, h->gstatus_d);
+  LAUNCH_ND(k_shape_slots<2>, k_shape_slots<3>, nblk(count), h->P, h->g, slots_d, count, Ns_d, dNs_d, h->gstatus_d);
   HIPCHK(hipGetLastError());
   std::vector<double> Ns((size_t)count * NS), dNs((size_t)count * NS * ND);
   std::vector<u64> lo(np), hi(np);
@@ -3359,7 +3380,15 @@ extern "C" int nlps_gpu_set_node_numbering(nlps_gpu* h, const int* lattice_of_fi
 
 // canonical tile lists from per-node counters (TileTab) instead of the per-tile counting sort: every mode but the
 // deterministic one (which needs ranks that do not depend on the arrival order of an atomic)
-static bool node_lists(const nlps_gpu* h) { return h->tile_ordering && !h->deterministic && h->node_lists_on; }
+static bool node_lists(const nlps_gpu* h) { return !h->deterministic; }
+static TileTab tile_tab(const nlps_gpu* h) {
+  TileTab tab;
+  for (int a = 0; a < 3; a++) tab.nt[a] = h->nt[a];
+  tab.node_cnt = h->node_cnt_d;
+  tab.mask = h->tabm_d;
+  tab.base = h->tabo_d;
+  return tab;
+}
 static TileCnt tile_cnt(nlps_gpu* h, bool on) {
   TileCnt tc;
   for (int a = 0; a < 3; a++) tc.nt[a] = h->nt[a];
@@ -3403,7 +3432,7 @@ static TileD tile_view(nlps_gpu* h, int cls = 0) {  // cls: 0 all tiles, 1 bound
   td.start = h->tile_start_d;
   td.count = h->tile_count_d;
   td.order_m = h->order_d;
-  td.order = (h->tile_ordering || h->deterministic) ? h->order2_d : h->order_d;
+  td.order = h->order2_d;
   return td;
 }
 
@@ -3449,25 +3478,16 @@ static void launch_k2(nlps_gpu* h, bool p2g, int cls, double dt, double gamma_nm
   TileD td = tile_view(h, cls);
   if (signal) arm_signal(h, td, 0);
   if (h->deterministic && p2g) {  // one wave per tile, sorted list, slab flush (nlps_gpu_set_deterministic)
-    const dim3 grid1(h->ntw), blk1(64);
-    if (h->nd == 2) hipLaunchKernelGGL((k2_tile<2, true, 64, 1>), grid1, blk1, 0, h->stream, h->P, h->g, h->N, td, h->prm, dt, gamma_nm, h->gstatus_d);
-    else hipLaunchKernelGGL((k2_tile<3, true, 64, 1>), grid1, blk1, 0, h->stream, h->P, h->g, h->N, td, h->prm, dt, gamma_nm, h->gstatus_d);
+    LAUNCH_ND_BLK((k2_tile<2, true, 64, 1>), (k2_tile<3, true, 64, 1>), h->ntw, 64, h->P, h->g, h->N, td, h->prm, dt, gamma_nm,
+                  h->gstatus_d);
     return;
   }
-  const dim3 blk(BLK);
-#define NLPS_K2L(NDv, P2Gv)                                                                              \
-  do {                                                                                                   \
-    hipLaunchKernelGGL((k2_tile<NDv, P2Gv>), dim3(h->ntw * K2_SPLIT), blk, 0, h->stream, h->P, h->g, h->N, td,         \
-                       h->prm, dt, gamma_nm, h->gstatus_d);                                              \
-  } while (0)
-  if (h->nd == 2) {
-    if (p2g) NLPS_K2L(2, true);
-    else NLPS_K2L(2, false);
-  } else {
-    if (p2g) NLPS_K2L(3, true);
-    else NLPS_K2L(3, false);
-  }
-#undef NLPS_K2L
+  with_nd(h->nd, [&](auto D) {
+    with_bool(p2g, [&](auto P2G) {
+      hipLaunchKernelGGL((k2_tile<CT(D), CT(P2G)>), dim3(h->ntw * K2_SPLIT), dim3(BLK), 0, h->stream, h->P, h->g, h->N, td,
+                         h->prm, dt, gamma_nm, h->gstatus_d);
+    });
+  });
 }
 
 // S1: closest-node update + 1-ring activation + binning of the particles to I0-tiles, then lists, beta and the
@@ -3497,44 +3517,27 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
     const int TB = h->nd == 3 ? TileCfg<3>::TB : TileCfg<2>::TB;
     TileScanArgs ts{h->tile_count_d + h->tile0, h->tile_start_d + h->tile0, h->ntw, h->tile0, h->ntiles / h->nt[h->nd - 1], TB,
                     h->band_lo, h->band_hi, h->work1_d, h->work2_d, h->nwork_d, deferred ? h->tile_cursor_d + h->tile0 : nullptr};
-    TileTab tab;
-    for (int a = 0; a < 3; a++) tab.nt[a] = h->nt[a];
-    tab.node_cnt = h->node_cnt_d;
-    tab.mask = h->tabm_d;
-    tab.base = h->tabo_d;
     const int nb = 1 + (h->nwn + 1023) / 1024 + (node_lists(h) ? (h->ntw + 15) / 16 : 0);
     int* fo = (h->adaptive_resort > 0.0 && !h->deterministic) ? h->foreign_d : nullptr;
-    if (h->nd == 2) hipLaunchKernelGGL(k_dilate_scan<2>, dim3(nb), dim3(1024), 0, h->stream, h->n0, h->nwn, h->g, h->N, ts, fo, h->foreign_h, tab, clear_in_dilate ? 1 : 0);
-    else hipLaunchKernelGGL(k_dilate_scan<3>, dim3(nb), dim3(1024), 0, h->stream, h->n0, h->nwn, h->g, h->N, ts, fo, h->foreign_h, tab, clear_in_dilate ? 1 : 0);
+    LAUNCH_ND_BLK(k_dilate_scan<2>, k_dilate_scan<3>, nb, 1024, h->n0, h->nwn, h->g, h->N, ts, fo, h->foreign_h, tile_tab(h),
+                  clear_in_dilate ? 1 : 0);
   }
   HIPCHK(hipGetLastError());
   if (halo(h, h->N.active, 1, 1, 1, overlap ? 1 : 0)) return 1;
-  if ((h->deterministic || h->tile_ordering) && !h->order2_d) {
+  if (!h->order2_d) {
     HIPCHK(hipMalloc((void**)&h->order2_d, h->P.npad * sizeof(int)));
     HIPCHK(hipMemsetAsync(h->order2_d, 0, h->P.npad * sizeof(int), h->stream));
   }
   if (node_lists(h)) {  // both lists in one pass, the canonical one through the layer tables of this step (TileTab)
-    TileTab tab;
-    for (int a = 0; a < 3; a++) tab.nt[a] = h->nt[a];
-    tab.node_cnt = h->node_cnt_d;
-    tab.mask = h->tabm_d;
-    tab.base = h->tabo_d;
     const int* adopt = ahead ? h->P.I0n : nullptr;
-    if (h->nd == 2) hipLaunchKernelGGL(k_fill_orders<2>, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, h->P.tile, h->P.rank, h->nrank_d, h->P.I0, adopt, h->tile_start_d, h->g, tab, h->order_d, h->order2_d, deferred ? h->tile_cursor_d : (int*)nullptr, h->node_cnt_d);
-    else hipLaunchKernelGGL(k_fill_orders<3>, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, h->P.tile, h->P.rank, h->nrank_d, h->P.I0, adopt, h->tile_start_d, h->g, tab, h->order_d, h->order2_d, deferred ? h->tile_cursor_d : (int*)nullptr, h->node_cnt_d);
-  } else {
+    LAUNCH_ND(k_fill_orders<2>, k_fill_orders<3>, nblk(np), np, h->P.tile, h->P.rank, h->nrank_d, h->P.I0, adopt, h->tile_start_d,
+              h->g, tile_tab(h), h->order_d, h->order2_d, deferred ? h->tile_cursor_d : (int*)nullptr, h->node_cnt_d);
+  } else {  // deterministic mode: the exact per-tile sort
     if (ahead) hipLaunchKernelGGL(k_commit_I0, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, (const int*)h->P.I0n, h->P.I0);
     hipLaunchKernelGGL(k_fill_order, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, h->P.tile, h->P.rank, h->tile_start_d,
                        h->order_d);
-    if (h->deterministic) {
-      TileD td = tile_view(h, 0);
-      if (h->nd == 2) hipLaunchKernelGGL((k_tile_order<2, true>), dim3(h->ntw), dim3(256), 0, h->stream, h->P, h->g, td, (const int*)h->order_d, h->order2_d);
-      else hipLaunchKernelGGL((k_tile_order<3, true>), dim3(h->ntw), dim3(256), 0, h->stream, h->P, h->g, td, (const int*)h->order_d, h->order2_d);
-    } else if (h->tile_ordering) {
-      TileD td = tile_view(h, 0);
-      if (h->nd == 2) hipLaunchKernelGGL((k_tile_order<2, false>), dim3(h->ntw), dim3(256), 0, h->stream, h->P, h->g, td, (const int*)h->order_d, h->order2_d);
-      else hipLaunchKernelGGL((k_tile_order<3, false>), dim3(h->ntw), dim3(256), 0, h->stream, h->P, h->g, td, (const int*)h->order_d, h->order2_d);
-    }
+    LAUNCH_ND_BLK((k_tile_order<2, true>), (k_tile_order<3, true>), h->ntw, 256, h->P, h->g, tile_view(h, 0), (const int*)h->order_d,
+                  h->order2_d);
   }
   HIPCHK(hipGetLastError());
   if (h->timing) HIPCHK(hipEventRecord(h->ev[1], h->stream));
@@ -3745,8 +3748,7 @@ extern "C" int nlps_gpu_lumped_mass(nlps_gpu* h, double* M) {
   HIPCHK(hipMemsetAsync(h->gridA, 0, (size_t)h->g.nnodes * sizeof(double), h->stream));
   {
     TileD td = tile_view(h);
-    if (ND == 2) hipLaunchKernelGGL((kb_p2g_tile<2, 0>), dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, h->gridA);
-    else hipLaunchKernelGGL((kb_p2g_tile<3, 0>), dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, h->gridA);
+    LAUNCH_ND((kb_p2g_tile<2, 0>), (kb_p2g_tile<3, 0>), h->ntw, h->P, h->g, td, h->gridA);
   }
   HIPCHK(hipGetLastError());
   if (halo(h, h->gridA, 1, 8, 0)) return 1;
@@ -3759,8 +3761,7 @@ extern "C" int nlps_gpu_nodal_field_n(nlps_gpu* h, double* V, double* A, const d
   HIPCHK(hipMemsetAsync(h->gridA, 0, (size_t)h->g.nnodes * 2 * ND * sizeof(double), h->stream));
   {
     TileD td = tile_view(h);
-    if (ND == 2) hipLaunchKernelGGL((kb_p2g_tile<2, 1>), dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, h->gridA);
-    else hipLaunchKernelGGL((kb_p2g_tile<3, 1>), dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, h->gridA);
+    LAUNCH_ND((kb_p2g_tile<2, 1>), (kb_p2g_tile<3, 1>), h->ntw, h->P, h->g, td, h->gridA);
   }
   HIPCHK(hipGetLastError());
   if (halo(h, h->gridA, 2 * ND, 8, 0)) return 1;
@@ -3777,13 +3778,12 @@ extern "C" int nlps_gpu_compatibility(nlps_gpu* h, const double* dU, const doubl
   TileD td = tile_view(h);
   const dim3 grid(h->ntw * K3_SPLIT), blk(K3_BLK);
   const double* dV = dU_dt ? h->gridB : nullptr;
-  if (h->nd == 2) {
-    if (dV) hipLaunchKernelGGL((k3_tile<2, 0, 2>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm, h->gstatus_d, dV);
-    else hipLaunchKernelGGL((k3_tile<2, 0, 0>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm, h->gstatus_d, dV);
-  } else {
-    if (dV) hipLaunchKernelGGL((k3_tile<3, 0, 2>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm, h->gstatus_d, dV);
-    else hipLaunchKernelGGL((k3_tile<3, 0, 0>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm, h->gstatus_d, dV);
-  }
+  with_nd(h->nd, [&](auto D) {
+    with_bool(dV != nullptr, [&](auto RATES) {  // MODE 2: the rate tensors too
+      hipLaunchKernelGGL((k3_tile<CT(D), 0, CT(RATES) ? 2 : 0>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
+                         h->gstatus_d, dV);
+    });
+  });
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -3849,8 +3849,7 @@ extern "C" int nlps_gpu_internal_forces(nlps_gpu* h, double* R) {
   HIPCHK(hipMemsetAsync(h->N.force, 0, (size_t)h->g.nnodes * ND * sizeof(double), h->stream));
   {
     TileD td = tile_view(h);
-    if (ND == 2) hipLaunchKernelGGL(kb_fint_tile<2>, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, h->N.force, h->gstatus_d);
-    else hipLaunchKernelGGL(kb_fint_tile<3>, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, h->N.force, h->gstatus_d);
+    LAUNCH_ND(kb_fint_tile<2>, kb_fint_tile<3>, h->ntw, h->P, h->g, td, h->N.force, h->gstatus_d);
   }
   HIPCHK(hipGetLastError());
   if (halo(h, h->N.force, ND, 8, 0)) return 1;
@@ -3934,8 +3933,7 @@ static int traction_to_grid(nlps_gpu* h, const char* who, double* out, const nlp
   if (ND == 3) HIPCHK(hipMemcpyAsync(A_d, A.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_inverse_perm, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->perm_d, np, h->sval_d);
   HIPCHK(hipMemsetAsync(out, 0, (size_t)h->g.nnodes * ND * sizeof(double), h->stream));
-  if (ND == 2) hipLaunchKernelGGL(k_traction<2>, dim3(nblk(n)), dim3(BLK), 0, h->stream, h->P, h->g, n, ids_d, h->sval_d, T_d, A_d, thickness, out);
-  else hipLaunchKernelGGL(k_traction<3>, dim3(nblk(n)), dim3(BLK), 0, h->stream, h->P, h->g, n, ids_d, h->sval_d, T_d, A_d, thickness, out);
+  LAUNCH_ND(k_traction<2>, k_traction<3>, nblk(n), h->P, h->g, n, ids_d, h->sval_d, T_d, A_d, thickness, out);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));  // (the host vectors above are about to go)
   (void)hipFree(ids_d);
@@ -3990,8 +3988,8 @@ extern "C" int nlps_gpu_update_kinetics(nlps_gpu* h, double alpha_blend, const d
   {
     TileD td = tile_view(h);
     const int qs = quasi_static ? 1 : 0;
-    if (ND == 2) hipLaunchKernelGGL(kb_kinetics_tile<2>, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, alpha_blend, h->gridB, h->gridB + st, h->gridB + 2 * st, h->gridB + 3 * st, qs);
-    else hipLaunchKernelGGL(kb_kinetics_tile<3>, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, alpha_blend, h->gridB, h->gridB + st, h->gridB + 2 * st, h->gridB + 3 * st, qs);
+    LAUNCH_ND(kb_kinetics_tile<2>, kb_kinetics_tile<3>, h->ntw, h->P, h->g, td, alpha_blend, h->gridB, h->gridB + st,
+              h->gridB + 2 * st, h->gridB + 3 * st, qs);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -4055,18 +4053,18 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     const NodeRanges r = node_ranges(h, part);
     if (!det || r.an + r.bn == 0) return;
     TileD td = tile_view(h, 0);
-    if (ND == 2) hipLaunchKernelGGL((k_slab_gather<2, 3>), dim3(nblk(r.an + r.bn)), dim3(BLK), 0, h->stream, r.a0, r.an, r.b0, r.bn, h->g, td, h->N.nm);
-    else hipLaunchKernelGGL((k_slab_gather<3, 4>), dim3(nblk(r.an + r.bn)), dim3(BLK), 0, h->stream, r.a0, r.an, r.b0, r.bn, h->g, td, h->N.nm);
+    LAUNCH_ND((k_slab_gather<2, 3>), (k_slab_gather<3, 4>), nblk(r.an + r.bn), r.a0, r.an, r.b0, r.bn, h->g, td, h->N.nm);
   };
   auto gather_force = [&](int part) {
     const NodeRanges r = node_ranges(h, part);
     if (!det || r.an + r.bn == 0) return;
     TileD td = tile_view(h, 0);
     td.slab_n = __builtin_popcount(h->law_present);
-    if (ND == 2) hipLaunchKernelGGL((k_slab_gather<2, 2>), dim3(nblk(r.an + r.bn)), dim3(BLK), 0, h->stream, r.a0, r.an, r.b0, r.bn, h->g, td, h->N.force);
-    else hipLaunchKernelGGL((k_slab_gather<3, 3>), dim3(nblk(r.an + r.bn)), dim3(BLK), 0, h->stream, r.a0, r.an, r.b0, r.bn, h->g, td, h->N.force);
+    LAUNCH_ND((k_slab_gather<2, 2>), (k_slab_gather<3, 3>), nblk(r.an + r.bn), r.a0, r.an, r.b0, r.bn, h->g, td, h->N.force);
   };
-  const bool fuse_early = h->fuse_search && h->P.np > 0;
+  // the search of the next step rides on K5 (k5_tile<., ., true>, seeds and bins included).  A slab rank that holds no
+  // particles has nothing to search: it launches k5_tile<., ., false> and leaves `searched` / `ahead` false.
+  const bool ride = h->P.np > 0;
   // Folded form (k3_tile_lazy / k5_tile_lazy): one law, the Dirichlet sets small enough to travel as kernel arguments:
   // no nodal kernels between the stages (dU, accelerations, reactions are made later if somebody asks).  With a ghost
   // exchange too, in every overlap form: a K3 / K5 launch comes behind the pick-up of the exchange its nodes need (interior
@@ -4074,18 +4072,25 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   // (measured: 3 % faster per step at 1 M particles -- three launches less -- and equal within the noise at 4 M and 8 M,
   // where the window loads of 17 k tiles redo the two divisions per node 16 times over: on below 2 M particles,
   // NLPS_LAZY_NODAL=2 always)
-  const bool lazy = (h->lazy_nodal == 2 || (h->lazy_nodal == 1 && h->P.np <= 2000000)) && fuse_early && h->fuse_search == 1 && !det && h->uniform_law >= 0 &&
+  const bool lazy = (h->lazy_nodal == 2 || (h->lazy_nodal == 1 && h->P.np <= 2000000)) && ride && !det && h->uniform_law >= 0 &&
                     h->uniform_law <= NLPS_KLAW_FRICTIONAL && nbcc <= NLPS_MAX_BC_INLINE;
+  const bool inline_bc = nbcc <= NLPS_MAX_BC_INLINE;  // the Dirichlet sets of this step travel as one kernel argument
+  BcStep bs;
+  memset(&bs, 0, sizeof bs);
+  if (inline_bc) {
+    bs.n = nbcc;
+    for (int i = 0; i < nbcc; i++) {
+      bs.dim[i] = bcc[i].dim;
+      bs.bits[i] = h->bcs[i].n > 0 ? dirbits_of(bcc[i], step, h->nsteps) : 0;
+      for (int k = 0; k < 3; k++) bs.v[i][k] = (k < bcc[i].dim) ? bcc[i].value[(size_t)k * h->nsteps + step] : 0.0;
+    }
+  }
+  const unsigned* bm = (inline_bc && nbcc > 0) ? h->bcmask_d : nullptr;
   LazyNodal ln;
   if (lazy) {
     memset(&ln, 0, sizeof ln);
-    ln.fs.bc.n = nbcc;
-    for (int i = 0; i < nbcc; i++) {
-      ln.fs.bc.dim[i] = bcc[i].dim;
-      ln.fs.bc.bits[i] = h->bcs[i].n > 0 ? dirbits_of(bcc[i], step, h->nsteps) : 0;
-      for (int k = 0; k < 3; k++) ln.fs.bc.v[i][k] = (k < bcc[i].dim) ? bcc[i].value[(size_t)k * h->nsteps + step] : 0.0;
-    }
-    ln.fs.bcmask = nbcc > 0 ? h->bcmask_d : nullptr;
+    ln.fs.bc = bs;
+    ln.fs.bcmask = bm;
     for (int a = 0; a < 3; a++) ln.fs.gv[a] = gv[a];
     ln.n0 = h->n0;
     ln.nwn = h->nwn;
@@ -4096,20 +4101,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     if (lazy) return;  // (K3 makes dU of its window nodes itself)
     const NodeRanges r = node_ranges(h, part);
     if (r.an + r.bn == 0) return;
-    BcStep bs;
-    bs.n = 0;
-    const bool inline_bc = nbcc <= NLPS_MAX_BC_INLINE;
-    if (inline_bc) {
-      bs.n = nbcc;
-      for (int i = 0; i < nbcc; i++) {
-        bs.dim[i] = bcc[i].dim;
-        bs.bits[i] = h->bcs[i].n > 0 ? dirbits_of(bcc[i], step, h->nsteps) : 0;
-        for (int k = 0; k < 3; k++) bs.v[i][k] = (k < bcc[i].dim) ? bcc[i].value[(size_t)k * h->nsteps + step] : 0.0;
-      }
-    }
-    const unsigned* bm = (inline_bc && nbcc > 0) ? h->bcmask_d : nullptr;
-    if (ND == 2) hipLaunchKernelGGL(k_nodal_dU<2>, dim3(nblk(r.an + r.bn)), dim3(BLK), 0, h->stream, r.a0, r.an, r.b0, r.bn, h->N, bm, bs);
-    else hipLaunchKernelGGL(k_nodal_dU<3>, dim3(nblk(r.an + r.bn)), dim3(BLK), 0, h->stream, r.a0, r.an, r.b0, r.bn, h->N, bm, bs);
+    LAUNCH_ND(k_nodal_dU<2>, k_nodal_dU<3>, nblk(r.an + r.bn), r.a0, r.an, r.b0, r.bn, h->N, bm, bs);
     if (inline_bc) return;
     // Dirichlet values (nodes of the same range only)
     const NodeRanges in = node_ranges(h, 1);
@@ -4119,210 +4111,120 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
       for (int k = 0; k < bcc[i].dim && k < 3; k++) v[k] = bcc[i].value[(size_t)k * h->nsteps + step];
       int bits = dirbits_of(bcc[i], step, h->nsteps);
       const int r0 = part == 0 ? 0 : in.a0, r1 = part == 0 ? h->g.nnodes : in.a0 + in.an, inside = part == 2 ? 0 : 1;
-      if (ND == 2)
-        hipLaunchKernelGGL(k_bc<2>, dim3(nblk(h->bcs[i].n)), dim3(BLK), 0, h->stream, h->bcs[i].dnodes, h->bcs[i].n,
-                           bcc[i].dim, bits, v[0], v[1], v[2], h->N, r0, r1, inside);
-      else
-        hipLaunchKernelGGL(k_bc<3>, dim3(nblk(h->bcs[i].n)), dim3(BLK), 0, h->stream, h->bcs[i].dnodes, h->bcs[i].n,
-                           bcc[i].dim, bits, v[0], v[1], v[2], h->N, r0, r1, inside);
+      LAUNCH_ND(k_bc<2>, k_bc<3>, nblk(h->bcs[i].n), h->bcs[i].dnodes, h->bcs[i].n, bcc[i].dim, bits, v[0], v[1], v[2], h->N, r0,
+                r1, inside);
     }
   };
-  // the search of the next step rides on K5 (k5_tile<., ., true>) unless the lists must come from an exact sort
-  const bool fuse = h->fuse_search && h->P.np > 0;
   bool tiles_cleared = false;
   auto nodal_accel = [&](int part) {
     if (lazy) return;  // (K5 makes the accelerations itself; K3's workgroups have reset the search accumulators)
     const NodeRanges r = node_ranges(h, part);
-    const bool fbin = fuse && h->fuse_search == 1;
-    int* ctile = (fbin && !tiles_cleared) ? h->tile_count2_d + h->tile0 : nullptr;
+    int* ctile = (ride && !tiles_cleared) ? h->tile_count2_d + h->tile0 : nullptr;
     if (r.an + r.bn == 0 && !ctile) return;
     tiles_cleared = true;
-    int* cnode = (fbin && node_lists(h)) ? h->node_cnt_d : nullptr;
-    if (ND == 2) hipLaunchKernelGGL(k_nodal_accel<2>, dim3(nblk(std::max(1, r.an + r.bn))), dim3(BLK), 0, h->stream, r.a0, r.an, r.b0, r.bn, h->N, gv[0], gv[1], gv[2], fbin ? 1 : 0, cnode, ctile, h->ntw);
-    else hipLaunchKernelGGL(k_nodal_accel<3>, dim3(nblk(std::max(1, r.an + r.bn))), dim3(BLK), 0, h->stream, r.a0, r.an, r.b0, r.bn, h->N, gv[0], gv[1], gv[2], fbin ? 1 : 0, cnode, ctile, h->ntw);
+    int* cnode = (ride && node_lists(h)) ? h->node_cnt_d : nullptr;
+    LAUNCH_ND(k_nodal_accel<2>, k_nodal_accel<3>, nblk(std::max(1, r.an + r.bn)), r.a0, r.an, r.b0, r.bn, h->N, gv[0], gv[1], gv[2],
+              ride ? 1 : 0, cnode, ctile, h->ntw);
   };
-  auto launch_k3 = [&](int cls, bool signal = false) {
+  const int law = h->uniform_law;  // -1: several laws in the cloud (law_present)
+  const bool one_mat = ND == 3 && h->nmats == 1 && law >= 1 && law <= 3;  // its constants by scalar loads (k3_body, UMAT)
+  const dim3 grid3(h->ntw * K3_SPLIT), blk3(K3_BLK);
+  const double* const no_dU = nullptr;
+  auto launch_k3 = [&](int cls, bool signal) {
     TileD td = tile_view(h, cls);
-    if (signal) {  // several laws: only the last launch releases the exchange (launches of one stream run in order)
-      if (h->uniform_law >= 0 || !h->k3_per_law) arm_signal(h, td, 1);
-    }
-#define NLPS_K3(NDv, LAWv)                                                                                      \
-  do {                                                                                                          \
-    hipLaunchKernelGGL((k3_tile<NDv, LAWv, 1>), dim3(h->ntw * K3_SPLIT), dim3(K3_BLK), 0, h->stream, h->P, h->g,          \
-                       h->N, td, h->mats_d, h->prm, h->gstatus_d, (const double*)nullptr);                      \
-  } while (0)
-#define NLPS_K3D(NDv, LAWv)                                                                                     \
-  hipLaunchKernelGGL((k3_tile<NDv, LAWv, 1, true, 64>), dim3(h->ntw), dim3(64), 0, h->stream, h->P, h->g, h->N, td, \
-                     h->mats_d, h->prm, h->gstatus_d, (const double*)nullptr)
+    const bool per_law = law < 0 && h->k3_per_law;  // one launch of the single-law kernel per law present (FILT)
+    if (signal && !per_law) arm_signal(h, td, 1);
     if (det) {  // one wave per tile and per law present, particles in list order, one slab per (tile, law)
       td.slab_n = __builtin_popcount(h->law_present);
       td.slab_slot = -1;
-      for (int l = 0; l <= NLPS_KLAW_FRICTIONAL; l++) {
-        if (!(h->law_present & (1 << l))) continue;
+      for_each_law_present(h->law_present, [&](int l, bool) {
         td.slab_slot++;
-        if (ND == 2) {
-          if (l == 0) NLPS_K3D(2, 0);
-          else if (l == 1) NLPS_K3D(2, 1);
-          else if (l == 2) NLPS_K3D(2, 2);
-          else if (l == 3) NLPS_K3D(2, 3);
-          else NLPS_K3D(2, 4);
-        } else {
-          if (l == 0) NLPS_K3D(3, 0);
-          else if (l == 1) NLPS_K3D(3, 1);
-          else if (l == 2) NLPS_K3D(3, 2);
-          else if (l == 3) NLPS_K3D(3, 3);
-          else NLPS_K3D(3, 4);
-        }
-      }
-      return;
+        with_nd(ND, [&](auto D) {
+          with_law(l, [&](auto L) {
+            hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 1, true, 64>), dim3(h->ntw), dim3(64), 0, h->stream, h->P, h->g, h->N, td,
+                               h->mats_d, h->prm, h->gstatus_d, no_dU);
+          });
+        });
+      });
+    } else if (one_mat) {
+      with_law_in<1, 3>(law, [&](auto L) {
+        hipLaunchKernelGGL((k3_tile<3, CT(L), 1, false, K3_BLK, true>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
+                           h->prm, h->gstatus_d, no_dU);
+      });
+    } else if (law >= 0) {
+      with_nd(ND, [&](auto D) {
+        with_law(law, [&](auto L) {
+          hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 1>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
+                             h->gstatus_d, no_dU);
+        });
+      });
+    } else if (!per_law) {  // several laws, many mixed tiles: the kernel that dispatches on the law at run time
+      with_nd(ND, [&](auto D) {
+        hipLaunchKernelGGL((k3_tile<CT(D), -1, 1>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
+                           h->gstatus_d, no_dU);
+      });
+    } else {  // only the last launch releases the exchange (launches of one stream run in order)
+      for_each_law_present(h->law_present, [&](int l, bool last) {
+        if (signal && last) arm_signal(h, td, 1);
+        with_nd(ND, [&](auto D) {
+          with_law(l, [&](auto L) {
+            hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 1, true>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
+                               h->prm, h->gstatus_d, no_dU);
+          });
+        });
+      });
     }
-#undef NLPS_K3D
-#define NLPS_K3F(NDv, LAWv)                                                                                     \
-  hipLaunchKernelGGL((k3_tile<NDv, LAWv, 1, true>), dim3(h->ntw * K3_SPLIT), dim3(K3_BLK), 0, h->stream, h->P, h->g, h->N, td, \
-                     h->mats_d, h->prm, h->gstatus_d, (const double*)nullptr)
-    const int law = h->uniform_law;
-#define NLPS_K3U(LAWv)                                                                                          \
-  hipLaunchKernelGGL((k3_tile<3, LAWv, 1, false, K3_BLK, true>), dim3(h->ntw * K3_SPLIT), dim3(K3_BLK), 0, h->stream, h->P, \
-                     h->g, h->N, td, h->mats_d, h->prm, h->gstatus_d, (const double*)nullptr)
-    if (ND == 3 && h->nmats == 1 && law >= 1 && law <= 3) {  // one material (k3_body, UMAT)
-      if (law == 1) NLPS_K3U(1);
-      else if (law == 2) NLPS_K3U(2);
-      else NLPS_K3U(3);
-    } else if (ND == 2) {
-      if (law == 0) NLPS_K3(2, 0);
-      else if (law == 1) NLPS_K3(2, 1);
-      else if (law == 2) NLPS_K3(2, 2);
-      else if (law == 3) NLPS_K3(2, 3);
-      else if (law == 4) NLPS_K3(2, 4);
-      else if (!h->k3_per_law) NLPS_K3(2, -1);
-      else {  // several laws in the cloud: one launch of the single-law kernel per law present
-        const int last = 31 - __builtin_clz((unsigned)h->law_present);
-        for (int l = 0; l <= NLPS_KLAW_FRICTIONAL; l++) {
-          if (!(h->law_present & (1 << l))) continue;
-          if (signal && l == last) arm_signal(h, td, 1);
-          if (l == 0) NLPS_K3F(2, 0);
-          else if (l == 1) NLPS_K3F(2, 1);
-          else if (l == 2) NLPS_K3F(2, 2);
-          else if (l == 3) NLPS_K3F(2, 3);
-          else NLPS_K3F(2, 4);
-        }
-      }
-    } else {
-      if (law == 0) NLPS_K3(3, 0);
-      else if (law == 1) NLPS_K3(3, 1);
-      else if (law == 2) NLPS_K3(3, 2);
-      else if (law == 3) NLPS_K3(3, 3);
-      else if (law == 4) NLPS_K3(3, 4);
-      else if (!h->k3_per_law) NLPS_K3(3, -1);
-      else {
-        const int last = 31 - __builtin_clz((unsigned)h->law_present);
-        for (int l = 0; l <= NLPS_KLAW_FRICTIONAL; l++) {
-          if (!(h->law_present & (1 << l))) continue;
-          if (signal && l == last) arm_signal(h, td, 1);
-          if (l == 0) NLPS_K3F(3, 0);
-          else if (l == 1) NLPS_K3F(3, 1);
-          else if (l == 2) NLPS_K3F(3, 2);
-          else if (l == 3) NLPS_K3F(3, 3);
-          else NLPS_K3F(3, 4);
-        }
-      }
-    }
-#undef NLPS_K3F
-#undef NLPS_K3
-#undef NLPS_K3U
   };
-  K5Search ks;
-  ks.rank1 = h->rank1_d;
-  ks.bin = h->fuse_search == 1;
-  bool ks_made = false;
-  auto launch_k5 = [&](int cls) {
-    TileD td = tile_view(h, cls);
-    if (fuse && !ks_made) {  // (one TileCnt per step: it consumes the re-home flag of the adaptive re-sort)
-      ks.tc = tile_cnt(h, true);
-      ks.tc.count = h->tile_count2_d;  // (tile_count_d sizes the lists this very launch walks)
-      ks.tc.defer = (h->defer_ranks && ks.bin && node_lists(h)) ? 1 : 0;
-      h->ranks_deferred = ks.tc.defer != 0;
-      ks_made = true;
-    }
-#define NLPS_K5(NDv, LAWv)                                                                               \
-  do {                                                                                                   \
-    if (fuse)                                                                                            \
-      hipLaunchKernelGGL((k5_tile<NDv, LAWv, true>), dim3(h->ntw * K5_SPLIT), dim3(K5_BLK), 0, h->stream, h->P, h->g, \
-                         h->N, td, dt, gamma_nm, ks);                                                    \
-    else                                                                                                 \
-      hipLaunchKernelGGL((k5_tile<NDv, LAWv, false>), dim3(h->ntw * K5_SPLIT), dim3(K5_BLK), 0, h->stream, h->P, h->g, \
-                         h->N, td, dt, gamma_nm, ks);                                                    \
-  } while (0)
-    const int law = h->uniform_law;
-    if (ND == 2) {
-      if (law == 0 || law == 1) NLPS_K5(2, 0);
-      else NLPS_K5(2, 2);
-    } else {
-      if (law == 0 || law == 1) NLPS_K5(3, 0);
-      else NLPS_K5(3, 2);
-    }
-#undef NLPS_K5
-  };
-  auto launch_k3_lazy = [&](int cls, bool signal) {
+  auto launch_k3_lazy = [&](int cls, bool signal) {  // (lazy: one law, 0 .. NLPS_KLAW_FRICTIONAL)
     TileD td = tile_view(h, cls);
     if (signal) arm_signal(h, td, 1);
     ln.tile_count = h->tile_count2_d + h->tile0;  // (after search_and_lists, which swaps the two counter arrays)
-#define NLPS_K3L(NDv, LAWv)                                                                                              \
-  hipLaunchKernelGGL((k3_tile_lazy<NDv, LAWv>), dim3(h->ntw * K3_SPLIT), dim3(K3_BLK), 0, h->stream, h->P, h->g, h->N, td, \
-                     h->mats_d, h->prm, h->gstatus_d, ln)
-#define NLPS_K3LU(LAWv)                                                                                                  \
-  hipLaunchKernelGGL((k3_tile_lazy<3, LAWv, true>), dim3(h->ntw * K3_SPLIT), dim3(K3_BLK), 0, h->stream, h->P, h->g, h->N, td, \
-                     h->mats_d, h->prm, h->gstatus_d, ln)
-    const int law = h->uniform_law;
-    if (ND == 3 && h->nmats == 1 && law >= 1 && law <= 3) {  // one material: its constants by scalar loads (k3_body, UMAT)
-      if (law == 1) NLPS_K3LU(1);
-      else if (law == 2) NLPS_K3LU(2);
-      else NLPS_K3LU(3);
-    } else if (ND == 2) {
-      if (law == 0) NLPS_K3L(2, 0);
-      else if (law == 1) NLPS_K3L(2, 1);
-      else if (law == 2) NLPS_K3L(2, 2);
-      else if (law == 3) NLPS_K3L(2, 3);
-      else NLPS_K3L(2, 4);
+    if (one_mat) {
+      with_law_in<1, 3>(law, [&](auto L) {
+        hipLaunchKernelGGL((k3_tile_lazy<3, CT(L), true>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
+                           h->gstatus_d, ln);
+      });
     } else {
-      if (law == 0) NLPS_K3L(3, 0);
-      else if (law == 1) NLPS_K3L(3, 1);
-      else if (law == 2) NLPS_K3L(3, 2);
-      else if (law == 3) NLPS_K3L(3, 3);
-      else NLPS_K3L(3, 4);
+      with_nd(ND, [&](auto D) {
+        with_law(law, [&](auto L) {
+          hipLaunchKernelGGL((k3_tile_lazy<CT(D), CT(L)>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
+                             h->gstatus_d, ln);
+        });
+      });
     }
-#undef NLPS_K3L
-#undef NLPS_K3LU
   };
-  auto launch_k5_lazy = [&](int cls) {
+  K5Search ks;
+  ks.rank1 = h->rank1_d;
+  ks.bin = 1;
+  bool ks_made = false;
+  auto k5 = [&](int cls) {
     const TileD td = tile_view(h, cls);
-    if (!ks_made) {  // (one TileCnt per step: it consumes the re-home flag of the adaptive re-sort)
+    if (ride && !ks_made) {  // (one TileCnt per step: it consumes the re-home flag of the adaptive re-sort)
       ks.tc = tile_cnt(h, true);
-      ks.tc.count = h->tile_count2_d;
-      ks.tc.defer = (h->defer_ranks && ks.bin && node_lists(h)) ? 1 : 0;
+      ks.tc.count = h->tile_count2_d;  // (tile_count_d sizes the lists this very launch walks)
+      ks.tc.defer = node_lists(h) ? 1 : 0;
       h->ranks_deferred = ks.tc.defer != 0;
       ks_made = true;
     }
-#define NLPS_K5L(NDv, LAWv)                                                                                             \
-  hipLaunchKernelGGL((k5_tile_lazy<NDv, LAWv>), dim3(h->ntw * K5_SPLIT), dim3(K5_BLK), 0, h->stream, h->P, h->g, h->N, td, \
-                     dt, gamma_nm, ks, ln, h->gstatus_d)
-    const int law = h->uniform_law;
-    if (ND == 2) {
-      if (law == 0 || law == 1) NLPS_K5L(2, 0);
-      else NLPS_K5L(2, 2);
-    } else {
-      if (law == 0 || law == 1) NLPS_K5L(3, 0);
-      else NLPS_K5L(3, 2);
-    }
-#undef NLPS_K5L
+    const dim3 grid(h->ntw * K5_SPLIT), blk(K5_BLK);
+    with_nd(ND, [&](auto D) {
+      // K5 exists in two forms: LAW = 0 serves laws 0 and 1, LAW = 2 every other law and the cloud of several
+      with_bool(law == 0 || law == 1, [&](auto L01) {
+        constexpr int LAW = CT(L01) ? 0 : 2;
+        if (lazy) {
+          hipLaunchKernelGGL((k5_tile_lazy<CT(D), LAW>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, dt, gamma_nm, ks, ln,
+                             h->gstatus_d);
+        } else {
+          with_bool(ride, [&](auto SEARCH) {
+            hipLaunchKernelGGL((k5_tile<CT(D), LAW, CT(SEARCH)>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, dt, gamma_nm, ks);
+          });
+        }
+      });
+    });
   };
   auto k3 = [&](int cls, bool signal = false) {
     if (lazy) launch_k3_lazy(cls, signal);
     else launch_k3(cls, signal);
-  };
-  auto k5 = [&](int cls) {
-    if (lazy) launch_k5_lazy(cls);
-    else launch_k5(cls);
   };
   h->nodal_stale = false;
   // S1 + S2 (ev[1] is recorded between the search and the lists/Newton/P2G kernel; the nodal accumulators of
@@ -4393,8 +4295,8 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   }  // !ov2
   h->P.flip ^= 1;  // F_n <- F_n+1, b_e,n <- b_e,n+1 by renaming
   h->rolled = true;
-  h->searched = fuse;                      // K5 has updated the closest nodes for the positions it wrote ...
-  h->ahead = fuse && h->fuse_search == 1;  // ... and binned the particles for the next step
+  h->searched = ride;  // K5 has updated the closest nodes for the positions it wrote ...
+  h->ahead = ride;     // ... and binned the particles for the next step
   if (h->timing) {
     HIPCHK(hipEventRecord(h->ev[6], h->stream));
     // calibration bracket: a kernel of K3's grid and argument block that does nothing; what it reads is the part of
@@ -4700,56 +4602,31 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
     TileD td = tile_view(h);
     td.slab = nullptr;  // (level-B semantics: atomics also in deterministic mode, like kb_fint_tile)
     const dim3 grid(h->ntw * K3_SPLIT), blk(K3_BLK);
-#define NLPS_K3R(NDv, LAWv)                                                                                          \
-  hipLaunchKernelGGL((k3_tile<NDv, LAWv, 3>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm, h->gstatus_d, \
-                     (const double*)nullptr)
     const int law = h->uniform_law;
-    // a cloud of several laws: one launch per law present of the kernel compiled for that law, every workgroup compacting
-    // its tile's particles of that law first (FILT, as the explicit step's per-law launches)
-#define NLPS_K3RF(NDv, LAWv)                                                                                          \
-  hipLaunchKernelGGL((k3_tile<NDv, LAWv, 3, true>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm, \
-                     h->gstatus_d, (const double*)nullptr)
     if (law < 0) {
-      for (int l = 0; l <= NLPS_KLAW_FRICTIONAL; l++) {
-        if (!(h->law_present & (1 << l))) continue;
-        if (ND == 2) {
-          if (l == 0) NLPS_K3RF(2, 0);
-          else if (l == 1) NLPS_K3RF(2, 1);
-          else if (l == 2) NLPS_K3RF(2, 2);
-          else if (l == 3) NLPS_K3RF(2, 3);
-          else NLPS_K3RF(2, 4);
-        } else {
-          if (l == 0) NLPS_K3RF(3, 0);
-          else if (l == 1) NLPS_K3RF(3, 1);
-          else if (l == 2) NLPS_K3RF(3, 2);
-          else if (l == 3) NLPS_K3RF(3, 3);
-          else NLPS_K3RF(3, 4);
-        }
-      }
-    } else
-#define NLPS_K3RU(LAWv)                                                                                              \
-  hipLaunchKernelGGL((k3_tile<3, LAWv, 3, false, K3_BLK, true>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm, \
-                     h->gstatus_d, (const double*)nullptr)
-    if (ND == 3 && h->nmats == 1 && law >= 1 && law <= 3) {  // one material (k3_body, UMAT)
-      if (law == 1) NLPS_K3RU(1);
-      else if (law == 2) NLPS_K3RU(2);
-      else NLPS_K3RU(3);
-    } else if (ND == 2) {
-      if (law == 0) NLPS_K3R(2, 0);
-      else if (law == 1) NLPS_K3R(2, 1);
-      else if (law == 2) NLPS_K3R(2, 2);
-      else if (law == 3) NLPS_K3R(2, 3);
-      else NLPS_K3R(2, 4);
+      // a cloud of several laws: one launch per law present of the kernel compiled for that law, every workgroup compacting
+      // its tile's particles of that law first (FILT, as the explicit step's per-law launches)
+      for_each_law_present(h->law_present, [&](int l, bool) {
+        with_nd(ND, [&](auto D) {
+          with_law(l, [&](auto L) {
+            hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 3, true>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
+                               h->gstatus_d, (const double*)nullptr);
+          });
+        });
+      });
+    } else if (ND == 3 && h->nmats == 1 && law >= 1 && law <= 3) {  // one material (k3_body, UMAT)
+      with_law_in<1, 3>(law, [&](auto L) {
+        hipLaunchKernelGGL((k3_tile<3, CT(L), 3, false, K3_BLK, true>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
+                           h->prm, h->gstatus_d, (const double*)nullptr);
+      });
     } else {
-      if (law == 0) NLPS_K3R(3, 0);
-      else if (law == 1) NLPS_K3R(3, 1);
-      else if (law == 2) NLPS_K3R(3, 2);
-      else if (law == 3) NLPS_K3R(3, 3);
-      else NLPS_K3R(3, 4);
+      with_nd(ND, [&](auto D) {
+        with_law(law, [&](auto L) {
+          hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 3>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
+                             h->gstatus_d, (const double*)nullptr);
+        });
+      });
     }
-#undef NLPS_K3R
-#undef NLPS_K3RU
-#undef NLPS_K3RF
   }
   HIPCHK(hipGetLastError());
   if (h->timing) HIPCHK(hipEventRecord(h->ev[3], h->stream));
@@ -4813,16 +4690,11 @@ extern "C" int nlps_gpu_tangent_assemble(nlps_gpu* h, long long* nnz) {
     const int ngrid = std::min(np, h->g.nnodes);  // upper bound of the number of groups; surplus workgroups exit
     // a cloud of Neo-Hookean particles only: the upper half of every row, the rest by symmetry in nlps_gpu_tangent_coo
     h->ktan_sym = h->tangent_symmetric && h->uniform_law == NLPS_MAT_NEO_HOOKEAN;
-    if (ND == 2)
-      hipLaunchKernelGGL(k_tangent_nh_grouped<2>, dim3(ngrid), dim3(TAN_NT), 0, h->stream, h->P, h->g, h->mats_d, np, h->skey2_d,
-                         h->sval2_d, h->khead_d, h->kng_d, h->kst_d, h->ktouched_d, h->gstatus_d, h->ktan_sym ? 1 : 0);
-    else
-      hipLaunchKernelGGL(k_tangent_nh_grouped<3>, dim3(ngrid), dim3(TAN_NT), 0, h->stream, h->P, h->g, h->mats_d, np, h->skey2_d,
-                         h->sval2_d, h->khead_d, h->kng_d, h->kst_d, h->ktouched_d, h->gstatus_d, h->ktan_sym ? 1 : 0);
+    LAUNCH_ND_BLK(k_tangent_nh_grouped<2>, k_tangent_nh_grouped<3>, ngrid, TAN_NT, h->P, h->g, h->mats_d, np, h->skey2_d, h->sval2_d,
+                  h->khead_d, h->kng_d, h->kst_d, h->ktouched_d, h->gstatus_d, h->ktan_sym ? 1 : 0);
   } else if (np > 0) {
     h->ktan_sym = false;
-    if (ND == 2) hipLaunchKernelGGL(k_tangent_nh<2>, dim3(np), dim3(64), 0, h->stream, h->P, h->g, h->mats_d, h->kst_d, h->ktouched_d, h->gstatus_d);
-    else hipLaunchKernelGGL(k_tangent_nh<3>, dim3(np), dim3(64), 0, h->stream, h->P, h->g, h->mats_d, h->kst_d, h->ktouched_d, h->gstatus_d);
+    LAUNCH_ND_BLK(k_tangent_nh<2>, k_tangent_nh<3>, np, 64, h->P, h->g, h->mats_d, h->kst_d, h->ktouched_d, h->gstatus_d);
   }
   LAUNCH_ND((k_tangent_count<2>), (k_tangent_count<3>), ((int)nn + 3) / 4, (int)nn, h->ktouched_d, h->kcnt_d);  // (one wave per row node)
   HIPCHK(hipGetLastError());
@@ -4963,10 +4835,7 @@ extern "C" int nlps_gpu_tangent_operator(nlps_gpu* h, double alpha_1, const doub
   }
   if (np > 0) {
     const int nb = (np + TANOP_SETUP_NT - 1) / TANOP_SETUP_NT;
-    if (ND == 2)
-      hipLaunchKernelGGL(k_tanop_setup<2>, dim3(nb), dim3(TANOP_SETUP_NT), 0, h->stream, h->P, h->g, h->mats_d, h->top_d, np, h->gstatus_d);
-    else
-      hipLaunchKernelGGL(k_tanop_setup<3>, dim3(nb), dim3(TANOP_SETUP_NT), 0, h->stream, h->P, h->g, h->mats_d, h->top_d, np, h->gstatus_d);
+    LAUNCH_ND_BLK(k_tanop_setup<2>, k_tanop_setup<3>, nb, TANOP_SETUP_NT, h->P, h->g, h->mats_d, h->top_d, np, h->gstatus_d);
   }
   HIPCHK(hipGetLastError());
   if (check_status(h, ST_NEWTON | ST_CONSTITUTIVE, "nlps_gpu_tangent_operator()")) return 1;  // (synchronises)
@@ -4999,12 +4868,7 @@ static int tanop_product(nlps_gpu* h, const double* v, double* y, const KspPc* p
   }
   if (h->top_np > 0) {
     const TileD td = tile_view(h);
-    if (ND == 2)
-      hipLaunchKernelGGL(k_tanop_apply<2>, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, (const double*)h->top_d, h->top_np,
-                         (const double*)xg, yg);
-    else
-      hipLaunchKernelGGL(k_tanop_apply<3>, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, (const double*)h->top_d, h->top_np,
-                         (const double*)xg, yg);
+    LAUNCH_ND(k_tanop_apply<2>, k_tanop_apply<3>, h->ntw, h->P, h->g, td, (const double*)h->top_d, h->top_np, (const double*)xg, yg);
   }
   HIPCHK(hipGetLastError());
   if (halo(h, yg, ND, 8, 0)) return 1;
@@ -5040,12 +4904,7 @@ static int tanop_bdiag(nlps_gpu* h, double* out) {
   int st = hipMemsetAsync(h->top_g, 0, (size_t)nn * E * sizeof(double), h->stream) != hipSuccess;
   if (!st && h->top_np > 0) {
     const TileD td = tile_view(h);
-    if (ND == 2)
-      hipLaunchKernelGGL(k_tanop_bdiag<2>, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, (const double*)h->top_d, h->top_np,
-                         h->top_g);
-    else
-      hipLaunchKernelGGL(k_tanop_bdiag<3>, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, td, (const double*)h->top_d, h->top_np,
-                         h->top_g);
+    LAUNCH_ND(k_tanop_bdiag<2>, k_tanop_bdiag<3>, h->ntw, h->P, h->g, td, (const double*)h->top_d, h->top_np, h->top_g);
     st = hipGetLastError() != hipSuccess;
   }
   if (!st) st = halo(h, h->top_g, E, 8, 0);

@@ -1745,7 +1745,8 @@ __global__ void k_slab_gather(int a0, int an, int b0, int bn, GridD g, TileD td,
 struct K5Search {
   const uint8_t* rank1;  // chain positions of the 3^d candidates per boundary class (get_closest_node tie-break)
   TileCnt tc;
-  int bin;  // 0: closest-node update only (I0n); the seeds and bins are left to k_search in its adopt form
+  int bin;  // 0: closest-node update only (I0n); the seeds and bins are left to k_search in its adopt form.  (The host always
+            // sets 1 now; the field goes with a later change of the kernels that read it.)
 };
 template <int ND, int LAW, bool SEARCH>
 __device__ __forceinline__ void k5_body(const PView& P, const GridD& g, const NView& N, const TileD& td, double dt,

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Developer tool: builds a variant of the library with extra compiler flags (kernel experiments).
-# -DNLPS_DEV=1: the only build that reads NLPS_* environment switches and accepts the NLPS_ABL_* / NLPS_PHASE_TIMING macros.
+# -DNLPS_DEV=1: the only build that reads the environment switches (NLPS_LAZY_NODAL, NLPS_ADAPTIVE_RESORT) and accepts the NLPS_ABL_* / NLPS_PHASE_TIMING macros.
 #   tools/build_variant.sh NAME [-DNLPS_...=v ...]   ->  build/exp/lib_NAME.so   (run with NLPS_GPU_LIB=... tools/kbench.py)
 set -e
 cd "$(dirname "$0")/.."

@@ -21,12 +21,11 @@ ap.add_argument("--cells", type=int, default=50)
 ap.add_argument("--law", default="nh")
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--phases", action="store_true")
-ap.add_argument("--no-order", action="store_true")
 ap.add_argument("--det", action="store_true", help="deterministic mode")
 ap.add_argument("--stir", type=int, default=0, help="untimed shear steps first (DESIGN.md stirred cloud)")
 ap.add_argument("--resort", action="store_true", help="one periodic re-sort of the fused step before the timed steps")
 ap.add_argument("--adaptive", type=float, default=0.0, help="adaptive re-sort budget (also during the stir and the timed steps)")
-ap.add_argument("--opt", action="append", default=[], help="NAME=VALUE for nlps_gpu_debug_option (fuse_search, lazy_nodal, ...)")
+ap.add_argument("--opt", action="append", default=[], help="NAME=VALUE for nlps_gpu_debug_option (lazy_nodal, tangent_symmetric)")
 ap.add_argument("--tag", default=os.path.basename(os.environ.get("NLPS_GPU_LIB", "product")))
 a = ap.parse_args()
 nlps = importlib.import_module("nl-partsol_amd.nlps")
@@ -61,9 +60,6 @@ nst = a.steps + 10
 S = nlps.Solver(3, case["grid_n"], case["origin"], case["h"], case["cloud"], case["materials"], nsteps=nst)
 nodes = synth.plane_nodes(case["grid_n"], 2, 0)
 bcs = nlps.BccSet([{"nodes": nodes, "dim": 3, "dir": np.ones((3, nst), dtype=np.int32), "value": np.zeros((3, nst))}])
-if a.no_order:
-    S.L.nlps_gpu_debug_set_tile_ordering.argtypes = [C.c_void_p, C.c_int]
-    S.L.nlps_gpu_debug_set_tile_ordering(S.h, 0)
 if a.det:
     S.set_deterministic(True)
 for kv in a.opt:
