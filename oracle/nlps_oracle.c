@@ -1880,6 +1880,13 @@ static void stiffness_density_neo_hookean(double *Kd, int ndim, const double *dN
       Kd[i * ndim + j] = c0 * dNa_n1[i] * dNb_n1[j] + G * lenght_0 * (i == j) + c1 * dNa_n1[j] * dNb_n1[i];
 }
 
+/* exported for tests/test_reference_parity.py: one pair of nodes against the reference's own function */
+void orc_stiffness_density_neo_hookean(double *Kd, int ndim, const double *dNa_n1, const double *dNb_n1,
+                                       const double *dNa_n, const double *dNb_n, const double *F_n, double J,
+                                       const orc_material *mat) {
+  stiffness_density_neo_hookean(Kd, ndim, dNa_n1, dNb_n1, dNa_n, dNb_n, F_n, J, mat);
+}
+
 /* Spectral stiffness density shared by compute_stiffness_density_Hencky__Constitutive__ (Hyperelastic/Hencky.c:98-229:
  * b = F_n1 F_n1^T, moduli AA = [lambda + 2G on the diagonal, lambda elsewhere]) and
  * compute_stiffness_elastoplastic__Constitutive__ (Plasticity/Elastoplastic-Tangent-Matrix.c:42-163: b = b_e,n+1,

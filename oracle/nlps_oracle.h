@@ -5,15 +5,12 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library, and only as the
  * checker / CPU baseline.  The product path (nl-partsol_amd/) never links, imports or calls it.
  *
- * PARITY UNPINNED: the reference ships no golden vectors or asserting tests
- * for this path, and its sources on the path include <lapacke.h> and link LAPACK
- * (nl-partsol/src/Matlib/MatrixOp.c:13, Matlib/TensorLib.c:13, Particles/compute-Strains.c:13,
- * Constitutive/Plasticity/Drucker-Prager.h:25), neither of which exists in the build image, so the
- * reference cannot be compiled here without writing stand-ins.  This file is therefore a careful
- * plain-C restatement of the reference's algorithm, function by function, each citing the reference
- * file:line it follows; the third-party arithmetic it replaces (LAPACK dsyev / dgetrf+dgetri, the
- * pinned dependency is "whatever LAPACK the host links", not vendored) is restated in closed form /
- * cyclic Jacobi and is cross-checked in tests against scipy's LAPACK (same routines).
+ * PARITY: the reference ships no golden vectors or asserting tests for this path
+ * (SURVEY.md section 4).  This file is a plain-C restatement of the reference's algorithm, function by function, each
+ * citing the reference file:line it follows; the third-party arithmetic it replaces (LAPACK dsyev / dgetrf+dgetri) is
+ * restated in closed form / cyclic Jacobi.  In 2-D it is held to the reference's own objects, built unmodified against
+ * scipy's LAPACK (oracle/orc.py::build_ref, oracle/ref_bridge.c), by tests/test_reference_parity.py; 3-D rests on the
+ * code shared with 2-D, because the reference's 3-D TensorLib.c does not compile.
  *
  * All paths are relative to /root/reference/nl-partsol/src unless noted.
  */
@@ -146,6 +143,9 @@ int orc_nodal_traction_forces(double *R, const orc_particles *P, const orc_mesh 
                               const double *val, double thickness, const double *area0);
 int orc_stiffness_density_spectral(double *Kd, int ndim, const double *dN_alpha_n1, const double *dN_beta_n1,
                                    const double *b, const double *Cmod, const double *Stress);
+void orc_stiffness_density_neo_hookean(double *Kd, int ndim, const double *dNa_n1, const double *dNb_n1,
+                                       const double *dNa_n, const double *dNb_n, const double *F_n, double J,
+                                       const orc_material *mat);
 int orc_tangent_matrix(double *K, int *pattern, double alpha_1, const double *lumped_mass, const orc_particles *P,
                        const orc_mesh *M, const orc_material *mats, const int *nodes2mask, const int *dofs2mask,
                        int nactive);

@@ -1,8 +1,8 @@
 """ctypes binding of the CPU oracle (oracle/nlps_oracle.c).
 
 TEST INFRASTRUCTURE ONLY — imported by tests/, __graft_entry__.smoke() and bench.py's
-cpu_baseline leg, never by the product package (nl-partsol_amd/).  PARITY UNPINNED: see
-oracle/nlps_oracle.h and DESIGN.md.
+cpu_baseline leg, never by the product package (nl-partsol_amd/).  Pinned in 2-D against the reference's own objects
+(build_ref() below, tests/test_reference_parity.py).
 """
 import ctypes as C
 import os
@@ -88,6 +88,91 @@ def build(force=False):
         if name == ("libnlps_oracle_fast.so" if _FAST else "libnlps_oracle.so"):
             out = so
     return out
+
+
+REF_ROOT = "/root/reference/nl-partsol"
+REF_DIR = os.path.join(_HERE, "_ref")
+REF_LIB = os.path.join(REF_DIR, "libnlps_ref2d.so")
+_REF_SUBDIRS = ("Matlib", "Nodes", "Particles", "Constitutive")
+_REF_CFLAGS = ["-O2", "-fPIC", "-w", "-fno-fast-math", "-ffp-contract=off", "-DUSE_PLAINSTRAIN",
+               "-Ddgetrf_=scipy_dgetrf_", "-Ddgetri_=scipy_dgetri_"]
+
+
+def build_ref(force=False, jobs=None):
+    """Builds oracle/_ref/libnlps_ref2d.so: the reference's own 2-D sources of src/{Matlib,Nodes,Particles,Constitutive},
+    unmodified, plus oracle/ref_bridge.c, against the LAPACK(E) of scipy's bundled OpenBLAS (oracle/ref_shim/lapacke.h
+    renames the calls).  Returns the library's path, or None when the reference tree or the OpenBLAS is absent.
+    Nothing under oracle/_ref/ is committed; BUILD_INFO.json there records what went in."""
+    import glob
+    import json
+    from concurrent.futures import ThreadPoolExecutor
+    src_root = os.path.join(REF_ROOT, "src")
+    if not os.path.isdir(src_root):
+        return None
+    try:
+        import scipy
+    except ImportError:
+        return None
+    libs_dir = os.path.normpath(os.path.join(os.path.dirname(scipy.__file__), "..", "scipy.libs"))
+    blas = sorted(glob.glob(os.path.join(libs_dir, "libscipy_openblas*.so*")))
+    if not blas:
+        return None
+    bridge = os.path.join(_HERE, "ref_bridge.c")
+    shim = os.path.join(_HERE, "ref_shim")
+    info_path = os.path.join(REF_DIR, "BUILD_INFO.json")
+    sources = []
+    for sub in _REF_SUBDIRS:
+        sources += sorted(glob.glob(os.path.join(src_root, sub, "**", "*.c"), recursive=True))
+    parser = os.path.join(src_root, "InOutFun", "Parser.c")
+    gcc_version = subprocess.run(["gcc", "--version"], capture_output=True, text=True).stdout.splitlines()[0]
+    # what the library is made from: up to date only if BUILD_INFO.json records exactly this and nothing is newer
+    inputs = sources + [p for p in (parser,) if os.path.exists(p)] + [bridge, os.path.join(shim, "lapacke.h")]
+    recipe = {"reference_files": [os.path.relpath(p, REF_ROOT) for p in inputs if p.startswith(REF_ROOT)],
+              "cflags": _REF_CFLAGS, "openblas": os.path.basename(blas[-1]), "gcc": gcc_version}
+    if not force and os.path.exists(REF_LIB) and os.path.exists(info_path):
+        try:
+            with open(info_path) as f:
+                info = json.load(f)
+        except ValueError:
+            info = {}
+        if info.get("recipe") == recipe and os.path.getmtime(REF_LIB) >= max(os.path.getmtime(p) for p in inputs):
+            return REF_LIB
+    obj_dir = os.path.join(REF_DIR, "obj")
+    os.makedirs(obj_dir, exist_ok=True)
+    inc = ["-I" + shim, "-I" + src_root]
+
+    def compile_one(src, extra=()):
+        name = os.path.relpath(src, REF_ROOT) if src.startswith(REF_ROOT) else os.path.basename(src)
+        obj = os.path.join(obj_dir, name.replace(os.sep, "_") + ".o")
+        r = subprocess.run(["gcc", "-c", *_REF_CFLAGS, *extra, *inc, src, "-o", obj], capture_output=True, text=True)
+        return obj, r.returncode, r.stderr
+
+    jobs = max(1, min(16, jobs or os.cpu_count() or 1))
+    with ThreadPoolExecutor(jobs) as ex:
+        done = list(ex.map(compile_one, sources))
+    failed = [(s, err) for s, (_, rc, err) in zip(sources, done) if rc]
+    if failed:
+        raise RuntimeError("reference sources failed to compile:\n" + "\n".join(f"{s}\n{e}" for s, e in failed))
+    objs = [o for o, _, _ in done]
+    # `parse` (InOutFun/Parser.c) is all the readers under src/Nodes need from outside the four directories
+    bridge_flags = []
+    compiled = [os.path.relpath(s, REF_ROOT) for s in sources]
+    if os.path.exists(parser):
+        o, rc, _ = compile_one(parser)
+        if rc == 0:
+            objs.append(o)
+            bridge_flags = ["-DREF_HAVE_PARSER"]
+            compiled.append(os.path.relpath(parser, REF_ROOT))
+    o, rc, err = compile_one(bridge, bridge_flags)
+    if rc:
+        raise RuntimeError("oracle/ref_bridge.c failed to compile:\n" + err)
+    objs.append(o)
+    link = ["gcc", "-shared", "-o", REF_LIB, *objs, blas[-1], "-Wl,-rpath," + libs_dir, "-lm"]
+    subprocess.check_call(link)
+    with open(info_path, "w") as f:
+        json.dump({"reference_files": compiled, "bridge": "oracle/ref_bridge.c", "cflags": _REF_CFLAGS + bridge_flags,
+                   "openblas": os.path.basename(blas[-1]), "gcc": gcc_version, "jobs": jobs, "recipe": recipe}, f, indent=1)
+    return REF_LIB
 
 
 def lib():
@@ -439,6 +524,17 @@ def stiffness_density_spectral(dN_alpha_n1, dN_beta_n1, b, Cmod, stress, ndim):
     a = [np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (dN_alpha_n1, dN_beta_n1, b, Cmod, stress)]
     st = f(_d(out), ndim, *[_d(x) for x in a])
     assert st == 0
+    return out.reshape(ndim, ndim)
+
+
+def stiffness_density_neo_hookean(dNa_n1, dNb_n1, dNa_n, dNb_n, F_n, J, mat, ndim):
+    """compute_stiffness_density_Neo_Hookean, Neo-Hookean.c:89-141, for one pair of nodes (row-major d x d)."""
+    out = np.zeros(ndim * ndim)
+    f = lib().orc_stiffness_density_neo_hookean
+    f.argtypes = [_dp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_double, C.POINTER(Material)]
+    f.restype = None
+    a = [np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (dNa_n1, dNb_n1, dNa_n, dNb_n, F_n)]
+    f(_d(out), ndim, *[_d(x) for x in a], float(J), C.byref(mat))
     return out.reshape(ndim, ndim)
 
 
