@@ -55,100 +55,9 @@ struct ParamsD {
 
 #define NLPS_TOL_NR 10E-6  // Macros.h:40
 
-// tunables of the row/plane loops (measured at 1 M particles)
-#ifndef NLPS_JUNROLL_MOMENTS
-#define NLPS_JUNROLL_MOMENTS 5  // rows per iteration of the moments row loop (1 = real loop, 5 = unrolled)
-#endif
-#ifndef NLPS_K2_WAVES
-#define NLPS_K2_WAVES 3  // 168 VGPRs + 132 B of scratch per lane; the spill-free 2-wave build is ~7 % slower
-#endif
-// The reference warm-starts the lambda Newton iteration from the previous step's lambda (LME.c:998) and
-// stops at |r| <= TOL_wrapper_LME = 1e-10, so its lambda carries a solver error of ~1e-10/|J| that
-// depends on the iteration path.  Starting from the extrapolation 2 lambda_n - lambda_(n-1) saves about
-// one of four evaluations (K2 0.39 -> 0.33 ms) and converges to the same root, but to a DIFFERENT point
-// of that tolerance ball (measured: lambda differs by 1.5e-8 relative from the reference path).  Parity
-// with the reference path is kept: OFF by default.
-#ifndef NLPS_LAMBDA_EXTRAPOLATE
-#define NLPS_LAMBDA_EXTRAPOLATE 0
-#endif
-// The last pass of the lambda Newton iteration only confirms |r| <= TOL_wrapper_LME; when the bound on the next
-// residual says it will, it is replaced by a second-order update of Z and of the separable factors (k2_tile)
-#ifndef NLPS_NEWTON_PREDICT_LAST
-#define NLPS_NEWTON_PREDICT_LAST 1
-#endif
-#ifndef NLPS_JUNROLL_K3
-#define NLPS_JUNROLL_K3 5  // unrolled gather rows: the LDS reads of the next rows overlap this row's arithmetic (-3 %)
-#endif
-#ifndef NLPS_JUNROLL_K5
-#define NLPS_JUNROLL_K5 5
-#endif
-#ifndef NLPS_JUNROLL_SCATTER
-#define NLPS_JUNROLL_SCATTER 5
-#endif
-#ifndef NLPS_K3_WAVES_2D
-#define NLPS_K3_WAVES_2D 2
-#endif
-#ifndef NLPS_K2_WAVES_2D
-#define NLPS_K2_WAVES_2D 3
-#endif
-// plane loops (k): 1 = real loop (compact code; ez5[k], lz5[k] and the plane bits are selected at run time),
-// 5 = unrolled
-#ifndef NLPS_KUNROLL_MASK
-#define NLPS_KUNROLL_MASK 5  // K2 -2 %; the others measured: K2 scatter / K3 scatter +-1 %, K5 +14 %, K3 gather and the moments spill
-#endif
-#ifndef NLPS_KUNROLL_K2S
-#define NLPS_KUNROLL_K2S 1
-#endif
-#ifndef NLPS_KUNROLL_K3G
-#define NLPS_KUNROLL_K3G 1
-#endif
-#ifndef NLPS_KUNROLL_K3S
-#define NLPS_KUNROLL_K3S 1
-#endif
-#ifndef NLPS_KUNROLL_K5
-#define NLPS_KUNROLL_K5 1
-#endif
-#ifndef NLPS_KUNROLL_MOM
-#define NLPS_KUNROLL_MOM 1
-#endif
-#ifndef NLPS_SCATTER_POP
-#define NLPS_SCATTER_POP 1  // scatter loops of K2 / K3: membership by pop_member (one vector instruction per node)
-#endif
-#ifndef NLPS_JACOBI_RSQ
-#define NLPS_JACOBI_RSQ 1  // sym_eigen: the Jacobi rotation from two reciprocal square roots (no division, no sqrt)
-#endif
-#ifndef NLPS_LAW_CONTRACT
-#define NLPS_LAW_CONTRACT 1  // a * b + c contracted to fma inside the constitutive laws and their 3 x 3 helpers (the library is built -ffp-contract=off for the index maps)
-#endif
-#if NLPS_LAW_CONTRACT
+// a * b + c contracted to fma inside the constitutive laws and their 3 x 3 helpers (the library is built
+// -ffp-contract=off for the index maps)
 #define NLPS_FP_CONTRACT _Pragma("clang fp contract(fast)")
-#else
-#define NLPS_FP_CONTRACT
-#endif
-#ifndef NLPS_MASK_BY_COLUMNS
-#define NLPS_MASK_BY_COLUMNS 1  // K2's radius test by (i, j) columns with add-with-carry bit assembly (nlps_tile_kernels.hpp)
-#endif
-#ifndef NLPS_JUNROLL_MASK
-#define NLPS_JUNROLL_MASK 5  // neighbourhood-mask rows unrolled: no run-time index into ly2[] (8 selects per row); K2 0.294 -> 0.282 ms
-#endif
-#ifndef NLPS_K3_TWOPASS
-#define NLPS_K3_TWOPASS 1  // K3: gather pass and moments pass separately (see k3_tile)
-#endif
-#ifndef NLPS_K3_DIRECT
-#define NLPS_K3_DIRECT 1  // K3 gather without plane partial sums (see k3_tile)
-#endif
-#ifndef NLPS_K3_WAVES_NH
-#define NLPS_K3_WAVES_NH 3  // fused 3-D Neo-Hookean K3 (two-pass gather): 0.294 -> 0.267 ms at 1 M particles
-#endif
-#ifndef NLPS_K3_WAVES_HENCKY
-#define NLPS_K3_WAVES_HENCKY 3
-#endif
-#ifndef NLPS_K3_WAVES_DP
-#define NLPS_K3_WAVES_DP 2
-#endif
-#ifndef NLPS_K3_WAVES
-#define NLPS_K3_WAVES 2  // Hencky / Drucker-Prager need > 256 VGPRs otherwise (1 wave/SIMD: 0.54 -> 0.37 ms at 2)
-#endif
 
 __device__ __forceinline__ double dsqr(double a) { return a == 0.0 ? 0.0 : a * a; }  // Macros.h:49-50
 
@@ -267,10 +176,7 @@ __device__ __forceinline__ bool rcond_below_gate(const double* A) {
   const double mq = m + qmax;
   const double lhs = (N == 3) ? m * m * m : m * m;
   const double rhs = 2.0e-8 * anorm * nl * ((N == 3) ? mq * mq : mq);
-  bool sure = (lhs >= rhs) && (m > 1.0e-90) && (anorm < 1.0e90);
-#if NLPS_RCOND_EXACT
-  sure = false;
-#endif
+  const bool sure = (lhs >= rhs) && (m > 1.0e-90) && (anorm < 1.0e90);
   if (__builtin_amdgcn_ballot_w64(!sure) == 0ull) return false;  // wave-uniform: every lane is surely above the gate
   return rcond_ref<N>(A) < 1E-8;
 }
@@ -280,8 +186,8 @@ __device__ __forceinline__ bool rcond_below_gate(const double* A) {
 template <int N>
 __device__ __forceinline__ void sym_eigen(double* w, double* v, const double* Ain) {
   NLPS_FP_CONTRACT
-  // cyclic Jacobi on the upper triangle (Rutishauser's update formulas): per rotation one sqrt, one
-  // division and one reciprocal square root; the rotated pair is annihilated exactly.
+  // cyclic Jacobi on the upper triangle (Rutishauser's update formulas): per rotation two reciprocal
+  // square roots; the rotated pair is annihilated exactly.
   double d[N], o[N == 3 ? 3 : 1];  // diagonal; off-diagonals o[0] = a01, o[1] = a02, o[2] = a12
 #pragma unroll
   for (int i = 0; i < N; i++) {
@@ -309,17 +215,11 @@ __device__ __forceinline__ void sym_eigen(double* w, double* v, const double* Ai
       const double apq = o[r];
       if (apq != 0.0) {
         const double df = d[q] - d[p];
-#if NLPS_JACOBI_RSQ
         // the small-angle rotation from two reciprocal square roots (no division, no sqrt): with h = sqrt(df^2 + 4 apq^2),
         // cos 2 theta = |df| / h, so c^2 = (1 + |df| / h) / 2 in [1/2, 1], s = sgn(df) apq / (h c), t = s / c
         const double rh = rsqrt(fma(df, df, 4.0 * apq * apq));
         const double c2 = fma(0.5 * fabs(df), rh, 0.5), ic = rsqrt(c2);
         const double c = c2 * ic, sn = (df >= 0.0 ? apq : -apq) * rh * ic, t = sn * ic;
-#else
-        // t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)), theta = df / (2 apq)
-        const double t = (df >= 0.0 ? 2.0 : -2.0) * apq / (fabs(df) + sqrt(fma(df, df, 4.0 * apq * apq)));
-        const double c = rsqrt(fma(t, t, 1.0)), sn = t * c;
-#endif
         d[p] -= t * apq;
         d[q] += t * apq;
         o[r] = 0.0;
@@ -1233,28 +1133,10 @@ __device__ __forceinline__ double masked_weight_pop(double e, unsigned& b) {
   const int hi = __builtin_amdgcn_inverse_ballot_w64(m) ? __double2hiint(e) : 0;
   return __hiloint2double(hi, __double2loint(e));
 }
-#ifndef NLPS_MASK_POP
-#define NLPS_MASK_POP 1
-#endif
 __device__ __forceinline__ void masked_row(double* m, const double* ex, unsigned bits) {
-#if NLPS_MASK_POP
   unsigned b = bits << 27;  // bit 4 of the row first
 #pragma unroll
   for (int i = 4; i >= 0; i--) m[i] = masked_weight_pop(ex[i], b);
-#else
-#pragma unroll
-  for (int i = 0; i < 5; i++) m[i] = masked_weight(ex[i], bits, i);
-#endif
-}
-
-// The same with an EXACT zero for a non-member (both words cleared): for values that are stored or accumulated on
-// their own, where a denormal left-over would survive (the window scatters in their branch-free form).
-#ifndef NLPS_SCATTER_BRANCHFREE
-#define NLPS_SCATTER_BRANCHFREE 0
-#endif
-__device__ __forceinline__ double masked_zero(double e, unsigned bits, int i) {
-  const int m = __builtin_amdgcn_sbfe((int)bits, (unsigned)i, 1u);
-  return __hiloint2double(__double2hiint(e) & m, __double2loint(e) & m);
 }
 
 // Membership test of the scatter loops in ONE vector instruction per stencil node: the 25 bits of a plane sit at the top
@@ -1266,24 +1148,6 @@ __device__ __forceinline__ bool pop_member(unsigned& b) {
   unsigned long long m;
   asm("v_add_co_u32 %0, %1, %0, %0" : "+v"(b), "=s"(m));
   return __builtin_amdgcn_inverse_ballot_w64(m);
-}
-
-// Wave-uniform test "does any lane of the wave hold a member in this stencil row".  The particles of a wave
-// come from one tile and one corner class (k_sort_keys), so their 125-bit masks nearly coincide and a row no
-// lane uses can be skipped with one scalar branch; a skipped row would only have added exact zeros, so results
-// do not change by a bit.  OFF by default: with gamma = 3 and the GramsBox h_avg (1.42 h in 3-D) the cut-off
-// radius is 3.0 h, 102 of the 125 nodes are members and no row is empty (measured: K2/K3 unchanged, K5 +7 %);
-// it pays for gamma >= 6, where the radius drops to 2.1 h and 10 of 25 rows go.
-#ifndef NLPS_WAVE_ROW_SKIP
-#define NLPS_WAVE_ROW_SKIP 0
-#endif
-__device__ __forceinline__ bool wave_row_used(unsigned bits) {
-#if NLPS_WAVE_ROW_SKIP
-  return __builtin_amdgcn_ballot_w64(bits != 0u) != 0ull;
-#else
-  (void)bits;
-  return true;
-#endif
 }
 
 // Z^-1, r = sum p l, J = sum p l(x)l - r(x)r  (LME.c:766-832) by rows and planes.
@@ -1298,15 +1162,14 @@ __device__ __forceinline__ void lme_moments_h(const Lme<ND>& c, double& Zinv, do
   (void)ly5;
   (void)lz5;
   double M0 = 0.0, M1x = 0.0, M1y = 0.0, M1z = 0.0, M2xx = 0.0, M2xy = 0.0, M2xz = 0.0, M2yy = 0.0, M2yz = 0.0, M2zz = 0.0;
-  // real (not unrolled) plane loop, unrolled rows: compact code, short live ranges
-#pragma unroll NLPS_KUNROLL_MOM
+  // real (not unrolled) plane loop, unrolled rows: compact code, short live ranges (the unrolled plane loop spills)
+#pragma unroll 1
   for (int k = 0; k < Lme<ND>::KN; k++) {
     const unsigned pb = plane_bits<ND>(c, k);
     double P00 = 0.0, P10 = 0.0, P20 = 0.0, P01 = 0.0, P11 = 0.0, P02 = 0.0;
-#pragma unroll NLPS_JUNROLL_MOMENTS
+#pragma unroll 5
     for (int j = 0; j < 5; j++) {
       const unsigned bits = (pb >> (5 * j)) & 31u;
-      if (!wave_row_used(bits)) continue;
       double mw[5];
       masked_row(mw, c.ex, bits);
       const double m0 = mw[0], m1 = mw[1], m2 = mw[2], m3 = mw[3], m4 = mw[4];

@@ -1605,7 +1605,7 @@ struct nlps_gpu {
   int* tile_count_d;
   int* tile_count2_d = nullptr;  // the counters the search ahead (k5_tile) fills while tile_count_d still sizes the lists in use
   int* tile_start_d;
-  int2 *work1_d = nullptr, *work2_d = nullptr;  // compacted (tile, part) work lists, see TileD
+  int2* work1_d = nullptr;  // compacted work list of the non-empty tiles, see TileD
   // canonical lists from per-node counters (TileTab): node_cnt[nnodes], nrank[npad], layer tables [ntiles][LMAX]
   int *node_cnt_d = nullptr, *nrank_d = nullptr, *tabo_d = nullptr;
   int* tile_cursor_d = nullptr;  // [ntiles + 1] list cursors of the deferred ranks (TileCnt::defer, k_fill_orders)
@@ -1622,11 +1622,11 @@ struct nlps_gpu {
   bool rehome = true;
   double adaptive_resort = 0.8, debt = 0.0;  // default budget: about one re-sort's cost
   int adaptive_min_steps = 4;
-  int* nwork_d = nullptr;   // ranges[3 classes][2 splits][begin,end] of the work lists (tile_scan_block)
+  int* nwork_d = nullptr;   // ranges[3 classes][begin,end] of the work list (tile_scan_block)
   int *dmg_first_d = nullptr, *dmg_last_d = nullptr;  // eigenerosion: run of every node in the I0-sorted particle list
   int *dmg_first0_d = nullptr, *dmg_last0_d = nullptr, *dmg_sorted0_d = nullptr;  // the same for the snapshot's closest nodes
   bool beps_snapshot = false;  // F_X0 / F_I00 hold the configuration of Initialize_Beps = true
-  double* slab_d = nullptr; // P2G window slabs [ntiles][K2_SPLIT][1+ND][NW] (TileD::slab), deterministic mode only
+  double* slab_d = nullptr; // P2G window slabs [ntiles][slab_n][1+ND][NW] (TileD::slab), deterministic mode only
   bool deterministic = false;
   int band_lo = -(1 << 30), band_hi = 1 << 30;  // ghost bands: layers <= band_lo and >= band_hi are shared with neighbours
   int overlap = 0;          // halo exchanges: 0 blocking in place; 1 behind the interior tiles of the NEXT stage (split
@@ -2175,8 +2175,7 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
   if (dev_alloc(h, &h->tile_count2_d, (size_t)h->ntiles + 1)) return 1;
   if (dev_alloc(h, &h->tile_start_d, (size_t)h->ntiles + 1)) return 1;
   if (dev_alloc(h, &h->work1_d, (size_t)h->ntiles)) return 1;
-  if (dev_alloc(h, &h->work2_d, (size_t)h->ntiles * 2)) return 1;
-  if (dev_alloc(h, &h->nwork_d, 16)) return 1;
+  if (dev_alloc(h, &h->nwork_d, 6)) return 1;
 #if NLPS_DEV
   if (const char* e = getenv("NLPS_ADAPTIVE_RESORT")) h->adaptive_resort = atof(e);  // (0 = off)
 #endif
@@ -2539,7 +2538,7 @@ extern "C" int nlps_gpu_destroy(nlps_gpu* h) {
   void* ptrs[] = {h->P.d, h->Pd_alt, h->P.I0, h->P.I0n, h->P.mat, h->P.nn, h->P.status, h->P.mlo, h->P.mhi, h->N.active, h->N.seed, h->N.nm,
                   h->N.dU, h->N.force, h->N.accel, h->N.reaction, h->N.fixed, h->h_avg_d, h->beta_t2_d, h->n2m_d, h->d2m_d, h->canon_d, h->mask_flags_d, h->mask_idx_d,
                   h->fixedm_d, h->bsum_d, h->total_d, h->gstatus_d, h->gridA, h->gridB, h->maskedA, h->mats_d,
-                  h->rank1_d, h->P.tile, h->P.rank, h->order_d, h->order2_d, h->tile_count_d, h->tile_count2_d, h->tile_start_d, h->work1_d, h->work2_d, h->nwork_d, h->slab_d, h->dmg_first_d, h->dmg_last_d, h->dmg_first0_d, h->dmg_last0_d, h->dmg_sorted0_d, h->perm_d, h->skey_d, h->skey2_d, h->sval_d, h->sval2_d,
+                  h->rank1_d, h->P.tile, h->P.rank, h->order_d, h->order2_d, h->tile_count_d, h->tile_count2_d, h->tile_start_d, h->work1_d, h->nwork_d, h->slab_d, h->dmg_first_d, h->dmg_last_d, h->dmg_first0_d, h->dmg_last0_d, h->dmg_sorted0_d, h->perm_d, h->skey_d, h->skey2_d, h->sval_d, h->sval2_d,
                   h->gather_tmp, h->cub_tmp, h->gid_d, h->leaving_d, h->mig_slot_d, h->mig_cnt_d, h->mig_down_d, h->mig_up_d, h->kst_d, h->ktouched_d, h->kcnt_d, h->koffs_d, h->kscan_tmp, h->khead_d, h->kng_d, h->vec_d, h->bcmask_d, h->home_d, h->foreign_d, h->node_cnt_d, h->nrank_d, h->tabo_d, h->tabm_d, h->tile_cursor_d, h->top_d, h->top_m, h->top_g, h->top_b,
                   h->ksp_pc, h->ksp_v, h->ksp_part, h->ksp_s, h->ksp_bad_d, h->ksp_hdev};
   for (void* p : ptrs)
@@ -3425,9 +3424,8 @@ static TileD tile_view(nlps_gpu* h, int cls = 0) {  // cls: 0 all tiles, 1 bound
   td.sig_cnt = nullptr;
   td.sig_flag = nullptr;
   td.sig_seq = 0;
-  td.work[0] = h->work1_d;
-  td.work[1] = h->work2_d;
-  td.range = h->nwork_d + 4 * cls;
+  td.work = h->work1_d;
+  td.range = h->nwork_d + 2 * cls;
   td.phase = h->phase_d;
   td.start = h->tile_start_d;
   td.count = h->tile_count_d;
@@ -3478,13 +3476,13 @@ static void launch_k2(nlps_gpu* h, bool p2g, int cls, double dt, double gamma_nm
   TileD td = tile_view(h, cls);
   if (signal) arm_signal(h, td, 0);
   if (h->deterministic && p2g) {  // one wave per tile, sorted list, slab flush (nlps_gpu_set_deterministic)
-    LAUNCH_ND_BLK((k2_tile<2, true, 64, 1>), (k2_tile<3, true, 64, 1>), h->ntw, 64, h->P, h->g, h->N, td, h->prm, dt, gamma_nm,
+    LAUNCH_ND_BLK((k2_tile<2, true, 64>), (k2_tile<3, true, 64>), h->ntw, 64, h->P, h->g, h->N, td, h->prm, dt, gamma_nm,
                   h->gstatus_d);
     return;
   }
   with_nd(h->nd, [&](auto D) {
     with_bool(p2g, [&](auto P2G) {
-      hipLaunchKernelGGL((k2_tile<CT(D), CT(P2G)>), dim3(h->ntw * K2_SPLIT), dim3(BLK), 0, h->stream, h->P, h->g, h->N, td,
+      hipLaunchKernelGGL((k2_tile<CT(D), CT(P2G)>), dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, h->N, td,
                          h->prm, dt, gamma_nm, h->gstatus_d);
     });
   });
@@ -3516,7 +3514,7 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
   {
     const int TB = h->nd == 3 ? TileCfg<3>::TB : TileCfg<2>::TB;
     TileScanArgs ts{h->tile_count_d + h->tile0, h->tile_start_d + h->tile0, h->ntw, h->tile0, h->ntiles / h->nt[h->nd - 1], TB,
-                    h->band_lo, h->band_hi, h->work1_d, h->work2_d, h->nwork_d, deferred ? h->tile_cursor_d + h->tile0 : nullptr};
+                    h->band_lo, h->band_hi, h->work1_d, h->nwork_d, deferred ? h->tile_cursor_d + h->tile0 : nullptr};
     const int nb = 1 + (h->nwn + 1023) / 1024 + (node_lists(h) ? (h->ntw + 15) / 16 : 0);
     int* fo = (h->adaptive_resort > 0.0 && !h->deterministic) ? h->foreign_d : nullptr;
     LAUNCH_ND_BLK(k_dilate_scan<2>, k_dilate_scan<3>, nb, 1024, h->n0, h->nwn, h->g, h->N, ts, fo, h->foreign_h, tile_tab(h),
@@ -3776,7 +3774,7 @@ extern "C" int nlps_gpu_compatibility(nlps_gpu* h, const double* dU, const doubl
   if (dU_dt && to_grid(h, h->gridB, dU_dt, h->nd)) return 1;
   if (dU_dt) h->level_b_fields = true;
   TileD td = tile_view(h);
-  const dim3 grid(h->ntw * K3_SPLIT), blk(K3_BLK);
+  const dim3 grid(h->ntw), blk(K3_BLK);
   const double* dV = dU_dt ? h->gridB : nullptr;
   with_nd(h->nd, [&](auto D) {
     with_bool(dV != nullptr, [&](auto RATES) {  // MODE 2: the rate tensors too
@@ -4128,7 +4126,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   };
   const int law = h->uniform_law;  // -1: several laws in the cloud (law_present)
   const bool one_mat = ND == 3 && h->nmats == 1 && law >= 1 && law <= 3;  // its constants by scalar loads (k3_body, UMAT)
-  const dim3 grid3(h->ntw * K3_SPLIT), blk3(K3_BLK);
+  const dim3 grid3(h->ntw), blk3(K3_BLK);
   const double* const no_dU = nullptr;
   auto launch_k3 = [&](int cls, bool signal) {
     TileD td = tile_view(h, cls);
@@ -4206,7 +4204,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
       h->ranks_deferred = ks.tc.defer != 0;
       ks_made = true;
     }
-    const dim3 grid(h->ntw * K5_SPLIT), blk(K5_BLK);
+    const dim3 grid(h->ntw), blk(K5_BLK);
     with_nd(ND, [&](auto D) {
       // K5 exists in two forms: LAW = 0 serves laws 0 and 1, LAW = 2 every other law and the cloud of several
       with_bool(law == 0 || law == 1, [&](auto L01) {
@@ -4301,7 +4299,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     HIPCHK(hipEventRecord(h->ev[6], h->stream));
     // calibration bracket: a kernel of K3's grid and argument block that does nothing; what it reads is the part of
     // a one-kernel bracket that is not kernel time (records, dispatch, launch of the empty grid)
-    hipLaunchKernelGGL(k_null_bracket, dim3(h->ntw * K3_SPLIT), dim3(BLK), 0, h->stream, h->P, h->g, h->N,
+    hipLaunchKernelGGL(k_null_bracket, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, h->N,
                        tile_view(h, 0), h->mats_d, h->prm, h->gstatus_d, (const double*)nullptr);
     HIPCHK(hipEventRecord(h->ev[7], h->stream));
     HIPCHK(hipEventSynchronize(h->ev[7]));
@@ -4601,7 +4599,7 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
   {
     TileD td = tile_view(h);
     td.slab = nullptr;  // (level-B semantics: atomics also in deterministic mode, like kb_fint_tile)
-    const dim3 grid(h->ntw * K3_SPLIT), blk(K3_BLK);
+    const dim3 grid(h->ntw), blk(K3_BLK);
     const int law = h->uniform_law;
     if (law < 0) {
       // a cloud of several laws: one launch per law present of the kernel compiled for that law, every workgroup compacting

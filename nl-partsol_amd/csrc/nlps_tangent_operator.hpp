@@ -152,7 +152,7 @@ __global__ __launch_bounds__(BLK) void k_tanop_apply(PView P, GridD g, TileD td,
   __shared__ double acc[ND * NW];  // (K x) of the window, field-major (kb_fint_tile's layout)
   const int wb = td.range[0] + (int)blockIdx.x;
   if (wb >= td.range[1]) return;
-  const int tile = td.work[0][wb].x;
+  const int tile = td.work[wb].x;
   const int cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(BLK) void k_tanop_bdiag(PView P, GridD g, TileD td,
   __shared__ double acc[E * NW];
   const int wb = td.range[0] + (int)blockIdx.x;
   if (wb >= td.range[1]) return;
-  const int tile = td.work[0][wb].x;
+  const int tile = td.work[wb].x;
   const int cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);

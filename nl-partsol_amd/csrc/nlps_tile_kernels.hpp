@@ -41,32 +41,12 @@ struct TileCfg<2> {
   static constexpr int WA = 20, PSA = 400, NWA = 400;  // a 16-lane group is one row of 16 consecutive slots already
 };
 
-// A tile's particle list is shared by TILE_SPLIT workgroups (each builds the window, takes every
-// TILE_SPLIT-th chunk of 256 particles and flushes with atomics): twice as many, half as long work
-// units shorten the partially filled last round of workgroups (tail) without changing the data flow.
-// Measured at 1 M particles: pays for K2 (0.42 -> 0.39 ms), costs for K3 (double window load + flush).
-#ifndef NLPS_K2_SPLIT
-#define NLPS_K2_SPLIT 1  // r02: 1 and 2 are equal at 1 M particles (0.242 / 0.243 ms), 1 is 2 % faster at 8 M and halves the flush
-#endif
-// workgroup sizes of the tile kernels (K2 keeps BLK: its work list splits tiles at BLK particles).  Measured at 1 M
+// One workgroup per tile.  (Measured and dropped: a tile's list dealt over two workgroups, each with its own window
+// and flush -- K2 equal at 1 M particles (0.242 / 0.243 ms) and 2 % slower at 8 M with twice the flush, K3 and K5 pay
+// the second window load.)
+// workgroup sizes of the tile kernels (K2 keeps BLK).  Measured at 1 M
 // particles: K3 with 64 / 128 / 256 / 512 threads 0.402 / 0.327 / 0.312 / 0.338 ms, K5 with 128 / 256 / 512 0.097 / 0.100 / 0.111 ms.
-#ifndef NLPS_K3_BLK
-#define NLPS_K3_BLK 256
-#endif
-#ifndef NLPS_K5_BLK
-#define NLPS_K5_BLK 256
-#endif
-static constexpr int K3_BLK = NLPS_K3_BLK, K5_BLK = NLPS_K5_BLK;
-#ifndef NLPS_K3_SPLIT
-#define NLPS_K3_SPLIT 1
-#endif
-#ifndef NLPS_K5_SPLIT
-#define NLPS_K5_SPLIT 1
-#endif
-#ifndef NLPS_K5_PREFETCH
-#define NLPS_K5_PREFETCH 1  // corrector operands requested before the gather loop: K5 0.097 -> 0.092 ms (1 M particles)
-#endif
-static constexpr int K2_SPLIT = NLPS_K2_SPLIT, K3_SPLIT = NLPS_K3_SPLIT, K5_SPLIT = NLPS_K5_SPLIT;
+static constexpr int K3_BLK = 256, K5_BLK = 256;
 
 struct TileD {
   int nt[3];
@@ -74,7 +54,7 @@ struct TileD {
   int tile0;  // first tile of the launched range (node window)
   int ntw;    // tiles in that range
   // Deterministic mode (nlps_gpu_set_deterministic), nullptr otherwise: the P2G results leave a workgroup as ONE plain,
-  // coalesced copy of its LDS window into the slab of its (tile, part), slab[(tile * SPLIT + part)][field][window slot];
+  // coalesced copy of its LDS window into the slab of its tile, slab[tile * slab_n + slab_slot][field][window slot];
   // k_slab_gather then sums, for every node, the <= 2^d windows that hold it in a fixed order.  No global atomics and
   // an inter-tile summation order that never changes -- measured 7 % slower per step than the atomic flush (the
   // no-return atomics hide behind the other workgroups' arithmetic, the gather is two more passes over the grid).
@@ -84,14 +64,14 @@ struct TileD {
   const int* count;
   const int* order;   // tile lists: canonical (layer, closest node) order when per-tile ordering is on (K2, K3)
   const int* order_m; // tile lists as binned: runs of memory-consecutive particles (K5 and the level-B gathers)
-  // compacted work lists (tile_scan_block): work[S-1][b] = (tile, part) for the b-th workgroup of a kernel that
-  // splits a tile's particles over S workgroups, only for non-empty (tile, part) pairs; nwork[S-1] entries.
+  // compacted work list (tile_scan_block): work[b].x = tile of the b-th workgroup, non-empty tiles only.
   // Consecutive workgroups go to different XCDs, so a compacted list spreads the populated tiles evenly over
   // the 8 XCDs whatever the shape of the cloud (tile-index order left XCDs 23 % apart for the cube).
-  const int2* work[2];
-  // Workgroup range of the launch inside work[S-1]: {begin, end} at range[2*(S-1)].  The lists hold the tiles whose
-  // window touches a ghost band (nodes shared with a neighbouring rank) first, so a launch can take all tiles,
-  // only the "boundary" ones or only the "interior" ones (overlap of the halo exchange with interior work).
+  const int2* work;
+  // Workgroup range of the launch inside work: {begin, end}.  The list holds the tiles whose window touches a ghost
+  // band (nodes shared with a neighbouring rank) first, so a launch can take all tiles, only the "boundary" ones or
+  // only the "interior" ones (overlap of the halo exchange with interior work): one {begin, end} pair per class,
+  // all / boundary / interior (tile_scan_block), and range points at the pair of the launched class.
   const int* range;
   unsigned long long* phase;  // -DNLPS_PHASE_TIMING=1 only: per-phase wave-cycle sums (developer profiling)
   // Single-launch overlap of the halo exchange (multi-GPU): the work list holds the boundary tiles first; every boundary
@@ -130,20 +110,19 @@ __device__ __forceinline__ void tile_signal_empty(const TileD& td, int nb) {
     __hip_atomic_store(td.sig_flag, td.sig_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Work item of this workgroup: tile, part and the number of parts its tile list is dealt into
+// Work item of this workgroup: its position in the work list and the tile found there
 struct TileWork {
-  int tile, part, nparts, wb;
+  int tile, wb;
 };
-template <int SPLIT>
 __device__ __forceinline__ bool tile_work_item(const TileD& td, TileWork& w) {
-  w.wb = td.range[2 * (SPLIT - 1)] + (int)blockIdx.x;
-  if (w.wb >= td.range[2 * (SPLIT - 1) + 1]) return false;
-  const int2 wk = td.work[SPLIT - 1][w.wb];
-  w.tile = wk.x;
-  w.part = wk.y;
-  w.nparts = SPLIT;
+  w.wb = td.range[0] + (int)blockIdx.x;
+  if (w.wb >= td.range[1]) return false;
+  w.tile = td.work[w.wb].x;
   return true;
 }
+// boundary workgroups of a launch over all tiles (they come first): the end of the boundary class's range, which lies
+// behind the pair td.range points at
+__device__ __forceinline__ int tile_boundary_count(const TileD& td) { return td.sig_flag ? td.range[3] : 0; }
 
 // Developer profiling: wall-clock cycles per kernel phase, summed per wave (slot spread over 1024 rows to keep
 // the atomics off one address).  Compiled out by default.
@@ -228,23 +207,24 @@ __device__ __forceinline__ int window_base(const int* ijk, const int* w0) {
   return (ijk[0] - w0[0]) + W * (ijk[1] - w0[1]) + (ND == 3 ? PS * (ijk[2] - w0[2]) : 0);
 }
 
-// block-wide exclusive scan of one int per thread (1024 threads = 16 waves); returns the exclusive prefix,
+// block-wide exclusive scan of one value per thread (1024 threads = 16 waves); returns the exclusive prefix,
 // *total = sum.  Wave-level shuffles + one pass over the 16 wave totals: two barriers instead of twenty.
-__device__ __forceinline__ int block_scan_1024(int v, int* sh, int* total) {
+template <typename T>
+__device__ __forceinline__ T block_scan_1024(T v, T* sh, T* total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
+  T incl = v;
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(incl, off);
+    const T t = __shfl_up(incl, off);
     if (lane >= off) incl += t;
   }
   __syncthreads();  // sh[] may still be read from the previous scan
   if (lane == 63) sh[wave] = incl;
   __syncthreads();
-  int base = 0, tot = 0;
+  T base = 0, tot = 0;
 #pragma unroll
   for (int w = 0; w < 16; w++) {
-    const int t = sh[w];
+    const T t = sh[w];
     if (w < wave) base += t;
     tot += t;
   }
@@ -252,40 +232,16 @@ __device__ __forceinline__ int block_scan_1024(int v, int* sh, int* total) {
   return base + incl - v;
 }
 
-// the same for four 16-bit counters packed into one 64-bit word (sums below 65536 each)
-__device__ __forceinline__ unsigned long long block_scan_1024_u64(unsigned long long v, unsigned long long* sh,
-                                                                  unsigned long long* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned long long incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned long long t = __shfl_up(incl, off);
-    if (lane >= off) incl += t;
-  }
-  __syncthreads();
-  if (lane == 63) sh[wave] = incl;
-  __syncthreads();
-  unsigned long long base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 16; w++) {
-    const unsigned long long t = sh[w];
-    if (w < wave) base += t;
-    tot += t;
-  }
-  *total = tot;
-  return base + incl - v;
-}
-
-// exclusive scan of the per-tile particle counts + the compacted work lists (one 1024-thread block).
+// exclusive scan of the per-tile particle counts + the compacted work list (one 1024-thread block).
 // count/start are already offset to the first tile of the node window; tile0 = that tile's index.
 // A tile is "boundary" when its node window reaches a ghost band: slow-axis layers <= band_lo or >= band_hi
-// (tpl = tiles per slow-axis tile layer, TB = tile edge).  ranges[cls][S-1] = {begin, end} in work<S> for
+// (tpl = tiles per slow-axis tile layer, TB = tile edge).  ranges[cls] = {begin, end} in work1 for
 // cls 0 = all, 1 = boundary, 2 = interior.
 struct TileScanArgs {
   const int* count;
   int* start;
   int n, tile0, tpl, TB, band_lo, band_hi;
-  int2 *work1, *work2;
+  int2* work1;
   int* ranges;
   int* cursor;  // [n] or nullptr: a copy of start[] for k_fill_orders to hand out list positions from (deferred ranks)
 };
@@ -294,47 +250,29 @@ __device__ __forceinline__ void tile_scan_block(const TileScanArgs& a) {
   int* __restrict__ start = a.start;
   const int n = a.n, tile0 = a.tile0, tpl = a.tpl, TB = a.TB, band_lo = a.band_lo, band_hi = a.band_hi;
   int2* __restrict__ work1 = a.work1;
-  int2* __restrict__ work2 = a.work2;
   int* __restrict__ ranges = a.ranges;
   __shared__ int sh[1024];
+  __shared__ u64 sh64[16];
   int chunk = (n + 1023) / 1024;
-  int lo = threadIdx.x * chunk, hi = min(n, lo + chunk), c = 0, b1 = 0, b2 = 0, i1 = 0, i2 = 0;
+  int lo = threadIdx.x * chunk, hi = min(n, lo + chunk), c = 0;
+  u64 bi = 0ull;  // non-empty boundary tiles of this thread's chunk in the low word, interior ones in the high word
   for (int q = lo; q < hi; q++) {
     const int cq = count[q];
     c += cq;
     const int tz = (tile0 + q) / tpl;
     const bool bnd = (tz * TB - 2 <= band_lo) || (tz * TB + TB + 1 >= band_hi);
-    const int e1 = cq > 0, e2 = (cq > 0) + (cq > BLK);
-    if (bnd) {
-      b1 += e1;
-      b2 += e2;
-    } else {
-      i1 += e1;
-      i2 += e2;
-    }
+    if (cq > 0) bi += bnd ? 1ull : (1ull << 32);
   }
-  int nb1, nb2, ni1, ni2, tot;
+  int tot;
   int run = block_scan_1024(c, sh, &tot);
-  __shared__ unsigned long long sh64[16];
-  int rb1, rb2, ri1, ri2;
-  if (n < 32768) {  // the four list counters as 16-bit fields of one scan (each sum is below 2 n)
-    unsigned long long wt;
-    const unsigned long long wp = block_scan_1024_u64((unsigned long long)b1 | ((unsigned long long)b2 << 16) |
-                                                          ((unsigned long long)i1 << 32) | ((unsigned long long)i2 << 48),
-                                                      sh64, &wt);
-    rb1 = (int)(wp & 0xFFFFull), rb2 = (int)((wp >> 16) & 0xFFFFull), ri1 = (int)((wp >> 32) & 0xFFFFull), ri2 = (int)(wp >> 48);
-    nb1 = (int)(wt & 0xFFFFull), nb2 = (int)((wt >> 16) & 0xFFFFull), ni1 = (int)((wt >> 32) & 0xFFFFull), ni2 = (int)(wt >> 48);
-  } else {
-    rb1 = block_scan_1024(b1, sh, &nb1);
-    rb2 = block_scan_1024(b2, sh, &nb2);
-    ri1 = block_scan_1024(i1, sh, &ni1);
-    ri2 = block_scan_1024(i2, sh, &ni2);
-  }
-  ri1 += nb1;
-  ri2 += nb2;
+  // both list counters in ONE scan, as the 32-bit halves of a word (each sum is at most n): no second scan, no size limit
+  u64 wt;
+  const u64 wp = block_scan_1024(bi, sh64, &wt);
+  const int nb = (int)(unsigned)wt, ni = (int)(wt >> 32);
+  int rb = (int)(unsigned)wp, ri = nb + (int)(wp >> 32);
   if (threadIdx.x == 0) {
-    const int r[12] = {0, nb1 + ni1, 0, nb2 + ni2, 0, nb1, 0, nb2, nb1, nb1 + ni1, nb2, nb2 + ni2};
-    for (int k = 0; k < 12; k++) ranges[k] = r[k];
+    const int r[6] = {0, nb + ni, 0, nb, nb, nb + ni};
+    for (int k = 0; k < 6; k++) ranges[k] = r[k];
   }
   for (int q = lo; q < hi; q++) {
     const int cq = count[q];
@@ -344,11 +282,7 @@ __device__ __forceinline__ void tile_scan_block(const TileScanArgs& a) {
     if (cq > 0) {
       const int tz = (tile0 + q) / tpl;
       const bool bnd = (tz * TB - 2 <= band_lo) || (tz * TB + TB + 1 >= band_hi);
-      int& r1 = bnd ? rb1 : ri1;
-      int& r2 = bnd ? rb2 : ri2;
-      work1[r1++] = make_int2(tile0 + q, 0);
-      work2[r2++] = make_int2(tile0 + q, 0);
-      if (cq > BLK) work2[r2++] = make_int2(tile0 + q, 1);
+      work1[bnd ? rb++ : ri++] = make_int2(tile0 + q, 0);
     }
   }
 }
@@ -382,7 +316,7 @@ __global__ __launch_bounds__(256) void k_tile_order(PView P, GridD g, TileD td, 
   __shared__ int maxc;
   const int wb = td.range[0] + (int)blockIdx.x;
   if (wb >= td.range[1]) return;
-  const int tile = td.work[0][wb].x;
+  const int tile = td.work[wb].x;
   const int n = td.count[tile];
   const int start = td.start[tile];
   if (n > CAP || n <= 1) {
@@ -474,15 +408,6 @@ __global__ __launch_bounds__(256) void k_tile_order(PView P, GridD g, TileD td, 
 // Developer ablations (tools/kbench.py, never in the product build): NLPS_ABL_ATOM = 1 keeps the arithmetic of the window
 // scatters but issues no LDS atomic (the test value never occurs); NLPS_ABL_GATHER = 1 replaces the window reads of the
 // gathers by a register constant.  They bound what the LDS work of a kernel costs beside its arithmetic.
-#ifndef NLPS_K3_TWOPASS_ALL
-#define NLPS_K3_TWOPASS_ALL 0
-#endif
-#ifndef NLPS_K3_PRELOAD_FN
-#define NLPS_K3_PRELOAD_FN 0  // measured: 40 B of scratch appear, K3 0.213 -> 0.217 ms
-#endif
-#ifndef NLPS_K3_RELOAD
-#define NLPS_K3_RELOAD 1
-#endif
 #ifndef NLPS_ABL_ATOM
 #define NLPS_ABL_ATOM 0
 #endif
@@ -497,23 +422,13 @@ __device__ __forceinline__ void lds_add(double* a, double v) {
 }
 
 // ---- 3-D window helpers without divisions: the 8 x 8 x 8 window is walked as r = lx + 8 (ly + 8 lz) -----------------
-#ifndef NLPS_FAST_WINDOWS
-#define NLPS_FAST_WINDOWS 1
-#endif
 // One z value of a gather window as its OWN ds_read_b64.  The back end pairs the reads of two neighbouring slots into
 // ds_read2_b64, which the LDS serves in 8 cycles over 32 banks (two ds_read_b64: 4 cycles over 64 banks) and which puts
 // the rows by and by + 2 of the tile on the same banks (rows of 8 doubles = 16 of its 32 slots): K5 spent 38 % of its
 // LDS cycles on those conflicts.  A volatile access is not paired; with planes of 68 the 32 lanes of a ds_read_b64
 // group (bx + 8 by + 68 bz, bz in {0, 1}) fall on 32 different 8-byte slots.
-#ifndef NLPS_Z_SINGLE_READS
-#define NLPS_Z_SINGLE_READS 1
-#endif
 __device__ __forceinline__ double lds_z(const double* z, int i) {
-#if NLPS_Z_SINGLE_READS
   return *(const volatile __attribute__((address_space(3))) double*)(z + i);  // (z is a __shared__ array: keep the access a ds_read)
-#else
-  return z[i];
-#endif
 }
 
 // global node of window cell r (3-D); inside = false outside the grid
@@ -669,12 +584,12 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
   constexpr int W = TileCfg<ND>::W, NW = TileCfg<ND>::NW, NF = 1 + ND, NROWS = WinRows<ND>::NROWS;
   constexpr int WA = TileCfg<ND>::WA, PSA = TileCfg<ND>::PSA, NWA = TileCfg<ND>::NWA;
   constexpr int KN = Lme<ND>::KN;
-  const int wb = tw.wb, tile = tw.tile, part = tw.part, nparts = tw.nparts;
+  const int wb = tw.wb, tile = tw.tile;
   const int cnt = td.count[tile];
   PH_INIT
   int w0[3];
   tile_origin<ND>(td, tile, w0);
-  if (ND == 3 && NLPS_FAST_WINDOWS) {
+  if (ND == 3) {
     if (P2G)
       for (int idx = threadIdx.x; idx < NF * NWA; idx += NT) acc[idx] = 0.0;
     window_actrows3<NT>(g, w0, N.active, actrow);
@@ -693,7 +608,7 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
   __syncthreads();
   const int start = td.start[tile];
   PH(0)
-  for (int s = part * NT + threadIdx.x; s < cnt; s += NT * nparts) {
+  for (int s = threadIdx.x; s < cnt; s += NT) {
     const int p = td.order[start + s];
     Lme<ND> c;
     double x[ND], lam[ND];
@@ -701,13 +616,6 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
     for (int a = 0; a < ND; a++) {
       x[a] = PF(P, F_X + a, p);
       lam[a] = PF(P, F_LAM + a, p);
-#if NLPS_LAMBDA_EXTRAPOLATE
-      if (P2G) {  // start Newton from 2 lambda_n - lambda_{n-1}: same root, usually one iteration fewer
-        const double lp = PF(P, F_LAMP + a, p);
-        PF(P, F_LAMP + a, p) = lam[a];
-        lam[a] = 2.0 * lam[a] - lp;
-      }
-#endif
     }
     const int I0 = P.I0[p];
     c.geom(g, x, I0);
@@ -735,7 +643,6 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
       if (ND == 3) lz2[i] = c.lz[i % KN] * c.lz[i % KN];
     }
     u64 mlo = 0ull, mhi = 0ull;
-#if NLPS_MASK_BY_COLUMNS
     {
       // Radius test of the 125 stencil nodes, one (i, j) column of five planes at a time: the left-to-right sum of
       // generalised_Euclidean_distance (MatrixOp.c:895-920), (lx^2 + ly^2) + lz^2, shares its first addition over the
@@ -771,29 +678,6 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
         put_plane(mlo, mhi, pbk[k] & act, k);
       }
     }
-#else
-#pragma unroll NLPS_KUNROLL_MASK
-    for (int k = 0; k < KN; k++) {
-      const double lz2k = (ND == 3) ? lz2[k] : 0.0;
-      unsigned pbits = 0u;
-#pragma unroll NLPS_JUNROLL_MASK
-      for (int j = 0; j < 5; j++) {
-        const int row = (by + j - 2) + (ND == 3 ? W * (bz + k - 2) : 0);
-        const unsigned actbits = (actrow[row] >> (bx - 2)) & 31u;
-        unsigned rb = 0u;
-#pragma unroll
-        for (int i = 0; i < 5; i++) {
-          double sq = 0.0;  // same left-to-right sum as generalised_Euclidean_distance (MatrixOp.c:895-920)
-          sq += lx2[i];
-          sq += ly2[j];
-          if (ND == 3) sq += lz2k;
-          rb |= (sq <= T2) ? (1u << i) : 0u;
-        }
-        pbits |= (rb & actbits) << (5 * j);
-      }
-      put_plane(mlo, mhi, pbits, k);
-    }
-#endif
     c.mlo = mlo;
     c.mhi = mhi;
     const int nn = __popcll(mlo) + __popcll(mhi);
@@ -834,7 +718,6 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
           dl2 = fma(d, d, dl2);
         }
         NumIter++;
-#if NLPS_NEWTON_PREDICT_LAST
         // The reference's next pass would only confirm convergence: with D = -J^-1 r exactly, r(lambda + D) =
         // (1/2) T[D,D] + ..., T the third central moment of l under p, and |T_s[D,D]| <= max|l_a - r| D.J_s.D with
         // D.J.D = |D.r|.  Members satisfy |l_a| <= Ra, so |r_next| <= (1/2)(Ra + |r|) |D.r| (1 + O(|D| Ra)).  A hundred
@@ -865,7 +748,6 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
             break;
           }
         }
-#endif
       } else {
         break;
       }
@@ -897,12 +779,11 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
     }
     const double mz = PF(P, F_MASS, pl) * Zinv;
     NLPS_YZ_LOCALS(c);
-#pragma unroll NLPS_KUNROLL_K2S
+#pragma unroll 1  // real plane loop: unrolled it measured +-1 %
     for (int k = 0; k < KN; k++) {
       const unsigned pb = plane_bits<ND>(c, k);
       const double wz = mz * ez5[k];
       const int basek = base + (ND == 3 ? PSA * (k - 2) : 0);
-#if NLPS_SCATTER_POP && !NLPS_SCATTER_BRANCHFREE
       unsigned pbs = pb << 7;  // pop_member: bit 24 (j = 4, i = 4) first
 #pragma unroll
       for (int j = 4; j >= 0; j--) {
@@ -917,33 +798,6 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
             for (int a = 0; a < ND; a++) lds_add(&acc[(1 + a) * NWA + li], v0 * dd[a]);
           }
       }
-      continue;
-#endif
-#pragma unroll NLPS_JUNROLL_SCATTER
-      for (int j = 0; j < 5; j++) {
-        const unsigned bits = (pb >> (5 * j)) & 31u;
-        if (!wave_row_used(bits)) continue;
-        const double w = wz * ey5[j];
-#pragma unroll
-        for (int i = 0; i < 5; i++)
-#if NLPS_SCATTER_BRANCHFREE
-        {  // every window slot of the stencil exists: non-members add an exact zero instead of branching around
-          const int li = basek + (i - 2) + WA * (j - 2);
-          const double v0 = w * masked_zero(c.ex[i], bits, i);
-          lds_add(&acc[li], v0);
-#pragma unroll
-          for (int a = 0; a < ND; a++) lds_add(&acc[(1 + a) * NWA + li], v0 * dd[a]);
-        }
-#else
-          if ((bits >> i) & 1u) {
-            const int li = basek + (i - 2) + WA * (j - 2);
-            const double v0 = w * c.ex[i];
-            lds_add(&acc[li], v0);
-#pragma unroll
-            for (int a = 0; a < ND; a++) lds_add(&acc[(1 + a) * NWA + li], v0 * dd[a]);
-          }
-#endif
-      }
     }
     PH(3)
   }
@@ -951,11 +805,11 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
   __syncthreads();
   PH(4)
   if (td.slab) {
-    double* out = td.slab + ((size_t)tile * td.slab_n + td.slab_slot) * (NF * NWA);  // slab mode runs SPLIT = 1
+    double* out = td.slab + ((size_t)tile * td.slab_n + td.slab_slot) * (NF * NWA);
     for (int q = threadIdx.x; q < NWA * NF; q += NT) out[q] = acc[q];
     return;
   }
-  if (ND == 3 && NLPS_FAST_WINDOWS) {
+  if (ND == 3) {
     window_flush3<NF, NT>(g, w0, acc, N.nm);
   } else {
     for (int q = threadIdx.x; q < NWA * NF; q += NT) {
@@ -971,17 +825,19 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
   PH(5)
   tile_signal(td, wb, nbnd);
 }
-// NT / SPLIT: threads per workgroup and workgroups per tile.  The default is (BLK, K2_SPLIT); deterministic mode runs one
-// wave per tile (64, 1): the sorted tile list is then accumulated in list order by a single instruction stream.
-template <int ND, bool P2G, int NT = BLK, int SPLIT = K2_SPLIT>
-__global__ __launch_bounds__(NT, NT == 64 ? 1 : (ND == 2 ? NLPS_K2_WAVES_2D : NLPS_K2_WAVES)) void k2_tile(PView P, GridD g, NView N, TileD td, ParamsD prm, double dt,
+// NT: threads per workgroup.  The default is BLK; deterministic mode runs one wave per tile (64): the sorted tile list
+// is then accumulated in list order by a single instruction stream.
+// K2_WAVES: 168 VGPRs + 132 B of scratch per lane; the spill-free 2-wave build is ~7 % slower
+static constexpr int K2_WAVES = 3, K2_WAVES_2D = 3;
+template <int ND, bool P2G, int NT = BLK>
+__global__ __launch_bounds__(NT, NT == 64 ? 1 : (ND == 2 ? K2_WAVES_2D : K2_WAVES)) void k2_tile(PView P, GridD g, NView N, TileD td, ParamsD prm, double dt,
                                                double gamma_nm, int* __restrict__ gstatus) {
   __shared__ double acc[(1 + ND) * TileCfg<ND>::NWA];
   __shared__ unsigned actrow[WinRows<ND>::NROWS];
-  const int nbnd = td.sig_flag ? td.range[4 + 2 * (SPLIT - 1) + 1] : 0;  // boundary workgroups come first (cls 0 view)
+  const int nbnd = tile_boundary_count(td);
   tile_signal_empty(td, nbnd);
   TileWork tw;
-  if (!tile_work_item<SPLIT>(td, tw)) return;
+  if (!tile_work_item(td, tw)) return;
   k2_body<ND, P2G, NT>(P, g, N, td, prm, dt, gamma_nm, gstatus, tw, nbnd, acc, actrow, nullptr);
 }
 
@@ -1002,13 +858,17 @@ __global__ __launch_bounds__(NT, NT == 64 ? 1 : (ND == 2 ? NLPS_K2_WAVES_2D : NL
 // law present; the run-time dispatch over all laws in one kernel needed 436 B of scratch per lane and 0.51 ms).
 // waves per SIMD the register budget is set for: the fused 3-D Neo-Hookean stage fits three (two-pass gather), the
 // same goes for Hencky once its LME factors are rebuilt after the stress update (RELOAD below), the plastic laws keep two
+static constexpr int K3_WAVES_2D = 2;
+static constexpr int K3_WAVES_NH = 3;  // fused 3-D Neo-Hookean K3 (two-pass gather): 0.294 -> 0.267 ms at 1 M particles
+static constexpr int K3_WAVES_HENCKY = 3, K3_WAVES_DP = 2;
+static constexpr int K3_WAVES = 2;  // Hencky / Drucker-Prager need > 256 VGPRs otherwise (1 wave/SIMD: 0.54 -> 0.37 ms at 2)
 template <int ND, int LAW, int MODE>
 struct K3Waves {
-  static constexpr int value = ND == 2 ? NLPS_K3_WAVES_2D
-                               : ((MODE == 1 || MODE == 3) && LAW == NLPS_MAT_NEO_HOOKEAN) ? NLPS_K3_WAVES_NH
-                               : ((MODE == 1 || MODE == 3) && LAW == NLPS_MAT_HENCKY)      ? NLPS_K3_WAVES_HENCKY
-                               : ((MODE == 1 || MODE == 3) && LAW == NLPS_MAT_DRUCKER_PRAGER) ? NLPS_K3_WAVES_DP
-                                                                               : NLPS_K3_WAVES;
+  static constexpr int value = ND == 2 ? K3_WAVES_2D
+                               : ((MODE == 1 || MODE == 3) && LAW == NLPS_MAT_NEO_HOOKEAN) ? K3_WAVES_NH
+                               : ((MODE == 1 || MODE == 3) && LAW == NLPS_MAT_HENCKY)      ? K3_WAVES_HENCKY
+                               : ((MODE == 1 || MODE == 3) && LAW == NLPS_MAT_DRUCKER_PRAGER) ? K3_WAVES_DP
+                                                                               : K3_WAVES;
 };
 // the LDS of k3_tile, owned by the caller of k3_body (the kernels below)
 template <int ND, int MODE, bool FILT>
@@ -1052,7 +912,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
   int& nsel = *lds.nsel;
   int* const wcnt = lds.wcnt;
   constexpr int WA = TileCfg<ND>::WA, PSA = TileCfg<ND>::PSA, NWA = TileCfg<ND>::NWA;
-  const int wb = tw.wb, tile = tw.tile, part = tw.part, nparts = tw.nparts;
+  const int wb = tw.wb, tile = tw.tile;
   int cnt = td.count[tile];
   PH_INIT
   constexpr int SELCAP = FILT ? 4096 : 1;
@@ -1101,10 +961,10 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
   }
   int w0[3];
   tile_origin<ND>(td, tile, w0);
-  for (int idx0 = threadIdx.x; idx0 < ((ND == 3 && NLPS_FAST_WINDOWS) ? 512 : NW); idx0 += NT) {
+  for (int idx0 = threadIdx.x; idx0 < ((ND == 3) ? 512 : NW); idx0 += NT) {
     bool in;
     int node, idx;
-    if (ND == 3 && NLPS_FAST_WINDOWS) {
+    if (ND == 3) {
       node = window_cell3(g, w0, idx0, in);
       idx = (idx0 & 63) + PS * (idx0 >> 6);
     } else {
@@ -1137,7 +997,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
   const double2* dv2 = reinterpret_cast<const double2*>(dvxy);
   const int start = td.start[tile];
   PH(8)
-  for (int s = part * NT + threadIdx.x; s < cnt; s += NT * nparts) {
+  for (int s = threadIdx.x; s < cnt; s += NT) {
     const int p = (FILT && listed) ? sel[FILT ? s : 0] : td.order[start + s];
     if (FILT && !listed && mats[P.mat[p]].type != LAW) continue;  // oversized tile: filter per lane
     Lme<ND> c;
@@ -1168,11 +1028,10 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     // which is what lets the elastic laws run at three waves per SIMD; it costs ~350 more VALU instructions a particle.
     // (the level-B modes keep the single pass: with and without rate tensors they must give the same F bit for bit)
     // and the laws that stay at two waves per SIMD keep it too: there the second set of masked weights only costs)
-    constexpr bool TWOPASS = (NLPS_K3_TWOPASS != 0) && ND == 3 && SCATTER && (K3Waves<ND, LAW, MODE>::value >= 3 || NLPS_K3_TWOPASS_ALL);
-    // NLPS_K3_PRELOAD_FN (off): F_n requested between the two passes -- the moments pass touches no memory and keeps fewer
+    constexpr bool TWOPASS = ND == 3 && SCATTER && K3Waves<ND, LAW, MODE>::value >= 3;
+    // (measured and dropped: F_n requested between the two passes -- the moments pass touches no memory and keeps fewer
     // values alive than the gather, so the nine loads would land under it instead of in front of the F update; at 168
-    // registers the nine values do not fit beside it (40 B of scratch, 2 % slower)
-    constexpr bool PRELOAD_FN = TWOPASS && (NLPS_K3_PRELOAD_FN != 0);
+    // registers the nine values do not fit beside it: 40 B of scratch, K3 0.213 -> 0.217 ms)
     double Fn[ND * ND], fzz = 0.0;
     if (TWOPASS) {
 #pragma unroll 1
@@ -1180,7 +1039,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
         const unsigned pb = plane_bits<ND>(c, k);
         const int basek = base + PS * (k - 2);
         const double zd0 = ez5[k], zd1 = zd0 * (double)(k - 2);
-#pragma unroll NLPS_JUNROLL_K3
+#pragma unroll 5  // unrolled gather rows: the LDS reads of the next rows overlap this row's arithmetic (-3 %)
         for (int j = 0; j < 5; j++) {
           const unsigned bits = (pb >> (5 * j)) & 31u;
           double m[5], R0[ND], R1[ND];
@@ -1216,11 +1075,6 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
           }
         }
       }
-      if (PRELOAD_FN) {
-        int pm = p;
-        asm volatile("" : "+v"(pm));
-        load_block<ND>(P, fFN(P), pm, Fn, fzz);
-      }
 #pragma unroll 1
       for (int k = 0; k < KN; k++) {
         const unsigned pb = plane_bits<ND>(c, k);
@@ -1255,7 +1109,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
         Jzz = fma(z2, P00, Jzz);
       }
     }
-#pragma unroll NLPS_KUNROLL_K3G
+#pragma unroll 1  // real plane loop: unrolled it spills
     for (int k = 0; k < (TWOPASS ? 0 : KN); k++) {
       const unsigned pb = plane_bits<ND>(c, k);
       const int basek = base + (ND == 3 ? PS * (k - 2) : 0);
@@ -1266,12 +1120,11 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
       for (int a = 0; a < ND; a++) Gx[a] = Gy[a] = Gz[a] = Hx[a] = Hy[a] = Hz[a] = 0.0;
       // DIRECT (3-D, no rate tensors): every row goes straight into the totals with its y*z weight -- 15 doubles of
       // plane partials less to keep alive (the kernel then fits three waves per SIMD), for 5 more FMAs per row
-      constexpr bool DIRECT = (NLPS_K3_DIRECT != 0) && ND == 3 && SCATTER && LAW == NLPS_MAT_NEO_HOOKEAN;
+      constexpr bool DIRECT = ND == 3 && SCATTER && LAW == NLPS_MAT_NEO_HOOKEAN;
       const double zd0 = ez5[k], zd1 = zd0 * (double)(k - 2), zd2 = zd1 * (double)(k - 2);
-#pragma unroll NLPS_JUNROLL_K3
+#pragma unroll 5  // (as in the two-pass gather)
       for (int j = 0; j < 5; j++) {
         const unsigned bits = (pb >> (5 * j)) & 31u;
-        if (!wave_row_used(bits)) continue;
         // INDEX space (as lme_moments_h): with l_x(i) = a_x - h (i - 2) the row weights are the integers
         // u = i - 2 in {-2..2}: no l arrays live in the loop, u = 0 terms vanish, +-1 are sign modifiers.
         double m[5], R0[ND], R1[ND], V0r[ND], V1r[ND];
@@ -1443,7 +1296,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
         for (int m = 0; m < ND; m++) v = fma(G[i * ND + m] * Zinv, Jm1[j * ND + m], v);
         DF[i * ND + j] = ((i == j) ? 1.0 : 0.0) - v;
       }
-    if (!PRELOAD_FN) load_block<ND>(P, fFN(P), pl, Fn, fzz);
+    load_block<ND>(P, fFN(P), pl, Fn, fzz);
 #pragma unroll
     for (int i = 0; i < ND; i++)
 #pragma unroll
@@ -1517,7 +1370,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
       // Measured at 1 M particles: Hencky at three waves per SIMD without scratch 0.290 ms (0.295 at two); Drucker-Prager
       // gains nothing from it (two waves with the reload 0.363 ms, three 0.358 ms with 212 B of scratch, 0.348 ms as it
       // was): those kernels are bound by their instruction count (4100 / 5900 static), not by latency.
-      constexpr bool RELOAD = (NLPS_K3_RELOAD != 0) && ND == 3 && SCATTER && LAW != NLPS_MAT_NEO_HOOKEAN && K3Waves<ND, LAW, MODE>::value >= 3;
+      constexpr bool RELOAD = ND == 3 && SCATTER && LAW != NLPS_MAT_NEO_HOOKEAN && K3Waves<ND, LAW, MODE>::value >= 3;
       Lme<ND> cs;
       if (RELOAD) {
         int p2 = pl;
@@ -1546,7 +1399,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
         Ba[a] = v;
       }
       const int basea = window_base_a<ND>(c.ijk, w0);
-#pragma unroll NLPS_KUNROLL_K3S
+#pragma unroll 1  // real plane loop: unrolled it measured +-1 %
       for (int k = 0; k < KN; k++) {
         const unsigned pb = plane_bits<ND>(c, k);
         const int basek = basea + (ND == 3 ? PSA * (k - 2) : 0);
@@ -1555,7 +1408,6 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
         double cz[ND];
 #pragma unroll
         for (int a = 0; a < ND; a++) cz[a] = (ND == 3) ? fma(hB[a * ND + (2 % ND)], ck, Ba[a]) : Ba[a];
-#if NLPS_SCATTER_POP && !NLPS_SCATTER_BRANCHFREE
         unsigned pbs = pb << 7;  // pop_member: bit 24 (j = 4, i = 4) first
 #pragma unroll
         for (int j = 4; j >= 0; j--) {
@@ -1571,34 +1423,6 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
 #pragma unroll
               for (int a = 0; a < ND; a++) lds_add(&fac[a * NWA + li], we * fma(hB[a * ND + 0], (double)(i - 2), cr[a]));
             }
-        }
-        continue;
-#endif
-#pragma unroll NLPS_JUNROLL_SCATTER
-        for (int j = 0; j < 5; j++) {
-          const unsigned bits = (pb >> (5 * j)) & 31u;
-          if (!wave_row_used(bits)) continue;
-          const double w = wz * ey5[j];
-          double cr[ND];
-#pragma unroll
-          for (int a = 0; a < ND; a++) cr[a] = fma(hB[a * ND + 1], (double)(j - 2), cz[a]);
-#pragma unroll
-          for (int i = 0; i < 5; i++)
-#if NLPS_SCATTER_BRANCHFREE
-          {
-            const int li = basek + (i - 2) + WA * (j - 2);
-            const double we = w * masked_zero(c.ex[i], bits, i);
-#pragma unroll
-            for (int a = 0; a < ND; a++) lds_add(&fac[a * NWA + li], we * fma(hB[a * ND + 0], (double)(i - 2), cr[a]));
-          }
-#else
-            if ((bits >> i) & 1u) {
-              const int li = basek + (i - 2) + WA * (j - 2);
-              const double we = w * c.ex[i];
-#pragma unroll
-              for (int a = 0; a < ND; a++) lds_add(&fac[a * NWA + li], we * fma(hB[a * ND + 0], (double)(i - 2), cr[a]));
-            }
-#endif
         }
       }
     } else {
@@ -1618,7 +1442,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     for (int qq = threadIdx.x; qq < NWA * ND; qq += NT) out[qq] = fac[qq];
     return;
   }
-  if (ND == 3 && NLPS_FAST_WINDOWS) {
+  if (ND == 3) {
     window_flush3<ND, NT>(g, w0, fac, N.force);
   } else {
     for (int qq = threadIdx.x; qq < NWA * ND; qq += NT) {
@@ -1647,10 +1471,10 @@ __global__ __launch_bounds__(NT, (NT == 64 ? 1 : (K3Waves<ND, LAW, MODE>::value)
   __shared__ int sel[L::SELCAP];
   __shared__ int nsel;
   __shared__ int wcnt[NT / 64];
-  const int nbnd = ((MODE == 1 || MODE == 3) && td.sig_flag) ? td.range[4 + 2 * (K3_SPLIT - 1) + 1] : 0;
+  const int nbnd = (MODE == 1 || MODE == 3) ? tile_boundary_count(td) : 0;
   if (MODE == 1 || MODE == 3) tile_signal_empty(td, nbnd);
   TileWork tw;
-  if (!tile_work_item<K3_SPLIT>(td, tw)) return;
+  if (!tile_work_item(td, tw)) return;
   const L lds{dvxy, dvz, duxy, duz, fac, sel, &nsel, wcnt};
   k3_body<ND, LAW, MODE, FILT, NT, UMAT>(P, g, N, td, mats, prm, gstatus, dVgrid, tw, nbnd, lds, nullptr);
 }
@@ -1687,10 +1511,10 @@ __global__ __launch_bounds__(K3_BLK, (K3Waves<ND, LAW, 1>::value)) void k3_tile_
       if (ln.node_cnt) ln.node_cnt[ln.n0 + i] = 0;
     }
   }
-  const int nbnd = td.sig_flag ? td.range[4 + 2 * (K3_SPLIT - 1) + 1] : 0;  // (overlap mode 2, as k3_tile)
+  const int nbnd = tile_boundary_count(td);  // (overlap mode 2, as k3_tile)
   tile_signal_empty(td, nbnd);
   TileWork tw;
-  if (!tile_work_item<K3_SPLIT>(td, tw)) return;
+  if (!tile_work_item(td, tw)) return;
   const L lds{dvxy, dvz, duxy, duz, fac, sel, &nsel, wcnt};
   k3_body<ND, LAW, 1, false, K3_BLK, UMAT>(P, g, N, td, mats, prm, gstatus, nullptr, tw, nbnd, lds, &ln.fs);
 }
@@ -1753,14 +1577,14 @@ __device__ __forceinline__ void k5_body(const PView& P, const GridD& g, const NV
                                         double gamma_nm, const K5Search& ks, const TileWork& tw, double* axy, double* az,
                                         const NodalFold* fs, int* __restrict__ gstatus) {
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN;
-  const int tile = tw.tile, part = tw.part, nparts = tw.nparts;
+  const int tile = tw.tile;
   const int cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
-  for (int idx0 = threadIdx.x; idx0 < ((ND == 3 && NLPS_FAST_WINDOWS) ? 512 : NW); idx0 += K5_BLK) {
+  for (int idx0 = threadIdx.x; idx0 < ((ND == 3) ? 512 : NW); idx0 += K5_BLK) {
     bool in;
     int node, idx;
-    if (ND == 3 && NLPS_FAST_WINDOWS) {
+    if (ND == 3) {
       node = window_cell3(g, w0, idx0, in);
       idx = (idx0 & 63) + PS * (idx0 >> 6);
     } else {
@@ -1785,7 +1609,7 @@ __device__ __forceinline__ void k5_body(const PView& P, const GridD& g, const NV
   const double2* a2 = reinterpret_cast<const double2*>(axy);
   const int start = td.start[tile];
   // (SEARCH: the binning is wave-cooperative, so every lane of a wave makes the same number of trips)
-  for (int s0 = part * K5_BLK; s0 < cnt; s0 += K5_BLK * nparts) {
+  for (int s0 = 0; s0 < cnt; s0 += K5_BLK) {
     const int s = s0 + (int)threadIdx.x;
     const bool have = s < cnt;
     if (!SEARCH && !have) continue;
@@ -1809,6 +1633,7 @@ __device__ __forceinline__ void k5_body(const PView& P, const GridD& g, const NV
 #pragma unroll
       for (int a = 0; a < ND; a++) sv[a] = 0.0;
       // the operands of the corrector are requested before the gather loop, so that their latency runs under it
+      // (K5 0.097 -> 0.092 ms at 1 M particles)
       double dd_[ND], vel_[ND], dis_[ND];
 #pragma unroll
       for (int a = 0; a < ND; a++) {
@@ -1816,15 +1641,14 @@ __device__ __forceinline__ void k5_body(const PView& P, const GridD& g, const NV
         vel_[a] = PF(P, F_VEL + a, p);
         dis_[a] = PF(P, F_DIS + a, p);
       }
-#pragma unroll NLPS_KUNROLL_K5
+#pragma unroll 1  // real plane loop: unrolled it measured +14 %
       for (int k = 0; k < KN; k++) {
         const unsigned pb = plane_bits<ND>(c, k);
         const int basek = base + (ND == 3 ? PS * (k - 2) : 0);
         const double z0 = ez5[k];
-#pragma unroll NLPS_JUNROLL_K5
+#pragma unroll 5  // unrolled rows, as in K3's gather
         for (int j = 0; j < 5; j++) {
           const unsigned bits = (pb >> (5 * j)) & 31u;
-          if (!wave_row_used(bits)) continue;
           double A0 = 0.0, R[ND], mw[5];
 #pragma unroll
           for (int a = 0; a < ND; a++) R[a] = 0.0;
@@ -1882,7 +1706,7 @@ __global__ __launch_bounds__(K5_BLK) void k5_tile(PView P, GridD g, NView N, Til
   __shared__ __attribute__((aligned(16))) double axy[2 * TileCfg<ND>::NW];
   __shared__ double az[(ND == 3) ? TileCfg<ND>::NW : 1];
   TileWork tw;
-  if (!tile_work_item<K5_SPLIT>(td, tw)) return;
+  if (!tile_work_item(td, tw)) return;
   k5_body<ND, LAW, SEARCH>(P, g, N, td, dt, gamma_nm, ks, tw, axy, az, nullptr, nullptr);
 }
 
@@ -1892,7 +1716,7 @@ __global__ __launch_bounds__(K5_BLK) void k5_tile_lazy(PView P, GridD g, NView N
   __shared__ __attribute__((aligned(16))) double axy[2 * TileCfg<ND>::NW];
   __shared__ double az[(ND == 3) ? TileCfg<ND>::NW : 1];
   TileWork tw;
-  if (!tile_work_item<K5_SPLIT>(td, tw)) return;
+  if (!tile_work_item(td, tw)) return;
   k5_body<ND, LAW, true>(P, g, N, td, dt, gamma_nm, ks, tw, axy, az, &ln.fs, gstatus);
 }
 
@@ -1933,7 +1757,7 @@ __global__ __launch_bounds__(BLK) void kb_p2g_tile(PView P, GridD g, TileD td, d
   __shared__ double acc[NF * NW];
   const int wb = td.range[0] + (int)blockIdx.x;
   if (wb >= td.range[1]) return;
-  const int tile = td.work[0][wb].x;
+  const int tile = td.work[wb].x;
   const int cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
@@ -1999,7 +1823,7 @@ __global__ __launch_bounds__(BLK) void kb_fint_tile(PView P, GridD g, TileD td, 
   __shared__ double fac[ND * NW];
   const int wb = td.range[0] + (int)blockIdx.x;
   if (wb >= td.range[1]) return;
-  const int tile = td.work[0][wb].x;
+  const int tile = td.work[wb].x;
   const int cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
@@ -2071,7 +1895,7 @@ __global__ __launch_bounds__(BLK) void kb_kinetics_tile(PView P, GridD g, TileD 
   __shared__ __attribute__((aligned(16))) double win[NW * NV];
   const int wb = td.range[0] + (int)blockIdx.x;
   if (wb >= td.range[1]) return;
-  const int tile = td.work[0][wb].x;
+  const int tile = td.work[wb].x;
   const int cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);

@@ -1,6 +1,11 @@
 #!/bin/bash
 # Developer tool: builds a variant of the library with extra compiler flags (kernel experiments).
-# -DNLPS_DEV=1: the only build that reads the environment switches (NLPS_LAZY_NODAL, NLPS_ADAPTIVE_RESORT) and accepts the NLPS_ABL_* / NLPS_PHASE_TIMING macros.
+# -DNLPS_DEV=1: the only build that reads the environment switches (NLPS_LAZY_NODAL, NLPS_ADAPTIVE_RESORT).
+# What a developer build can still set (measurement instruments, not alternative products):
+#   -DNLPS_PHASE_TIMING=1   per-phase wave-cycle sums of the tile kernels (tools/kbench.py --phases)
+#   -DNLPS_ABL_ATOM=1       the window scatters issue no LDS atomic (WRONG results by design)
+#   -DNLPS_ABL_GATHER=1     the gathers read a register constant instead of their window (WRONG results by design)
+# Tuning numbers (waves per SIMD, workgroup sizes, unroll factors) are plain constants beside the code they tune: edit them.
 #   tools/build_variant.sh NAME [-DNLPS_...=v ...]   ->  build/exp/lib_NAME.so   (run with NLPS_GPU_LIB=... tools/kbench.py)
 set -e
 cd "$(dirname "$0")/.."
