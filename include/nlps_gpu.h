@@ -433,6 +433,92 @@ typedef struct {
 } nlps_ksp;
 int nlps_gpu_tangent_solve(nlps_gpu *h, const double *b, double *x, nlps_ksp *ksp);
 
+/* ------------------------------------------------------------------ nonlinear solve and the implicit time step
+ * nlps_gpu_newton_solve: the SNESSolve of the maintained driver (U-Newmark-beta.c:270-356) in one call -- Newton with a
+ * line search around nlps_gpu_lagrangian_evaluation (the residual R), nlps_gpu_tangent_operator and
+ * nlps_gpu_tangent_solve, with every vector on the device from the first residual to the returned dU.
+ * dU: the initial guess on entry and the solution on return, masked [N_A*d], host or device like every other vector of
+ * the call.  Un_dt, Un_dt2, M, alpha, gravity, loads, nloads, step, thickness, area0: as for
+ * nlps_gpu_lagrangian_evaluation; alpha[0] is the alpha_1 of the operator, zeros in alpha give the quasi-static driver.
+ * The algorithm (it follows SNESSolve_NEWTONLS, SNESConvergedDefault and the bt line search with their defaults, and it
+ * is the definition of this call):
+ *   F = R(X), fnorm0 = ||F||.  fnorm0 not finite: FNORM_NAN.  fnorm0 < atol: FNORM_ABS after 0 iterations.
+ *   While iterations < max_it:
+ *     1. nlps_gpu_tangent_operator(alpha[0], M, apply_dirichlet) at the state the last residual left.
+ *     2. K Y = F by nlps_gpu_tangent_solve with snes->ksp and x0 = 0.  ksp.reason < 0: DIVERGED_LINEAR_SOLVE (PETSc's
+ *        default of one allowed failure); X stays as it is.
+ *     3. The line search: X <- X - lambda Y, the new F and fnorm.
+ *     4. iterations++.   5. snorm = lambda ||Y||, xnorm = ||X||.
+ *     6. In this order: fnorm not finite -> FNORM_NAN; fnorm < atol -> FNORM_ABS; function_evaluations > max_funcs ->
+ *        FUNCTION_COUNT; fnorm <= rtol fnorm0 -> FNORM_RELATIVE; snorm < stol xnorm -> SNORM_RELATIVE;
+ *        fnorm > divtol fnorm0 -> DTOL.
+ *   Leaving the loop without a reason: MAX_IT.
+ *   Line search NLPS_LS_BASIC: lambda = 1, one evaluation.
+ *   Line search NLPS_LS_BT (Dennis-Schnabel A6.3.1 as PETSc's bt does it), f = the current norm, g = a trial's norm:
+ *     ||Y|| > ls_maxstep: Y is scaled down to that length.  ||Y|| = 0: lambda = 1 is taken as it is.
+ *     s = F . (K Y), one product on the snapshotted operator; s > 0: s = -s; s == 0: s = -1.
+ *     minlambda = ls_steptol / max_i(|y_i| / max(|x_i|, 1)).
+ *     lambda = 1 is accepted when g^2 / 2 <= f^2 / 2 + ls_alpha lambda s (the test of every trial).
+ *     Otherwise the quadratic step lambda_t = -s / (g^2 - f^2 - 2 s), clamped to [0.1 lambda, 0.5 lambda]; after that up
+ *     to ls_max_it cubic steps through the last two trials, same clamp.  A trial whose norm is not finite halves lambda
+ *     without interpolation (so does a cubic step one of whose two trials is not finite).
+ *     lambda < minlambda ahead of a cubic step, or running out of steps: X is restored, DIVERGED_LINE_SEARCH (iterations
+ *     does not count the failed iterate).  ls_max_it = 0 switches backtracking off: a rejected full step fails.
+ * Differences from PETSc: right preconditioning and the true-residual norm in the linear solve (nlps_gpu_tangent_solve),
+ * x0 = 0 for every linear solve, no Jacobian lagging (a new operator every iterate, PETSc's default).
+ * State after the call, whatever the reason: the particle state (DF, F_n1, J_n1, Stress, W, b_e_n1, Kappa_n1, EPS_n1,
+ * C_ep) is the one a residual evaluation at the returned dU leaves, so nlps_gpu_roll_state and nlps_gpu_update_kinetics
+ * can follow directly.  A rejected trial is never the last evaluation: after a restore the residual is evaluated at X
+ * again, and that evaluation counts in function_evaluations.
+ * Returns 1 where nlps_gpu_lagrangian_evaluation, nlps_gpu_tangent_operator or nlps_gpu_tangent_solve return 1 (a handle
+ * that exchanges halos included: single rank only), for snes == NULL, a negative tolerance, max_it < 0, ls_max_it < 0 or
+ * an unknown line search; 0 when the solve ran, converged or not (snes->reason).
+ * Host vectors cross PCIe once per call (dU in and out, the three constant vectors in).  The work vectors (X, Y, W, F,
+ * K Y, the constant vectors) and the partial sums are kept on the handle and only grow: 8 * (8 n + 5 ceil(n / 512)) bytes,
+ * n = N_A d, beside the workspace of the linear solve.  No allocation inside the loop.  One stream synchronisation per
+ * residual evaluation (the scalars of the line search arrive with it), besides the operator's and the linear solve's. */
+enum { NLPS_LS_BASIC = 0, NLPS_LS_BT = 1 };
+enum {
+  NLPS_SNES_CONVERGED_FNORM_ABS = 2, NLPS_SNES_CONVERGED_FNORM_RELATIVE = 3, NLPS_SNES_CONVERGED_SNORM_RELATIVE = 4,
+  NLPS_SNES_DIVERGED_FUNCTION_COUNT = -2, NLPS_SNES_DIVERGED_LINEAR_SOLVE = -3, NLPS_SNES_DIVERGED_FNORM_NAN = -4,
+  NLPS_SNES_DIVERGED_MAX_IT = -5, NLPS_SNES_DIVERGED_LINE_SEARCH = -6, NLPS_SNES_DIVERGED_DTOL = -9
+}; /* PETSc's SNESConvergedReason values */
+typedef struct {
+  /* in */
+  int max_it, max_funcs;           /* driver: Parameters_Solver.MaxIter, 10000 */
+  double atol, rtol, stol, divtol; /* driver: 100*TOL_Newmark_beta, TOL_Newmark_beta, 1e-8, 1e4 */
+  int linesearch;                  /* NLPS_LS_* */
+  double ls_alpha, ls_steptol, ls_maxstep; /* bt defaults 1e-4, 1e-12, 1e8 */
+  int ls_max_it;                           /* bt default 40 */
+  int apply_dirichlet;             /* as nlps_gpu_tangent_operator; the driver: 1 */
+  nlps_ksp ksp;                    /* settings of every linear solve (x_is_guess is ignored); on return the last solve's outputs */
+  double *fnorm_history;           /* host, max_it + 1, or NULL */
+  double *lambda_history;          /* host, max_it: the accepted step length of each iterate, or NULL */
+  int *ksp_iterations;             /* host, max_it: Arnoldi steps of each iterate, or NULL */
+  /* out */
+  int reason, iterations, function_evaluations, linear_iterations;
+  double fnorm0, fnorm, snorm, xnorm;
+} nlps_snes;
+int nlps_gpu_newton_solve(nlps_gpu *h, double *dU, const double *Un_dt, const double *Un_dt2, const double *M,
+                          const double *alpha, const double *gravity, const nlps_bcc *loads, int nloads, int step,
+                          double thickness, const double *area0, nlps_snes *snes);
+
+/* nlps_gpu_newmark_step: the body of the driver's time loop (U-Newmark-beta.c:192-404) in one call, in the driver's
+ * order: nlps_gpu_local_search, nlps_gpu_active_masks(bcc, nbcc, step), nlps_gpu_lumped_mass, nlps_gpu_nodal_field_n, the
+ * Newmark parameters of :497-514 from beta, gamma, dt, nlps_gpu_form_initial_guess(dt, use_explicit_trial, bcc, step),
+ * nlps_gpu_newton_solve, nlps_gpu_nodal_kinetic_increments, nlps_gpu_roll_state and
+ * nlps_gpu_update_kinetics(alpha_blend).  The nodal vectors (M, Un_dt, Un_dt2, dU and the increments) are kept on the
+ * handle; none leaves the device unless dU_out is a host pointer.  *nactive (may be NULL) = N_A of this step; dU_out
+ * (may be NULL, host or device) receives the N_A*d converged increments and needs room for nnodes*d doubles.
+ * The particle update runs only when snes->reason > 0.  Otherwise the call returns 0 with the reason set, and the
+ * particles sit at the last evaluated state, not rolled and not moved: the caller decides what to do (a smaller step,
+ * other tolerances, stop).  Returns 1 where one of the composed calls returns 1, and for a dt or beta that is not
+ * positive. */
+typedef struct { double beta, gamma, dt, alpha_blend; int use_explicit_trial; } nlps_newmark;
+int nlps_gpu_newmark_step(nlps_gpu *h, const nlps_bcc *bcc, int nbcc, int step, const nlps_newmark *nm,
+                          const double *gravity, const nlps_bcc *loads, int nloads, double thickness,
+                          const double *area0, nlps_snes *snes, int *nactive, double *dU_out /* or NULL */);
+
 /* ------------------------------------------------------------------ multi-GPU hooks */
 
 /* Halo exchange callback, invoked by explicit_step / the P2G stages after a nodal scatter, on the

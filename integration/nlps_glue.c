@@ -373,3 +373,99 @@ int nlps_glue_linear_solve(const nlps_glue *G, const double *b_ptr, double *x_pt
   }
   return EXIT_SUCCESS;
 }
+
+/* the driver's SNES settings (U-Newmark-beta.c:170-172, :328-334): SNESSetTolerances(100 TOL, TOL, default stol 1e-8,
+ * MaxIter, default 10000 evaluations), divergence tolerance 1e4, the bt line search with PETSc's defaults, PCJACOBI and
+ * GMRES(30) with KSP's default tolerances (rtol 1e-5, atol 1e-50, dtol 1e5, 10000 iterations) */
+static nlps_snes nlps_glue_snes(double TOL, int MaxIter) {
+  nlps_snes S;
+  memset(&S, 0, sizeof S);
+  S.max_it = MaxIter;
+  S.max_funcs = 10000;
+  S.atol = 100.0 * TOL;
+  S.rtol = TOL;
+  S.stol = 1e-8;
+  S.divtol = 1e4;
+  S.linesearch = NLPS_LS_BT;
+  S.ls_alpha = 1e-4;
+  S.ls_steptol = 1e-12;
+  S.ls_maxstep = 1e8;
+  S.ls_max_it = 40;
+  S.apply_dirichlet = 1;
+  S.ksp.pc = NLPS_PC_JACOBI;
+  S.ksp.restart = 30;
+  S.ksp.max_it = 10000;
+  S.ksp.rtol = 1e-5;
+  S.ksp.atol = 1e-50;
+  S.ksp.dtol = 1e5;
+  return S;
+}
+
+static int nlps_glue_snes_report(const nlps_glue *G, int STATUS, const nlps_snes *S) {
+  if (STATUS != EXIT_SUCCESS) {
+    fprintf(stderr, "" RED "%s" RESET "\n", nlps_gpu_last_error(G->gpu));
+    return EXIT_FAILURE;
+  }
+  if (S->reason < 0) {
+    fprintf(stderr, "" RED "nlps_gpu_newton_solve: no convergence (reason %d) after %d iterations, ||F|| = %e of %e" RESET "\n",
+            S->reason, S->iterations, S->fnorm, S->fnorm0);
+    return EXIT_FAILURE;
+  }
+  return EXIT_SUCCESS;
+}
+
+/* The SNESSolve(snes, NULL, dU) of U-Newmark-beta.c:356 as one library call, after VecGetArray(dU, &dU_ptr) (the
+ * initial guess of __form_initial_guess in, the converged increment out) and VecGetArrayRead of ctx->U_n_dt, U_n_dt2 and
+ * Lumped_Mass: neither SNES nor KSP nor a Jacobian matrix is needed any more.  TOL = Parameters_Solver.TOL_Newmark_beta,
+ * MaxIter = Parameters_Solver.MaxIter; the other arguments as nlps_glue_lagrangian_evaluation.  *snes_iterations /
+ * *ksp_iterations (may be NULL) are what print_convergence_stats reports (:2078).  A solve that does not converge prints
+ * its reason and returns EXIT_FAILURE, where the driver tests SNESGetConvergedReason. */
+int nlps_glue_newton_solve(const nlps_glue *G, Particle MPM_Mesh, double *dU_ptr, const double *Un_dt_ptr,
+                           const double *Un_dt2_ptr, const double *Lumped_Mass_ptr, const double alpha[6],
+                           const double *gravity, const nlps_bcc *neumann, int nneumann, int TimeStep, double TOL,
+                           int MaxIter, int *snes_iterations, int *ksp_iterations) {
+#if NumberDimensions == 2
+  const double thickness = Thickness_Plain_Stress;
+  const double *area0 = NULL;
+#else
+  const double thickness = 1.0;
+  const double *area0 = MPM_Mesh.Phi.Area_0.nV;
+#endif
+  nlps_snes S = nlps_glue_snes(TOL, MaxIter);
+  const int STATUS = nlps_gpu_newton_solve(G->gpu, dU_ptr, Un_dt_ptr, Un_dt2_ptr, Lumped_Mass_ptr, alpha, gravity, neumann,
+                                           nneumann, TimeStep, thickness, area0, &S);
+  if (snes_iterations) *snes_iterations = S.iterations;
+  if (ksp_iterations) *ksp_iterations = S.linear_iterations;
+  return nlps_glue_snes_report(G, STATUS, &S);
+}
+
+/* The body of the time loop, U-Newmark-beta.c:192-404, as one library call: local search, masks, lumped mass, nodal
+ * field, Newmark parameters, initial guess, SNESSolve, kinetic increments and the particle update, with every nodal
+ * vector on the device.  bcc / nbcc from nlps_glue_boundaries; beta, gamma, Use_explicit_trial of Parameters_Solver
+ * (:144-147), DeltaTimeStep of __compute_deltat (:180); alpha_blend = 1 is the driver's FLIP / PIC blend (:148).
+ * *Nactivenodes (may be NULL) = the active nodes of the step.  Returns EXIT_FAILURE when the solve did not converge: the
+ * particles are then left at the last evaluated state, not updated. */
+int nlps_glue_newmark_step(const nlps_glue *G, Particle MPM_Mesh, const nlps_bcc *bcc, int nbcc, int TimeStep, double beta,
+                           double gamma, double DeltaTimeStep, bool Use_explicit_trial, const double *gravity,
+                           const nlps_bcc *neumann, int nneumann, double TOL, int MaxIter, int *Nactivenodes,
+                           int *snes_iterations, int *ksp_iterations) {
+#if NumberDimensions == 2
+  const double thickness = Thickness_Plain_Stress;
+  const double *area0 = NULL;
+#else
+  const double thickness = 1.0;
+  const double *area0 = MPM_Mesh.Phi.Area_0.nV;
+#endif
+  nlps_snes S = nlps_glue_snes(TOL, MaxIter);
+  nlps_newmark NM;
+  NM.beta = beta;
+  NM.gamma = gamma;
+  NM.dt = DeltaTimeStep;
+  NM.alpha_blend = 1.0;
+  NM.use_explicit_trial = Use_explicit_trial ? 1 : 0;
+  const int STATUS = nlps_gpu_newmark_step(G->gpu, bcc, nbcc, TimeStep, &NM, gravity, neumann, nneumann, thickness, area0, &S,
+                                           Nactivenodes, NULL);
+  if (snes_iterations) *snes_iterations = S.iterations;
+  if (ksp_iterations) *ksp_iterations = S.linear_iterations;
+  return nlps_glue_snes_report(G, STATUS, &S);
+}

@@ -1315,6 +1315,7 @@ __global__ __launch_bounds__(BLK) void k_fill_orders(int np, const int* __restri
 #include "nlps_tangent_kernels.hpp"
 #include "nlps_tangent_operator.hpp"
 #include "nlps_krylov.hpp"
+#include "nlps_newton.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // physical re-sort of the particle SoA (maintenance, every few dozen steps): restores the
@@ -1681,6 +1682,19 @@ struct nlps_gpu {
   KspHost* ksp_h = nullptr;  // pinned: what the host reads per step
   KspHost* ksp_hd = nullptr; // its device alias (nullptr: the kernels write ksp_hdev and the host copies)
   KspHost* ksp_hdev = nullptr;
+  // Newton solve (nlps_gpu_newton_solve, nlps_newton.hpp), allocated on first use and kept (they only grow)
+  double* snes_v = nullptr;     // [8 n]: X, Y, W, F, K Y and the device copies of Un_dt, Un_dt2, M
+  size_t snes_v_cap = 0;
+  double* snes_part = nullptr;  // [5 nb]: per-block partials of the trial update (3 columns) and the dots (2)
+  size_t snes_part_cap = 0;
+  double* snes_h = nullptr;     // pinned [SNES_H_N]: the scalars the host reads after a residual evaluation
+  double* snes_hd = nullptr;    // its device alias (nullptr: the kernels write snes_hdev and a copy follows them)
+  double* snes_hdev = nullptr;
+  bool snes_tail = false;       // the next fused residual evaluation queues F . F ahead of its own synchronisation
+  int snes_nb = 0;
+  // implicit time step (nlps_gpu_newmark_step): M, Un_dt, Un_dt2, dU, dU_dt, dU_dt2, masked [N_A d] each
+  double* nm_v = nullptr;
+  size_t nm_v_cap = 0;
   int* order_d;
   // canonical (layer, closest node) order of every tile list each step for the LDS-atomic-bound K2 and K3; the
   // memory-bound K5 keeps the lists as binned.  13 us per step at 1 M particles.  A freshly sorted cloud has its lists in
@@ -2540,7 +2554,7 @@ extern "C" int nlps_gpu_destroy(nlps_gpu* h) {
                   h->fixedm_d, h->bsum_d, h->total_d, h->gstatus_d, h->gridA, h->gridB, h->maskedA, h->mats_d,
                   h->rank1_d, h->P.tile, h->P.rank, h->order_d, h->order2_d, h->tile_count_d, h->tile_count2_d, h->tile_start_d, h->work1_d, h->nwork_d, h->slab_d, h->dmg_first_d, h->dmg_last_d, h->dmg_first0_d, h->dmg_last0_d, h->dmg_sorted0_d, h->perm_d, h->skey_d, h->skey2_d, h->sval_d, h->sval2_d,
                   h->gather_tmp, h->cub_tmp, h->gid_d, h->leaving_d, h->mig_slot_d, h->mig_cnt_d, h->mig_down_d, h->mig_up_d, h->kst_d, h->ktouched_d, h->kcnt_d, h->koffs_d, h->kscan_tmp, h->khead_d, h->kng_d, h->vec_d, h->bcmask_d, h->home_d, h->foreign_d, h->node_cnt_d, h->nrank_d, h->tabo_d, h->tabm_d, h->tile_cursor_d, h->top_d, h->top_m, h->top_g, h->top_b,
-                  h->ksp_pc, h->ksp_v, h->ksp_part, h->ksp_s, h->ksp_bad_d, h->ksp_hdev};
+                  h->ksp_pc, h->ksp_v, h->ksp_part, h->ksp_s, h->ksp_bad_d, h->ksp_hdev, h->snes_v, h->snes_part, h->snes_hdev, h->nm_v};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& b : h->bcs)
@@ -2549,6 +2563,7 @@ extern "C" int nlps_gpu_destroy(nlps_gpu* h) {
   if (h->lagr_d) (void)hipFree(h->lagr_d);
   if (h->status_h) (void)hipHostFree(h->status_h);
   if (h->ksp_h) (void)hipHostFree(h->ksp_h);
+  if (h->snes_h) (void)hipHostFree(h->snes_h);
   for (int i = 0; i < 8; i++) (void)hipEventDestroy(h->ev[i]);
   for (hipEvent_t e : h->evw)
     if (e) (void)hipEventDestroy(e);
@@ -4524,6 +4539,8 @@ __global__ void k_lagrangian_nodal(int nnodes, const int* __restrict__ n2m, cons
   }
 }
 
+static int snes_fnorm_launch(nlps_gpu* h, const double* F);  // (defined with nlps_gpu_newton_solve)
+
 extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const double* dU, const double* Un_dt,
                                               const double* Un_dt2, const double* M, const double* alpha,
                                               const double* gravity, const nlps_bcc* loads, int nloads, int step,
@@ -4639,6 +4656,7 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
             (const int*)h->d2m_d, (const double*)h->N.force, any ? (const double*)h->gridA : (const double*)nullptr, r, m, u, v,
             a, alpha[0], alpha[1], alpha[2], b[0], b[1], b[2], (const int*)h->gstatus_d, h->status_hd);
   HIPCHK(hipGetLastError());
+  if (h->snes_tail && snes_fnorm_launch(h, r)) return 1;  // (nlps_gpu_newton_solve: ||R||^2 arrives with the wait below)
   if (io.finish()) {
     h->err = "nlps_gpu_lagrangian_evaluation: HIP error";
     return 1;
@@ -5175,4 +5193,278 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
   }
   if (io.back.empty()) HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Newton solve (nlps_newton.hpp): the driver's SNESSolve (NEWTONLS, basic or bt line search) in one call
+// ------------------------------------------------------------------------------------------------
+static int snes_grow(nlps_gpu* h, const char* who, double** p, size_t* cap, size_t n, const char* what) {
+  if (n <= *cap) return 0;
+  if (*p) HIPCHK(hipFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  if (tanop_alloc(h, who, (void**)p, n * sizeof(double), what)) return 1;
+  *cap = n;
+  return 0;
+}
+
+// queues F . F of a device residual towards the host word (stream order, no wait)
+static int snes_fnorm_launch(nlps_gpu* h, const double* F) {
+  const int n = h->nactive * h->nd, nb = h->snes_nb;
+  double* const hw = h->snes_hd ? h->snes_hd : h->snes_hdev;
+  double* const part = h->snes_part + (size_t)3 * nb;
+  hipLaunchKernelGGL(k_snes_dots, dim3(nb), dim3(KSP_NT), 0, h->stream, n, F, (const double*)nullptr, part, nb);
+  hipLaunchKernelGGL(k_snes_finish, dim3(1), dim3(KSP_NT), 0, h->stream, (const double*)part, nb, -1, hw + SNES_H_FF);
+  HIPCHK(hipGetLastError());
+  if (!h->snes_hd) HIPCHK(hipMemcpyAsync(h->snes_h, h->snes_hdev, SNES_H_N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  h->snes_tail = false;
+  return 0;
+}
+
+// what every residual evaluation of one solve shares (device pointers)
+struct SnesResidual {
+  const double *v, *a, *m, *alpha, *gravity;
+  const nlps_bcc* loads;
+  int nloads, step;
+  double thickness;
+  const double* area0;
+};
+
+// F = R(x) and its norm: the fused evaluation queues the norm ahead of its own synchronisation (snes_tail), the
+// composition of the separate stages is followed by the norm and a wait
+static int snes_residual(nlps_gpu* h, const SnesResidual& r, const double* x, double* F, nlps_snes* snes, double* fnorm) {
+  h->snes_tail = true;
+  const int st = nlps_gpu_lagrangian_evaluation(h, F, x, r.v, r.a, r.m, r.alpha, r.gravity, r.loads, r.nloads, r.step,
+                                                r.thickness, r.area0, 0);
+  const bool queued = !h->snes_tail;
+  h->snes_tail = false;
+  if (st) return 1;
+  if (!queued) {
+    if (snes_fnorm_launch(h, F)) return 1;
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  snes->function_evaluations++;
+  *fnorm = sqrt(((volatile double*)h->snes_h)[SNES_H_FF]);
+  return 0;
+}
+
+extern "C" int nlps_gpu_newton_solve(nlps_gpu* h, double* dU, const double* Un_dt, const double* Un_dt2, const double* M,
+                                     const double* alpha, const double* gravity, const nlps_bcc* loads, int nloads, int step,
+                                     double thickness, const double* area0, nlps_snes* snes) {
+  const char* who = "nlps_gpu_newton_solve";
+  if (!snes) {
+    h->err = "nlps_gpu_newton_solve: snes is required";
+    return 1;
+  }
+  snes->reason = snes->iterations = snes->function_evaluations = snes->linear_iterations = 0;
+  snes->fnorm0 = snes->fnorm = snes->snorm = snes->xnorm = 0.0;
+  if (need_masks(h, who)) return 1;
+  if (h->halo || (h->rccl && h->rccl->world > 1)) {
+    h->err = "nlps_gpu_newton_solve: single rank only: this handle exchanges halos (a halo callback or an RCCL world > 1), "
+             "and norms across ranks would need an owner mask and an allreduce";
+    return 1;
+  }
+  if (!dU || !Un_dt || !Un_dt2 || !M || !alpha) {
+    h->err = "nlps_gpu_newton_solve: dU, Un_dt, Un_dt2, M and alpha are required";
+    return 1;
+  }
+  if (!(snes->atol >= 0.0) || !(snes->rtol >= 0.0) || !(snes->stol >= 0.0) || !(snes->divtol >= 0.0) || snes->max_it < 0) {
+    h->err = "nlps_gpu_newton_solve: atol, rtol, stol, divtol and max_it must be >= 0";
+    return 1;
+  }
+  const bool bt = snes->linesearch == NLPS_LS_BT;
+  if (!bt && snes->linesearch != NLPS_LS_BASIC) {
+    h->err = "nlps_gpu_newton_solve: linesearch must be NLPS_LS_BASIC or NLPS_LS_BT";
+    return 1;
+  }
+  if (bt && (snes->ls_max_it < 0 || !(snes->ls_alpha >= 0.0) || !(snes->ls_steptol >= 0.0) || !(snes->ls_maxstep > 0.0))) {
+    h->err = "nlps_gpu_newton_solve: ls_max_it, ls_alpha and ls_steptol must be >= 0 and ls_maxstep > 0";
+    return 1;
+  }
+  const size_t n = (size_t)h->nactive * h->nd;
+  const int nb = (int)std::max<size_t>((n + KSP_TILE - 1) / KSP_TILE, 1);
+  if (snes_grow(h, who, &h->snes_v, &h->snes_v_cap, 8 * std::max<size_t>(n, 1), "the work vectors") ||
+      snes_grow(h, who, &h->snes_part, &h->snes_part_cap, (size_t)5 * nb, "the partial sums"))
+    return 1;
+  h->snes_nb = nb;
+  if (!h->snes_h) {
+    HIPCHK(hipHostMalloc((void**)&h->snes_h, SNES_H_N * sizeof(double), hipHostMallocDefault));
+    memset(h->snes_h, 0, SNES_H_N * sizeof(double));
+    if (hipHostGetDevicePointer((void**)&h->snes_hd, h->snes_h, 0) != hipSuccess) {
+      (void)hipGetLastError();
+      h->snes_hd = nullptr;
+      if (tanop_alloc(h, who, (void**)&h->snes_hdev, SNES_H_N * sizeof(double), "the scalars of the line search")) return 1;
+    }
+  }
+  volatile double* const hv = h->snes_h;
+  double* const hw = h->snes_hd ? h->snes_hd : h->snes_hdev;
+  double *X = h->snes_v, *Y = X + n, *W = Y + n, *F = W + n, *T = F + n;
+  // host vectors cross once: dU into X, the three constant vectors into their slots
+  if (n > 0) HIPCHK(hipMemcpyAsync(X, dU, n * sizeof(double), hipMemcpyDefault, h->stream));
+  const double* cst[3] = {Un_dt, Un_dt2, M};
+  for (int q = 0; q < 3; q++) {
+    if (is_device_ptr(cst[q]) || n == 0) continue;
+    double* d = T + (size_t)(q + 1) * n;
+    HIPCHK(hipMemcpyAsync(d, cst[q], n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    cst[q] = d;
+  }
+  const SnesResidual res{cst[0], cst[1], cst[2], alpha, gravity, loads, nloads, step, thickness, area0};
+  const dim3 gs(nb), bs(KSP_NT);
+  // W = X - lambda Y with its three scalars towards the host word (stream order)
+  auto trial = [&](double lambda) -> int {
+    hipLaunchKernelGGL(k_snes_trial, gs, bs, 0, h->stream, (int)n, (const double*)X, (const double*)Y, lambda, W, h->snes_part, nb);
+    hipLaunchKernelGGL(k_snes_finish, dim3(3), bs, 0, h->stream, (const double*)h->snes_part, nb, 2, hw + SNES_H_WW);
+    HIPCHK(hipGetLastError());
+    return 0;
+  };
+  double fnorm = 0.0;
+  if (snes_residual(h, res, X, F, snes, &fnorm)) return 1;
+  snes->fnorm0 = snes->fnorm = fnorm;
+  if (snes->fnorm_history) snes->fnorm_history[0] = fnorm;
+  int reason = 0;
+  if (!std::isfinite(fnorm)) reason = NLPS_SNES_DIVERGED_FNORM_NAN;
+  else if (fnorm < snes->atol) reason = NLPS_SNES_CONVERGED_FNORM_ABS;
+  const double fnorm0 = fnorm;
+  while (!reason && snes->iterations < snes->max_it) {
+    const int it = snes->iterations;
+    if (nlps_gpu_tangent_operator(h, alpha[0], res.m, snes->apply_dirichlet, nullptr)) return 1;
+    nlps_ksp k = snes->ksp;
+    k.x_is_guess = 0;
+    const int kst = nlps_gpu_tangent_solve(h, F, Y, &k);
+    snes->ksp.reason = k.reason;
+    snes->ksp.iterations = k.iterations;
+    snes->ksp.rnorm = k.rnorm;
+    snes->ksp.bnorm = k.bnorm;
+    snes->ksp.bytes = k.bytes;
+    if (kst) return 1;
+    snes->linear_iterations += k.iterations;
+    if (snes->ksp_iterations) snes->ksp_iterations[it] = k.iterations;
+    if (k.reason < 0) {  // (the state is still the one of the evaluation at X)
+      reason = NLPS_SNES_DIVERGED_LINEAR_SOLVE;
+      break;
+    }
+    double lambda = 1.0, ynorm = 0.0, gnorm = 0.0;
+    bool accepted = true;
+    if (!bt) {
+      if (trial(1.0) || snes_residual(h, res, W, F, snes, &gnorm)) return 1;
+      ynorm = sqrt(hv[SNES_H_YY]);
+    } else {
+      // the slope F . (K Y) on the snapshotted operator, then the full step: its evaluation brings every scalar over
+      if (n > 0 && tanop_product(h, Y, T, nullptr)) return 1;
+      double* const part = h->snes_part + (size_t)3 * nb;
+      hipLaunchKernelGGL(k_snes_dots, gs, bs, 0, h->stream, (int)n, (const double*)F, n > 0 ? (const double*)T : (const double*)nullptr, part, nb);
+      hipLaunchKernelGGL(k_snes_finish, dim3(n > 0 ? 2 : 1), bs, 0, h->stream, (const double*)part, nb, -1, hw + SNES_H_FF);
+      HIPCHK(hipGetLastError());
+      if (trial(1.0) || snes_residual(h, res, W, F, snes, &gnorm)) return 1;
+      double s = n > 0 ? hv[SNES_H_FT] : 0.0, ratio = hv[SNES_H_RATIO], ysc = 1.0;
+      ynorm = sqrt(hv[SNES_H_YY]);
+      if (ynorm > snes->ls_maxstep) {  // Y is too long: the full step was evaluated for nothing (it counts), the scaled one follows
+        ysc = snes->ls_maxstep / ynorm;
+        s *= ysc;
+        ratio *= ysc;
+        ynorm = snes->ls_maxstep;
+        if (trial(ysc) || snes_residual(h, res, W, F, snes, &gnorm)) return 1;
+      }
+      if (s > 0.0) s = -s;
+      if (s == 0.0) s = -1.0;
+      const double minlambda = snes->ls_steptol / ratio, f2 = fnorm * fnorm;
+      auto accept = [&](double g, double lam) { return std::isfinite(g) && 0.5 * g * g <= 0.5 * f2 + snes->ls_alpha * lam * s; };
+      auto clamp = [](double lt, double lam) { return lt > 0.5 * lam ? 0.5 * lam : (lt <= 0.1 * lam ? 0.1 * lam : lt); };
+      if (ynorm != 0.0 && !accept(gnorm, lambda)) {
+        accepted = false;
+        if (snes->ls_max_it > 0) {
+          // the quadratic step through f, the slope and the full step
+          double g2 = gnorm * gnorm;
+          double lprev = lambda, g2prev = g2;
+          lambda = std::isfinite(g2) ? clamp(-s / (g2 - f2 - 2.0 * lambda * s), lambda) : 0.5 * lambda;
+          if (trial(lambda * ysc) || snes_residual(h, res, W, F, snes, &gnorm)) return 1;
+          accepted = accept(gnorm, lambda);
+          for (int c = 0; !accepted && c < snes->ls_max_it; c++) {
+            if (lambda < minlambda) break;
+            g2 = gnorm * gnorm;
+            double lt = 0.5 * lambda;
+            if (std::isfinite(g2) && std::isfinite(g2prev)) {  // the cubic through the last two trials
+              const double t1 = 0.5 * (g2 - f2) - lambda * s, t2 = 0.5 * (g2prev - f2) - lprev * s;
+              const double a = (t1 / (lambda * lambda) - t2 / (lprev * lprev)) / (lambda - lprev);
+              const double b = (-lprev * t1 / (lambda * lambda) + lambda * t2 / (lprev * lprev)) / (lambda - lprev);
+              double d = b * b - 3.0 * a * s;
+              if (d < 0.0) d = 0.0;
+              lt = a == 0.0 ? -s / (2.0 * b) : (-b + sqrt(d)) / (3.0 * a);
+              lt = clamp(lt, lambda);
+            }
+            lprev = lambda;
+            g2prev = g2;
+            lambda = lt;
+            if (trial(lambda * ysc) || snes_residual(h, res, W, F, snes, &gnorm)) return 1;
+            accepted = accept(gnorm, lambda);
+          }
+        }
+      }
+    }
+    if (!accepted) {  // X is restored: the state of a rejected trial must not be the one the call leaves
+      if (snes_residual(h, res, X, F, snes, &fnorm)) return 1;
+      reason = NLPS_SNES_DIVERGED_LINE_SEARCH;
+      break;
+    }
+    std::swap(X, W);
+    fnorm = gnorm;
+    snes->iterations = it + 1;
+    snes->fnorm = fnorm;
+    snes->snorm = lambda * ynorm;
+    snes->xnorm = sqrt(hv[SNES_H_WW]);
+    if (snes->fnorm_history) snes->fnorm_history[it + 1] = fnorm;
+    if (snes->lambda_history) snes->lambda_history[it] = lambda;
+    if (!std::isfinite(fnorm)) reason = NLPS_SNES_DIVERGED_FNORM_NAN;
+    else if (fnorm < snes->atol) reason = NLPS_SNES_CONVERGED_FNORM_ABS;
+    else if (snes->function_evaluations > snes->max_funcs) reason = NLPS_SNES_DIVERGED_FUNCTION_COUNT;
+    else if (fnorm <= snes->rtol * fnorm0) reason = NLPS_SNES_CONVERGED_FNORM_RELATIVE;
+    else if (snes->snorm < snes->stol * snes->xnorm) reason = NLPS_SNES_CONVERGED_SNORM_RELATIVE;
+    else if (fnorm > snes->divtol * fnorm0) reason = NLPS_SNES_DIVERGED_DTOL;
+  }
+  if (!reason) reason = NLPS_SNES_DIVERGED_MAX_IT;
+  snes->reason = reason;
+  snes->fnorm = fnorm;
+  if (n > 0) HIPCHK(hipMemcpyAsync(dU, X, n * sizeof(double), hipMemcpyDefault, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the body of the implicit driver's time loop (U-Newmark-beta.c:192-404) in one call
+// ------------------------------------------------------------------------------------------------
+extern "C" int nlps_gpu_newmark_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc, int step, const nlps_newmark* nm,
+                                     const double* gravity, const nlps_bcc* loads, int nloads, double thickness,
+                                     const double* area0, nlps_snes* snes, int* nactive, double* dU_out) {
+  const char* who = "nlps_gpu_newmark_step";
+  if (!nm || !snes) {
+    h->err = "nlps_gpu_newmark_step: nm and snes are required";
+    return 1;
+  }
+  if (!(nm->dt > 0.0) || !(nm->beta > 0.0)) {
+    h->err = "nlps_gpu_newmark_step: dt and beta must be positive";
+    return 1;
+  }
+  if (nlps_gpu_local_search(h)) return 1;                                               // :197
+  int na = 0;
+  if (nlps_gpu_active_masks(h, bcc, nbcc, step, &na, nullptr, nullptr, nullptr)) return 1;  // :205-209
+  if (nactive) *nactive = na;
+  const size_t n = (size_t)na * h->nd;
+  if (snes_grow(h, who, &h->nm_v, &h->nm_v_cap, 6 * std::max<size_t>(n, 1), "the nodal vectors of the step")) return 1;
+  double *M = h->nm_v, *V = M + n, *A = V + n, *dU = A + n, *dV = dU + n, *dA = dV + n;
+  if (nlps_gpu_lumped_mass(h, M)) return 1;                                             // :223
+  if (nlps_gpu_nodal_field_n(h, V, A, M)) return 1;                                     // :241
+  const double beta = nm->beta, gamma = nm->gamma, dt = nm->dt;                         // :497-514
+  const double alpha[6] = {1.0 / (beta * dt * dt), 1.0 / (beta * dt), (1.0 - 2.0 * beta) / (2.0 * beta), gamma / (beta * dt),
+                           1.0 - gamma / beta, (1.0 - gamma / (2.0 * beta)) * dt};
+  if (n > 0) HIPCHK(hipMemsetAsync(dU, 0, n * sizeof(double), h->stream));
+  if (nlps_gpu_form_initial_guess(h, dU, V, A, dt, nm->use_explicit_trial, bcc, nbcc, step)) return 1;  // :255
+  if (nlps_gpu_newton_solve(h, dU, V, A, M, alpha, gravity, loads, nloads, step, thickness, area0, snes)) return 1;  // :356
+  if (dU_out && n > 0) {
+    HIPCHK(hipMemcpyAsync(dU_out, dU, n * sizeof(double), hipMemcpyDefault, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  if (snes->reason <= 0) return 0;  // (not converged: the particles stay at the last evaluated state, not rolled)
+  if (nlps_gpu_nodal_kinetic_increments(h, dV, dA, dU, V, A, alpha)) return 1;          // :380
+  if (nlps_gpu_roll_state(h)) return 1;                                                 // :393
+  return nlps_gpu_update_kinetics(h, nm->alpha_blend, dU, V, dV, dA);                   // :396
 }

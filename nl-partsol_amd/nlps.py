@@ -67,6 +67,27 @@ KSP_REASONS = {1: "converged_bzero", 2: "converged_rtol", 3: "converged_atol", -
                -5: "diverged_breakdown", -9: "diverged_nanorinf"}
 
 
+class Snes(C.Structure):  # nlps_snes: nlps_gpu_newton_solve's settings and results
+    _fields_ = [("max_it", C.c_int), ("max_funcs", C.c_int), ("atol", C.c_double), ("rtol", C.c_double),
+                ("stol", C.c_double), ("divtol", C.c_double), ("linesearch", C.c_int), ("ls_alpha", C.c_double),
+                ("ls_steptol", C.c_double), ("ls_maxstep", C.c_double), ("ls_max_it", C.c_int),
+                ("apply_dirichlet", C.c_int), ("ksp", Ksp), ("fnorm_history", _dp), ("lambda_history", _dp),
+                ("ksp_iterations", _ip), ("reason", C.c_int), ("iterations", C.c_int),
+                ("function_evaluations", C.c_int), ("linear_iterations", C.c_int), ("fnorm0", C.c_double),
+                ("fnorm", C.c_double), ("snorm", C.c_double), ("xnorm", C.c_double)]
+
+
+class Newmark(C.Structure):  # nlps_newmark
+    _fields_ = [("beta", C.c_double), ("gamma", C.c_double), ("dt", C.c_double), ("alpha_blend", C.c_double),
+                ("use_explicit_trial", C.c_int)]
+
+
+LINE_SEARCHES = {"basic": 0, "bt": 1}  # NLPS_LS_BASIC / _BT
+SNES_REASONS = {2: "converged_fnorm_abs", 3: "converged_fnorm_relative", 4: "converged_snorm_relative",
+                -2: "diverged_function_count", -3: "diverged_linear_solve", -4: "diverged_fnorm_nan",
+                -5: "diverged_max_it", -6: "diverged_line_search", -9: "diverged_dtol"}
+
+
 class Bcc(C.Structure):
     _fields_ = [("nnodes", C.c_int), ("nodes", _ip), ("dim", C.c_int), ("dir", _ip), ("value", _dp)]
 
@@ -89,7 +110,7 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_form_initial_guess", "nlps_gpu_nodal_kinetic_increments", "nlps_gpu_nodal_inertial_forces",
            "nlps_gpu_tangent_assemble", "nlps_gpu_tangent_set_grouped", "nlps_gpu_tangent_coo",
            "nlps_gpu_sparsity_pattern", "nlps_gpu_tangent_operator", "nlps_gpu_tangent_apply",
-           "nlps_gpu_tangent_block_diagonal", "nlps_gpu_tangent_solve",
+           "nlps_gpu_tangent_block_diagonal", "nlps_gpu_tangent_solve", "nlps_gpu_newton_solve", "nlps_gpu_newmark_step",
            "nlps_gpu_migration_select", "nlps_gpu_migration_commit", "nlps_gpu_num_particles",
            "nlps_gpu_set_particle_ids", "nlps_gpu_download_ids",
            "nlps_gpu_set_timing", "nlps_gpu_get_timing", "nlps_host_stencil_tables",
@@ -144,6 +165,11 @@ def lib():
         L.nlps_gpu_tangent_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.nlps_gpu_tangent_block_diagonal.argtypes = [C.c_void_p, C.c_void_p]
         L.nlps_gpu_tangent_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Ksp)]
+        L.nlps_gpu_newton_solve.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [_dp, _dp, C.POINTER(Bcc), C.c_int, C.c_int,
+                                            C.c_double, C.c_void_p, C.POINTER(Snes)]
+        L.nlps_gpu_newmark_step.argtypes = [C.c_void_p, C.POINTER(Bcc), C.c_int, C.c_int, C.POINTER(Newmark), _dp,
+                                            C.POINTER(Bcc), C.c_int, C.c_double, C.c_void_p, C.POINTER(Snes), _ip,
+                                            C.c_void_p]
         L.nlps_gpu_migration_select.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_void_p)]
         L.nlps_gpu_migration_commit.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -648,6 +674,90 @@ class Solver:
                     rnorm=k.rnorm, bnorm=k.bnorm, bytes=int(k.bytes),
                     history=hist[: k.iterations + 1].copy() if hist is not None else None)
         return out, info
+
+    @staticmethod
+    def _snes(max_it, max_funcs, atol, rtol, stol, divtol, linesearch, ls_alpha, ls_steptol, ls_maxstep, ls_max_it,
+              apply_dirichlet, ksp):
+        """(nlps_snes, the host arrays it points to) from keyword settings; ksp: the keywords of tangent_solve"""
+        if linesearch not in LINE_SEARCHES:
+            raise ValueError(f"linesearch must be one of {sorted(LINE_SEARCHES)}")
+        kw = dict(pc="jacobi", restart=30, max_it=10000, rtol=1e-5, atol=0.0, dtol=1e5)
+        kw.update(ksp or {})
+        if kw["pc"] not in PC_KINDS:
+            raise ValueError(f"pc must be one of {sorted(PC_KINDS)}")
+        m = max(int(max_it), 0)
+        keep = dict(fnorm=np.zeros(m + 1), lam=np.zeros(max(m, 1)), kits=np.zeros(max(m, 1), dtype=np.int32))
+        k = Ksp(pc=PC_KINDS[kw["pc"]], restart=int(kw["restart"]), max_it=int(kw["max_it"]), x_is_guess=0,
+                rtol=float(kw["rtol"]), atol=float(kw["atol"]), dtol=float(kw["dtol"]), history=None)
+        sn = Snes(max_it=int(max_it), max_funcs=int(max_funcs), atol=float(atol), rtol=float(rtol), stol=float(stol),
+                  divtol=float(divtol), linesearch=LINE_SEARCHES[linesearch], ls_alpha=float(ls_alpha),
+                  ls_steptol=float(ls_steptol), ls_maxstep=float(ls_maxstep), ls_max_it=int(ls_max_it),
+                  apply_dirichlet=1 if apply_dirichlet else 0, ksp=k, fnorm_history=_d(keep["fnorm"]),
+                  lambda_history=_d(keep["lam"]), ksp_iterations=_i(keep["kits"]))
+        return sn, keep
+
+    @staticmethod
+    def _snes_info(sn, keep):
+        it = sn.iterations
+        failed = 1 if sn.reason == -3 else 0  # (the iterate whose linear solve failed still reports its Arnoldi steps)
+        return dict(reason=sn.reason, reason_name=SNES_REASONS.get(sn.reason, str(sn.reason)), iterations=it,
+                    function_evaluations=sn.function_evaluations, linear_iterations=sn.linear_iterations,
+                    fnorm0=sn.fnorm0, fnorm=sn.fnorm, snorm=sn.snorm, xnorm=sn.xnorm,
+                    fnorm_history=keep["fnorm"][: it + 1].copy(), lambda_history=keep["lam"][:it].copy(),
+                    ksp_iterations=keep["kits"][: it + failed].copy(), ksp_reason=sn.ksp.reason, ksp_rnorm=sn.ksp.rnorm)
+
+    def newton_solve(self, dU, Un_dt, Un_dt2, M, alpha, gravity=None, loads=None, step=0, thickness=1.0, area0=None,
+                     max_it=50, max_funcs=10000, atol=1e-8, rtol=1e-10, stol=1e-8, divtol=1e4, linesearch="bt",
+                     ls_alpha=1e-4, ls_steptol=1e-12, ls_maxstep=1e8, ls_max_it=40, apply_dirichlet=True, ksp=None,
+                     out=None):
+        """The driver's SNESSolve on the device (nlps_gpu_newton_solve): Newton with a "basic" or "bt" line search around
+        lagrangian_evaluation, tangent_operator and tangent_solve.  dU: the initial guess (left as it is unless it is also
+        out); vectors are numpy arrays (host) or torch tensors (device), the result is of dU's kind.  ksp: a dict of
+        tangent_solve's settings (pc, restart, max_it, rtol, atol, dtol; the driver's PCJACOBI / GMRES(30) / 1e-5 by
+        default).  Returns (dU, info): info = dict(reason (an NLPS_SNES_* value), reason_name, iterations,
+        function_evaluations, linear_iterations, fnorm0, fnorm, snorm, xnorm, fnorm_history (iterations + 1),
+        lambda_history and ksp_iterations (one per iterate), ksp_reason, ksp_rnorm (the last linear solve))."""
+        if out is None:
+            out = dU.copy() if isinstance(dU, np.ndarray) else dU.clone()
+        elif out is not dU:
+            if isinstance(out, np.ndarray):
+                out[:] = dU if isinstance(dU, np.ndarray) else dU.detach().cpu().numpy()
+            else:
+                import torch
+                out.copy_(torch.as_tensor(dU, dtype=torch.float64))
+        sn, keep = self._snes(max_it, max_funcs, atol, rtol, stol, divtol, linesearch, ls_alpha, ls_steptol, ls_maxstep,
+                              ls_max_it, apply_dirichlet, ksp)
+        al = np.ascontiguousarray(alpha, dtype=np.float64)
+        gv = None if gravity is None else np.ascontiguousarray(gravity, dtype=np.float64)
+        a0 = None if area0 is None else np.ascontiguousarray(area0, dtype=np.float64)
+        self._chk(self.L.nlps_gpu_newton_solve(
+            self.h, _vp(out), _vp(Un_dt), _vp(Un_dt2), _vp(M), _d(al), _d(gv), None if loads is None else loads.arr,
+            0 if loads is None else loads.n, int(step), float(thickness), None if a0 is None else a0.ctypes.data,
+            C.byref(sn)))
+        return out, self._snes_info(sn, keep)
+
+    def newmark_step(self, bcs, step, dt, gravity=None, beta=0.25, gamma=0.5, alpha_blend=1.0, use_explicit_trial=True,
+                     loads=None, thickness=1.0, area0=None, max_it=50, max_funcs=10000, atol=1e-8, rtol=1e-10,
+                     stol=1e-8, divtol=1e4, linesearch="bt", ls_alpha=1e-4, ls_steptol=1e-12, ls_maxstep=1e8,
+                     ls_max_it=40, ksp=None, dU_out=None):
+        """One time step of the implicit driver on the device (nlps_gpu_newmark_step): search, masks, lumped mass, nodal
+        field, initial guess, newton_solve, kinetic increments, roll and particle update.  The particles are updated only
+        when info["reason"] > 0.  dU_out: a numpy array or torch tensor of at least nnodes*ndim doubles that receives the
+        converged increments (its first nactive*ndim entries), or None.  Returns newton_solve's info with "nactive"."""
+        sn, keep = self._snes(max_it, max_funcs, atol, rtol, stol, divtol, linesearch, ls_alpha, ls_steptol, ls_maxstep,
+                              ls_max_it, True, ksp)
+        nm = Newmark(float(beta), float(gamma), float(dt), float(alpha_blend), 1 if use_explicit_trial else 0)
+        gv = None if gravity is None else np.ascontiguousarray(gravity, dtype=np.float64)
+        a0 = None if area0 is None else np.ascontiguousarray(area0, dtype=np.float64)
+        na = C.c_int(0)
+        self._chk(self.L.nlps_gpu_newmark_step(
+            self.h, bcs.arr, bcs.n, int(step), C.byref(nm), _d(gv), None if loads is None else loads.arr,
+            0 if loads is None else loads.n, float(thickness), None if a0 is None else a0.ctypes.data, C.byref(sn),
+            C.byref(na), _vp(dU_out)))
+        self.nactive = na.value
+        info = self._snes_info(sn, keep)
+        info["nactive"] = na.value
+        return info
 
     def create_sparsity_pattern(self):                  # __create_sparsity_pattern (after jacobian_evaluation)
         pat = np.zeros(self.nactive * self.ndim, dtype=np.int32)
