@@ -35,6 +35,7 @@
 #include "../../include/nlps_gpu.h"
 #include "nlps_device.hpp"
 #include "nlps_tables.hpp"
+#include "nlps_host_mem.hpp"
 
 // one kernel name per dimension, the same arguments: the 2-D or the 3-D one on the handle's stream
 #define LAUNCH_ND_BLK(kern2, kern3, grid, block, ...)                                              \
@@ -1517,9 +1518,8 @@ __global__ void k_node_tables(int nn, const double* __restrict__ h_avg, double g
 struct BcDev {
   const int* host_nodes;
   int n;
-  int* dnodes;
+  DevBuf<int> dnodes;
 };
-
 
 struct nlps_gpu {
   int nd, T;
@@ -1531,30 +1531,34 @@ struct nlps_gpu {
   bool own_stream;
   std::string err;
 
+  // The device arrays below are owned here (DevBuf frees them when the handle is deleted); P, N and the other views that
+  // kernels take by value hold pointers borrowed from them, filled where the arrays are made.
   PView P;
+  DevBuf<double> Pd;  // P.d
+  DevBuf<int> P_I0, P_I0n, P_mat, P_nn, P_status, P_tile, P_rank;
+  DevBuf<u64> P_mlo, P_mhi;
   std::vector<int> perm;  // sorted slot -> caller's particle index
   NView N;
-  double* h_avg_d;
-  double4* beta_t2_d = nullptr;  // NView::beta_t2
-  MatD* mats_d;
+  DevBuf<unsigned char> N_active, N_seed, N_fixed;
+  DevBuf<double> N_nm, N_dU, N_force, N_accel, N_reaction;
+  DevBuf<double> h_avg_d;
+  DevBuf<double4> beta_t2_d;  // NView::beta_t2
+  DevBuf<MatD> mats_d;
   int nmats;
   int uniform_law;  // material law shared by every particle, or -1
   int law_present;  // bit l set: some material follows law l
   bool k3_per_law = true;  // several laws: one K3 launch per law (few mixed tiles) or one run-time-dispatch kernel
-  uint8_t* rank1_d;
+  DevBuf<uint8_t> rank1_d;
   nlps_host::StencilTables tab;
 
   // masks
-  int* n2m_d;
-  int* d2m_d;
+  DevBuf<int> n2m_d, d2m_d;
   // nlps_gpu_set_node_numbering: lattice node of file node A (canon_d), and the scratch of the file-order mask scan
-  int* canon_d = nullptr;
-  unsigned char* mask_flags_d = nullptr;
-  int* mask_idx_d = nullptr;
-  unsigned char* fixedm_d;
-  int* bsum_d;
-  int* total_d;
-  int* gstatus_d;
+  DevBuf<int> canon_d;
+  DevBuf<unsigned char> mask_flags_d;
+  DevBuf<int> mask_idx_d;
+  DevBuf<unsigned char> fixedm_d;
+  DevBuf<int> bsum_d, total_d, gstatus_d;
   int nactive, nfree;
   bool masks_valid;
   bool binned;  // order[] / tile tables describe the current I0s
@@ -1570,11 +1574,10 @@ struct nlps_gpu {
   const unsigned* last_bm = nullptr;
   double last_gv[3] = {0, 0, 0};
   // migration
-  int* gid_d = nullptr;               // global particle id (default: the caller's index)
-  unsigned char* leaving_d = nullptr;  // 0 stay, 1 leaves downwards, 2 upwards (between select and commit)
-  int* mig_slot_d = nullptr;
-  int* mig_cnt_d = nullptr;
-  double *mig_down_d = nullptr, *mig_up_d = nullptr;
+  DevBuf<int> gid_d;               // global particle id (default: the caller's index)
+  DevBuf<unsigned char> leaving_d;  // 0 stay, 1 leaves downwards, 2 upwards (between select and commit)
+  DevBuf<int> mig_slot_d, mig_cnt_d;
+  DevBuf<double> mig_down_d, mig_up_d;
   int mig_n[2] = {0, 0};
   bool mig_selected = false;
   bool migrated = false;             // downloads are ordered by ascending global id from now on
@@ -1582,70 +1585,67 @@ struct nlps_gpu {
   bool level_b_fields = false;  // C_ep / rate tensors hold data (a level-B constitutive or rate call was made)
 
   // scratch nodal arrays
-  double* gridA;  // [nnodes][2*ND] general purpose
-  double* gridB;  // [nnodes][ND] x4 for kinetics
-  double* maskedA;
-  size_t maskedA_cap;
+  DevBuf<double> gridA;  // [nnodes][2*ND] general purpose
+  DevBuf<double> gridB;  // [nnodes][ND] x4 for kinetics
+  DevBuf<double> maskedA;
 
   std::vector<BcDev> bcs;
-  unsigned* bcmask_d = nullptr;  // per node: bit i = member of Dirichlet set i (<= NLPS_MAX_BC_INLINE sets; k_nodal_dU)
+  DevBuf<unsigned> bcmask_d;  // per node: bit i = member of Dirichlet set i (<= NLPS_MAX_BC_INLINE sets; k_nodal_dU)
 
   // periodic physical re-sort
-  int* perm_d;            // sorted slot -> caller's particle index (device copy of perm)
+  DevBuf<int> perm_d;     // sorted slot -> caller's particle index (device copy of perm)
   bool perm_dirty;        // device perm newer than the host copy
   int resort_every, steps_since_sort;
-  unsigned long long *skey_d, *skey2_d;
-  int *sval_d, *sval2_d;
-  void* cub_tmp;
-  size_t cub_tmp_bytes;
-  double* gather_tmp;     // [npad] scratch for the gather of the integer arrays
-  double* Pd_alt = nullptr;  // twin of P.d, target of the re-sort (allocated at the first one)
+  DevBuf<unsigned long long> skey_d, skey2_d;
+  DevBuf<int> sval_d, sval2_d;
+  DevBuf<char> cub_tmp;
+  size_t cub_tmp_bytes = 0;
+  DevBuf<double> gather_tmp;  // [npad] scratch for the gather of the integer arrays
+  DevBuf<double> Pd_alt;      // twin of Pd, target of the re-sort (allocated at the first one)
 
   // per-step tile binning
   int nt[3], ntiles;
-  int* tile_count_d;
-  int* tile_count2_d = nullptr;  // the counters the search ahead (k5_tile) fills while tile_count_d still sizes the lists in use
-  int* tile_start_d;
-  int2* work1_d = nullptr;  // compacted work list of the non-empty tiles, see TileD
+  DevBuf<int> tile_count_d;
+  DevBuf<int> tile_count2_d;  // the counters the search ahead (k5_tile) fills while tile_count_d still sizes the lists in use
+  DevBuf<int> tile_start_d;
+  DevBuf<int2> work1_d;  // compacted work list of the non-empty tiles, see TileD
   // canonical lists from per-node counters (TileTab): node_cnt[nnodes], nrank[npad], layer tables [ntiles][LMAX]
-  int *node_cnt_d = nullptr, *nrank_d = nullptr, *tabo_d = nullptr;
-  int* tile_cursor_d = nullptr;  // [ntiles + 1] list cursors of the deferred ranks (TileCnt::defer, k_fill_orders)
+  DevBuf<int> node_cnt_d, nrank_d, tabo_d;
+  DevBuf<int> tile_cursor_d;  // [ntiles + 1] list cursors of the deferred ranks (TileCnt::defer, k_fill_orders)
   bool ranks_deferred = false;   // the search riding on K5 only counted in the step before: the lists of this step take their ranks from cursors
-  unsigned long long* tabm_d = nullptr;
+  DevBuf<unsigned long long> tabm_d;
   // adaptive re-sort (nlps_gpu_set_adaptive_resort): see TileCnt::home.  The count of displaced particles of a step
   // reaches the pinned host word at the end of its search stage; explicit_step adds count / NumGP to `debt` every
   // step and re-sorts ahead of the interval when the debt since the last re-sort exceeds `adaptive_resort`
-  int* home_d = nullptr;
-  int* foreign_d = nullptr;
-  int* foreign_h = nullptr;
-  int* status_h = nullptr;  // pinned landing word of check_status (one asynchronous copy + one synchronise per check)
-  int* status_hd = nullptr; // the same word as the device sees it (hipHostGetDevicePointer): a kernel at the end of a call can leave the status there itself
+  DevBuf<int> home_d, foreign_d;
+  Pinned<int> foreign_h;
+  // pinned landing word of check_status (one asynchronous copy + one synchronise per check); through its device alias a
+  // kernel at the end of a call can leave the status there itself
+  Pinned<int> status_h;
   bool rehome = true;
   double adaptive_resort = 0.8, debt = 0.0;  // default budget: about one re-sort's cost
   int adaptive_min_steps = 4;
-  int* nwork_d = nullptr;   // ranges[3 classes][begin,end] of the work list (tile_scan_block)
-  int *dmg_first_d = nullptr, *dmg_last_d = nullptr;  // eigenerosion: run of every node in the I0-sorted particle list
-  int *dmg_first0_d = nullptr, *dmg_last0_d = nullptr, *dmg_sorted0_d = nullptr;  // the same for the snapshot's closest nodes
+  DevBuf<int> nwork_d;      // ranges[3 classes][begin,end] of the work list (tile_scan_block)
+  DevBuf<int> dmg_first_d, dmg_last_d;  // eigenerosion: run of every node in the I0-sorted particle list
+  DevBuf<int> dmg_first0_d, dmg_last0_d, dmg_sorted0_d;  // the same for the snapshot's closest nodes
   bool beps_snapshot = false;  // F_X0 / F_I00 hold the configuration of Initialize_Beps = true
-  double* slab_d = nullptr; // P2G window slabs [ntiles][slab_n][1+ND][NW] (TileD::slab), deterministic mode only
+  DevBuf<double> slab_d;    // P2G window slabs [ntiles][slab_n][1+ND][NW] (TileD::slab), deterministic mode only
   bool deterministic = false;
   int band_lo = -(1 << 30), band_hi = 1 << 30;  // ghost bands: layers <= band_lo and >= band_hi are shared with neighbours
   int overlap = 0;          // halo exchanges: 0 blocking in place; 1 behind the interior tiles of the NEXT stage (split
                             // launches, two-phase callback); 2 behind the interior tiles of the SAME launch (library RCCL only)
-  unsigned long long* phase_d = nullptr;
-  double* vec_d = nullptr;  // scratch pool for host vectors of the a21 per-dof updates
-  size_t vec_cap = 0;
+  DevBuf<unsigned long long> phase_d;
+  DevBuf<double> vec_d;  // scratch pool for host vectors of the a21 per-dof updates
   // nlps_gpu_lagrangian_evaluation with host vectors: device copies of Un_dt, Un_dt2, M, which do not change between the
   // evaluations of one SNES solve (NLPS_LAGR_SAME_STEP reuses them: two transfers per evaluation instead of five)
-  double* lagr_d = nullptr;
-  size_t lagr_cap = 0;
+  DevBuf<double> lagr_d;
   bool lagr_valid = false;
   // tangent assembly, allocated on first use
-  double* kst_d = nullptr;           // [nnodes][S][d*d]
-  unsigned char* ktouched_d = nullptr;  // [nnodes][S]
-  int *kcnt_d = nullptr, *koffs_d = nullptr;  // visited blocks per row node, exclusive scan
-  int *khead_d = nullptr, *kng_d = nullptr;   // group heads of the I0-sorted particle list, group count
-  void* kscan_tmp = nullptr;
+  DevBuf<double> kst_d;               // [nnodes][S][d*d]
+  DevBuf<unsigned char> ktouched_d;   // [nnodes][S]
+  DevBuf<int> kcnt_d, koffs_d;  // visited blocks per row node, exclusive scan
+  DevBuf<int> khead_d, kng_d;   // group heads of the I0-sorted particle list, group count
+  DevBuf<char> kscan_tmp;
   size_t kscan_bytes = 0;
   long long knnz_blocks = -1;
   bool tangent_grouped = true;  // one workgroup per closest node (false: one wave per particle, kept for comparison)
@@ -1653,13 +1653,10 @@ struct nlps_gpu {
   bool ktan_sym = false;          // how the last nlps_gpu_tangent_assemble filled the stencil array (nlps_gpu_tangent_coo mirrors the rest)
   // matrix-free tangent (nlps_gpu_tangent_operator), allocated on first use.  tan_gen counts the calls that move, reorder
   // or re-list particles (tan_stale); the operator is valid while top_gen == tan_gen.
-  double* top_d = nullptr;  // Dh [d^4][top_np]
-  size_t top_cap = 0;       // doubles
-  double* top_m = nullptr;  // alpha_1 M snapshot, masked [N_A d] (valid when top_mass)
-  size_t top_mcap = 0;
-  double* top_g = nullptr;  // grid scratch [nnodes][d^2]: x and K x (2 d fields) or the diagonal blocks (d^2)
-  double* top_b = nullptr;  // staging of nlps_gpu_tangent_block_diagonal for host destinations [N_A d^2]
-  size_t top_bcap = 0;
+  DevBuf<double> top_d;  // Dh [d^4][top_np]
+  DevBuf<double> top_m;  // alpha_1 M snapshot, masked [N_A d] (valid when top_mass)
+  DevBuf<double> top_g;  // grid scratch [nnodes][d^2]: x and K x (2 d fields) or the diagonal blocks (d^2)
+  DevBuf<double> top_b;  // staging of nlps_gpu_tangent_block_diagonal for host destinations [N_A d^2]
   int top_np = 0;
   bool top_mass = false, top_dir = false;
   unsigned long long tan_gen = 1, top_gen = 0;  // top_gen 0: no operator yet
@@ -1670,38 +1667,27 @@ struct nlps_gpu {
   // ksp_pc was built from.
   unsigned long long top_serial = 0, ksp_pc_serial = 0;
   int ksp_pc_kind = -1;
-  double* ksp_pc = nullptr;  // [N_A d^2]: the inverted blocks (PBJACOBI) or reciprocals on the block diagonals (JACOBI)
-  size_t ksp_pc_cap = 0;
-  double* ksp_v = nullptr;   // [(m + 3) n]: the basis V[0..m], z = M^-1 v, t = K x
-  size_t ksp_v_cap = 0;
-  double* ksp_part = nullptr;  // [(m + 2) nb]: per-block partial sums
-  size_t ksp_part_cap = 0;
-  double* ksp_s = nullptr;   // the cycle's small state (KspSmall)
-  size_t ksp_s_cap = 0;
-  int* ksp_bad_d = nullptr;  // first masked node whose PC block does not invert
-  KspHost* ksp_h = nullptr;  // pinned: what the host reads per step
-  KspHost* ksp_hd = nullptr; // its device alias (nullptr: the kernels write ksp_hdev and the host copies)
-  KspHost* ksp_hdev = nullptr;
+  DevBuf<double> ksp_pc;    // [N_A d^2]: the inverted blocks (PBJACOBI) or reciprocals on the block diagonals (JACOBI)
+  DevBuf<double> ksp_v;     // [(m + 3) n]: the basis V[0..m], z = M^-1 v, t = K x
+  DevBuf<double> ksp_part;  // [(m + 2) nb]: per-block partial sums
+  DevBuf<double> ksp_s;     // the cycle's small state (KspSmall)
+  DevBuf<int> ksp_bad_d;    // first masked node whose PC block does not invert
+  Mirrored<KspHost> ksp_h;  // what the host reads per step
   // Newton solve (nlps_gpu_newton_solve, nlps_newton.hpp), allocated on first use and kept (they only grow)
-  double* snes_v = nullptr;     // [8 n]: X, Y, W, F, K Y and the device copies of Un_dt, Un_dt2, M
-  size_t snes_v_cap = 0;
-  double* snes_part = nullptr;  // [5 nb]: per-block partials of the trial update (3 columns) and the dots (2)
-  size_t snes_part_cap = 0;
-  double* snes_h = nullptr;     // pinned [SNES_H_N]: the scalars the host reads after a residual evaluation
-  double* snes_hd = nullptr;    // its device alias (nullptr: the kernels write snes_hdev and a copy follows them)
-  double* snes_hdev = nullptr;
+  DevBuf<double> snes_v;     // [8 n]: X, Y, W, F, K Y and the device copies of Un_dt, Un_dt2, M
+  DevBuf<double> snes_part;  // [5 nb]: per-block partials of the trial update (3 columns) and the dots (2)
+  Mirrored<double> snes_h;   // [SNES_H_N]: the scalars the host reads after a residual evaluation
   bool snes_tail = false;       // the next fused residual evaluation queues F . F ahead of its own synchronisation
   int snes_nb = 0;
   // implicit time step (nlps_gpu_newmark_step): M, Un_dt, Un_dt2, dU, dU_dt, dU_dt2, masked [N_A d] each
-  double* nm_v = nullptr;
-  size_t nm_v_cap = 0;
-  int* order_d;
+  DevBuf<double> nm_v;
+  DevBuf<int> order_d;
   // canonical (layer, closest node) order of every tile list each step for the LDS-atomic-bound K2 and K3; the
   // memory-bound K5 keeps the lists as binned.  13 us per step at 1 M particles.  A freshly sorted cloud has its lists in
   // that order already (0.685 vs 0.677 ms/step), but once particles have changed closest node -- 45 steps into the bench
   // cloud's fall -- K2 runs 0.231 instead of 0.300 ms and K3 0.260 instead of 0.304, and the stirred cloud of DESIGN.md
   // 0.84 instead of 0.95 ms/step
-  int* order2_d = nullptr;  // canonical tile lists (k_fill_orders; k_tile_order in deterministic mode), allocated on first use
+  DevBuf<int> order2_d;  // canonical tile lists (k_fill_orders; k_tile_order in deterministic mode), allocated on first use
 
   nlps_halo_fn halo;
   void* halo_ctx;
@@ -1834,21 +1820,23 @@ static void host_h_avg(const nlps_grid& G, const nlps_host::StencilTables& tab, 
   }
 }
 
-template <class T>
-static int dev_alloc(nlps_gpu* h, T** p, size_t n) {
-  HIPCHK(hipMalloc((void**)p, n * sizeof(T)));
-  // default stream, like the uploads that may follow: on the handle's stream a caller-provided NON-BLOCKING
-  // stream (torch's are) could run this after them and wipe the upload
-  HIPCHK(hipMemset(*p, 0, n * sizeof(T)));
+// n zeroed elements; view: the pointer of a kernel view (PView, NView) that borrows the block
+template <class T, class V = T>
+static int dev_alloc(nlps_gpu* h, DevBuf<T>& b, size_t n, V** view = nullptr) {
+  HIPCHK(b.alloc_zeroed(n));
+  if (view) *view = b.get();
   return 0;
 }
 
-static int ensure_masked(nlps_gpu* h, size_t n) {
-  if (n <= h->maskedA_cap) return 0;
-  if (h->maskedA) HIPCHK(hipFree(h->maskedA));
-  HIPCHK(hipMalloc((void**)&h->maskedA, n * sizeof(double)));
-  h->maskedA_cap = n;
-  return 0;
+// grow-only scratch of the handle (contents discarded when it grows)
+template <class T>
+static int reserve(nlps_gpu* h, const char* who, DevBuf<T>& b, size_t n, const char* what) {
+  if (b.reserve(n) == hipSuccess) return 0;
+  (void)hipGetLastError();
+  char buf[200];
+  snprintf(buf, sizeof buf, "%s: cannot allocate %zu bytes for %s", who, n * sizeof(T), what);
+  h->err = buf;
+  return 1;
 }
 
 extern "C" int nlps_host_stencil_tables(int ndim, unsigned char* rank1, unsigned char* order2, unsigned char* count2,
@@ -1984,17 +1972,9 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
   h->timing = false;
   h->masks_valid = false;
   h->binned = false;
-  h->maskedA = nullptr;
-  h->maskedA_cap = 0;
-  h->perm_d = nullptr;
   h->perm_dirty = false;
   h->resort_every = 50;
   h->steps_since_sort = 0;
-  h->skey_d = h->skey2_d = nullptr;
-  h->sval_d = h->sval2_d = nullptr;
-  h->cub_tmp = nullptr;
-  h->cub_tmp_bytes = 0;
-  h->gather_tmp = nullptr;
   memset(h->ms, 0, sizeof(h->ms));
   if (grid->ndim != 2 && grid->ndim != 3) {
     h->err = "ndim must be 2 or 3";
@@ -2053,38 +2033,38 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
   }
 
   h->tab = nlps_host::build_tables(g.nd);
-  HIPCHK(hipMalloc((void**)&h->rank1_d, 27 * 27));
+  HIPCHK(h->rank1_d.reserve(27 * 27));
   HIPCHK(hipMemcpy(h->rank1_d, h->tab.rank1, 27 * 27, hipMemcpyHostToDevice));
 
   // nodal arrays
   size_t nn = (size_t)g.nnodes;
   int ND = g.nd;
-  if (dev_alloc(h, &h->N.active, nn)) return 1;
-  if (dev_alloc(h, &h->N.seed, nn)) return 1;
-  if (dev_alloc(h, &h->N.nm, nn * (1 + ND))) return 1;
-  if (dev_alloc(h, &h->N.dU, nn * ND)) return 1;
-  if (dev_alloc(h, &h->N.force, nn * ND)) return 1;
-  if (dev_alloc(h, &h->N.accel, nn * ND)) return 1;
-  if (dev_alloc(h, &h->N.reaction, nn * ND)) return 1;
-  if (dev_alloc(h, &h->N.fixed, nn * ND)) return 1;
-  if (dev_alloc(h, &h->h_avg_d, nn)) return 1;
-  if (dev_alloc(h, &h->n2m_d, nn)) return 1;
-  if (dev_alloc(h, &h->d2m_d, nn * ND)) return 1;
-  if (dev_alloc(h, &h->fixedm_d, nn * ND)) return 1;
-  if (dev_alloc(h, &h->bsum_d, nn * ND / 1024 + 2)) return 1;
-  if (dev_alloc(h, &h->total_d, 4)) return 1;
-  if (dev_alloc(h, &h->gstatus_d, 4)) return 1;
-  if (dev_alloc(h, &h->gridA, nn * 2 * ND)) return 1;
-  if (dev_alloc(h, &h->gridB, nn * 4 * ND)) return 1;
+  if (dev_alloc(h, h->N_active, nn, &h->N.active)) return 1;
+  if (dev_alloc(h, h->N_seed, nn, &h->N.seed)) return 1;
+  if (dev_alloc(h, h->N_nm, nn * (1 + ND), &h->N.nm)) return 1;
+  if (dev_alloc(h, h->N_dU, nn * ND, &h->N.dU)) return 1;
+  if (dev_alloc(h, h->N_force, nn * ND, &h->N.force)) return 1;
+  if (dev_alloc(h, h->N_accel, nn * ND, &h->N.accel)) return 1;
+  if (dev_alloc(h, h->N_reaction, nn * ND, &h->N.reaction)) return 1;
+  if (dev_alloc(h, h->N_fixed, nn * ND, &h->N.fixed)) return 1;
+  if (dev_alloc(h, h->h_avg_d, nn)) return 1;
+  if (dev_alloc(h, h->n2m_d, nn)) return 1;
+  if (dev_alloc(h, h->d2m_d, nn * ND)) return 1;
+  if (dev_alloc(h, h->fixedm_d, nn * ND)) return 1;
+  if (dev_alloc(h, h->bsum_d, nn * ND / 1024 + 2)) return 1;
+  if (dev_alloc(h, h->total_d, 4)) return 1;
+  if (dev_alloc(h, h->gstatus_d, 4)) return 1;
+  if (dev_alloc(h, h->gridA, nn * 2 * ND)) return 1;
+  if (dev_alloc(h, h->gridB, nn * 4 * ND)) return 1;
   {
     std::vector<double> hv;
     if (grid->h_avg) hv.assign(grid->h_avg, grid->h_avg + nn);
     else host_h_avg(*grid, h->tab, hv);
     HIPCHK(hipMemcpy(h->h_avg_d, hv.data(), nn * sizeof(double), hipMemcpyHostToDevice));
     h->N.h_avg = h->h_avg_d;
-    HIPCHK(hipMalloc((void**)&h->beta_t2_d, nn * sizeof(double4)));
+    HIPCHK(h->beta_t2_d.reserve(nn));
     hipLaunchKernelGGL(k_node_tables, dim3(nblk((int)nn)), dim3(BLK), 0, 0, (int)nn, (const double*)h->h_avg_d,
-                       h->prm.gamma_lme, h->prm.neg_log_tol_zero, h->beta_t2_d);
+                       h->prm.gamma_lme, h->prm.neg_log_tol_zero, h->beta_t2_d.get());
     HIPCHK(hipGetLastError());
     h->N.beta_t2 = h->beta_t2_d;
   }
@@ -2103,7 +2083,7 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
   {
     std::vector<MatD> md(nmats);
     for (int i = 0; i < nmats; i++) md[i] = make_mat(mats[i], g.nd);
-    HIPCHK(hipMalloc((void**)&h->mats_d, sizeof(MatD) * nmats));
+    HIPCHK(h->mats_d.reserve(nmats));
     HIPCHK(hipMemcpy(h->mats_d, md.data(), sizeof(MatD) * nmats, hipMemcpyHostToDevice));
   }
 
@@ -2173,43 +2153,41 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
     h->slab_lo = std::max(0, lo - 3);
     h->slab_hi = std::min(g.n[slab_axis] - 1, hi + 3);
   }
-  HIPCHK(hipMalloc((void**)&h->P.d, (size_t)NFD * h->P.npad * sizeof(double)));
-  HIPCHK(hipMemset(h->P.d, 0, (size_t)NFD * h->P.npad * sizeof(double)));
-  if (dev_alloc(h, &h->P.I0, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->P.I0n, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->P.mat, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->P.nn, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->P.status, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->P.mlo, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->P.mhi, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->P.tile, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->P.rank, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->order_d, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->tile_count_d, (size_t)h->ntiles + 1)) return 1;
-  if (dev_alloc(h, &h->tile_count2_d, (size_t)h->ntiles + 1)) return 1;
-  if (dev_alloc(h, &h->tile_start_d, (size_t)h->ntiles + 1)) return 1;
-  if (dev_alloc(h, &h->work1_d, (size_t)h->ntiles)) return 1;
-  if (dev_alloc(h, &h->nwork_d, 6)) return 1;
+  if (dev_alloc(h, h->Pd, (size_t)NFD * h->P.npad, &h->P.d)) return 1;
+  if (dev_alloc(h, h->P_I0, h->P.npad, &h->P.I0)) return 1;
+  if (dev_alloc(h, h->P_I0n, h->P.npad, &h->P.I0n)) return 1;
+  if (dev_alloc(h, h->P_mat, h->P.npad, &h->P.mat)) return 1;
+  if (dev_alloc(h, h->P_nn, h->P.npad, &h->P.nn)) return 1;
+  if (dev_alloc(h, h->P_status, h->P.npad, &h->P.status)) return 1;
+  if (dev_alloc(h, h->P_mlo, h->P.npad, &h->P.mlo)) return 1;
+  if (dev_alloc(h, h->P_mhi, h->P.npad, &h->P.mhi)) return 1;
+  if (dev_alloc(h, h->P_tile, h->P.npad, &h->P.tile)) return 1;
+  if (dev_alloc(h, h->P_rank, h->P.npad, &h->P.rank)) return 1;
+  if (dev_alloc(h, h->order_d, h->P.npad)) return 1;
+  if (dev_alloc(h, h->tile_count_d, (size_t)h->ntiles + 1)) return 1;
+  if (dev_alloc(h, h->tile_count2_d, (size_t)h->ntiles + 1)) return 1;
+  if (dev_alloc(h, h->tile_start_d, (size_t)h->ntiles + 1)) return 1;
+  if (dev_alloc(h, h->work1_d, (size_t)h->ntiles)) return 1;
+  if (dev_alloc(h, h->nwork_d, 6)) return 1;
 #if NLPS_DEV
   if (const char* e = getenv("NLPS_ADAPTIVE_RESORT")) h->adaptive_resort = atof(e);  // (0 = off)
 #endif
-  if (dev_alloc(h, &h->node_cnt_d, (size_t)h->g.nnodes)) return 1;
-  if (dev_alloc(h, &h->nrank_d, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->tile_cursor_d, (size_t)h->ntiles + 1)) return 1;
+  if (dev_alloc(h, h->node_cnt_d, (size_t)h->g.nnodes)) return 1;
+  if (dev_alloc(h, h->nrank_d, h->P.npad)) return 1;
+  if (dev_alloc(h, h->tile_cursor_d, (size_t)h->ntiles + 1)) return 1;
   {
     const size_t nnw = h->g.nd == 3 ? TileTabCfg<3>::NNW : TileTabCfg<2>::NNW;
-    if (dev_alloc(h, &h->tabo_d, (size_t)h->ntiles * TileTab::LMAX * nnw)) return 1;
-    if (dev_alloc(h, &h->tabm_d, (size_t)h->ntiles * TileTab::LMAX * nnw)) return 1;
+    if (dev_alloc(h, h->tabo_d, (size_t)h->ntiles * TileTab::LMAX * nnw)) return 1;
+    if (dev_alloc(h, h->tabm_d, (size_t)h->ntiles * TileTab::LMAX * nnw)) return 1;
   }
-  if (dev_alloc(h, &h->home_d, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->foreign_d, 64 * 32)) return 1;
-  HIPCHK(hipHostMalloc((void**)&h->foreign_h, sizeof(int), hipHostMallocDefault));
-  *h->foreign_h = 0;
-  HIPCHK(hipHostMalloc((void**)&h->status_h, sizeof(int), hipHostMallocDefault));
-  *h->status_h = 0;
-  if (hipHostGetDevicePointer((void**)&h->status_hd, h->status_h, 0) != hipSuccess) h->status_hd = nullptr;  // (then check_status copies)
+  if (dev_alloc(h, h->home_d, h->P.npad)) return 1;
+  if (dev_alloc(h, h->foreign_d, 64 * 32)) return 1;
+  HIPCHK(h->foreign_h.alloc());
+  *h->foreign_h.host() = 0;
+  HIPCHK(h->status_h.alloc());  // (without a device alias check_status copies)
+  *h->status_h.host() = 0;
 #if NLPS_PHASE_TIMING
-  if (dev_alloc(h, &h->phase_d, 16 * 1024)) return 1;
+  if (dev_alloc(h, h->phase_d, 16 * 1024)) return 1;
 #endif
   {
     std::vector<double> tmp(h->P.npad);
@@ -2261,21 +2239,21 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
     }
   }
   // re-sort buffers
-  if (dev_alloc(h, &h->perm_d, h->P.npad)) return 1;
+  if (dev_alloc(h, h->perm_d, h->P.npad)) return 1;
   HIPCHK(hipMemcpy(h->perm_d, h->perm.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice));
-  if (dev_alloc(h, &h->gid_d, h->P.npad)) return 1;
+  if (dev_alloc(h, h->gid_d, h->P.npad)) return 1;
   HIPCHK(hipMemcpy(h->gid_d, h->perm.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice));
-  if (dev_alloc(h, &h->leaving_d, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->mig_slot_d, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->mig_cnt_d, 2)) return 1;
-  if (dev_alloc(h, &h->skey_d, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->skey2_d, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->sval_d, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->sval2_d, h->P.npad)) return 1;
-  if (dev_alloc(h, &h->gather_tmp, h->P.npad)) return 1;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, h->cub_tmp_bytes, h->skey_d, h->skey2_d, h->sval_d, h->sval2_d,
+  if (dev_alloc(h, h->leaving_d, h->P.npad)) return 1;
+  if (dev_alloc(h, h->mig_slot_d, h->P.npad)) return 1;
+  if (dev_alloc(h, h->mig_cnt_d, 2)) return 1;
+  if (dev_alloc(h, h->skey_d, h->P.npad)) return 1;
+  if (dev_alloc(h, h->skey2_d, h->P.npad)) return 1;
+  if (dev_alloc(h, h->sval_d, h->P.npad)) return 1;
+  if (dev_alloc(h, h->sval2_d, h->P.npad)) return 1;
+  if (dev_alloc(h, h->gather_tmp, h->P.npad)) return 1;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, h->cub_tmp_bytes, h->skey_d.get(), h->skey2_d.get(), h->sval_d.get(), h->sval2_d.get(),
                                             (int)h->P.npad, 0, 64, h->stream));
-  HIPCHK(hipMalloc(&h->cub_tmp, h->cub_tmp_bytes + 16));
+  HIPCHK(h->cub_tmp.reserve(h->cub_tmp_bytes + 16));
   HIPCHK(hipStreamSynchronize(h->stream));
   // the uploads above are ordered on the default stream only: a caller-provided non-blocking stream (torch
   // streams are) would not wait for their DMA
@@ -2304,11 +2282,11 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
     LAUNCH_ND(k_sort_keys<2>, k_sort_keys<3>, nblk(np), h->P, h->g, tc, h->skey_d, h->sval_d, leaving, h->mats_d);
     HIPCHK(hipGetLastError());
     size_t bytes = h->cub_tmp_bytes;
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(h->cub_tmp, bytes, h->skey_d, h->skey2_d, h->sval_d, h->sval2_d, np, 0, 64,
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(h->cub_tmp.get(), bytes, h->skey_d.get(), h->skey2_d.get(), h->sval_d.get(), h->sval2_d.get(), np, 0, 64,
                                               h->stream));
   }
   if (from_lists) {  // particles that are in no list go behind the lists (k_mark_listed / k_append_unlisted)
-    unsigned char* listed = reinterpret_cast<unsigned char*>(h->gather_tmp);  // [npad] bytes of the gather scratch, idle here
+    unsigned char* listed = reinterpret_cast<unsigned char*>(h->gather_tmp.get());  // [npad] bytes of the gather scratch, idle here
     HIPCHK(hipMemsetAsync(h->mig_cnt_d, 0, sizeof(int), h->stream));
     HIPCHK(hipMemsetAsync(listed, 0, (size_t)np, h->stream));
     const int last = h->tile0 + h->ntw - 1;
@@ -2323,7 +2301,7 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
   // the field block moves into its twin in one launch and the two swap roles (no copy back; the twin costs a second
   // NFD x npad block of HBM, allocated at the first re-sort)
   if (!h->Pd_alt) {
-    HIPCHK(hipMalloc((void**)&h->Pd_alt, (size_t)NFD * npad * sizeof(double)));
+    HIPCHK(h->Pd_alt.reserve((size_t)NFD * npad));
     HIPCHK(hipMemsetAsync(h->Pd_alt, 0, (size_t)NFD * npad * sizeof(double), h->stream));
   }
   if (live_only && !h->level_b_fields) {
@@ -2345,7 +2323,8 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
     hipLaunchKernelGGL(k_gather_fields, dim3(nblk(np), (nf + GATHER_FIELDS - 1) / GATHER_FIELDS), dim3(BLK), 0, h->stream,
                        h->Pd_alt, (const double*)h->P.d, idx, np, npad, nf);
   }
-  std::swap(h->P.d, h->Pd_alt);
+  h->Pd.swap(h->Pd_alt);
+  h->P.d = h->Pd;  // (the view is passed by value: it must follow the owner)
   {
     // (the twin block now holds the OLD field values, which nothing reads any more: its head is the scratch of the
     // integer arrays -- 2 x npad doubles for the mask words, then 7 x npad ints)
@@ -2355,7 +2334,7 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
     A.ua[0] = h->P.mlo;
     A.ua[1] = h->P.mhi;
     static_assert((int)NFD >= 6, "the scratch of the integer arrays needs 2 + 3.5 components of the twin block");
-    unsigned long long* su = reinterpret_cast<unsigned long long*>(h->Pd_alt);
+    unsigned long long* su = reinterpret_cast<unsigned long long*>(h->Pd_alt.get());
     int* si = reinterpret_cast<int*>(h->Pd_alt + 2 * npad);
     hipLaunchKernelGGL(k_gather_small, dim3(nblk(np)), dim3(BLK), 0, h->stream, A, idx, np, npad, si, su);
     hipLaunchKernelGGL(k_copy_small, dim3(nblk(np)), dim3(BLK), 0, h->stream, A, np, npad, (const int*)si,
@@ -2427,11 +2406,10 @@ extern "C" int nlps_gpu_migration_select(nlps_gpu* h, int keep_lo, int keep_hi, 
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(h->mig_n, h->mig_cnt_d, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (h->mig_down_d) (void)hipFree(h->mig_down_d);
-  if (h->mig_up_d) (void)hipFree(h->mig_up_d);
-  h->mig_down_d = h->mig_up_d = nullptr;
-  HIPCHK(hipMalloc((void**)&h->mig_down_d, ((size_t)h->mig_n[0] + 1) * MIG_WORDS * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&h->mig_up_d, ((size_t)h->mig_n[1] + 1) * MIG_WORDS * sizeof(double)));
+  h->mig_down_d.reset();  // (a new block at the size of this selection every call)
+  h->mig_up_d.reset();
+  HIPCHK(h->mig_down_d.reserve(((size_t)h->mig_n[0] + 1) * MIG_WORDS));
+  HIPCHK(h->mig_up_d.reserve(((size_t)h->mig_n[1] + 1) * MIG_WORDS));
   if (h->mig_n[0] + h->mig_n[1] > 0) {
     hipLaunchKernelGGL(k_mig_pack, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->P, h->leaving_d, h->mig_slot_d, h->perm_d,
                        h->gid_d, h->mig_down_d, h->mig_up_d);
@@ -2441,8 +2419,8 @@ extern "C" int nlps_gpu_migration_select(nlps_gpu* h, int keep_lo, int keep_hi, 
   *n_down = h->mig_n[0];
   *n_up = h->mig_n[1];
   *row_words = MIG_WORDS;
-  if (down_rows) *down_rows = h->mig_down_d;
-  if (up_rows) *up_rows = h->mig_up_d;
+  if (down_rows) *down_rows = h->mig_down_d.get();
+  if (up_rows) *up_rows = h->mig_up_d.get();
   h->mig_selected = true;
   return 0;
 }
@@ -2467,14 +2445,13 @@ extern "C" int nlps_gpu_migration_commit(nlps_gpu* h, const void* rows_a, int n_
   int first = np;
   for (int k = 0; k < 2; k++) {
     if (cnt[k] <= 0) continue;
-    double* tmp = nullptr;
-    HIPCHK(hipMalloc((void**)&tmp, (size_t)cnt[k] * MIG_WORDS * sizeof(double)));
+    DevBuf<double> tmp;
+    HIPCHK(tmp.reserve((size_t)cnt[k] * MIG_WORDS));
     HIPCHK(hipMemcpyAsync(tmp, src[k], (size_t)cnt[k] * MIG_WORDS * sizeof(double), hipMemcpyDefault, h->stream));
     hipLaunchKernelGGL(k_mig_unpack, dim3(nblk(cnt[k])), dim3(BLK), 0, h->stream, h->P, first, cnt[k], tmp, h->perm_d,
                        h->gid_d, h->leaving_d);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
-    (void)hipFree(tmp);
     first += cnt[k];
   }
   h->P.np = np + n_in;
@@ -2540,7 +2517,7 @@ extern "C" int nlps_gpu_set_adaptive_resort(nlps_gpu* h, double budget, int min_
 }
 extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_displaced(nlps_gpu* h, int* count, double* debt) {
   HIPCHK(hipStreamSynchronize(h->stream));  // developer read-out: the count of the last completed search stage
-  *count = h->foreign_h ? *(volatile int*)h->foreign_h : 0;
+  *count = h->foreign_h.host() ? *(volatile int*)h->foreign_h.host() : 0;
   *debt = h->debt;
   return 0;
 }
@@ -2549,26 +2526,13 @@ extern "C" int nlps_gpu_destroy(nlps_gpu* h) {
   if (!h) return 0;
   (void)nlps_gpu_rccl_detach(h);
   (void)hipStreamSynchronize(h->stream);
-  void* ptrs[] = {h->P.d, h->Pd_alt, h->P.I0, h->P.I0n, h->P.mat, h->P.nn, h->P.status, h->P.mlo, h->P.mhi, h->N.active, h->N.seed, h->N.nm,
-                  h->N.dU, h->N.force, h->N.accel, h->N.reaction, h->N.fixed, h->h_avg_d, h->beta_t2_d, h->n2m_d, h->d2m_d, h->canon_d, h->mask_flags_d, h->mask_idx_d,
-                  h->fixedm_d, h->bsum_d, h->total_d, h->gstatus_d, h->gridA, h->gridB, h->maskedA, h->mats_d,
-                  h->rank1_d, h->P.tile, h->P.rank, h->order_d, h->order2_d, h->tile_count_d, h->tile_count2_d, h->tile_start_d, h->work1_d, h->nwork_d, h->slab_d, h->dmg_first_d, h->dmg_last_d, h->dmg_first0_d, h->dmg_last0_d, h->dmg_sorted0_d, h->perm_d, h->skey_d, h->skey2_d, h->sval_d, h->sval2_d,
-                  h->gather_tmp, h->cub_tmp, h->gid_d, h->leaving_d, h->mig_slot_d, h->mig_cnt_d, h->mig_down_d, h->mig_up_d, h->kst_d, h->ktouched_d, h->kcnt_d, h->koffs_d, h->kscan_tmp, h->khead_d, h->kng_d, h->vec_d, h->bcmask_d, h->home_d, h->foreign_d, h->node_cnt_d, h->nrank_d, h->tabo_d, h->tabm_d, h->tile_cursor_d, h->top_d, h->top_m, h->top_g, h->top_b,
-                  h->ksp_pc, h->ksp_v, h->ksp_part, h->ksp_s, h->ksp_bad_d, h->ksp_hdev, h->snes_v, h->snes_part, h->snes_hdev, h->nm_v};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (auto& b : h->bcs)
-    if (b.dnodes) (void)hipFree(b.dnodes);
-  if (h->foreign_h) (void)hipHostFree(h->foreign_h);
-  if (h->lagr_d) (void)hipFree(h->lagr_d);
-  if (h->status_h) (void)hipHostFree(h->status_h);
-  if (h->ksp_h) (void)hipHostFree(h->ksp_h);
-  if (h->snes_h) (void)hipHostFree(h->snes_h);
   for (int i = 0; i < 8; i++) (void)hipEventDestroy(h->ev[i]);
   for (hipEvent_t e : h->evw)
     if (e) (void)hipEventDestroy(e);
-  if (h->own_stream) (void)hipStreamDestroy(h->stream);
+  // the members free their memory here: after the synchronise above, before the stream they were used on goes
+  const hipStream_t owned = h->own_stream ? h->stream : nullptr;
   delete h;
+  if (owned) (void)hipStreamDestroy(owned);
   return 0;
 }
 
@@ -2735,11 +2699,11 @@ extern "C" int nlps_gpu_shape_functions(nlps_gpu* h, int first, int count, doubl
   std::vector<int> slot_of(np), slots(count), I0(np);
   for (int s = 0; s < np; s++) slot_of[h->perm[s]] = s;
   for (int q = 0; q < count; q++) slots[q] = slot_of[first + q];
-  int* slots_d = nullptr;
-  double *Ns_d = nullptr, *dNs_d = nullptr;
-  HIPCHK(hipMalloc((void**)&slots_d, (size_t)count * sizeof(int)));
-  HIPCHK(hipMalloc((void**)&Ns_d, (size_t)count * NS * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&dNs_d, (size_t)count * NS * ND * sizeof(double)));
+  DevBuf<int> slots_d;
+  DevBuf<double> Ns_d, dNs_d;
+  HIPCHK(slots_d.reserve((size_t)count));
+  HIPCHK(Ns_d.reserve((size_t)count * NS));
+  HIPCHK(dNs_d.reserve((size_t)count * NS * ND));
   HIPCHK(hipMemcpyAsync(slots_d, slots.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
   LAUNCH_ND(k_shape_slots<2>, k_shape_slots<3>, nblk(count), h->P, h->g, slots_d, count, Ns_d, dNs_d, h->gstatus_d);
   HIPCHK(hipGetLastError());
@@ -2751,9 +2715,6 @@ extern "C" int nlps_gpu_shape_functions(nlps_gpu* h, int first, int count, doubl
   HIPCHK(hipMemcpy(I0.data(), h->P.I0, (size_t)np * sizeof(int), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(lo.data(), h->P.mlo, (size_t)np * sizeof(u64), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(hi.data(), h->P.mhi, (size_t)np * sizeof(u64), hipMemcpyDeviceToHost));
-  (void)hipFree(slots_d);
-  (void)hipFree(Ns_d);
-  (void)hipFree(dNs_d);
   const GridD& g = h->g;
   for (int q = 0; q < count; q++) {
     const int s = slots[q];
@@ -2853,18 +2814,17 @@ struct RcclHalo {
   int rank = 0, world = 1, mode = 0;  // mode 0: neighbour send/recv, 1: all-reduce of the whole array
   std::vector<int> lo, hi;            // node layers rank r may touch (inclusive)
   hipStream_t side = nullptr;
-  void* rbuf[2] = {nullptr, nullptr};  // receive buffers: from rank-1, from rank+1
-  size_t rbuf_bytes[2] = {0, 0};
+  DevBuf<char> rbuf[2];  // receive buffers: from rank-1, from rank+1
   struct Ev {
     hipEvent_t start = nullptr, done = nullptr;
     bool pending = false;
   };
   std::map<const void*, Ev> ev;  // one pair of events per nodal array, re-recorded every step
   bool self_loop = false;        // world 1 self-test: the rank is its own two neighbours
-  int* mig_cnt_d = nullptr;      // nlps_gpu_rccl_migrate: {rows to below, rows to above, rows from below, rows from above}
+  DevBuf<int> mig_cnt_d;         // nlps_gpu_rccl_migrate: {rows to below, rows to above, rows from below, rows from above}
   // single-launch overlap (TileD::sig_flag): counters in device memory, flags in signal memory, one pair per stage
-  unsigned* sig_cnt = nullptr;   // [2]
-  unsigned* sig_flag[2] = {nullptr, nullptr};
+  DevBuf<unsigned> sig_cnt;      // [2]
+  DevBuf<unsigned> sig_flag[2];
   unsigned sig_seq = 0;
   bool can_wait_value = false;
 };
@@ -2935,11 +2895,9 @@ static int rccl_exchange_on(nlps_gpu* h, void* dptr, int nfield, int elem, int k
       if (a > b) continue;
     }
     const size_t count = (size_t)(b - a + 1) * plane * nfield, bytes = count * elem;
-    if (bytes > R->rbuf_bytes[k]) {
+    if (bytes > R->rbuf[k].size()) {
       HIPCHK(hipDeviceSynchronize());
-      if (R->rbuf[k]) HIPCHK(hipFree(R->rbuf[k]));
-      HIPCHK(hipMalloc(&R->rbuf[k], bytes));
-      R->rbuf_bytes[k] = bytes;
+      HIPCHK(R->rbuf[k].reserve(bytes));
     }
     parts[np++] = {(char*)dptr + (size_t)a * plane * nfield * elem, count, R->self_loop ? R->rank : nb, k};
   }
@@ -2948,7 +2906,7 @@ static int rccl_exchange_on(nlps_gpu* h, void* dptr, int nfield, int elem, int k
   for (int q = 0; q < np; q++) {
     // self-test: what goes "down" comes back as what arrives "from above" and vice versa
     RCCLCHK(g_rccl.Send(parts[q].sl, parts[q].count, dt, parts[q].peer, R->comm, s));
-    RCCLCHK(g_rccl.Recv(R->rbuf[R->self_loop ? 1 - parts[q].k : parts[q].k], parts[q].count, dt, parts[q].peer, R->comm, s));
+    RCCLCHK(g_rccl.Recv(R->rbuf[R->self_loop ? 1 - parts[q].k : parts[q].k].get(), parts[q].count, dt, parts[q].peer, R->comm, s));
   }
   RCCLCHK(g_rccl.GroupEnd());
   // after the sends in stream order, so the neighbour got the un-summed slice
@@ -2956,9 +2914,9 @@ static int rccl_exchange_on(nlps_gpu* h, void* dptr, int nfield, int elem, int k
     const size_t n = parts[q].count;
     const unsigned grid = (unsigned)((n + 255) / 256);
     if (elem == 8 && kind == 0)
-      hipLaunchKernelGGL(k_halo_add<double>, dim3(grid), dim3(256), 0, s, (double*)parts[q].sl, (const double*)R->rbuf[parts[q].k], n);
+      hipLaunchKernelGGL(k_halo_add<double>, dim3(grid), dim3(256), 0, s, (double*)parts[q].sl, (const double*)R->rbuf[parts[q].k].get(), n);
     else
-      hipLaunchKernelGGL(k_halo_max, dim3(grid), dim3(256), 0, s, (unsigned char*)parts[q].sl, (const unsigned char*)R->rbuf[parts[q].k], n);
+      hipLaunchKernelGGL(k_halo_max, dim3(grid), dim3(256), 0, s, (unsigned char*)parts[q].sl, (const unsigned char*)R->rbuf[parts[q].k].get(), n);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -3053,10 +3011,8 @@ static int rccl_attach_common(nlps_gpu* h, ncclComm_t comm, bool own, int rank, 
     return 1;
   }
   {
-    bool ok = hipMalloc((void**)&R->sig_cnt, 2 * sizeof(unsigned)) == hipSuccess &&
-              hipMemset(R->sig_cnt, 0, 2 * sizeof(unsigned)) == hipSuccess;
-    for (int k = 0; k < 2 && ok; k++)
-      ok = hipMalloc((void**)&R->sig_flag[k], 8) == hipSuccess && hipMemset(R->sig_flag[k], 0, 8) == hipSuccess;
+    bool ok = R->sig_cnt.alloc_zeroed(2) == hipSuccess;
+    for (int k = 0; k < 2 && ok; k++) ok = R->sig_flag[k].alloc_zeroed(2) == hipSuccess;
     if (!ok) (void)hipGetLastError();
     R->can_wait_value = ok;
   }
@@ -3120,12 +3076,12 @@ extern "C" int nlps_gpu_rccl_detach(nlps_gpu* h) {
     if (kv.second.start) (void)hipEventDestroy(kv.second.start);
     if (kv.second.done) (void)hipEventDestroy(kv.second.done);
   }
-  for (int k = 0; k < 2; k++) {
-    if (R->rbuf[k]) (void)hipFree(R->rbuf[k]);
-    if (R->sig_flag[k]) (void)hipFree(R->sig_flag[k]);
+  for (int k = 0; k < 2; k++) {  // (the buffers go before the stream and the communicator that used them)
+    R->rbuf[k].reset();
+    R->sig_flag[k].reset();
   }
-  if (R->sig_cnt) (void)hipFree(R->sig_cnt);
-  if (R->mig_cnt_d) (void)hipFree(R->mig_cnt_d);
+  R->sig_cnt.reset();
+  R->mig_cnt_d.reset();
   if (R->side) (void)hipStreamDestroy(R->side);
   if (R->own_comm && R->comm) (void)g_rccl.CommDestroy(R->comm);
   delete R;
@@ -3210,12 +3166,11 @@ static int rccl_migrate(nlps_gpu* h, int keep_lo, int keep_hi, int* sent_down, i
     if (R->rank == 0) keep_lo = 0;
     if (R->rank == R->world - 1) keep_hi = nl - 1;
   }
-  double* rows_in[2] = {nullptr, nullptr};
+  DevBuf<double> rows_in[2];
   auto fatal = [&](const std::string& what) {  // unrecoverable local error in the middle of the collective
     h->err = "nlps_gpu_rccl_migrate: " + what + " (communicator aborted)";
     fprintf(stderr, "\033[1;31mError in nlps_gpu: %s\033[0m\n", h->err.c_str());
-    for (int k = 0; k < 2; k++)
-      if (rows_in[k]) (void)hipFree(rows_in[k]);
+    for (int k = 0; k < 2; k++) rows_in[k].reset();
     if (R->comm) (void)g_rccl.CommAbort(R->comm);
     R->comm = nullptr;
     return 1;
@@ -3252,7 +3207,7 @@ static int rccl_migrate(nlps_gpu* h, int keep_lo, int keep_hi, int* sent_down, i
     if (bad) return 1;
     return nlps_gpu_migration_commit(h, nullptr, 0, nullptr, 0);
   }
-  if (!R->mig_cnt_d) MIG_HIP(hipMalloc((void**)&R->mig_cnt_d, 8 * sizeof(int)));
+  MIG_HIP(R->mig_cnt_d.reserve(8));
   // 1. how many rows come from each neighbour
   int cnt[8] = {n_out[0], n_out[1], 0, 0, 0, 0, 0, 0};
   MIG_HIP(hipMemcpyAsync(R->mig_cnt_d, cnt, 8 * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -3283,20 +3238,18 @@ static int rccl_migrate(nlps_gpu* h, int keep_lo, int keep_hi, int* sent_down, i
   }
   // 3. the rows
   for (int k = 0; k < 2; k++)
-    if (n_in[k] > 0) MIG_HIP(hipMalloc((void**)&rows_in[k], (size_t)n_in[k] * rw * sizeof(double)));
+    if (n_in[k] > 0) MIG_HIP(rows_in[k].reserve((size_t)n_in[k] * rw));
   MIG_RCCL(g_rccl.GroupStart());
   for (int k = 0; k < 2; k++) {
     if (!has[k]) continue;
     if (n_out[k] > 0) MIG_RCCL(g_rccl.Send(rows_out[k], (size_t)n_out[k] * rw, ncclDouble, peer[k], R->comm, h->stream));
-    if (n_in[k] > 0) MIG_RCCL(g_rccl.Recv(rows_in[k], (size_t)n_in[k] * rw, ncclDouble, peer[k], R->comm, h->stream));
+    if (n_in[k] > 0) MIG_RCCL(g_rccl.Recv(rows_in[k].get(), (size_t)n_in[k] * rw, ncclDouble, peer[k], R->comm, h->stream));
   }
   MIG_RCCL(g_rccl.GroupEnd());
   MIG_HIP(hipStreamSynchronize(h->stream));
 #undef MIG_HIP
 #undef MIG_RCCL
-  const int st = nlps_gpu_migration_commit(h, rows_in[0], n_in[0], rows_in[1], n_in[1]);
-  for (int k = 0; k < 2; k++)
-    if (rows_in[k]) (void)hipFree(rows_in[k]);
+  const int st = nlps_gpu_migration_commit(h, rows_in[0].get(), n_in[0], rows_in[1].get(), n_in[1]);
   if (received) *received = n_in[0] + n_in[1];
   return st;
 }
@@ -3368,8 +3321,7 @@ extern "C" int nlps_gpu_set_node_numbering(nlps_gpu* h, const int* lattice_of_fi
   if (!lattice_of_file) {
     if (h->canon_d) {
       HIPCHK(hipStreamSynchronize(h->stream));
-      (void)hipFree(h->canon_d);
-      h->canon_d = nullptr;
+      h->canon_d.reset();
     }
     return 0;
   }
@@ -3383,9 +3335,9 @@ extern "C" int nlps_gpu_set_node_numbering(nlps_gpu* h, const int* lattice_of_fi
     seen[l] = 1;
   }
   if (!h->canon_d) {
-    HIPCHK(hipMalloc((void**)&h->canon_d, (size_t)nn * sizeof(int)));
-    if (!h->mask_flags_d) HIPCHK(hipMalloc((void**)&h->mask_flags_d, (size_t)nn));
-    if (!h->mask_idx_d) HIPCHK(hipMalloc((void**)&h->mask_idx_d, (size_t)nn * sizeof(int)));
+    HIPCHK(h->canon_d.reserve((size_t)nn));
+    HIPCHK(h->mask_flags_d.reserve((size_t)nn));  // (these two stay when the numbering is taken back)
+    HIPCHK(h->mask_idx_d.reserve((size_t)nn));
   }
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(h->canon_d, lattice_of_file, (size_t)nn * sizeof(int), hipMemcpyHostToDevice));
@@ -3515,7 +3467,7 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
   const bool ahead = h->ahead && !init;
   const bool deferred = ahead && h->ranks_deferred && node_lists(h);  // that search only counted: ranks from cursors (k_fill_orders)
   h->ranks_deferred = false;
-  if (ahead) std::swap(h->tile_count_d, h->tile_count2_d);  // the counters that search filled size the lists from here on
+  if (ahead) h->tile_count_d.swap(h->tile_count2_d);  // the counters that search filled size the lists from here on
   const bool clear_in_dilate = ahead && p2g;  // nothing but the nodal accumulators to reset: k_dilate_scan does it
   if (!clear_in_dilate)
     LAUNCH_ND((k_step_clear<2>), (k_step_clear<3>), nblk(std::max(h->nwn, h->ntw)), h->n0, h->nwn, h->N,
@@ -3532,13 +3484,13 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
                     h->band_lo, h->band_hi, h->work1_d, h->nwork_d, deferred ? h->tile_cursor_d + h->tile0 : nullptr};
     const int nb = 1 + (h->nwn + 1023) / 1024 + (node_lists(h) ? (h->ntw + 15) / 16 : 0);
     int* fo = (h->adaptive_resort > 0.0 && !h->deterministic) ? h->foreign_d : nullptr;
-    LAUNCH_ND_BLK(k_dilate_scan<2>, k_dilate_scan<3>, nb, 1024, h->n0, h->nwn, h->g, h->N, ts, fo, h->foreign_h, tile_tab(h),
+    LAUNCH_ND_BLK(k_dilate_scan<2>, k_dilate_scan<3>, nb, 1024, h->n0, h->nwn, h->g, h->N, ts, fo, h->foreign_h.host(), tile_tab(h),
                   clear_in_dilate ? 1 : 0);
   }
   HIPCHK(hipGetLastError());
   if (halo(h, h->N.active, 1, 1, 1, overlap ? 1 : 0)) return 1;
   if (!h->order2_d) {
-    HIPCHK(hipMalloc((void**)&h->order2_d, h->P.npad * sizeof(int)));
+    HIPCHK(h->order2_d.reserve(h->P.npad));
     HIPCHK(hipMemsetAsync(h->order2_d, 0, h->P.npad * sizeof(int), h->stream));
   }
   if (node_lists(h)) {  // both lists in one pass, the canonical one through the layer tables of this step (TileTab)
@@ -3578,12 +3530,12 @@ static int materialise_roll(nlps_gpu* h) {
   return 0;
 }
 
-// mirrored: the last kernel of the call has already stored the status word into the pinned host word (status_hd)
+// mirrored: the last kernel of the call has already stored the status word into the pinned host word (the alias of status_h)
 static int check_status(nlps_gpu* h, int fatal_mask, const char* where, bool mirrored) {
   // the status word travels to a pinned host word in stream order: one wait instead of a synchronise and a blocking copy
-  if (!mirrored) HIPCHK(hipMemcpyAsync(h->status_h, h->gstatus_d, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (!mirrored) HIPCHK(hipMemcpyAsync(h->status_h.host(), h->gstatus_d, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  const int st = *(volatile int*)h->status_h;
+  const int st = *(volatile int*)h->status_h.host();
   if (st & fatal_mask) {
     char buf[160];
     snprintf(buf, sizeof buf, "Error in %s: particle failure flags 0x%x (1 Newton, 2 connectivity, 4 J<=0, 8 law, 16 outside node window)",
@@ -3627,18 +3579,16 @@ static int ensure_bcs(nlps_gpu* h, const nlps_bcc* bcc, int nbcc) {
   for (int i = 0; same && i < nbcc; i++) same = h->bcs[i].host_nodes == bcc[i].nodes && h->bcs[i].n == bcc[i].nnodes;
   if (same) return 0;
   if (materialise_nodal(h)) return 1;  // (the nodal arrays of the last folded step still want the old sets' mask)
-  for (auto& b : h->bcs)
-    if (b.dnodes) (void)hipFree(b.dnodes);
   h->bcs.clear();
   for (int i = 0; i < nbcc; i++) {
-    BcDev b{bcc[i].nodes, bcc[i].nnodes, nullptr};
+    BcDev b{bcc[i].nodes, bcc[i].nnodes, {}};
     if (b.n > 0) {
-      HIPCHK(hipMalloc((void**)&b.dnodes, (size_t)b.n * sizeof(int)));
+      HIPCHK(b.dnodes.reserve((size_t)b.n));
       HIPCHK(hipMemcpy(b.dnodes, bcc[i].nodes, (size_t)b.n * sizeof(int), hipMemcpyHostToDevice));
     }
-    h->bcs.push_back(b);
+    h->bcs.push_back(std::move(b));
   }
-  if (!h->bcmask_d) HIPCHK(hipMalloc((void**)&h->bcmask_d, (size_t)h->g.nnodes * sizeof(unsigned)));
+  HIPCHK(h->bcmask_d.reserve((size_t)h->g.nnodes));
   HIPCHK(hipMemset(h->bcmask_d, 0, (size_t)h->g.nnodes * sizeof(unsigned)));
   if (nbcc <= NLPS_MAX_BC_INLINE)
     for (int i = 0; i < nbcc; i++)
@@ -3709,7 +3659,7 @@ static int to_grid(nlps_gpu* h, double* grid, const double* masked, int nf) {
   size_t n = (size_t)h->nactive * nf;
   const double* src = masked;
   if (!is_device_ptr(masked)) {
-    if (ensure_masked(h, n)) return 1;
+    if (reserve(h, "to_grid", h->maskedA, n, "the masked vector")) return 1;
     HIPCHK(hipMemcpyAsync(h->maskedA, masked, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     src = h->maskedA;
   }
@@ -3724,7 +3674,7 @@ static int from_grid(nlps_gpu* h, double* masked, const double* grid, int nf, in
   size_t n = (size_t)h->nactive * nf;
   if (n == 0) return 0;
   bool dev_out = is_device_ptr(masked);
-  if (ensure_masked(h, 2 * n)) return 1;
+  if (reserve(h, "from_grid", h->maskedA, 2 * n, "the masked vectors")) return 1;
   double* dst = dev_out ? masked : h->maskedA;
   if (!dev_out && mode == 1) HIPCHK(hipMemcpyAsync(dst, masked, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   const double* div = div_masked;
@@ -3820,18 +3770,18 @@ extern "C" int nlps_gpu_internal_forces(nlps_gpu* h, double* R) {
     const int np = h->P.np;
     const size_t nn = (size_t)h->g.nnodes;
     if (!h->dmg_first_d) {
-      HIPCHK(hipMalloc((void**)&h->dmg_first_d, nn * sizeof(int)));
-      HIPCHK(hipMalloc((void**)&h->dmg_last_d, nn * sizeof(int)));
+      HIPCHK(h->dmg_first_d.reserve(nn));
+      HIPCHK(h->dmg_last_d.reserve(nn));
     }
     HIPCHK(hipMemsetAsync(h->dmg_first_d, 0, nn * sizeof(int), h->stream));
     HIPCHK(hipMemsetAsync(h->dmg_last_d, 0, nn * sizeof(int), h->stream));
     hipLaunchKernelGGL(k_tangent_keys, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->P, h->skey_d, h->sval_d);
     size_t bytes = h->cub_tmp_bytes;
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(h->cub_tmp, bytes, h->skey_d, h->skey2_d, h->sval_d, h->sval2_d, np, 0, 32,
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(h->cub_tmp.get(), bytes, h->skey_d.get(), h->skey2_d.get(), h->sval_d.get(), h->sval2_d.get(), np, 0, 32,
                                               h->stream));
     hipLaunchKernelGGL(k_node_ranges, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, h->skey2_d, h->dmg_first_d, h->dmg_last_d);
     if (h->P.softening) {
-      double* T0 = reinterpret_cast<double*>(h->gather_tmp);  // [npad] scratch of the re-sort, idle here
+      double* T0 = h->gather_tmp.get();  // [npad] scratch of the re-sort, idle here
       LAUNCH_ND((k_soften_pass1<2>), (k_soften_pass1<3>), nblk(np), h->P, h->mats_d, T0);
       LAUNCH_ND((k_soften_pass2<2>), (k_soften_pass2<3>), nblk(np), h->P, h->g, h->mats_d, h->dmg_first_d, h->dmg_last_d, h->sval2_d,
                 (const uint8_t*)h->rank1_d, (const int*)h->perm_d, (const double*)T0, h->g.h);
@@ -3839,22 +3789,24 @@ extern "C" int nlps_gpu_internal_forces(nlps_gpu* h, double* R) {
       // frozen lists (Beps.c:30-36): the node tables of the snapshot's closest nodes, rebuilt per call like the others
       if (beps_snapshot(h)) return 1;
       if (!h->dmg_first0_d) {
-        HIPCHK(hipMalloc((void**)&h->dmg_first0_d, nn * sizeof(int)));
-        HIPCHK(hipMalloc((void**)&h->dmg_last0_d, nn * sizeof(int)));
-        HIPCHK(hipMalloc((void**)&h->dmg_sorted0_d, h->P.npad * sizeof(int)));
+        HIPCHK(h->dmg_first0_d.reserve(nn));
+        HIPCHK(h->dmg_last0_d.reserve(nn));
+        HIPCHK(h->dmg_sorted0_d.reserve(h->P.npad));
       }
-      std::swap(h->dmg_sorted0_d, h->sval2_d);  // dmg_sorted0_d: the CURRENT order just sorted; sval2_d: free for the next sort
+      // dmg_sorted0_d: the CURRENT order just sorted; sval2_d: free for the next sort.  (Both blocks hold npad ints, so
+      // an error return between the two swaps leaves either owner with a block of the right size.)
+      h->dmg_sorted0_d.swap(h->sval2_d);
       HIPCHK(hipMemsetAsync(h->dmg_first0_d, 0, nn * sizeof(int), h->stream));
       HIPCHK(hipMemsetAsync(h->dmg_last0_d, 0, nn * sizeof(int), h->stream));
       hipLaunchKernelGGL(k_beps_keys0, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->P, h->skey_d, h->sval_d);
       bytes = h->cub_tmp_bytes;
-      HIPCHK(hipcub::DeviceRadixSort::SortPairs(h->cub_tmp, bytes, h->skey_d, h->skey2_d, h->sval_d, h->sval2_d, np, 0, 32,
+      HIPCHK(hipcub::DeviceRadixSort::SortPairs(h->cub_tmp.get(), bytes, h->skey_d.get(), h->skey2_d.get(), h->sval_d.get(), h->sval2_d.get(), np, 0, 32,
                                                 h->stream));
       hipLaunchKernelGGL(k_node_ranges, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, h->skey2_d, h->dmg_first0_d, h->dmg_last0_d);
       // (current order in dmg_sorted0_d, snapshot order in sval2_d)
       LAUNCH_ND((k_damage<2>), (k_damage<3>), nblk(np), h->P, h->g, h->mats_d, h->dmg_first_d, h->dmg_last_d, h->dmg_sorted0_d,
                 h->dmg_first0_d, h->dmg_last0_d, h->sval2_d, h->g.h);
-      std::swap(h->dmg_sorted0_d, h->sval2_d);  // the sort buffers go back to where the re-sort expects them
+      h->dmg_sorted0_d.swap(h->sval2_d);  // the sort buffers go back to where the re-sort expects them
     }
     HIPCHK(hipGetLastError());
   }
@@ -3936,11 +3888,11 @@ static int traction_to_grid(nlps_gpu* h, const char* who, double* out, const nlp
   const int n = (int)ids.size();
   if (n == 0) return 0;
   *any = 1;
-  int* ids_d = nullptr;
-  double *T_d = nullptr, *A_d = nullptr;
-  HIPCHK(hipMalloc((void**)&ids_d, (size_t)n * sizeof(int)));
-  HIPCHK(hipMalloc((void**)&T_d, (size_t)n * ND * sizeof(double)));
-  if (ND == 3) HIPCHK(hipMalloc((void**)&A_d, (size_t)n * sizeof(double)));
+  DevBuf<int> ids_d;
+  DevBuf<double> T_d, A_d;
+  HIPCHK(ids_d.reserve((size_t)n));
+  HIPCHK(T_d.reserve((size_t)n * ND));
+  if (ND == 3) HIPCHK(A_d.reserve((size_t)n));
   HIPCHK(hipMemcpyAsync(ids_d, ids.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(T_d, T.data(), (size_t)n * ND * sizeof(double), hipMemcpyHostToDevice, h->stream));
   if (ND == 3) HIPCHK(hipMemcpyAsync(A_d, A.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -3949,9 +3901,6 @@ static int traction_to_grid(nlps_gpu* h, const char* who, double* out, const nlp
   LAUNCH_ND(k_traction<2>, k_traction<3>, nblk(n), h->P, h->g, n, ids_d, h->sval_d, T_d, A_d, thickness, out);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));  // (the host vectors above are about to go)
-  (void)hipFree(ids_d);
-  (void)hipFree(T_d);
-  if (A_d) (void)hipFree(A_d);
   return 0;
 }
 
@@ -4024,7 +3973,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   if (!h->Pd_alt && h->resort_every > 0 && h->P.np > 0) {
     // the twin block of the periodic re-sort, at the first step of the fused scheme rather than inside the first
     // re-sort: a hipMalloc of this size (1.3 GB per million particles) takes milliseconds, the re-sort itself 0.3
-    HIPCHK(hipMalloc((void**)&h->Pd_alt, (size_t)NFD * h->P.npad * sizeof(double)));
+    HIPCHK(h->Pd_alt.reserve((size_t)NFD * h->P.npad));
     HIPCHK(hipMemsetAsync(h->Pd_alt, 0, (size_t)NFD * h->P.npad * sizeof(double), h->stream));
   }
   if (!h->rolled && h->P.np > 0) {  // entering the fused scheme: rho J of every particle (see F_RHOJ)
@@ -4037,7 +3986,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   bool drifted = false;
   if (h->adaptive_resort > 0.0 && !h->deterministic && h->resort_every > 0 && h->P.np > 0) {  // (a re-sort moment read
     // from an asynchronous word is not reproducible: the deterministic mode keeps the fixed interval)
-    h->debt += (double)*(volatile int*)h->foreign_h / (double)h->P.np;
+    h->debt += (double)*(volatile int*)h->foreign_h.host() / (double)h->P.np;
     drifted = h->debt > h->adaptive_resort && h->steps_since_sort >= h->adaptive_min_steps;
   }
   if (h->resort_every > 0 && (h->steps_since_sort >= h->resort_every || drifted)) {
@@ -4059,7 +4008,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   if (det && !h->slab_d) {
     const size_t NWs = ND == 3 ? TileCfg<3>::NWA : TileCfg<2>::NWA;
     const size_t per_tile = std::max<size_t>((size_t)(1 + ND), (size_t)4 * ND) * NWs;  // K2: one slab; K3: one per law
-    HIPCHK(hipMalloc((void**)&h->slab_d, (size_t)h->ntiles * per_tile * sizeof(double)));
+    HIPCHK(h->slab_d.reserve((size_t)h->ntiles * per_tile));
   }
   // second half of the P2G flush: per node, the window slabs of the tiles that hold it (part: node ranges as below)
   auto gather_nm = [&](int part) {
@@ -4434,12 +4383,7 @@ static int vec_begin(nlps_gpu* h, const char* who, VecIO& io) {
   if (need_masks(h, who)) return 1;
   io.h = h;
   io.n = (size_t)h->nactive * h->nd;
-  if (io.n * 6 > h->vec_cap) {
-    if (h->vec_d) HIPCHK(hipFree(h->vec_d));
-    h->vec_cap = io.n * 6;
-    HIPCHK(hipMalloc((void**)&h->vec_d, h->vec_cap * sizeof(double)));
-  }
-  return 0;
+  return reserve(h, who, h->vec_d, io.n * 6, "the staging of host vectors");
 }
 
 extern "C" int nlps_gpu_form_initial_guess(nlps_gpu* h, double* dU, const double* Un_dt, const double* Un_dt2, double dt,
@@ -4559,18 +4503,15 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
   const bool fused = !(flags & (NLPS_LAGR_SEPARATE | NLPS_LAGR_RATES)) && !h->P.erosion && h->uniform_law <= NLPS_KLAW_FRICTIONAL &&
                      h->P.np > 0;
   if (!fused) {
-    double* dV = nullptr;
+    DevBuf<double> dV;
     if (flags & NLPS_LAGR_RATES) {  // __compute_nodal_velocity_increments, :1018
-      HIPCHK(hipMalloc((void**)&dV, std::max<size_t>(n, 1) * sizeof(double)));
-      if (nlps_gpu_nodal_kinetic_increments(h, dV, nullptr, dU, Un_dt, Un_dt2, alpha)) {
-        (void)hipFree(dV);
-        return 1;
-      }
+      HIPCHK(dV.reserve(std::max<size_t>(n, 1)));
+      if (nlps_gpu_nodal_kinetic_increments(h, dV, nullptr, dU, Un_dt, Un_dt2, alpha)) return 1;
     }
     int st = nlps_gpu_compatibility(h, dU, dV);
     if (dV) {
       (void)hipStreamSynchronize(h->stream);
-      (void)hipFree(dV);
+      dV.reset();
     }
     if (st) return 1;
     if (nlps_gpu_constitutive(h)) return 1;
@@ -4590,11 +4531,9 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
   const double* u = io.in(dU);
   const double* cst[3] = {Un_dt, Un_dt2, M};  // constant over the evaluations of one SNES solve
   if (!is_device_ptr(Un_dt) || !is_device_ptr(Un_dt2) || !is_device_ptr(M)) {
-    if (h->lagr_cap < 3 * n) {
-      if (h->lagr_d) HIPCHK(hipFree(h->lagr_d));
-      h->lagr_cap = 3 * n;
-      HIPCHK(hipMalloc((void**)&h->lagr_d, h->lagr_cap * sizeof(double)));
+    if (h->lagr_d.size() < 3 * n) {
       h->lagr_valid = false;
+      if (reserve(h, "nlps_gpu_lagrangian_evaluation", h->lagr_d, 3 * n, "the constant vectors of the step")) return 1;
     }
     if ((flags & NLPS_LAGR_SAME_STEP) && !h->lagr_valid) {
       h->err = "nlps_gpu_lagrangian_evaluation: NLPS_LAGR_SAME_STEP without an earlier evaluation since nlps_gpu_active_masks";
@@ -4654,7 +4593,7 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
     for (int k = 0; k < ND; k++) b[k] = gravity[k];
   LAUNCH_ND((k_lagrangian_nodal<2>), (k_lagrangian_nodal<3>), nblk(h->g.nnodes), h->g.nnodes, (const int*)h->n2m_d,
             (const int*)h->d2m_d, (const double*)h->N.force, any ? (const double*)h->gridA : (const double*)nullptr, r, m, u, v,
-            a, alpha[0], alpha[1], alpha[2], b[0], b[1], b[2], (const int*)h->gstatus_d, h->status_hd);
+            a, alpha[0], alpha[1], alpha[2], b[0], b[1], b[2], (const int*)h->gstatus_d, h->status_h.alias());
   HIPCHK(hipGetLastError());
   if (h->snes_tail && snes_fnorm_launch(h, r)) return 1;  // (nlps_gpu_newton_solve: ||R||^2 arrives with the wait below)
   if (io.finish()) {
@@ -4662,7 +4601,7 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
     return 1;
   }
   if (h->timing) HIPCHK(hipEventRecord(h->ev[6], h->stream));
-  if (check_status(h, ST_CONSTITUTIVE, "Stress_integration__Constitutive__()", h->status_hd != nullptr)) return 1;  // (synchronises)
+  if (check_status(h, ST_CONSTITUTIVE, "Stress_integration__Constitutive__()", h->status_h.alias() != nullptr)) return 1;  // (synchronises)
   if (h->timing) {
     for (int q = 0; q < 8; q++) h->ms[q] = 0.f;
     HIPCHK(hipEventElapsedTime(&h->ms[0], h->ev[0], h->ev[2]));
@@ -4681,14 +4620,14 @@ extern "C" int nlps_gpu_tangent_assemble(nlps_gpu* h, long long* nnz) {
   const int ND = h->nd, S = ND == 3 ? TanCfg<3>::S : TanCfg<2>::S;
   const size_t nn = (size_t)h->g.nnodes, nblk_st = nn * S;
   if (!h->kst_d) {
-    HIPCHK(hipMalloc((void**)&h->kst_d, nblk_st * ND * ND * sizeof(double)));
-    HIPCHK(hipMalloc((void**)&h->ktouched_d, nblk_st));
-    HIPCHK(hipMalloc((void**)&h->kcnt_d, (nn + 1) * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&h->koffs_d, (nn + 1) * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&h->khead_d, h->P.npad * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&h->kng_d, sizeof(int)));
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, h->kscan_bytes, h->kcnt_d, h->koffs_d, (int)nn + 1, h->stream));
-    HIPCHK(hipMalloc(&h->kscan_tmp, h->kscan_bytes + 16));
+    HIPCHK(h->kst_d.reserve(nblk_st * ND * ND));
+    HIPCHK(h->ktouched_d.reserve(nblk_st));
+    HIPCHK(h->kcnt_d.reserve(nn + 1));
+    HIPCHK(h->koffs_d.reserve(nn + 1));
+    HIPCHK(h->khead_d.reserve(h->P.npad));
+    HIPCHK(h->kng_d.reserve(1));
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, h->kscan_bytes, h->kcnt_d.get(), h->koffs_d.get(), (int)nn + 1, h->stream));
+    HIPCHK(h->kscan_tmp.reserve(h->kscan_bytes + 16));
   }
   HIPCHK(hipMemsetAsync(h->kst_d, 0, nblk_st * ND * ND * sizeof(double), h->stream));
   HIPCHK(hipMemsetAsync(h->ktouched_d, 0, nblk_st, h->stream));
@@ -4699,7 +4638,7 @@ extern "C" int nlps_gpu_tangent_assemble(nlps_gpu* h, long long* nnz) {
     // particles grouped by closest node (radix sort of (I0, p) in the re-sort buffers), one workgroup per node
     hipLaunchKernelGGL(k_tangent_keys, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->P, h->skey_d, h->sval_d);
     size_t bytes = h->cub_tmp_bytes;
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(h->cub_tmp, bytes, h->skey_d, h->skey2_d, h->sval_d, h->sval2_d, np, 0, 32,
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(h->cub_tmp.get(), bytes, h->skey_d.get(), h->skey2_d.get(), h->sval_d.get(), h->sval2_d.get(), np, 0, 32,
                                               h->stream));
     HIPCHK(hipMemsetAsync(h->kng_d, 0, sizeof(int), h->stream));
     hipLaunchKernelGGL(k_tangent_groups, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, h->skey2_d, h->khead_d, h->kng_d);
@@ -4715,7 +4654,7 @@ extern "C" int nlps_gpu_tangent_assemble(nlps_gpu* h, long long* nnz) {
   LAUNCH_ND((k_tangent_count<2>), (k_tangent_count<3>), ((int)nn + 3) / 4, (int)nn, h->ktouched_d, h->kcnt_d);  // (one wave per row node)
   HIPCHK(hipGetLastError());
   size_t bytes = h->kscan_bytes;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(h->kscan_tmp, bytes, h->kcnt_d, h->koffs_d, (int)nn + 1, h->stream));
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(h->kscan_tmp.get(), bytes, h->kcnt_d.get(), h->koffs_d.get(), (int)nn + 1, h->stream));
   int total = 0;
   HIPCHK(hipMemcpyAsync(&total, h->koffs_d + nn, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   if (check_status(h, ST_NEWTON | ST_CONSTITUTIVE, "nlps_gpu_tangent_assemble() (Neo-Hookean particles only)")) return 1;
@@ -4741,7 +4680,7 @@ extern "C" int nlps_gpu_tangent_coo(nlps_gpu* h, double alpha_1, const double* l
   if (ne == 0) return 0;
   const double* mass_d = nullptr;
   if (lumped_mass) {
-    if (ensure_masked(h, (size_t)h->nactive * ND)) return 1;
+    if (reserve(h, "nlps_gpu_tangent_coo", h->maskedA, (size_t)h->nactive * ND, "the mass term")) return 1;
     HIPCHK(hipMemcpyAsync(h->maskedA, lumped_mass, (size_t)h->nactive * ND * sizeof(double), hipMemcpyDefault, h->stream));
     mass_d = h->maskedA;
   }
@@ -4752,24 +4691,19 @@ extern "C" int nlps_gpu_tangent_coo(nlps_gpu* h, double alpha_1, const double* l
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
   }
-  int *rows_d = nullptr, *cols_d = nullptr;
-  double* vals_d = nullptr;
-  HIPCHK(hipMalloc((void**)&rows_d, ne * sizeof(int)));
-  HIPCHK(hipMalloc((void**)&cols_d, ne * sizeof(int)));
-  HIPCHK(hipMalloc((void**)&vals_d, ne * sizeof(double)));
+  DevBuf<int> rows_d, cols_d;
+  DevBuf<double> vals_d;
+  HIPCHK(rows_d.reserve(ne));
+  HIPCHK(cols_d.reserve(ne));
+  HIPCHK(vals_d.reserve(ne));
   LAUNCH_ND((k_tangent_emit<2>), (k_tangent_emit<3>), (nn + 3) / 4, nn, h->g, h->ktouched_d, h->kst_d, h->koffs_d, h->n2m_d,
-            apply_dirichlet ? h->d2m_d : (const int*)nullptr, alpha_1, mass_d, rows_d, cols_d, vals_d, h->ktan_sym ? 1 : 0);
-  int st = 0;
-  if (hipGetLastError() != hipSuccess) st = 1;
-  if (!st && hipMemcpyAsync(rows, rows_d, ne * sizeof(int), hipMemcpyDefault, h->stream) != hipSuccess) st = 1;
-  if (!st && hipMemcpyAsync(cols, cols_d, ne * sizeof(int), hipMemcpyDefault, h->stream) != hipSuccess) st = 1;
-  if (!st && hipMemcpyAsync(vals, vals_d, ne * sizeof(double), hipMemcpyDefault, h->stream) != hipSuccess) st = 1;
-  (void)hipStreamSynchronize(h->stream);
-  (void)hipFree(rows_d);
-  (void)hipFree(cols_d);
-  (void)hipFree(vals_d);
-  if (st) h->err = "nlps_gpu_tangent_coo: HIP error while emitting the triplets";
-  return st;
+            apply_dirichlet ? h->d2m_d : (const int*)nullptr, alpha_1, mass_d, rows_d.get(), cols_d.get(), vals_d.get(), h->ktan_sym ? 1 : 0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(rows, rows_d, ne * sizeof(int), hipMemcpyDefault, h->stream));
+  HIPCHK(hipMemcpyAsync(cols, cols_d, ne * sizeof(int), hipMemcpyDefault, h->stream));
+  HIPCHK(hipMemcpyAsync(vals, vals_d, ne * sizeof(double), hipMemcpyDefault, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));  // (the copies land in the caller's memory before the blocks go)
+  return 0;
 }
 
 extern "C" int nlps_gpu_sparsity_pattern(nlps_gpu* h, int* nnz_per_row) {
@@ -4779,15 +4713,13 @@ extern "C" int nlps_gpu_sparsity_pattern(nlps_gpu* h, int* nnz_per_row) {
   }
   if (need_masks(h, "nlps_gpu_sparsity_pattern")) return 1;
   const int ND = h->nd, nn = h->g.nnodes;
-  int* pat_d = nullptr;
-  HIPCHK(hipMalloc((void**)&pat_d, (size_t)h->nactive * ND * sizeof(int) + 16));
-  LAUNCH_ND((k_tangent_pattern<2>), (k_tangent_pattern<3>), nblk(nn), nn, h->kcnt_d, h->n2m_d, pat_d);
-  int st = hipGetLastError() != hipSuccess;
-  if (!st && hipMemcpyAsync(nnz_per_row, pat_d, (size_t)h->nactive * ND * sizeof(int), hipMemcpyDefault, h->stream) != hipSuccess) st = 1;
-  (void)hipStreamSynchronize(h->stream);
-  (void)hipFree(pat_d);
-  if (st) h->err = "nlps_gpu_sparsity_pattern: HIP error";
-  return st;
+  DevBuf<int> pat_d;
+  HIPCHK(pat_d.reserve((size_t)h->nactive * ND + 4));
+  LAUNCH_ND((k_tangent_pattern<2>), (k_tangent_pattern<3>), nblk(nn), nn, h->kcnt_d, h->n2m_d, pat_d.get());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(nnz_per_row, pat_d, (size_t)h->nactive * ND * sizeof(int), hipMemcpyDefault, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
 }
 
 
@@ -4807,16 +4739,6 @@ static int tanop_valid(nlps_gpu* h, const char* who) {
   return need_masks(h, who);
 }
 
-static int tanop_alloc(nlps_gpu* h, const char* who, void** p, size_t bytes, const char* what) {
-  if (hipMalloc(p, bytes) == hipSuccess) return 0;
-  (void)hipGetLastError();
-  *p = nullptr;
-  char buf[200];
-  snprintf(buf, sizeof buf, "%s: cannot allocate %zu bytes for %s", who, bytes, what);
-  h->err = buf;
-  return 1;
-}
-
 extern "C" int nlps_gpu_tangent_operator(nlps_gpu* h, double alpha_1, const double* lumped_mass, int apply_dirichlet,
                                          size_t* bytes) {
   if (need_masks(h, "nlps_gpu_tangent_operator")) return 1;
@@ -4824,24 +4746,10 @@ extern "C" int nlps_gpu_tangent_operator(nlps_gpu* h, double alpha_1, const doub
   h->top_gen = 0;  // (no operator until this call succeeds)
   const int ND = h->nd, E = ND * ND, np = h->P.np;
   const size_t nD = (size_t)E * E * std::max(np, 1), nm = (size_t)h->nactive * ND, ngr = (size_t)h->g.nnodes * E;
-  if (nD > h->top_cap) {
-    if (h->top_d) HIPCHK(hipFree(h->top_d));
-    h->top_d = nullptr;
-    h->top_cap = 0;
-    if (tanop_alloc(h, "nlps_gpu_tangent_operator", (void**)&h->top_d, nD * sizeof(double), ND == 3 ? "81 doubles per particle" : "16 doubles per particle"))
-      return 1;
-    h->top_cap = nD;
-  }
-  if (std::max<size_t>(nm, 1) > h->top_mcap) {
-    if (h->top_m) HIPCHK(hipFree(h->top_m));
-    h->top_m = nullptr;
-    h->top_mcap = 0;
-    if (tanop_alloc(h, "nlps_gpu_tangent_operator", (void**)&h->top_m, std::max<size_t>(nm, 1) * sizeof(double), "the mass term")) return 1;
-    h->top_mcap = std::max<size_t>(nm, 1);
-  }
-  if (!h->top_g) {  // (the grid does not change size)
-    if (tanop_alloc(h, "nlps_gpu_tangent_operator", (void**)&h->top_g, ngr * sizeof(double), "the grid scratch")) return 1;
-  }
+  const char* who = "nlps_gpu_tangent_operator";
+  if (reserve(h, who, h->top_d, nD, ND == 3 ? "81 doubles per particle" : "16 doubles per particle")) return 1;
+  if (reserve(h, who, h->top_m, std::max<size_t>(nm, 1), "the mass term")) return 1;
+  if (reserve(h, who, h->top_g, ngr, "the grid scratch")) return 1;  // (the grid does not change size)
   h->top_np = np;
   h->top_dir = apply_dirichlet != 0;
   h->top_mass = lumped_mass != nullptr;
@@ -4944,14 +4852,8 @@ extern "C" int nlps_gpu_tangent_block_diagonal(nlps_gpu* h, double* blocks) {
   if (nb == 0) return 0;
   double* out = blocks;
   const bool host = !is_device_ptr(blocks);
-  if (host && nb > h->top_bcap) {  // staging of a host destination: kept on the handle (hipMalloc synchronises)
-    if (h->top_b) HIPCHK(hipFree(h->top_b));
-    h->top_b = nullptr;
-    h->top_bcap = 0;
-    if (tanop_alloc(h, "nlps_gpu_tangent_block_diagonal", (void**)&h->top_b, nb * sizeof(double), "the staging of the blocks"))
-      return 1;
-    h->top_bcap = nb;
-  }
+  // staging of a host destination: kept on the handle (hipMalloc synchronises)
+  if (host && reserve(h, "nlps_gpu_tangent_block_diagonal", h->top_b, nb, "the staging of the blocks")) return 1;
   if (host) out = h->top_b;
   int st = tanop_bdiag(h, out);
   if (!st && host) st = hipMemcpyAsync(blocks, out, nb * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess;
@@ -4964,19 +4866,9 @@ extern "C" int nlps_gpu_tangent_block_diagonal(nlps_gpu* h, double* blocks) {
 // ------------------------------------------------------------------------------------------------
 // device GMRES on the matrix-free tangent (nlps_krylov.hpp): the driver's KSPSolve in one call
 // ------------------------------------------------------------------------------------------------
-static int ksp_grow(nlps_gpu* h, double** p, size_t* cap, size_t n, const char* what) {
-  if (n <= *cap) return 0;
-  if (*p) HIPCHK(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  if (tanop_alloc(h, "nlps_gpu_tangent_solve", (void**)p, n * sizeof(double), what)) return 1;
-  *cap = n;
-  return 0;
-}
-
 // the values the kernels left in the host word (one synchronisation)
 static int ksp_wait(nlps_gpu* h) {
-  if (!h->ksp_hd) HIPCHK(hipMemcpyAsync(h->ksp_h, h->ksp_hdev, sizeof(KspHost), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h->ksp_h.fetch(h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -4987,9 +4879,9 @@ static int ksp_pc_build(nlps_gpu* h, int kind) {
   if (kind == NLPS_PC_NONE || (h->ksp_pc_serial == h->top_serial && h->ksp_pc_kind == kind)) return 0;
   const int ND = h->nd, nA = h->nactive;
   h->ksp_pc_kind = -1;
-  if (ksp_grow(h, &h->ksp_pc, &h->ksp_pc_cap, (size_t)nA * ND * ND, "the preconditioner")) return 1;
-  if (!h->ksp_bad_d && tanop_alloc(h, "nlps_gpu_tangent_solve", (void**)&h->ksp_bad_d, sizeof(int), "the preconditioner check"))
-    return 1;
+  const char* who = "nlps_gpu_tangent_solve";
+  if (reserve(h, who, h->ksp_pc, (size_t)nA * ND * ND, "the preconditioner")) return 1;
+  if (reserve(h, who, h->ksp_bad_d, 1, "the preconditioner check")) return 1;
   if (tanop_bdiag(h, h->ksp_pc)) {
     if (h->err.find("nlps_gpu_tangent_solve") == std::string::npos)
       h->err = "nlps_gpu_tangent_solve: HIP error in the diagonal blocks of the preconditioner";
@@ -4998,9 +4890,9 @@ static int ksp_pc_build(nlps_gpu* h, int kind) {
   HIPCHK(hipMemsetAsync(h->ksp_bad_d, 0x7f, sizeof(int), h->stream));  // (0x7f7f7f7f: no node failed)
   LAUNCH_ND((k_ksp_pc_build<2>), (k_ksp_pc_build<3>), nblk(nA), nA, kind, h->ksp_pc, h->ksp_bad_d);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(&h->ksp_h->flags, h->ksp_bad_d, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&h->ksp_h.host()->flags, h->ksp_bad_d, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  const int bad = *(volatile int*)&h->ksp_h->flags;
+  const int bad = *(volatile int*)&h->ksp_h.host()->flags;
   if (bad < nA) {
     char buf[240];
     snprintf(buf, sizeof buf,
@@ -5062,18 +4954,13 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
     if (hist) hist[0] = 0.0;
     return 0;
   }
-  if (ksp_grow(h, &h->ksp_v, &h->ksp_v_cap, (size_t)(m + 3) * n, "the Krylov basis") ||
-      ksp_grow(h, &h->ksp_part, &h->ksp_part_cap, (size_t)(m + 2) * nb, "the partial sums") ||
-      ksp_grow(h, &h->ksp_s, &h->ksp_s_cap, L.size(), "the Hessenberg state"))
+  if (reserve(h, who, h->ksp_v, (size_t)(m + 3) * n, "the Krylov basis") ||
+      reserve(h, who, h->ksp_part, (size_t)(m + 2) * nb, "the partial sums") ||
+      reserve(h, who, h->ksp_s, L.size(), "the Hessenberg state"))
     return 1;
-  if (!h->ksp_h) {
-    HIPCHK(hipHostMalloc((void**)&h->ksp_h, sizeof(KspHost), hipHostMallocDefault));
-    memset(h->ksp_h, 0, sizeof(KspHost));
-    if (hipHostGetDevicePointer((void**)&h->ksp_hd, h->ksp_h, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      h->ksp_hd = nullptr;  // (then the kernels write a device copy and ksp_wait brings it over)
-      if (tanop_alloc(h, who, (void**)&h->ksp_hdev, sizeof(KspHost), "the step word")) return 1;
-    }
+  if (!h->ksp_h.host()) {  // (without a device alias the kernels write a device copy and ksp_wait brings it over)
+    HIPCHK(h->ksp_h.alloc());
+    memset(h->ksp_h.host(), 0, sizeof(KspHost));
   }
   if (ksp_pc_build(h, kind)) return 1;
   const double* bd = io.in(b);
@@ -5083,7 +4970,7 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
   double* const t = z + n;
   double* const part = h->ksp_part;
   double* const s = h->ksp_s;
-  KspHost* const hw = h->ksp_hd ? h->ksp_hd : h->ksp_hdev;
+  KspHost* const hw = h->ksp_h.target();
   const KspPc pcd{kind, h->ksp_pc, z};
   const dim3 gs(nb), bs(KSP_NT);
   // ||b|| and r0 = b - K x0 into V[0]
@@ -5101,8 +4988,8 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
                      (const double*)nullptr, (double*)nullptr, (const double*)nullptr);
   HIPCHK(hipGetLastError());
   if (ksp_wait(h)) return 1;
-  const double bnorm = sqrt(h->ksp_h->bn2);
-  double rnorm = sqrt(h->ksp_h->rn2);
+  const double bnorm = sqrt(h->ksp_h.host()->bn2);
+  double rnorm = sqrt(h->ksp_h.host()->rn2);
   const double tol = std::max(ksp->rtol * bnorm, ksp->atol);
   if (hist) hist[0] = rnorm;
   int its = 0, reason = 0;
@@ -5150,8 +5037,8 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
       hipLaunchKernelGGL(k_ksp_scale, gs, bs, 0, h->stream, (int)n, (const double*)w, w, 1.0, (const double*)(s + L.wn2()));
       HIPCHK(hipGetLastError());
       if (ksp_wait(h)) return 1;
-      const double est = h->ksp_h->est;
-      const int flags = h->ksp_h->flags;
+      const double est = h->ksp_h.host()->est;
+      const int flags = h->ksp_h.host()->flags;
       its++;
       if (hist) hist[its] = est;
       if ((flags & KSP_FLAG_NONFINITE) || !std::isfinite(est)) {
@@ -5181,7 +5068,7 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
                        (const double*)nullptr, (double*)nullptr, (const double*)nullptr);
     HIPCHK(hipGetLastError());
     if (ksp_wait(h)) return 1;
-    rnorm = sqrt(h->ksp_h->rn2);
+    rnorm = sqrt(h->ksp_h.host()->rn2);
   }
   ksp->reason = reason;
   ksp->iterations = its;
@@ -5198,25 +5085,16 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
 // ------------------------------------------------------------------------------------------------
 // Newton solve (nlps_newton.hpp): the driver's SNESSolve (NEWTONLS, basic or bt line search) in one call
 // ------------------------------------------------------------------------------------------------
-static int snes_grow(nlps_gpu* h, const char* who, double** p, size_t* cap, size_t n, const char* what) {
-  if (n <= *cap) return 0;
-  if (*p) HIPCHK(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  if (tanop_alloc(h, who, (void**)p, n * sizeof(double), what)) return 1;
-  *cap = n;
-  return 0;
-}
 
 // queues F . F of a device residual towards the host word (stream order, no wait)
 static int snes_fnorm_launch(nlps_gpu* h, const double* F) {
   const int n = h->nactive * h->nd, nb = h->snes_nb;
-  double* const hw = h->snes_hd ? h->snes_hd : h->snes_hdev;
+  double* const hw = h->snes_h.target();
   double* const part = h->snes_part + (size_t)3 * nb;
   hipLaunchKernelGGL(k_snes_dots, dim3(nb), dim3(KSP_NT), 0, h->stream, n, F, (const double*)nullptr, part, nb);
   hipLaunchKernelGGL(k_snes_finish, dim3(1), dim3(KSP_NT), 0, h->stream, (const double*)part, nb, -1, hw + SNES_H_FF);
   HIPCHK(hipGetLastError());
-  if (!h->snes_hd) HIPCHK(hipMemcpyAsync(h->snes_h, h->snes_hdev, SNES_H_N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h->snes_h.fetch(h->stream));
   h->snes_tail = false;
   return 0;
 }
@@ -5244,7 +5122,7 @@ static int snes_residual(nlps_gpu* h, const SnesResidual& r, const double* x, do
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   snes->function_evaluations++;
-  *fnorm = sqrt(((volatile double*)h->snes_h)[SNES_H_FF]);
+  *fnorm = sqrt(((volatile double*)h->snes_h.host())[SNES_H_FF]);
   return 0;
 }
 
@@ -5283,21 +5161,16 @@ extern "C" int nlps_gpu_newton_solve(nlps_gpu* h, double* dU, const double* Un_d
   }
   const size_t n = (size_t)h->nactive * h->nd;
   const int nb = (int)std::max<size_t>((n + KSP_TILE - 1) / KSP_TILE, 1);
-  if (snes_grow(h, who, &h->snes_v, &h->snes_v_cap, 8 * std::max<size_t>(n, 1), "the work vectors") ||
-      snes_grow(h, who, &h->snes_part, &h->snes_part_cap, (size_t)5 * nb, "the partial sums"))
+  if (reserve(h, who, h->snes_v, 8 * std::max<size_t>(n, 1), "the work vectors") ||
+      reserve(h, who, h->snes_part, (size_t)5 * nb, "the partial sums"))
     return 1;
   h->snes_nb = nb;
-  if (!h->snes_h) {
-    HIPCHK(hipHostMalloc((void**)&h->snes_h, SNES_H_N * sizeof(double), hipHostMallocDefault));
-    memset(h->snes_h, 0, SNES_H_N * sizeof(double));
-    if (hipHostGetDevicePointer((void**)&h->snes_hd, h->snes_h, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      h->snes_hd = nullptr;
-      if (tanop_alloc(h, who, (void**)&h->snes_hdev, SNES_H_N * sizeof(double), "the scalars of the line search")) return 1;
-    }
+  if (!h->snes_h.host()) {
+    HIPCHK(h->snes_h.alloc(SNES_H_N));
+    memset(h->snes_h.host(), 0, SNES_H_N * sizeof(double));
   }
-  volatile double* const hv = h->snes_h;
-  double* const hw = h->snes_hd ? h->snes_hd : h->snes_hdev;
+  volatile double* const hv = h->snes_h.host();
+  double* const hw = h->snes_h.target();
   double *X = h->snes_v, *Y = X + n, *W = Y + n, *F = W + n, *T = F + n;
   // host vectors cross once: dU into X, the three constant vectors into their slots
   if (n > 0) HIPCHK(hipMemcpyAsync(X, dU, n * sizeof(double), hipMemcpyDefault, h->stream));
@@ -5449,7 +5322,7 @@ extern "C" int nlps_gpu_newmark_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc,
   if (nlps_gpu_active_masks(h, bcc, nbcc, step, &na, nullptr, nullptr, nullptr)) return 1;  // :205-209
   if (nactive) *nactive = na;
   const size_t n = (size_t)na * h->nd;
-  if (snes_grow(h, who, &h->nm_v, &h->nm_v_cap, 6 * std::max<size_t>(n, 1), "the nodal vectors of the step")) return 1;
+  if (reserve(h, who, h->nm_v, 6 * std::max<size_t>(n, 1), "the nodal vectors of the step")) return 1;
   double *M = h->nm_v, *V = M + n, *A = V + n, *dU = A + n, *dV = dU + n, *dA = dV + n;
   if (nlps_gpu_lumped_mass(h, M)) return 1;                                             // :223
   if (nlps_gpu_nodal_field_n(h, V, A, M)) return 1;                                     // :241
