@@ -425,6 +425,37 @@ __global__ __launch_bounds__(BLK) void k_search(PView P, GridD g, NView N, const
   if (valid && (!tc.count || P.tile[p] >= 0)) N.seed[I0] = 1;
 }
 
+// The search that rides on k5_tile as a kernel of its own, launched between K3 and K5 of the folded one-rank step (async
+// lists, nlps_gpu_explicit_step): closest-node update, seed and full-rank binning of the NEXT step from the position K5
+// is about to write, x + d_dis, with the additions of k5_body (so I0n is the same number, bit for bit).  It visits what
+// K5 visits -- the particles of this step's lists, P.tile[] >= 0 -- and moves what K5 moves (load_lme: a particle
+// without a neighbourhood stays where it is and keeps its node).  I0n is written for EVERY particle (= I0 for one that is
+// in no list), so the host can adopt the whole array by exchanging the two pointers.
+template <int ND>
+__global__ __launch_bounds__(BLK) void k_search_ahead(PView P, GridD g, NView N, const uint8_t* __restrict__ rank1, TileCnt tc) {
+  const int p = blockIdx.x * BLK + threadIdx.x;
+  int I0n = 0;
+  bool binned = false;
+  if (p < P.np) {
+    I0n = P.I0[p];
+    binned = P.tile[p] >= 0;
+    if (binned && (P.mlo[p] | P.mhi[p]) != 0ull) {
+      double xn[ND], dn2 = 0.0;
+#pragma unroll
+      for (int a = 0; a < ND; a++) {
+        const double dd = PF(P, F_DDIS + a, p);
+        xn[a] = PF(P, F_X + a, p) + dd;
+        const double dn = PF(P, F_DIS + a, p) + dd;
+        dn2 += dsqr(dn);
+      }
+      if (sqrt(dn2) > 0.0) I0n = closest_node_update<ND>(g, rank1, xn, I0n);  // LME.c:924
+    }
+    P.I0n[p] = I0n;
+  }
+  bin_particle<ND>(P, g, tc, binned ? p : P.np, I0n, binned);
+  if (binned && P.tile[p] >= 0) N.seed[I0n] = 1;
+}
+
 // the closest nodes k5_tile found ahead become THE closest nodes (paths whose list kernels do not do it on their way)
 __global__ void k_commit_I0(int np, const int* __restrict__ I0n, int* __restrict__ I0) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1155,7 +1186,9 @@ __global__ void k_mark_fixed_masked(const int* __restrict__ nodes, int n, int di
 
 // The two kernels between the search and the tile lists in one launch (they do not depend on each other and both are
 // too small to fill the chip: 8 us + 10 us -> 10 us): workgroup 0 = exclusive scan of the tile counts + work lists
-// (tile_scan_block), the others = 1-ring activation of 1024 nodes each.
+// (tile_scan_block), the others = 1-ring activation of NT nodes each.  NT = 256: the launch on the side stream (async
+// lists), whose workgroups have to find room on compute units that K5's workgroups keep filled -- a workgroup of 16
+// waves does not, and waited for K5 to drain (profiles/r08_async_lists.md).
 // Layer tables of the canonical tile lists: layer r of a tile = the r-th particle of every node that has one, nodes in
 // lattice order.  The nodes of a tile form NNW words of 64 (3-D: 4^3 nodes = 1 word, 2-D: 16^2 = 4 words);
 // mask[tile][r][w] = the nodes of word w that reach layer r, base[tile][r][w] = list offset of the first of them.  A
@@ -1176,8 +1209,8 @@ struct TileTabCfg {
   static constexpr int NNW = NN / 64;
 };
 
-template <int ND>
-__global__ __launch_bounds__(1024) void k_dilate_scan(int n0, int nnodes, GridD g, NView N, TileScanArgs ts,
+template <int ND, int NT = 1024>
+__global__ __launch_bounds__(NT) void k_dilate_scan(int n0, int nnodes, GridD g, NView N, TileScanArgs ts,
                                                       int* __restrict__ foreign, int* __restrict__ foreign_host, TileTab tab,
                                                       int clear_nodal) {
   if (blockIdx.x == 0) {
@@ -1188,12 +1221,12 @@ __global__ __launch_bounds__(1024) void k_dilate_scan(int n0, int nnodes, GridD 
       for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
       if (threadIdx.x == 0) *foreign_host = v;
     }
-    tile_scan_block(ts);
+    tile_scan_block<NT>(ts);
     return;
   }
-  const int nbd = (nnodes + 1023) >> 10;  // workgroups of the activation
+  const int nbd = (nnodes + NT - 1) / NT;  // workgroups of the activation
   if ((int)blockIdx.x <= nbd) {
-    const int A = ((int)blockIdx.x - 1) * 1024 + (int)threadIdx.x;
+    const int A = ((int)blockIdx.x - 1) * NT + (int)threadIdx.x;
     if (A < nnodes) {
       dilate_node<ND>(n0 + A, g, N);
       if (clear_nodal) {  // (k_step_clear's nodal part, when that kernel has nothing else to do: the search ran ahead)
@@ -1212,7 +1245,7 @@ __global__ __launch_bounds__(1024) void k_dilate_scan(int n0, int nnodes, GridD 
   // layer tables of the canonical tile lists (TileTab), one wave per tile
   constexpr int TB = TileCfg<ND>::TB, NNW = TileTabCfg<ND>::NNW;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int q = ((int)blockIdx.x - 1 - nbd) * 16 + wave;
+  const int q = ((int)blockIdx.x - 1 - nbd) * (NT / 64) + wave;
   if (q >= ts.n) return;
   const int tile = ts.tile0 + q;
   const int tx = tile % tab.nt[0], ty = (tile / tab.nt[0]) % tab.nt[1], tz = tile / (tab.nt[0] * tab.nt[1]);
@@ -1688,6 +1721,19 @@ struct nlps_gpu {
   // cloud's fall -- K2 runs 0.231 instead of 0.300 ms and K3 0.260 instead of 0.304, and the stirred cloud of DESIGN.md
   // 0.84 instead of 0.95 ms/step
   DevBuf<int> order2_d;  // canonical tile lists (k_fill_orders; k_tile_order in deterministic mode), allocated on first use
+  // Async lists (the folded one-rank explicit step, nlps_gpu_explicit_step): the search of the next step runs as a
+  // kernel of its own between K3 and K5 (k_search_ahead), and the activation and list kernels of the next step run on
+  // `side` while K5 runs on the handle's stream.  What they write and K5 still reads exists twice: the tile-list set
+  // (work list, its ranges, starts, both orders), the active flags and the nodal accumulators they reset; the step that
+  // finds lists_ready exchanges the sets (and the two closest-node arrays) instead of launching those kernels
+  // (adopt_ready_lists).  The names without a 2 are always the set in use, for every reader.
+  SideStream side;
+  bool async_lists = true;   // nlps_gpu_debug_option "async_lists"
+  bool lists_ready = false;  // `ahead`, and the twin set holds the lists, flags and reset accumulators made from it
+  DevBuf<int2> work1_2_d;
+  DevBuf<int> nwork2_d, tile_start2_d, order_2_d, order2_2_d;
+  DevBuf<unsigned char> N_active2, N_fixed2;
+  DevBuf<double> N_nm2, N_force2;
 
   nlps_halo_fn halo;
   void* halo_ctx;
@@ -1898,7 +1944,7 @@ extern "C" int nlps_gpu_set_node_window(nlps_gpu* h, int layer_lo, int layer_hi)
   HIPCHK(hipMemsetAsync(h->tile_count_d, 0, ((size_t)h->ntiles + 1) * sizeof(int), h->stream));
   h->masks_valid = false;
   h->binned = false;
-  h->ahead = false;
+  h->ahead = h->lists_ready = false;
   return 0;
 }
 
@@ -1999,6 +2045,7 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
     h->own_stream = true;
   }
   for (int i = 0; i < 8; i++) HIPCHK(hipEventCreate(&h->ev[i]));
+  HIPCHK(h->side.create());
 
   GridD& g = h->g;
   g.nd = grid->ndim;
@@ -2343,7 +2390,7 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
   HIPCHK(hipGetLastError());
   h->perm_dirty = true;
   h->binned = false;
-  h->ahead = false;  // (the per-particle tile / rank of a search done ahead belong to the old slots)
+  h->ahead = h->lists_ready = false;  // (the per-particle tile / rank of a search done ahead belong to the old slots)
   h->steps_since_sort = 0;
   h->rehome = true;  // the slots have new owners: the next search records their tiles
   h->debt = 0.0;
@@ -2471,12 +2518,13 @@ extern "C" int nlps_gpu_resort(nlps_gpu* h) { return resort(h); }
 extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_option(nlps_gpu* h, const char* name, double value) {
   const std::string k(name ? name : "");
   if (k == "lazy_nodal") h->lazy_nodal = (int)value;             // folded explicit step: 0 never, 1 below 2 M particles, 2 always
+  else if (k == "async_lists") h->async_lists = value != 0;      // one-rank folded step: next step's lists on the side stream (1) or in front of K2 (0)
   else if (k == "tangent_symmetric") h->tangent_symmetric = value != 0;  // Neo-Hookean clouds: half rows + mirror (1) or every pair (0)
   else {
     h->err = "nlps_gpu_debug_option: unknown option " + k;
     return 1;
   }
-  h->ahead = false;  // (lists made under another form are not reused)
+  h->ahead = h->lists_ready = false;  // (lists made under another form are not reused)
   return 0;
 }
 extern "C" int nlps_gpu_set_law_launch_mode(nlps_gpu* h, int mode) {
@@ -2493,7 +2541,7 @@ extern "C" int nlps_gpu_set_law_launch_mode(nlps_gpu* h, int mode) {
 }
 extern "C" int nlps_gpu_set_deterministic(nlps_gpu* h, int on) {
   h->deterministic = on != 0;
-  h->ahead = false;
+  h->ahead = h->lists_ready = false;
   h->rehome = true;
   h->debt = 0.0;
   return 0;
@@ -2510,7 +2558,7 @@ extern "C" int nlps_gpu_set_adaptive_resort(nlps_gpu* h, double budget, int min_
   }
   h->adaptive_resort = budget;
   h->adaptive_min_steps = min_steps;
-  h->ahead = false;
+  h->ahead = h->lists_ready = false;
   h->rehome = true;
   h->debt = 0.0;
   return 0;
@@ -3455,6 +3503,43 @@ static void launch_k2(nlps_gpu* h, bool p2g, int cls, double dt, double gamma_nm
   });
 }
 
+// Async lists: the twin set (see nlps_gpu::side), made at the first step that builds lists on the side stream
+static int ensure_list_twins(nlps_gpu* h) {
+  if (h->order_2_d) return 0;
+  const size_t nn = (size_t)h->g.nnodes, ND = (size_t)h->nd;
+  if (dev_alloc(h, h->work1_2_d, (size_t)h->ntiles)) return 1;
+  if (dev_alloc(h, h->nwork2_d, 6)) return 1;
+  if (dev_alloc(h, h->tile_start2_d, (size_t)h->ntiles + 1)) return 1;
+  if (dev_alloc(h, h->order2_2_d, h->P.npad)) return 1;
+  if (dev_alloc(h, h->N_active2, nn)) return 1;
+  if (dev_alloc(h, h->N_fixed2, nn * ND)) return 1;
+  if (dev_alloc(h, h->N_nm2, nn * (1 + ND))) return 1;
+  if (dev_alloc(h, h->N_force2, nn * ND)) return 1;
+  if (dev_alloc(h, h->order_2_d, h->P.npad)) return 1;
+  return 0;
+}
+// The step that finds the lists of its search built (lists_ready): the twin set becomes the set in use.  The closest
+// nodes of that search, I0n, hold a value for every particle (k_search_ahead), so they are adopted by exchanging the
+// two arrays; the tile counters change places as after any search done ahead (search_and_lists).
+static void adopt_ready_lists(nlps_gpu* h) {
+  h->work1_d.swap(h->work1_2_d);
+  h->nwork_d.swap(h->nwork2_d);
+  h->tile_start_d.swap(h->tile_start2_d);
+  h->order_d.swap(h->order_2_d);
+  h->order2_d.swap(h->order2_2_d);
+  h->N_active.swap(h->N_active2);
+  h->N_fixed.swap(h->N_fixed2);
+  h->N_nm.swap(h->N_nm2);
+  h->N_force.swap(h->N_force2);
+  h->N.active = h->N_active;
+  h->N.fixed = h->N_fixed;
+  h->N.nm = h->N_nm;
+  h->N.force = h->N_force;
+  h->P_I0.swap(h->P_I0n);
+  h->P.I0 = h->P_I0;
+  h->P.I0n = h->P_I0n;
+}
+
 // S1: closest-node update + 1-ring activation + binning of the particles to I0-tiles, then lists, beta and the
 // Newton iteration (+ predictor and P2G of mass / m*dD when `p2g`).  With `overlap` the exchange of the active
 // flags runs behind the tiles that do not touch a ghost band.
@@ -3464,10 +3549,17 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
   if (!p2g && materialise_nodal(h)) return 1;  // (a level-B search rewrites the active flags the lazy nodal arrays depend on)
   // ahead: the search of this step was done by the last kernel of the previous one (k5_tile<., ., true>); only the
   // nodal accumulators are reset here
-  const bool ahead = h->ahead && !init;
+  const bool ahead = h->ahead && !init, searched = h->searched;
   const bool deferred = ahead && h->ranks_deferred && node_lists(h);  // that search only counted: ranks from cursors (k_fill_orders)
   h->ranks_deferred = false;
   if (ahead) h->tile_count_d.swap(h->tile_count2_d);  // the counters that search filled size the lists from here on
+  // async lists: the side stream of the last step has run the activation and list kernels below into the twin set
+  // (a level-B search, p2g = false, has the nodal arrays of the last step made first and builds its lists here)
+  const bool ready = ahead && p2g && h->lists_ready;
+  h->lists_ready = false;
+  if (ready) adopt_ready_lists(h);
+  h->searched = h->ahead = false;  // consumed
+  if (!ready) {
   const bool clear_in_dilate = ahead && p2g;  // nothing but the nodal accumulators to reset: k_dilate_scan does it
   if (!clear_in_dilate)
     LAUNCH_ND((k_step_clear<2>), (k_step_clear<3>), nblk(std::max(h->nwn, h->ntw)), h->n0, h->nwn, h->N,
@@ -3475,9 +3567,8 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
   if (!ahead) {
     TileCnt tc = tile_cnt(h, true);
     if (init) LAUNCH_ND((k_init_I0<2>), (k_init_I0<3>), nblk(np), h->P, h->g, h->N, tc);
-    else LAUNCH_ND((k_search<2>), (k_search<3>), nblk(np), h->P, h->g, h->N, h->rank1_d, tc, h->searched ? 0 : 1);
+    else LAUNCH_ND((k_search<2>), (k_search<3>), nblk(np), h->P, h->g, h->N, h->rank1_d, tc, searched ? 0 : 1);
   }
-  h->searched = h->ahead = false;  // consumed
   {
     const int TB = h->nd == 3 ? TileCfg<3>::TB : TileCfg<2>::TB;
     TileScanArgs ts{h->tile_count_d + h->tile0, h->tile_start_d + h->tile0, h->ntw, h->tile0, h->ntiles / h->nt[h->nd - 1], TB,
@@ -3505,6 +3596,7 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
                   h->order2_d);
   }
   HIPCHK(hipGetLastError());
+  }  // !ready
   if (h->timing) HIPCHK(hipEventRecord(h->ev[1], h->stream));
   if (overlap == 1) {
     launch_k2(h, p2g, 2, dt, gamma_nm);
@@ -3925,7 +4017,7 @@ extern "C" int nlps_gpu_update_kinetics(nlps_gpu* h, double alpha_blend, const d
                                         const double* dU_dt, const double* dU_dt2) {
   tan_stale(h, "nlps_gpu_update_kinetics");
   if (need_masks(h, "nlps_gpu_update_kinetics")) return 1;
-  h->searched = h->ahead = false;  // the particles move: the next search is a search
+  h->searched = h->ahead = h->lists_ready = false;  // the particles move: the next search is a search
   int ND = h->nd;
   size_t st = (size_t)h->g.nnodes * ND;
   // Un_dt = dU_dt = dU_dt2 = NULL: the quasi-static driver's __update_Particles (U-Static.c:1380-1470) moves the
@@ -4036,6 +4128,13 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   // NLPS_LAZY_NODAL=2 always)
   const bool lazy = (h->lazy_nodal == 2 || (h->lazy_nodal == 1 && h->P.np <= 2000000)) && ride && !det && h->uniform_law >= 0 &&
                     h->uniform_law <= NLPS_KLAW_FRICTIONAL && nbcc <= NLPS_MAX_BC_INLINE;
+  // Async lists: the folded form of ONE rank (no ghost exchange, the whole grid as node window).  Nothing the list stage
+  // of the next step needs comes from K5 -- the position K5 writes is x + d_dis, and d_dis is K3's -- so the search
+  // leaves K5 for a kernel of its own in front of it (k_search_ahead, full ranks), and the activation and the list
+  // kernels run on the side stream beside K5, into the twin set (nlps_gpu::side); the handle's stream waits for them at
+  // the end of this call.  The multi-rank forms, the deterministic mode, the non-folded form and clouds of several laws
+  // keep the riding search and the deferred ranks.
+  const bool async_form = lazy && h->async_lists && !h->halo && !h->rccl && node_lists(h) && h->nwn == h->g.nnodes;
   const bool inline_bc = nbcc <= NLPS_MAX_BC_INLINE;  // the Dirichlet sets of this step travel as one kernel argument
   BcStep bs;
   memset(&bs, 0, sizeof bs);
@@ -4161,7 +4260,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   bool ks_made = false;
   auto k5 = [&](int cls) {
     const TileD td = tile_view(h, cls);
-    if (ride && !ks_made) {  // (one TileCnt per step: it consumes the re-home flag of the adaptive re-sort)
+    if (ride && !ks_made && !async_form) {  // (one TileCnt per step: it consumes the re-home flag of the adaptive re-sort)
       ks.tc = tile_cnt(h, true);
       ks.tc.count = h->tile_count2_d;  // (tile_count_d sizes the lists this very launch walks)
       ks.tc.defer = node_lists(h) ? 1 : 0;
@@ -4173,7 +4272,10 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
       // K5 exists in two forms: LAW = 0 serves laws 0 and 1, LAW = 2 every other law and the cloud of several
       with_bool(law == 0 || law == 1, [&](auto L01) {
         constexpr int LAW = CT(L01) ? 0 : 2;
-        if (lazy) {
+        if (async_form) {  // (its search has run: search_next_and_fork)
+          hipLaunchKernelGGL((k5_tile_lazy<CT(D), LAW, false>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, dt, gamma_nm, ks, ln,
+                             h->gstatus_d);
+        } else if (lazy) {
           hipLaunchKernelGGL((k5_tile_lazy<CT(D), LAW>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, dt, gamma_nm, ks, ln,
                              h->gstatus_d);
         } else {
@@ -4187,6 +4289,51 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   auto k3 = [&](int cls, bool signal = false) {
     if (lazy) launch_k3_lazy(cls, signal);
     else launch_k3(cls, signal);
+  };
+  // async lists, between K3 and K5: the search of the next step on the handle's stream, then -- unless the brackets of
+  // nlps_gpu_set_timing are on, which keep every kernel on the handle's stream and leave the lists to the next step, or
+  // the next step starts with a re-sort and has to search again anyway -- its activation and list kernels on the side
+  // stream, which K5 then runs beside.  They read what the search wrote (seeds, counters, tile / rank per particle, I0n)
+  // and write the twin set only; K5 reads neither.
+  bool forked = false;
+  auto search_next_and_fork = [&]() -> int {
+    const int np = h->P.np;
+    TileCnt tc = tile_cnt(h, true);  // (one per step: it consumes the re-home flag of the adaptive re-sort)
+    tc.count = h->tile_count2_d;     // (tile_count_d sizes the lists K5 walks)
+    h->ranks_deferred = false;
+    LAUNCH_ND((k_search_ahead<2>), (k_search_ahead<3>), nblk(np), h->P, h->g, h->N, h->rank1_d, tc);
+    HIPCHK(hipGetLastError());
+    const bool adaptive = h->adaptive_resort > 0.0 && h->resort_every > 0;
+    const bool resort_next = h->resort_every > 0 && (h->steps_since_sort >= h->resort_every ||
+                                                     (adaptive && h->debt > h->adaptive_resort && h->steps_since_sort >= h->adaptive_min_steps));
+    if (h->timing || resort_next) return 0;
+    if (ensure_list_twins(h)) return 1;
+    HIPCHK(h->side.fork(h->stream));
+    const hipStream_t ss = h->side.stream();
+    const int TB = ND == 3 ? TileCfg<3>::TB : TileCfg<2>::TB;
+    TileScanArgs ts{h->tile_count2_d + h->tile0, h->tile_start2_d + h->tile0, h->ntw, h->tile0, h->ntiles / h->nt[ND - 1], TB,
+                    h->band_lo, h->band_hi, h->work1_2_d, h->nwork2_d, nullptr};
+    NView N2 = h->N;  // (the seeds are the search's; flags and accumulators of the twin set)
+    N2.active = h->N_active2;
+    N2.fixed = h->N_fixed2;
+    N2.nm = h->N_nm2;
+    N2.force = h->N_force2;
+    // (workgroups of 256: they are placed beside K5's, which leave one wave per SIMD free -- see k_dilate_scan)
+    constexpr int SNT = 256;
+    const int nb = 1 + (h->nwn + SNT - 1) / SNT + (h->ntw + SNT / 64 - 1) / (SNT / 64);
+    int* fo = h->adaptive_resort > 0.0 ? h->foreign_d : nullptr;
+    with_nd(ND, [&](auto D) {
+      hipLaunchKernelGGL((k_dilate_scan<CT(D), SNT>), dim3(nb), dim3(SNT), 0, ss, h->n0, h->nwn, h->g, N2, ts, fo, h->foreign_h.host(),
+                         tile_tab(h), 1);
+      // (non-deferred: position = start + rank, canonical position from the rank inside the node; the closest node is read
+      // from I0n and nothing is committed -- K5 reads I0)
+      hipLaunchKernelGGL(k_fill_orders<CT(D)>, dim3(nblk(np)), dim3(BLK), 0, ss, np, h->P.tile, h->P.rank, h->nrank_d, h->P.I0n,
+                         (const int*)nullptr, h->tile_start2_d, h->g, tile_tab(h), h->order_2_d, h->order2_2_d, (int*)nullptr,
+                         h->node_cnt_d);
+    });
+    HIPCHK(hipGetLastError());
+    forked = true;
+    return 0;
   };
   h->nodal_stale = false;
   // S1 + S2 (ev[1] is recorded between the search and the lists/Newton/P2G kernel; the nodal accumulators of
@@ -4250,15 +4397,19 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     k5(1);
   } else {
     nodal_accel(0);
+    if (async_form && search_next_and_fork()) return 1;
     if (h->timing) HIPCHK(hipEventRecord(h->ev[5], h->stream));
     k5(0);
   }
   HIPCHK(hipGetLastError());
+  // (anything later on the handle's stream, from any entry of the API, is ordered behind the side work too)
+  if (forked) HIPCHK(h->side.join(h->stream));
   }  // !ov2
   h->P.flip ^= 1;  // F_n <- F_n+1, b_e,n <- b_e,n+1 by renaming
   h->rolled = true;
   h->searched = ride;  // K5 has updated the closest nodes for the positions it wrote ...
   h->ahead = ride;     // ... and binned the particles for the next step
+  h->lists_ready = forked;
   if (h->timing) {
     HIPCHK(hipEventRecord(h->ev[6], h->stream));
     // calibration bracket: a kernel of K3's grid and argument block that does nothing; what it reads is the part of

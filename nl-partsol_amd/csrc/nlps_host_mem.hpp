@@ -1,4 +1,5 @@
-// Host-side owners of the handle's device and pinned memory.  Three types and nothing else: no allocator, no pools.
+// Host-side owners of the handle's device and pinned memory, and of its side stream.  Four types and nothing else: no
+// allocator, no pools.
 // They know nothing of nlps_gpu or its error string: every acquiring call returns the hipError_t and the caller turns
 // it into a message.  The views that kernels take by value (PView, NView, TileD ...) hold pointers BORROWED from these.
 #pragma once
@@ -104,5 +105,41 @@ class Mirrored {
   T* target() const { return pin_.alias() ? pin_.alias() : dev_.get(); }
   hipError_t fetch(hipStream_t s) const {  // never waits
     return pin_.alias() ? hipSuccess : hipMemcpyAsync(pin_.host(), dev_.get(), n_ * sizeof(T), hipMemcpyDeviceToHost, s);
+  }
+};
+
+// Owner of one non-blocking stream and the two events (timing off) that fork work from another stream onto it and join
+// it back: what is launched on stream() between fork(s) and join(s) runs behind everything queued on s before the
+// fork and in front of everything queued on s after the join, and beside what s gets in between.
+class SideStream {
+  hipStream_t s_ = nullptr;
+  hipEvent_t fork_ = nullptr, join_ = nullptr;
+
+ public:
+  SideStream() = default;
+  SideStream(const SideStream&) = delete;
+  SideStream& operator=(const SideStream&) = delete;
+  ~SideStream() { reset(); }
+  void reset() {
+    if (s_) (void)hipStreamSynchronize(s_), (void)hipStreamDestroy(s_);
+    if (fork_) (void)hipEventDestroy(fork_);
+    if (join_) (void)hipEventDestroy(join_);
+    s_ = nullptr, fork_ = join_ = nullptr;
+  }
+  hipError_t create() {
+    hipError_t e = hipStreamCreateWithFlags(&s_, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&fork_, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&join_, hipEventDisableTiming);
+    if (e != hipSuccess) reset();
+    return e;
+  }
+  hipStream_t stream() const { return s_; }
+  hipError_t fork(hipStream_t from) {
+    const hipError_t e = hipEventRecord(fork_, from);
+    return e != hipSuccess ? e : hipStreamWaitEvent(s_, fork_, 0);
+  }
+  hipError_t join(hipStream_t into) {
+    const hipError_t e = hipEventRecord(join_, s_);
+    return e != hipSuccess ? e : hipStreamWaitEvent(into, join_, 0);
   }
 };

@@ -207,10 +207,10 @@ __device__ __forceinline__ int window_base(const int* ijk, const int* w0) {
   return (ijk[0] - w0[0]) + W * (ijk[1] - w0[1]) + (ND == 3 ? PS * (ijk[2] - w0[2]) : 0);
 }
 
-// block-wide exclusive scan of one value per thread (1024 threads = 16 waves); returns the exclusive prefix,
-// *total = sum.  Wave-level shuffles + one pass over the 16 wave totals: two barriers instead of twenty.
-template <typename T>
-__device__ __forceinline__ T block_scan_1024(T v, T* sh, T* total) {
+// block-wide exclusive scan of one value per thread (NT threads = NT / 64 waves); returns the exclusive prefix,
+// *total = sum.  Wave-level shuffles + one pass over the wave totals: two barriers instead of twenty.
+template <int NT, typename T>
+__device__ __forceinline__ T block_scan(T v, T* sh, T* total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   T incl = v;
 #pragma unroll
@@ -223,7 +223,7 @@ __device__ __forceinline__ T block_scan_1024(T v, T* sh, T* total) {
   __syncthreads();
   T base = 0, tot = 0;
 #pragma unroll
-  for (int w = 0; w < 16; w++) {
+  for (int w = 0; w < NT / 64; w++) {
     const T t = sh[w];
     if (w < wave) base += t;
     tot += t;
@@ -232,7 +232,8 @@ __device__ __forceinline__ T block_scan_1024(T v, T* sh, T* total) {
   return base + incl - v;
 }
 
-// exclusive scan of the per-tile particle counts + the compacted work list (one 1024-thread block).
+// exclusive scan of the per-tile particle counts + the compacted work list (one block of NT threads: 1024, or 256 for
+// the launch that has to find room beside K5's workgroups, see k_dilate_scan).
 // count/start are already offset to the first tile of the node window; tile0 = that tile's index.
 // A tile is "boundary" when its node window reaches a ghost band: slow-axis layers <= band_lo or >= band_hi
 // (tpl = tiles per slow-axis tile layer, TB = tile edge).  ranges[cls] = {begin, end} in work1 for
@@ -245,15 +246,16 @@ struct TileScanArgs {
   int* ranges;
   int* cursor;  // [n] or nullptr: a copy of start[] for k_fill_orders to hand out list positions from (deferred ranks)
 };
+template <int NT = 1024>
 __device__ __forceinline__ void tile_scan_block(const TileScanArgs& a) {
   const int* __restrict__ count = a.count;
   int* __restrict__ start = a.start;
   const int n = a.n, tile0 = a.tile0, tpl = a.tpl, TB = a.TB, band_lo = a.band_lo, band_hi = a.band_hi;
   int2* __restrict__ work1 = a.work1;
   int* __restrict__ ranges = a.ranges;
-  __shared__ int sh[1024];
-  __shared__ u64 sh64[16];
-  int chunk = (n + 1023) / 1024;
+  __shared__ int sh[NT / 64];
+  __shared__ u64 sh64[NT / 64];
+  int chunk = (n + NT - 1) / NT;
   int lo = threadIdx.x * chunk, hi = min(n, lo + chunk), c = 0;
   u64 bi = 0ull;  // non-empty boundary tiles of this thread's chunk in the low word, interior ones in the high word
   for (int q = lo; q < hi; q++) {
@@ -264,10 +266,10 @@ __device__ __forceinline__ void tile_scan_block(const TileScanArgs& a) {
     if (cq > 0) bi += bnd ? 1ull : (1ull << 32);
   }
   int tot;
-  int run = block_scan_1024(c, sh, &tot);
+  int run = block_scan<NT>(c, sh, &tot);
   // both list counters in ONE scan, as the 32-bit halves of a word (each sum is at most n): no second scan, no size limit
   u64 wt;
-  const u64 wp = block_scan_1024(bi, sh64, &wt);
+  const u64 wp = block_scan<NT>(bi, sh64, &wt);
   const int nb = (int)(unsigned)wt, ni = (int)(wt >> 32);
   int rb = (int)(unsigned)wp, ri = nb + (int)(wp >> 32);
   if (threadIdx.x == 0) {
@@ -1710,14 +1712,16 @@ __global__ __launch_bounds__(K5_BLK) void k5_tile(PView P, GridD g, NView N, Til
   k5_body<ND, LAW, SEARCH>(P, g, N, td, dt, gamma_nm, ks, tw, axy, az, nullptr, nullptr);
 }
 
-template <int ND, int LAW>
+// SEARCH = false: the one-rank form whose search is a kernel of its own in front of this one (k_search_ahead), so that
+// the lists of the next step can be built on a second stream while this kernel runs
+template <int ND, int LAW, bool SEARCH = true>
 __global__ __launch_bounds__(K5_BLK) void k5_tile_lazy(PView P, GridD g, NView N, TileD td, double dt, double gamma_nm, K5Search ks,
                                                        LazyNodal ln, int* __restrict__ gstatus) {
   __shared__ __attribute__((aligned(16))) double axy[2 * TileCfg<ND>::NW];
   __shared__ double az[(ND == 3) ? TileCfg<ND>::NW : 1];
   TileWork tw;
   if (!tile_work_item(td, tw)) return;
-  k5_body<ND, LAW, true>(P, g, N, td, dt, gamma_nm, ks, tw, axy, az, &ln.fs, gstatus);
+  k5_body<ND, LAW, SEARCH>(P, g, N, td, dt, gamma_nm, ks, tw, axy, az, &ln.fs, gstatus);
 }
 
 // ------------------------------------------------------------------------------------------------
