@@ -44,7 +44,9 @@ enum {
   NLPS_MAT_DRUCKER_PRAGER = 2, /* "Drucker-Prager",      Plasticity/Drucker-Prager.c:319-613 */
   NLPS_MAT_VON_MISES = 3,      /* "Von-Mises",           Plasticity/Von-Mises.c:212-392 */
   NLPS_MAT_MATSUOKA_NAKAI = 4, /* "Matsuoka-Nakai",      Plasticity/Matsuoka-Nakai.c:300-700 */
-  NLPS_MAT_LADE_DUNCAN = 5     /* "Lade-Duncan",         Plasticity/Lade-Duncan.c:290-692 */
+  NLPS_MAT_LADE_DUNCAN = 5,    /* "Lade-Duncan",         Plasticity/Lade-Duncan.c:290-692 */
+  NLPS_MAT_NEWTONIAN_FLUID = 6 /* "Newtonian-Fluid-Compressible", Fluid/Newtonian-Fluid.c:17-79: implicit path only, reads the
+                                  rate tensor dt_F_n1 (nlps_gpu_explicit_step refuses a cloud that holds it) */
 };
 
 /* Structured background grid (GramsBox mesh, InOutFun/Read_GramsBox.c:54): Q4 / H8 lattice, nodes
@@ -88,6 +90,9 @@ typedef struct {
   double cohesion, alpha_borja, a_borja[3];
   double ft, heps, wcrit; /* eigensoftening (Types.h:386-390, EigenSoftening.c:67-69): tensile strength, band width of the
                              cohesive fracture, critical opening displacement */
+  /* Newtonian-Fluid-Compressible (Newtonian-Fluid.c:31-34): Viscosity, Compressibility, n_Macdonald_model; the law also
+   * reads p_ref (ReferencePressure).  Appended: the members above keep their offsets */
+  double viscosity, compressibility, n_macdonald;
 } nlps_material;
 
 /* Particle fields, Types.h:184-283 / 548-623: HOST pointers to the reference's row-major arrays
@@ -194,7 +199,8 @@ int nlps_gpu_nodal_field_n(nlps_gpu *h, double *V, double *A, const double *M);
 
 /* __local_compatibility_conditions, U-Newmark-beta.c:1064-1160: DF, F_n1, J_n1 and, when dU_dt is given,
  * the rate tensors dt_DF, dt_F_n1 (compute-Strains.c:48-72,176-207; they feed only the Newtonian-fluid law,
- * Constitutive.c:84-108, so dU_dt may be NULL). */
+ * Constitutive.c:84-108, so dU_dt may be NULL for a cloud without that law; with it the caller gives dU_dt
+ * (nlps_gpu_nodal_kinetic_increments) and a NULL is refused: the stress would be made from stale rates). */
 int nlps_gpu_compatibility(nlps_gpu *h, const double *dU, const double *dU_dt);
 
 /* __constitutive_update -> Stress_integration__Constitutive__, U-Newmark-beta.c:1208-1242,
@@ -221,7 +227,9 @@ int nlps_gpu_update_kinetics(nlps_gpu *h, double alpha_blend, const double *dU, 
 
 /* Fused explicit predictor-corrector step (stage order and formulas of U-Verlet.c:229-253, 301-367,
  * 455-527, 530-676, 919-1010, 1024-1084; internal force in the Kirchhoff form of
- * U-Newmark-beta.c:1257-1374).  gravity[ndim] may be NULL.  One P2G+stress+G2P particle step. */
+ * U-Newmark-beta.c:1257-1374).  gravity[ndim] may be NULL.  One P2G+stress+G2P particle step.
+ * A cloud that holds Newtonian-Fluid-Compressible is refused at the start of the call (return 1, the law named in
+ * nlps_gpu_last_error): the law reads dt_F_n1 and the reference has no working explicit driver that defines that rate. */
 int nlps_gpu_explicit_step(nlps_gpu *h, const nlps_bcc *bcc, int nbcc, int step, double dt,
                            double gamma, const double *gravity);
 /* Number of active nodes after the last search (computes Nodes2Mask on the device). */
@@ -280,7 +288,8 @@ int nlps_gpu_rccl_selftest_exchange(nlps_gpu *h, void *dptr, int nfield, int ele
  * fused stress stage runs either as one launch per law of the kernel compiled for that law (mode 1: right when the
  * materials sit in blocks, nearly every tile of closest nodes then holds one law) or as one kernel that dispatches on
  * the law at run time (mode 2: right when the laws are interleaved particle by particle).  nlps_gpu_create picks the
- * mode from the share of tiles that hold more than one law; results are identical. */
+ * mode from the share of tiles that hold more than one law; results are identical.  Mode 2 is refused for a cloud that
+ * holds Matsuoka-Nakai / Lade-Duncan or Newtonian-Fluid-Compressible: the dispatch kernel does not hold those laws. */
 int nlps_gpu_set_law_launch_mode(nlps_gpu *h, int mode);
 
 /* Run-to-run bit-reproducible results ("race detection"): with on != 0 every nodal sum of the fused
@@ -318,8 +327,12 @@ int nlps_gpu_nodal_inertial_forces(nlps_gpu *h, double *R, const double *M, cons
  * R, dU, Un_dt, Un_dt2, M: masked [N_A*d], host (VecGetArray) or device pointers; R is OVERWRITTEN.  alpha[6] as for
  * the per-dof updates above, gravity[ndim] or NULL, loads / nloads / step / thickness / area0 as for
  * nlps_gpu_nodal_traction_forces (nloads = 0: none).  Needs nlps_gpu_local_search + nlps_gpu_active_masks first.
- * flags: NLPS_LAGR_RATES   also the rate tensors dt_DF, dt_F_n1 (compute-Strains.c:48-72,176-207; only the Newtonian-fluid
- *                          law, which is not on this path, reads them: off by default) -- runs the separate stages;
+ * A cloud that holds the Newtonian-Fluid-Compressible law carries the rate tensors by itself, no flag needed: its
+ * particles run the same one pass with a second gather window of dU_dt = alpha_4 dU + (alpha_5 - 1) Un_dt + alpha_6 Un_dt2
+ * (:1834-1870), dt_DF and dt_F_n1 = dt_DF F_n + DF dt_F_n stay in registers for the stress and are stored with the rest;
+ * in a mixed cloud the solids' launches are the ones above.
+ * flags: NLPS_LAGR_RATES   also the rate tensors dt_DF, dt_F_n1 (compute-Strains.c:48-72,176-207) for a cloud WITHOUT the
+ *                          fluid law, where nothing reads them: off by default -- runs the separate stages;
  *        NLPS_LAGR_SEPARATE the composition of the separate stage calls (same results; what the fused form is tested and
  *                          timed against).  The separate stages also run when the damage hooks are on
  *                          (driver_eigenerosion / _eigensoftening: every stress before any force).  A cloud of several laws
@@ -340,7 +353,8 @@ int nlps_gpu_lagrangian_evaluation(nlps_gpu *h, double *R, const double *dU, con
  * Drucker-Prager (Plasticity/Elastoplastic-Tangent-Matrix.c:42-163, with the C_ep of the last constitutive
  * update).  The d x d blocks V0 * stiffness_density(A, B) of every node pair a particle connects are summed on
  * the device, from the state the compatibility + constitutive stages left (DF, F_n, F_n1, J_n1, tau, b_e,n+1,
- * C_ep) and the current lists / lambda.  *nnz = number of COO entries = d*d * (number of structurally visited node
+ * C_ep) and the current lists / lambda.  The Newtonian-Fluid-Compressible law (Fluid/Newtonian-Fluid.c:83-190) is taken
+ * too, from F_n, F_n1, dt_F_n1, J_n1 and alpha_4 (nlps_gpu_set_tangent_alpha4); its blocks are not symmetric.  *nnz = number of COO entries = d*d * (number of structurally visited node
  * pairs, the reference's sparsity pattern).  Needs nlps_gpu_active_masks() first. */
 int nlps_gpu_tangent_assemble(nlps_gpu *h, long long *nnz);
 /* grouped != 0 (default): one workgroup per closest node sums the blocks of the particles sharing it before the
@@ -355,6 +369,12 @@ int nlps_gpu_tangent_coo(nlps_gpu *h, double alpha_1, const double *lumped_mass,
                          int *cols, double *vals);
 /* __create_sparsity_pattern (U-Newmark-beta.c:1568-1632): visited columns per dof row, nnz_per_row[N_A*d] */
 int nlps_gpu_sparsity_pattern(nlps_gpu *h, int *nnz_per_row);
+/* alpha_4 of the Newmark scheme (gamma / (beta dt), __compute_Newmark_parameters :497-514) for the tangent of the
+ * Newtonian-Fluid-Compressible law, the one law whose stiffness density reads it (Constitutive.c:298-314: the velocity
+ * increment is alpha_4 dU, so the viscous stress depends on dU through it).  Read by nlps_gpu_tangent_assemble and
+ * nlps_gpu_tangent_operator at their next call; default 0, the quasi-static value.  nlps_gpu_newton_solve and
+ * nlps_gpu_newmark_step set it from alpha[3] themselves.  The other laws ignore it. */
+int nlps_gpu_set_tangent_alpha4(nlps_gpu *h, double alpha_4);
 
 /* ------------------------------------------------------------------ matrix-free tangent (MatShell of __jacobian_evaluation)
  * The same K as nlps_gpu_tangent_assemble + nlps_gpu_tangent_coo, never formed: every block is bilinear in the

@@ -35,6 +35,7 @@ static int nlps_glue_law(const Material *M) {
   if (strcmp(M->Type, "Von-Mises") == 0) return NLPS_MAT_VON_MISES;
   if (strcmp(M->Type, "Matsuoka-Nakai") == 0) return NLPS_MAT_MATSUOKA_NAKAI;
   if (strcmp(M->Type, "Lade-Duncan") == 0) return NLPS_MAT_LADE_DUNCAN;
+  if (strcmp(M->Type, "Newtonian-Fluid-Compressible") == 0) return NLPS_MAT_NEWTONIAN_FLUID;
   return -1;
 }
 
@@ -176,6 +177,9 @@ int nlps_glue_create(nlps_glue *G, Mesh FEM_Mesh, Particle MPM_Mesh, Time_Int_Pa
     mats[m].cohesion = M->Cohesion;
     mats[m].alpha_borja = M->alpha_Hardening_Borja;
     for (int k = 0; k < 3; k++) mats[m].a_borja[k] = M->a_Hardening_Borja[k];
+    mats[m].viscosity = M->Viscosity;
+    mats[m].compressibility = M->Compressibility;
+    mats[m].n_macdonald = M->n_Macdonald_model;
   }
   nlps_particles p = nlps_glue_particles(MPM_Mesh);
   /* closest nodes in lattice numbering */

@@ -42,9 +42,20 @@ struct MatD {
   double ft, heps, wcrit;              // eigensoftening (EigenSoftening.c:67-69)
   // Matsuoka-Nakai (surface 0) / Lade-Duncan (surface 1): type = NLPS_KLAW_FRICTIONAL for both
   int surface;
-  double c_cotphi, alpha_b, a_b[3];
+  // (one law per material: the fluid's constants share the slots of the frictional laws', so the table keeps its row size
+  // and the kernels of the other laws the addresses they were compiled with)
+  union {
+    struct {
+      double c_cotphi, alpha_b, a_b[3];
+    };
+    // compressible Newtonian fluid (Newtonian-Fluid.c:31-34; ReferencePressure is p_ref): type = NLPS_KLAW_FLUID
+    struct {
+      double viscosity, K_fluid, n_macdonald;
+    };
+  };
 };
 #define NLPS_KLAW_FRICTIONAL 4
+#define NLPS_KLAW_FLUID 5  // NLPS_MAT_NEWTONIAN_FLUID: the one law that reads the rate tensors
 
 struct ParamsD {
   double gamma_lme, neg_log_tol_zero, tol_wrapper;
@@ -346,6 +357,58 @@ __device__ __forceinline__ void law_hencky(const MatD& m, const double* F, Stres
   o.tau_zz = Tp[2];
   o.W = 0.5 * (Tp[0] * Eh[0] + Tp[1] * Eh[1] + Tp[2] * Eh[2]);
   if (isnan(w[0]) || isnan(w[1])) o.fail = 1;
+}
+
+// Compressible Newtonian fluid, statement order of Fluid/Newtonian-Fluid.c:17-79: L = dt_F F^-1
+// (spatial_velocity_gradient__Particles__, compute-Strains.c:249-341), E = sym L, Macdonald pressure.  As upstream: in 2-D
+// the "trace" is E[0] + E[2], i.e. xx + yx (:59), and the out-of-plane entry is -pressure - (2/3) c0 trace (:74).  Writes
+// neither W nor an internal variable.  L (when asked for) and E are left for the tangent.  false: F does not invert.
+struct FluidCoef {
+  double pressure, c0;
+};
+__device__ double pow_cold(double x, double y);  // (out of line, below: pow's registers stay out of the caller's budget)
+__device__ __forceinline__ FluidCoef fluid_coefficients(const MatD& m, double J) {
+  FluidCoef k;
+  k.pressure = J * (m.p_ref + (m.K_fluid / m.n_macdonald) * (pow_cold(J, -m.n_macdonald) - 1.0));
+  k.c0 = J * m.viscosity;
+  return k;
+}
+template <int N>
+__device__ __forceinline__ bool law_newtonian_fluid(const MatD& m, const double* F, const double* dFdt, double J, double* tau,
+                                                    double& tau_zz, double* L_out = nullptr, double* E_out = nullptr) {
+  NLPS_FP_CONTRACT
+  double Fm1[N * N], L[N * N], E[N * N];
+  if (!inverse<N>(Fm1, F)) return false;
+#pragma unroll
+  for (int i = 0; i < N; i++)
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < N; k++) s += dFdt[i * N + k] * Fm1[k * N + j];
+      L[i * N + j] = s;
+    }
+#pragma unroll
+  for (int i = 0; i < N; i++)
+#pragma unroll
+    for (int j = 0; j < N; j++) E[i * N + j] = 0.5 * (L[i * N + j] + L[j * N + i]);
+  const FluidCoef k = fluid_coefficients(m, J);
+  const double trace_E = (N == 2) ? E[0] + E[2] : E[0] + E[4 % (N * N)] + E[8 % (N * N)];
+  const double dev = (2.0 / 3.0) * k.c0 * trace_E;
+#pragma unroll
+  for (int i = 0; i < N; i++)
+#pragma unroll
+    for (int j = 0; j < N; j++) tau[i * N + j] = ((i == j) ? -k.pressure - dev : 0.0) + 2.0 * k.c0 * E[i * N + j];
+  tau_zz = -k.pressure - dev;
+  if (L_out) {
+#pragma unroll
+    for (int q = 0; q < N * N; q++) L_out[q] = L[q];
+  }
+  if (E_out) {
+#pragma unroll
+    for (int q = 0; q < N * N; q++) E_out[q] = E[q];
+  }
+  return true;
 }
 
 // Von-Mises (J2) plasticity with combined isotropic (linear + Voce) / kinematic hardening in principal Hencky

@@ -81,7 +81,7 @@ static void with_law(int law, F&& f) {
 // the laws of a cloud of several (law_present of the handle), ascending: f(law, is it the last one)
 template <class F>
 static void for_each_law_present(unsigned mask, F&& f) {
-  for (int l = 0; l <= NLPS_KLAW_FRICTIONAL; l++)
+  for (int l = 0; l <= NLPS_KLAW_FLUID; l++)
     if (mask & (1u << l)) f(l, (mask >> (l + 1)) == 0);
 }
 
@@ -885,6 +885,17 @@ __global__ __launch_bounds__(BLK) void k_stress(PView P, const MatD* __restrict_
   }
   double Fn1[ND * ND], DF[ND * ND], tau[ND * ND], z;
   load_block<ND>(P, fFN1(P), p, Fn1, z);
+  if (mats[P.mat[p]].type == NLPS_KLAW_FLUID) {  // Constitutive.c:84-108: F_n1, dt_F_n1, J_n1 -> Stress, nothing else
+    double dFn1[ND * ND], tzz;
+    load_block<ND>(P, F_DTFN1, p, dFn1, z);
+    if (law_newtonian_fluid<ND>(mats[P.mat[p]], Fn1, dFn1, PF(P, F_JN1, p), tau, tzz)) {
+      store_block<ND>(P, F_TAU, p, tau, tzz, true);
+    } else {
+      atomicOr(&P.status[p], ST_CONSTITUTIVE);
+      atomicOr(gstatus, ST_CONSTITUTIVE);
+    }
+    return;
+  }
   load_block<ND>(P, F_DF, p, DF, z);
   int st = stress_update<ND, -1, true, FRIC>(P, p, mats, prm, Fn1, DF, PF(P, F_JN1, p), tau);
   if (st) {
@@ -1084,6 +1095,24 @@ __global__ void k_expand_reset(double* __restrict__ grid, const double* __restri
   if (A >= nnodes) return;
   int m = n2m[A];
   for (int f = 0; f < nf; f++) grid[(size_t)A * nf + f] = (m >= 0) ? masked[(size_t)m * nf + f] : 0.0;
+  if (A >= n0 && A < n0 + nwn)
+    for (int f = 0; f < nf; f++) zero[(size_t)A * nf + f] = 0.0;
+}
+
+// k_expand_reset of a cloud that holds the fluid law: also the nodal velocity increment of
+// __compute_nodal_velocity_increments (U-Newmark-beta.c:1834-1870), dU_dt = alpha_4 dU + (alpha_5 - 1) Un_dt + alpha_6 Un_dt2,
+// in grid numbering (the second gather window of k3_tile MODE 4)
+__global__ void k_expand_reset_rates(double* __restrict__ grid, double* __restrict__ gridv, const double* __restrict__ masked,
+                                     const double* __restrict__ v, const double* __restrict__ a, double a4, double a5m1, double a6,
+                                     const int* __restrict__ n2m, int nnodes, int nf, double* __restrict__ zero, int n0, int nwn) {
+  int A = blockIdx.x * blockDim.x + threadIdx.x;
+  if (A >= nnodes) return;
+  int m = n2m[A];
+  for (int f = 0; f < nf; f++) {
+    const size_t i = (size_t)(m >= 0 ? m : 0) * nf + f;
+    grid[(size_t)A * nf + f] = (m >= 0) ? masked[i] : 0.0;
+    gridv[(size_t)A * nf + f] = (m >= 0) ? a4 * masked[i] + a5m1 * v[i] + a6 * a[i] : 0.0;
+  }
   if (A >= n0 && A < n0 + nwn)
     for (int f = 0; f < nf; f++) zero[(size_t)A * nf + f] = 0.0;
 }
@@ -1681,6 +1710,7 @@ struct nlps_gpu {
   DevBuf<char> kscan_tmp;
   size_t kscan_bytes = 0;
   long long knnz_blocks = -1;
+  double tan_alpha4 = 0.0;  // alpha_4 of the fluid law's tangent (nlps_gpu_set_tangent_alpha4; 0 = quasi-static)
   bool tangent_grouped = true;  // one workgroup per closest node (false: one wave per particle, kept for comparison)
   bool tangent_symmetric = true;  // Neo-Hookean clouds: only the upper half of every row is assembled (nlps_gpu_debug_option "tangent_symmetric")
   bool ktan_sym = false;          // how the last nlps_gpu_tangent_assemble filled the stencil array (nlps_gpu_tangent_coo mirrors the rest)
@@ -1821,9 +1851,18 @@ static MatD make_mat(const nlps_material& m, int nd) {
     d.alpha_b = m.alpha_borja;
     for (int i = 0; i < 3; i++) d.a_b[i] = m.a_borja[i];
   }
+  if (m.type == NLPS_MAT_NEWTONIAN_FLUID) {
+    d.type = NLPS_KLAW_FLUID;
+    d.viscosity = m.viscosity;
+    d.K_fluid = m.compressibility;
+    d.n_macdonald = m.n_macdonald;
+  }
   return d;
 }
-static inline int klaw_of(int type) { return type >= NLPS_KLAW_FRICTIONAL ? NLPS_KLAW_FRICTIONAL : type; }
+static inline int klaw_of(int type) {
+  if (type == NLPS_MAT_NEWTONIAN_FLUID) return NLPS_KLAW_FLUID;
+  return type >= NLPS_KLAW_FRICTIONAL ? NLPS_KLAW_FRICTIONAL : type;
+}
 
 // h_avg exactly as compute_nodal_distance_local does it (Read_GramsBox.c:460-507): chain order sum
 static void host_h_avg(const nlps_grid& G, const nlps_host::StencilTables& tab, std::vector<double>& out) {
@@ -2120,8 +2159,9 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
   h->uniform_law = nmats > 0 ? klaw_of(mats[0].type) : -1;
   h->law_present = 0;
   for (int i = 0; i < nmats; i++) {
-    if (mats[i].type < 0 || mats[i].type > NLPS_MAT_LADE_DUNCAN) {
-      h->err = "material type outside 0..5 (Neo-Hookean, Hencky, Drucker-Prager, Von-Mises, Matsuoka-Nakai, Lade-Duncan)";
+    if (mats[i].type < 0 || mats[i].type > NLPS_MAT_NEWTONIAN_FLUID) {
+      h->err = "material type outside 0..6 (Neo-Hookean, Hencky, Drucker-Prager, Von-Mises, Matsuoka-Nakai, Lade-Duncan, "
+               "Newtonian-Fluid-Compressible)";
       return 1;
     }
     if (klaw_of(mats[i].type) != klaw_of(mats[0].type)) h->uniform_law = -1;
@@ -2194,7 +2234,7 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
       // interleaved particle by particle: every launch would touch every tile and every cache line (measured 0.68 ms
       // against 0.51 ms for the one kernel that dispatches on the law at run time), so that kernel stays for them.
       h->k3_per_law = used > 0 && 4 * mixed <= used;
-      if (h->law_present & (1 << NLPS_KLAW_FRICTIONAL)) h->k3_per_law = 1;  // not in the dispatch kernel (stress_update)
+      if (h->law_present & ((1 << NLPS_KLAW_FRICTIONAL) | (1 << NLPS_KLAW_FLUID))) h->k3_per_law = 1;  // not in the dispatch kernel (stress_update)
     }
     std::stable_sort(h->perm.begin(), h->perm.end(), [&](int a, int b) { return key[a] < key[b]; });
     h->slab_lo = std::max(0, lo - 3);
@@ -2273,6 +2313,7 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
     if (upload_field(h, F_STRF1, 1, host->Strain_f_n1 ? host->Strain_f_n1 : host->Strain_f_n, 1, tmp, nullptr, 0.0)) return 1;
     if (h->P.erosion) h->level_b_fields = true;  // the damage fields travel with the re-sort
     if (host->dt_F_n || host->dt_F_n1 || host->dt_DF) h->level_b_fields = true;
+    if (h->law_present & (1 << NLPS_KLAW_FLUID)) h->level_b_fields = true;  // the fluid's rate tensors are state: they travel with the re-sort
     if (host->dt_F_n && upload_field(h, F_DTFN, T, host->dt_F_n, T, tmp, nullptr, 0.0)) return 1;
     if (host->dt_F_n1 && upload_field(h, F_DTFN1, T, host->dt_F_n1, T, tmp, nullptr, 0.0)) return 1;
     if (host->dt_DF && upload_field(h, F_DTDF, T, host->dt_DF, T, tmp, nullptr, 0.0)) return 1;
@@ -2534,6 +2575,10 @@ extern "C" int nlps_gpu_set_law_launch_mode(nlps_gpu* h, int mode) {
   }
   if (mode == 2 && (h->law_present & (1 << NLPS_KLAW_FRICTIONAL))) {
     h->err = "nlps_gpu_set_law_launch_mode: the dispatch kernel does not hold Matsuoka-Nakai / Lade-Duncan";
+    return 1;
+  }
+  if (mode == 2 && (h->law_present & (1 << NLPS_KLAW_FLUID))) {
+    h->err = "nlps_gpu_set_law_launch_mode: the dispatch kernel does not hold Newtonian-Fluid-Compressible";
     return 1;
   }
   h->k3_per_law = mode == 1;
@@ -3826,6 +3871,11 @@ extern "C" int nlps_gpu_nodal_field_n(nlps_gpu* h, double* V, double* A, const d
 
 extern "C" int nlps_gpu_compatibility(nlps_gpu* h, const double* dU, const double* dU_dt) {
   if (need_masks(h, "nlps_gpu_compatibility")) return 1;
+  if (!dU_dt && (h->law_present & (1 << NLPS_KLAW_FLUID))) {
+    h->err = "nlps_gpu_compatibility: the cloud holds the Newtonian-Fluid-Compressible law, whose stress reads dt_F_n1: "
+             "dU_dt is required (nlps_gpu_nodal_kinetic_increments)";
+    return 1;
+  }
   if (materialise_roll(h)) return 1;
   if (to_grid(h, h->N.dU, dU, h->nd)) return 1;
   if (dU_dt && to_grid(h, h->gridB, dU_dt, h->nd)) return 1;
@@ -4055,6 +4105,11 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
                                       const double* gravity) {
   tan_stale(h, "nlps_gpu_explicit_step");
   int ND = h->nd;
+  if (h->law_present & (1 << NLPS_KLAW_FLUID)) {
+    h->err = "nlps_gpu_explicit_step: the cloud holds the Newtonian-Fluid-Compressible law, which reads the rate tensor dt_F_n1; "
+             "the reference has no working explicit driver that defines it (implicit path only)";
+    return 1;
+  }
   if (h->P.erosion) {
     h->err = "nlps_gpu_explicit_step: the eigenerosion hooks exist in the level-B stages only (the reference defines them in "
              "U-Newmark-beta.c / U-Static.c; its explicit drivers are stubs)";
@@ -4651,11 +4706,13 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
   // the fused one is measured and tested against), for what the fused kernel does not carry (rate tensors, which only the
   // Newtonian-fluid law reads; the damage hooks, which sit between the stress update and the force scatter and need
   // every particle's stress before any force)
-  const bool fused = !(flags & (NLPS_LAGR_SEPARATE | NLPS_LAGR_RATES)) && !h->P.erosion && h->uniform_law <= NLPS_KLAW_FRICTIONAL &&
-                     h->P.np > 0;
+  // (a cloud that holds the fluid law always carries the rates: fused in MODE 4, or through the separate stages)
+  const bool fluid = (h->law_present & (1 << NLPS_KLAW_FLUID)) != 0;
+  const bool fused = !(flags & NLPS_LAGR_SEPARATE) && (fluid || !(flags & NLPS_LAGR_RATES)) && !h->P.erosion &&
+                     h->uniform_law <= NLPS_KLAW_FLUID && h->P.np > 0;
   if (!fused) {
     DevBuf<double> dV;
-    if (flags & NLPS_LAGR_RATES) {  // __compute_nodal_velocity_increments, :1018
+    if ((flags & NLPS_LAGR_RATES) || fluid) {  // __compute_nodal_velocity_increments, :1018
       HIPCHK(dV.reserve(std::max<size_t>(n, 1)));
       if (nlps_gpu_nodal_kinetic_increments(h, dV, nullptr, dU, Un_dt, Un_dt2, alpha)) return 1;
     }
@@ -4700,8 +4757,12 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
   }
   const double *v = cst[0], *a = cst[1], *m = cst[2];
   // the caller's dU in grid numbering (the gather windows read N.dU), the force accumulator of the node window reset
-  hipLaunchKernelGGL(k_expand_reset, dim3(nblk(h->g.nnodes)), dim3(BLK), 0, h->stream, h->N.dU, u, h->n2m_d, h->g.nnodes, ND,
-                     h->N.force, h->n0, h->nwn);
+  if (fluid)
+    hipLaunchKernelGGL(k_expand_reset_rates, dim3(nblk(h->g.nnodes)), dim3(BLK), 0, h->stream, h->N.dU, h->gridB.get(), u, v, a,
+                       alpha[3], alpha[4] - 1.0, alpha[5], h->n2m_d, h->g.nnodes, ND, h->N.force, h->n0, h->nwn);
+  else
+    hipLaunchKernelGGL(k_expand_reset, dim3(nblk(h->g.nnodes)), dim3(BLK), 0, h->stream, h->N.dU, u, h->n2m_d, h->g.nnodes, ND,
+                       h->N.force, h->n0, h->nwn);
   if (h->timing) HIPCHK(hipEventRecord(h->ev[2], h->stream));
   {
     TileD td = tile_view(h);
@@ -4713,11 +4774,21 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
       // its tile's particles of that law first (FILT, as the explicit step's per-law launches)
       for_each_law_present(h->law_present, [&](int l, bool) {
         with_nd(ND, [&](auto D) {
+          if (l == NLPS_KLAW_FLUID) {  // the fluid's particles in the rate-carrying mode, the solids' in MODE 3
+            hipLaunchKernelGGL((k3_tile<CT(D), NLPS_KLAW_FLUID, 4, true>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
+                               h->prm, h->gstatus_d, (const double*)h->gridB.get());
+            return;
+          }
           with_law(l, [&](auto L) {
             hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 3, true>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
                                h->gstatus_d, (const double*)nullptr);
           });
         });
+      });
+    } else if (law == NLPS_KLAW_FLUID) {
+      with_nd(ND, [&](auto D) {
+        hipLaunchKernelGGL((k3_tile<CT(D), NLPS_KLAW_FLUID, 4>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
+                           h->gstatus_d, (const double*)h->gridB.get());
       });
     } else if (ND == 3 && h->nmats == 1 && law >= 1 && law <= 3) {  // one material (k3_body, UMAT)
       with_law_in<1, 3>(law, [&](auto L) {
@@ -4797,7 +4868,7 @@ extern "C" int nlps_gpu_tangent_assemble(nlps_gpu* h, long long* nnz) {
     // a cloud of Neo-Hookean particles only: the upper half of every row, the rest by symmetry in nlps_gpu_tangent_coo
     h->ktan_sym = h->tangent_symmetric && h->uniform_law == NLPS_MAT_NEO_HOOKEAN;
     LAUNCH_ND_BLK(k_tangent_nh_grouped<2>, k_tangent_nh_grouped<3>, ngrid, TAN_NT, h->P, h->g, h->mats_d, np, h->skey2_d, h->sval2_d,
-                  h->khead_d, h->kng_d, h->kst_d, h->ktouched_d, h->gstatus_d, h->ktan_sym ? 1 : 0);
+                  h->khead_d, h->kng_d, h->kst_d, h->ktouched_d, h->gstatus_d, h->ktan_sym ? 1 : 0, h->tan_alpha4);
   } else if (np > 0) {
     h->ktan_sym = false;
     LAUNCH_ND_BLK(k_tangent_nh<2>, k_tangent_nh<3>, np, 64, h->P, h->g, h->mats_d, h->kst_d, h->ktouched_d, h->gstatus_d);
@@ -4811,6 +4882,11 @@ extern "C" int nlps_gpu_tangent_assemble(nlps_gpu* h, long long* nnz) {
   if (check_status(h, ST_NEWTON | ST_CONSTITUTIVE, "nlps_gpu_tangent_assemble() (Neo-Hookean particles only)")) return 1;
   h->knnz_blocks = total;
   if (nnz) *nnz = (long long)total * ND * ND;
+  return 0;
+}
+
+extern "C" int nlps_gpu_set_tangent_alpha4(nlps_gpu* h, double alpha_4) {
+  h->tan_alpha4 = alpha_4;
   return 0;
 }
 
@@ -4910,7 +4986,8 @@ extern "C" int nlps_gpu_tangent_operator(nlps_gpu* h, double alpha_1, const doub
   }
   if (np > 0) {
     const int nb = (np + TANOP_SETUP_NT - 1) / TANOP_SETUP_NT;
-    LAUNCH_ND_BLK(k_tanop_setup<2>, k_tanop_setup<3>, nb, TANOP_SETUP_NT, h->P, h->g, h->mats_d, h->top_d, np, h->gstatus_d);
+    LAUNCH_ND_BLK(k_tanop_setup<2>, k_tanop_setup<3>, nb, TANOP_SETUP_NT, h->P, h->g, h->mats_d, h->top_d, np, h->gstatus_d,
+                  h->tan_alpha4);
   }
   HIPCHK(hipGetLastError());
   if (check_status(h, ST_NEWTON | ST_CONSTITUTIVE, "nlps_gpu_tangent_operator()")) return 1;  // (synchronises)
@@ -5301,6 +5378,7 @@ extern "C" int nlps_gpu_newton_solve(nlps_gpu* h, double* dU, const double* Un_d
     h->err = "nlps_gpu_newton_solve: atol, rtol, stol, divtol and max_it must be >= 0";
     return 1;
   }
+  h->tan_alpha4 = alpha[3];  // the fluid law's tangent reads alpha_4 (Constitutive.c:298-314)
   const bool bt = snes->linesearch == NLPS_LS_BT;
   if (!bt && snes->linesearch != NLPS_LS_BASIC) {
     h->err = "nlps_gpu_newton_solve: linesearch must be NLPS_LS_BASIC or NLPS_LS_BT";

@@ -661,14 +661,17 @@ extern "C" int nlps_host_read_deck(const char* path, nlps_deck* d) {
   return 0;
 }
 
-// Define-Material blocks (InOutFun/Material/Read_GramsMaterials2.c:51-175) of the six laws of this path:
+// Define-Material blocks (InOutFun/Material/Read_GramsMaterials2.c:51-175) of the seven laws of this path:
 //   Define-Material(idx=0,Model=Neo-Hookean-Wriggers | Hencky | Drucker-Prager | Von-Mises | Matsuoka-Nakai |
-//                   Lade-Duncan) { property = value ... }
+//                   Lade-Duncan | Newtonian-Fluid-Compressible) { property = value ... }
 // with the property names, defaults and completeness checks of Material/Hyperelastic/Neo-Hookean.c, Hencky.c and
 // Material/Plasticity/Drucker-Prager.c, Von-Mises.c, Matsuoka-Nakai.c, Lade-Duncan.c (the last two also set the
 // globals TOL_Radial_Returning / Max_Iterations_Radial_Returning to 1e-10 / 20 and 1e-14 / 10: the caller's
 // nlps_params).  The eigenerosion / eigensoftening constants (Ceps, Gf, ft,
 // heps, wcrit) are accepted and dropped, as the reference does when those drivers are off.
+// Newtonian-Fluid-Compressible (Material/Fluid/Compressible-Newtonian-Fluid.c:60-175) knows rho, Compressibility,
+// Reference-Pressure, Viscosity, Macdonald-parameter -- all five required (:155-199) -- and Fbar / Fbar-alpha; any other
+// key is "Undefined" there and here (E and nu among them).
 extern "C" int nlps_host_read_materials(const char* path, int max_materials, nlps_material* mats, double* rho,
                                         int* idx, int* nmats) {
   if (!path || !mats || !rho || !nmats || max_materials < 1) return fail("bad argument");
@@ -696,11 +699,12 @@ extern "C" int nlps_host_read_materials(const char* path, int max_materials, nlp
     else if (model == "Von-Mises") m.type = NLPS_MAT_VON_MISES;
     else if (model == "Matsuoka-Nakai") m.type = NLPS_MAT_MATSUOKA_NAKAI;
     else if (model == "Lade-Duncan") m.type = NLPS_MAT_LADE_DUNCAN;
+    else if (model == "Newtonian-Fluid-Compressible") m.type = NLPS_MAT_NEWTONIAN_FLUID;
     else return fail("Define-Material: model " + model + " is not one of the laws of this path");
     const std::string who = "Define-Material(" + model + ")";
     bool open = false, closed = false, has_rho = false, has_E = false, has_nu = false, has_phi = false, has_psi = false,
          has_eps0 = false, has_yield = false, fbar = false, has_alpha = false, has_a1 = false, has_a2 = false,
-         has_a3 = false, has_kappa0 = false;
+         has_a3 = false, has_kappa0 = false, has_K = false, has_p0 = false, has_mu = false, has_n = false;
     double H = 0.0, r = 0.0;
     while (!closed) {
       if (!in.next()) return fail(who + ": the block is not closed");
@@ -710,10 +714,19 @@ extern "C" int nlps_host_read_materials(const char* path, int max_materials, nlp
       const double v = np_ > 1 ? atof(kv[1]) : 0.0;
       const bool dp = m.type == NLPS_MAT_DRUCKER_PRAGER, vm = m.type == NLPS_MAT_VON_MISES;
       const bool ld = m.type == NLPS_MAT_LADE_DUNCAN, fr = ld || m.type == NLPS_MAT_MATSUOKA_NAKAI;
+      const bool fl = m.type == NLPS_MAT_NEWTONIAN_FLUID;
       if (!strcmp(k, "{") && np_ == 1) open = true;
       else if (!strcmp(k, "}") && np_ == 1) closed = true;
       else if (np_ != 2) return fail(who + ": Use this format -> Propertie = value");
       else if (!strcmp(k, "rho")) r = v, has_rho = true;
+      else if (fl && !strcmp(k, "Compressibility")) m.compressibility = v, has_K = true;
+      else if (fl && !strcmp(k, "Reference-Pressure")) m.p_ref = v, has_p0 = true;
+      else if (fl && !strcmp(k, "Viscosity")) m.viscosity = v, has_mu = true;
+      else if (fl && !strcmp(k, "Macdonald-parameter")) m.n_macdonald = v, has_n = true;
+      else if (fl && !strcmp(k, "Fbar"))
+        fbar = !strcmp(kv[1], "true") || !strcmp(kv[1], "True") || !strcmp(kv[1], "TRUE") || !strcmp(kv[1], "1");
+      else if (fl && !strcmp(k, "Fbar-alpha")) {
+      } else if (fl) return fail(who + ": Undefined " + k);
       else if (!strcmp(k, "E")) m.E = v, has_E = true;
       else if (!strcmp(k, "nu")) m.nu = v, has_nu = true;
       else if (!strcmp(k, "Ceps") || !strcmp(k, "Gf") || !strcmp(k, "ft") || !strcmp(k, "heps") || !strcmp(k, "wcrit")) {
@@ -747,7 +760,17 @@ extern "C" int nlps_host_read_materials(const char* path, int max_materials, nlp
       } else return fail(who + ": Undefined " + k);
     }
     (void)open;  // the reference notes the opening brace and never asks for it either
-    if (!(has_rho && has_E && has_nu)) return fail(who + ": rho, E and nu are required");
+    if (m.type == NLPS_MAT_NEWTONIAN_FLUID) {  // check_Compressible_Newtonian_Fluid_Material, :155-199
+      if (!(has_rho && has_K && has_p0 && has_mu && has_n)) {
+        std::string miss;
+        if (!has_rho) miss += " rho";
+        if (!has_K) miss += " Compressibility";
+        if (!has_p0) miss += " Reference-Pressure";
+        if (!has_mu) miss += " Viscosity";
+        if (!has_n) miss += " Macdonald-parameter";
+        return fail(who + ": Some parameter is missed for Compressible Newtonian Fluid material:" + miss);
+      }
+    } else if (!(has_rho && has_E && has_nu)) return fail(who + ": rho, E and nu are required");
     if (fbar) return fail(who + ": Fbar needs the quadratic-triangle patches this path does not cover");
     if (m.type == NLPS_MAT_DRUCKER_PRAGER) {
       if (!(has_phi && has_psi)) return fail(who + ": Friction-angle and Dilatancy-angle are required");

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(TAN_NT) void k_tangent_nh_grouped(PView P, GridD g,
                                                             const int* __restrict__ sorted, const int* __restrict__ head,
                                                             const int* __restrict__ ngroups, double* __restrict__ Kst,
                                                             unsigned char* __restrict__ touched,
-                                                            int* __restrict__ gstatus, int sym) {
+                                                            int* __restrict__ gstatus, int sym, double alpha4) {
   constexpr int S = TanCfg<ND>::S, MAXM = TanCfg<ND>::MAXM, KN = Lme<ND>::KN;
   __shared__ double gn[TAN_GROUP][MAXM][ND], g1[TAN_GROUP][MAXM][ND], ub[TAN_GROUP][MAXM][ND];
   __shared__ double coef[TAN_GROUP][3];  // V0*c0, V0*c1, V0*G of each particle (Neo-Hookean)
@@ -208,7 +208,10 @@ __global__ __launch_bounds__(TAN_NT) void k_tangent_nh_grouped(PView P, GridD g,
       const MatD m = mats[P.mat[p]];
       double Zinv = 0.0, r[ND], J[ND * ND], Jm1[ND * ND], DF[ND * ND], DFm1[ND * ND], Fn[ND * ND], bn[ND * ND], zz;
       bool ok = ok_lists;
-      const bool spectral = m.type != NLPS_MAT_NEO_HOOKEAN;
+      // the fluid law (Newtonian-Fluid.c:83-190) takes the general per-particle-tensor route of the spectral laws in phase
+      // B: every term is bilinear in g1_A, g1_B once gn_B . b_n gn_A is written g1_B . (DF b_n DF^T) g1_A
+      const bool fluid = m.type == NLPS_KLAW_FLUID;
+      const bool spectral = m.type != NLPS_MAT_NEO_HOOKEAN && !fluid;
       double nv[ND * ND];  // eigenvectors of b (spectral laws)
       if (ok) {
         lme_moments_h<ND>(c, Zinv, r, J);
@@ -223,6 +226,52 @@ __global__ __launch_bounds__(TAN_NT) void k_tangent_nh_grouped(PView P, GridD g,
         }
       }
       if (ok && !spectral) left_cauchy_green<ND>(bn, Fn);
+      if (ok && fluid) {
+        // sp_n <- L, sp_C <- E = sym L, sp_tau <- DF b_n DF^T, coef <- c1, c2, c0
+        double F1[ND * ND], dF1[ND * ND], tau[ND * ND], tzz, L[ND * ND], Es[ND * ND], Mb[ND * ND], T1[ND * ND];
+        load_block<ND>(P, fFN1(P), p, F1, zz);
+        load_block<ND>(P, F_DTFN1, p, dF1, zz);
+        const double Jp = PF(P, F_JN1, p);
+        if (!law_newtonian_fluid<ND>(m, F1, dF1, Jp, tau, tzz, L, Es)) {
+          if (lane == 0) {
+            atomicOr(&P.status[p], ST_CONSTITUTIVE);
+            atomicOr(gstatus, ST_CONSTITUTIVE);
+          }
+          ok = false;
+        } else {
+#pragma unroll
+          for (int a = 0; a < ND; a++)
+#pragma unroll
+            for (int b = 0; b < ND; b++) {
+              double v = 0.0;
+#pragma unroll
+              for (int q = 0; q < ND; q++) v = fma(DF[a * ND + q], bn[q * ND + b], v);
+              T1[a * ND + b] = v;
+            }
+#pragma unroll
+          for (int a = 0; a < ND; a++)
+#pragma unroll
+            for (int b = 0; b < ND; b++) {
+              double v = 0.0;
+#pragma unroll
+              for (int q = 0; q < ND; q++) v = fma(T1[a * ND + q], DF[b * ND + q], v);
+              Mb[a * ND + b] = v;
+            }
+          const FluidCoef k = fluid_coefficients(m, Jp);
+          const double dp = -m.K_fluid * pow(Jp, 1.0 - m.n_macdonald);  // :109
+          if (lane == 0) {
+#pragma unroll
+            for (int q = 0; q < ND * ND; q++) {
+              sp_n[jj][q] = L[q];
+              sp_C[jj][q] = Es[q];
+              sp_tau[jj][q] = Mb[q];
+            }
+            sp_lam[jj][0] = k.pressure + dp + (2.0 / 3.0) * alpha4 * k.c0;  // c1
+            sp_lam[jj][1] = k.pressure + alpha4 * k.c0;                      // c2
+            sp_tauv[jj][0] = k.c0;
+          }
+        }
+      }
       if (ok && spectral) {
         double bmat[ND * ND], tau[ND * ND], lamb[3] = {0, 0, 0}, tauv[3] = {0, 0, 0}, tv[ND * ND], Cm[ND * ND];
         load_block<ND>(P, F_TAU, p, tau, zz);
@@ -258,6 +307,22 @@ __global__ __launch_bounds__(TAN_NT) void k_tangent_nh_grouped(PView P, GridD g,
       if (lane == 0) {
         law_of[jj] = m.type;
         sp_V0[jj] = ok ? tangent_vol(P, p) : 0.0;
+      }
+      if (fluid) {
+        __builtin_amdgcn_wave_barrier();
+        __threadfence_block();
+        // D[k][l][i][j] = V0 ( -c1 d_ki d_lj + c2 d_kj d_li + 2 c0 (E[i][k] d_lj - E[i][l] d_kj)
+        //                      + (alpha4 c0 d_ij - c0 L[i][j]) (DF b_n DF^T)[l][k] - c0 d_li L[k][j] + 2/3 c0 d_ki L[l][j] )
+        constexpr int E4 = ND * ND * ND * ND;
+        for (int e4 = lane; e4 < E4; e4 += 64) {
+          const int j = e4 % ND, i = (e4 / ND) % ND, l = (e4 / (ND * ND)) % ND, k = e4 / (ND * ND * ND);
+          const double c1 = sp_lam[jj][0], c2 = sp_lam[jj][1], c0 = sp_tauv[jj][0];
+          double v = ((k == i && l == j) ? -c1 : 0.0) + ((k == j && l == i) ? c2 : 0.0);
+          v += 2.0 * c0 * ((l == j ? sp_C[jj][i * ND + k] : 0.0) - (k == j ? sp_C[jj][i * ND + l] : 0.0));
+          v += ((i == j ? alpha4 * c0 : 0.0) - c0 * sp_n[jj][i * ND + j]) * sp_tau[jj][l * ND + k];
+          v += -(l == i ? c0 * sp_n[jj][k * ND + j] : 0.0) + (k == i ? (2.0 / 3.0) * c0 * sp_n[jj][l * ND + j] : 0.0);
+          spD[jj][e4] = ok ? sp_V0[jj] * v : 0.0;
+        }
       }
 #pragma unroll
       for (int i = 0; i < 5; i++)

@@ -22,7 +22,8 @@
 static constexpr int TANOP_SETUP_NT = 64;
 template <int ND>
 __global__ __launch_bounds__(TANOP_SETUP_NT) void k_tanop_setup(PView P, GridD g, const MatD* __restrict__ mats,
-                                                                double* __restrict__ Dh, int ld, int* __restrict__ gstatus) {
+                                                                double* __restrict__ Dh, int ld, int* __restrict__ gstatus,
+                                                                double alpha4) {
   constexpr int E = ND * ND;
   __shared__ double sh_tanop[7 * E][TANOP_SETUP_NT];
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -65,6 +66,56 @@ __global__ __launch_bounds__(TANOP_SETUP_NT) void k_tanop_setup(PView P, GridD g
             const double v = c0 * Fi[mm * ND + i] * Fi[n * ND + j] + c1 * Fi[mm * ND + j] * Fi[n * ND + i] +
                              (i == j ? cG * bn[n * ND + mm] : 0.0);
             Dh[(size_t)(((mm * ND + n) * ND + i) * ND + j) * ld + p] = v;
+          }
+    return;
+  }
+  if (m.type == NLPS_KLAW_FLUID) {
+    // Newtonian-Fluid.c:83-190 with a1 = DF^-T gn_A, b1 = DF^-T gn_B pulled into the tensor:
+    // Dh = V0 ( -c1 Fi[m][i] Fi[n][j] + c2 Fi[m][j] Fi[n][i] + 2 c0 (E Fi^T)[i][m] Fi[n][j] - 2 c0 (E Fi^T)[i][n] Fi[m][j]
+    //           + (alpha4 c0 d_ij - c0 L[i][j]) b_n[n][m] - c0 Fi[n][i] (Fi L)[m][j] + 2/3 c0 Fi[m][i] (Fi L)[n][j] )
+    double Fn[E], bn[E], F1[E], dF1[E], tau[E], tzz, L[E], Es[E];
+    load_block<ND>(P, fFN(P), p, Fn, zz);
+    left_cauchy_green<ND>(bn, Fn);
+    load_block<ND>(P, fFN1(P), p, F1, zz);
+    load_block<ND>(P, F_DTFN1, p, dF1, zz);
+    const double Jp = PF(P, F_JN1, p);
+    if (!law_newtonian_fluid<ND>(m, F1, dF1, Jp, tau, tzz, L, Es)) {
+      atomicOr(&P.status[p], ST_CONSTITUTIVE);
+      atomicOr(gstatus, ST_CONSTITUTIVE);
+#pragma unroll
+      for (int e = 0; e < E * E; e++) Dh[(size_t)e * ld + p] = 0.0;
+      return;
+    }
+    const FluidCoef k = fluid_coefficients(m, Jp);
+    const double dp = -m.K_fluid * pow(Jp, 1.0 - m.n_macdonald);  // :109
+    const double c0 = k.c0, c1 = k.pressure + dp + (2.0 / 3.0) * alpha4 * c0, c2 = k.pressure + alpha4 * c0;
+    double EFt[E], FL[E];
+#pragma unroll
+    for (int a = 0; a < ND; a++)
+#pragma unroll
+      for (int b = 0; b < ND; b++) {
+        double u = 0.0, v = 0.0;
+#pragma unroll
+        for (int q = 0; q < ND; q++) {
+          u = fma(Es[a * ND + q], Fi[b * ND + q], u);
+          v = fma(Fi[a * ND + q], L[q * ND + b], v);
+        }
+        EFt[a * ND + b] = u;
+        FL[a * ND + b] = v;
+      }
+#pragma unroll
+    for (int mm = 0; mm < ND; mm++)
+#pragma unroll
+      for (int n = 0; n < ND; n++)
+#pragma unroll
+        for (int i = 0; i < ND; i++)
+#pragma unroll
+          for (int j = 0; j < ND; j++) {
+            const double v = -c1 * Fi[mm * ND + i] * Fi[n * ND + j] + c2 * Fi[mm * ND + j] * Fi[n * ND + i] +
+                             2.0 * c0 * (EFt[i * ND + mm] * Fi[n * ND + j] - EFt[i * ND + n] * Fi[mm * ND + j]) +
+                             ((i == j ? alpha4 * c0 : 0.0) - c0 * L[i * ND + j]) * bn[n * ND + mm] -
+                             c0 * Fi[n * ND + i] * FL[mm * ND + j] + (2.0 / 3.0) * c0 * Fi[mm * ND + i] * FL[n * ND + j];
+            Dh[(size_t)(((mm * ND + n) * ND + i) * ND + j) * ld + p] = V0 * v;
           }
     return;
   }

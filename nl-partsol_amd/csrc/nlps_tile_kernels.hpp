@@ -855,6 +855,10 @@ __global__ __launch_bounds__(NT, NT == 64 ? 1 : (ND == 2 ? K2_WAVES_2D : K2_WAVE
 // stages as MODE 1, same kernel skeleton and occupancy; what it adds are the stores of the n+1 state.
 // MODE 2: MODE 0 plus the rate tensors dt_DF = sum dV_A (x) grad N_A and dt_F_n1 = dt_DF F_n + DF dt_F_n
 // (compute-Strains.c:48-72, 176-207) from a second gather window dV.
+// MODE 4 (LAW = NLPS_KLAW_FLUID only): the residual of MODE 3 for the one law that reads the rate tensors -- MODE 3's pass
+// with MODE 2's second gather window: G and Gv from one member loop, DF, F_n1, J_n1, dt_DF, dt_F_n1, the fluid stress
+// (Newtonian-Fluid.c:17-79) from F_n1, dt_F_n1, J_n1 still in registers, the force scatter; stores what MODE 3 stores
+// plus the two rate tensors (the separate stages pass DF, F_n1, tau and both rate tensors through HBM between three launches).
 // FILT (clouds with several laws): the launch handles only the tile's particles whose material follows LAW; they are
 // compacted into an LDS list first, so every lane works and the kernel is the single-law specialisation (one launch per
 // law present; the run-time dispatch over all laws in one kernel needed 436 B of scratch per lane and 0.51 ms).
@@ -876,7 +880,7 @@ struct K3Waves {
 template <int ND, int MODE, bool FILT>
 struct K3Lds {
   static constexpr int NW = TileCfg<ND>::NW, NWA = TileCfg<ND>::NWA;
-  static constexpr bool RATES = (MODE == 2);
+  static constexpr bool RATES = (MODE == 2 || MODE == 4);
   static constexpr int SELCAP = FILT ? 4096 : 1;
   static constexpr int N_DVXY = RATES ? 2 * NW : 2, N_DVZ = (RATES && ND == 3) ? NW : 1, N_DUZ = (ND == 3) ? NW : 1;
   double* dvxy;  // [N_DVXY], 16-byte aligned
@@ -900,8 +904,9 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
                                         const K3Lds<ND, MODE, FILT>& lds, const NodalFold* fs) {
   NLPS_FP_CONTRACT
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN;
-  constexpr bool RATES = (MODE == 2);
-  constexpr bool SCATTER = (MODE == 1 || MODE == 3);  // the stress update and the force scatter follow the F update
+  constexpr bool RATES = (MODE == 2 || MODE == 4);
+  constexpr bool SCATTER = (MODE == 1 || MODE == 3 || MODE == 4);  // the stress update and the force scatter follow the F update
+  static_assert((MODE == 4) == (LAW == NLPS_KLAW_FLUID), "the rate-carrying residual is the fluid law's, and only its");
   // gather window of dU: {x,y} as one 16-B double2 per node (ds_read_b128) + z as a separate 8-B array
   // (ds_read_b64): with node strides of 16 B and 8 B the tile's 64 I0 positions hit distinct banks; a
   // padded 32-B AoS row put every second node on the same banks (41 % conflict cycles measured).
@@ -1321,6 +1326,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     // fused step: J goes straight to its n slot (nothing reads J_n inside the step; J_n+1 = J_n is restored with the
     // roll, k_copy_n_to_n1), so K5 has no copy to make
     PF(P, MODE == 1 ? F_JN : F_JN1, pl) = Jn1;
+    double dFk[(MODE == 4) ? ND * ND : 1];  // dt_F_n1, kept for the fluid stress (MODE 4)
     if (RATES) {
       double dDF[ND * ND], dFn[ND * ND], dFn1[ND * ND], zz;
 #pragma unroll
@@ -1344,6 +1350,10 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
         }
       store_block<ND>(P, F_DTDF, pl, dDF, 0.0, false);
       store_block<ND>(P, F_DTFN1, pl, dFn1, 0.0, false);
+      if (MODE == 4) {
+#pragma unroll
+        for (int q = 0; q < ND * ND; q++) dFk[q % ((MODE == 4) ? ND * ND : 1)] = dFn1[q];
+      }
     }
     if (!SCATTER) {
       if (st) {
@@ -1359,11 +1369,22 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     }
     double tau[ND * ND], B[ND * ND];
     // (MODE 3: C_ep kept for the tangent that may follow, everything to the n+1 slots)
-    st |= stress_update<ND, LAW, MODE == 3, (LAW == NLPS_KLAW_FRICTIONAL), MODE == 1>(P, pl, mats, prm, Fn1, DF, Jn1, tau, mat_idx);
+    if constexpr (MODE == 4) {
+      double tzz = 0.0;
+      if (law_newtonian_fluid<ND>(mats[mat_idx], Fn1, dFk, Jn1, tau, tzz)) {
+        store_block<ND>(P, F_TAU, pl, tau, tzz, true);
+      } else {  // F_n1 does not invert: no stress, no force of this particle
+        st |= ST_CONSTITUTIVE;
+#pragma unroll
+        for (int q = 0; q < ND * ND; q++) tau[q] = 0.0;
+      }
+    } else {
+      st |= stress_update<ND, LAW, MODE == 3, (LAW == NLPS_KLAW_FRICTIONAL), MODE == 1>(P, pl, mats, prm, Fn1, DF, Jn1, tau, mat_idx);
+    }
     // (MODE 1 accumulates -f_int, what the explicit scheme divides by the mass; MODE 3 the +f_int of the Lagrangian, :1359)
     // (measured and dropped, round 4: DF^-T J^-1 formed BEFORE the stress update so that DF and J^-1 need not live through
     // it -- the allocator then spills more, not less: Drucker-Prager at three waves 152 -> 192 B of scratch, Hencky 8 -> 44)
-    const bool fo_ok = force_operator<ND>(B, tau, DF, Jm1, PF(P, F_VOL0, pl), MODE == 3 ? 1.0 : -1.0);
+    const bool fo_ok = force_operator<ND>(B, tau, DF, Jm1, PF(P, F_VOL0, pl), MODE >= 3 ? 1.0 : -1.0);
     PH(11)
     if (fo_ok) {
       // RELOAD (the laws whose stress update sets the register budget): the LME factors are rebuilt from the particle's
@@ -1473,8 +1494,8 @@ __global__ __launch_bounds__(NT, (NT == 64 ? 1 : (K3Waves<ND, LAW, MODE>::value)
   __shared__ int sel[L::SELCAP];
   __shared__ int nsel;
   __shared__ int wcnt[NT / 64];
-  const int nbnd = (MODE == 1 || MODE == 3) ? tile_boundary_count(td) : 0;
-  if (MODE == 1 || MODE == 3) tile_signal_empty(td, nbnd);
+  const int nbnd = (MODE == 1 || MODE >= 3) ? tile_boundary_count(td) : 0;
+  if (MODE == 1 || MODE >= 3) tile_signal_empty(td, nbnd);
   TileWork tw;
   if (!tile_work_item(td, tw)) return;
   const L lds{dvxy, dvz, duxy, duz, fac, sel, &nsel, wcnt};

@@ -41,7 +41,8 @@ class Material(C.Structure):
                 ("theta_voce", C.c_double), ("K0_voce", C.c_double), ("Kinf_voce", C.c_double),
                 ("delta_voce", C.c_double), ("Ceps", C.c_double), ("Gf", C.c_double),
                 ("cohesion", C.c_double), ("alpha_borja", C.c_double), ("a_borja", C.c_double * 3),
-                ("ft", C.c_double), ("heps", C.c_double), ("wcrit", C.c_double)]
+                ("ft", C.c_double), ("heps", C.c_double), ("wcrit", C.c_double),
+                ("viscosity", C.c_double), ("compressibility", C.c_double), ("n_macdonald", C.c_double)]
 
 
 _PD = ["x_GC", "dis", "vel", "acc", "F_n", "F_n1", "DF", "Stress", "b_e_n", "b_e_n1", "J_n", "J_n1", "rho",
@@ -108,7 +109,7 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_rccl_unique_id", "nlps_gpu_rccl_attach", "nlps_gpu_rccl_attach_comm", "nlps_gpu_rccl_detach",
            "nlps_gpu_rccl_reduce", "nlps_gpu_rccl_info", "nlps_gpu_rccl_migrate", "nlps_gpu_rccl_selftest_migrate", "nlps_gpu_rccl_selftest_exchange", "nlps_gpu_touched_layers", "nlps_gpu_set_node_window", "nlps_gpu_set_ghost_bands",
            "nlps_gpu_form_initial_guess", "nlps_gpu_nodal_kinetic_increments", "nlps_gpu_nodal_inertial_forces",
-           "nlps_gpu_tangent_assemble", "nlps_gpu_tangent_set_grouped", "nlps_gpu_tangent_coo",
+           "nlps_gpu_tangent_assemble", "nlps_gpu_tangent_set_grouped", "nlps_gpu_set_tangent_alpha4", "nlps_gpu_tangent_coo",
            "nlps_gpu_sparsity_pattern", "nlps_gpu_tangent_operator", "nlps_gpu_tangent_apply",
            "nlps_gpu_tangent_block_diagonal", "nlps_gpu_tangent_solve", "nlps_gpu_newton_solve", "nlps_gpu_newmark_step",
            "nlps_gpu_migration_select", "nlps_gpu_migration_commit", "nlps_gpu_num_particles",
@@ -159,6 +160,7 @@ def lib():
         L.nlps_gpu_nodal_inertial_forces.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [_dp, _dp]
         L.nlps_gpu_tangent_assemble.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
         L.nlps_gpu_tangent_set_grouped.argtypes = [C.c_void_p, C.c_int]
+        L.nlps_gpu_set_tangent_alpha4.argtypes = [C.c_void_p, C.c_double]
         L.nlps_gpu_tangent_coo.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int, _ip, _ip, _dp]
         L.nlps_gpu_sparsity_pattern.argtypes = [C.c_void_p, _ip]
         L.nlps_gpu_tangent_operator.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
@@ -278,7 +280,7 @@ class Solver:
         self.params = params or default_params()
         mats = (Material * len(materials))()
         for k, m in enumerate(materials):
-            mats[k] = Material(int(m["type"]), float(m["E"]), float(m["nu"]), float(m.get("phi_deg", 0.0)),
+            mats[k] = Material(int(m["type"]), float(m.get("E", 0.0)), float(m.get("nu", 0.0)), float(m.get("phi_deg", 0.0)),
                                float(m.get("psi_deg", 0.0)), float(m.get("kappa_0", 0.0)),
                                float(m.get("exponent_ortiz", 1.0)), float(m.get("eps_0", 1.0)),
                                float(m.get("p_ref", 0.0)), float(m.get("hardening_modulus", 0.0)),
@@ -287,7 +289,9 @@ class Solver:
                                float(m.get("Ceps", 0.0)), float(m.get("Gf", 0.0)), float(m.get("cohesion", 0.0)),
                                float(m.get("alpha_borja", 0.0)),
                                (C.c_double * 3)(*[float(v) for v in m.get("a_borja", (0.0, 0.0, 0.0))]),
-                               float(m.get("ft", 0.0)), float(m.get("heps", 0.0)), float(m.get("wcrit", 1.0)))
+                               float(m.get("ft", 0.0)), float(m.get("heps", 0.0)), float(m.get("wcrit", 1.0)),
+                               float(m.get("viscosity", 0.0)), float(m.get("compressibility", 0.0)),
+                               float(m.get("n_macdonald", 0.0)))
         self._host = {}
         hp = Particles()
         hp.np = self.np
@@ -593,6 +597,10 @@ class Solver:
             self.h, _vp(R), _vp(dU), _vp(Un_dt), _vp(Un_dt2), _vp(M), _d(al), _d(gv), None if loads is None else loads.arr,
             0 if loads is None else loads.n, int(step), float(thickness), None if a0 is None else a0.ctypes.data, int(flags)))
         return R
+
+    def set_tangent_alpha4(self, alpha_4):
+        """alpha_4 of the Newmark scheme for the fluid law's tangent (0 = quasi-static, the default)."""
+        self._chk(self.L.nlps_gpu_set_tangent_alpha4(self.h, float(alpha_4)))
 
     def jacobian_evaluation(self, alpha_1=0.0, lumped_mass=None, apply_dirichlet=False, on_device=False):  # __jacobian_evaluation
         """COO triplets (rows, cols, vals) of the tangent matrix in masked dof numbering.  on_device: torch tensors on
