@@ -232,6 +232,29 @@ int nlps_gpu_update_kinetics(nlps_gpu *h, double alpha_blend, const double *dU, 
  * nlps_gpu_last_error): the law reads dt_F_n1 and the reference has no working explicit driver that defines that rate. */
 int nlps_gpu_explicit_step(nlps_gpu *h, const nlps_bcc *bcc, int nbcc, int step, double dt,
                            double gamma, const double *gravity);
+/* The damage hooks inside the explicit step (clouds created with driver_eigenerosion or driver_eigensoftening).  Off
+ * by default: nlps_gpu_explicit_step then refuses such a cloud (the hooks of the level-B stages are its only form).
+ * With on != 0 the step of such a cloud is the composition of the explicit step above with the hooks of the maintained
+ * driver at the places U-Newmark-beta.c puts them (the reference's explicit drivers are stubs):
+ *   1. search, active nodes, lumped mass, predictor, nodal dU with the Dirichlet sets, compatibility (DF, F_n1, J_n1,
+ *      rho), all as above;
+ *   2. after the search compute_Beps__Constitutive__(.., false): the epsilon-neighbourhoods of the particles whose total
+ *      displacement exceeds 1e-6 (Beps.c:30-36).  Eigenerosion: the other particles keep the lists of
+ *      Initialize_Beps = true, taken before the first step (U-Newmark-beta.c:182-183); eigensoftening: their lists are
+ *      empty (:213-215);
+ *   3. the constitutive update, which skips failed particles (Damage_n == 1: W = 0, stress untouched, :1218-1224);
+ *   4. the damage hook (:1313-1331): Damage_n1 (and Strain_f_n1), then every Kirchhoff stress scaled in place by
+ *      1 - Damage_n1; eigensoftening with the reference's sequential semantics (one particle after the other in the
+ *      caller's order);
+ *   5. internal forces from the scaled stress, nodal equilibrium, G2P, corrector;
+ *   6. the roll of the explicit step, and Damage_n <- Damage_n1, Strain_f_n <- Strain_f_n1 (:1950-1956).
+ * A download after such a step returns Stress = the scaled stress of that step, W = the unscaled energy (0 for a skipped
+ * particle), Damage_n == Damage_n1 and both Strain_f slots, like the level-B roll.
+ * The step runs on one rank, on the handle's stream, without sorts, synchronisation or allocation.  It returns 1 with
+ * the reason in nlps_gpu_last_error when a halo callback or an RCCL exchange is attached (an epsilon-neighbourhood across
+ * a slab face needs ghost particles), in deterministic mode, and for the fluid law (as above).
+ * The setter returns 1 for a cloud created without either driver. */
+int nlps_gpu_set_explicit_damage(nlps_gpu *h, int on);
 /* Number of active nodes after the last search (computes Nodes2Mask on the device). */
 int nlps_gpu_num_active(nlps_gpu *h, int *nactive);
 /* Nodal results of the last explicit step in masked numbering (any pointer may be NULL).  On one GPU without a ghost

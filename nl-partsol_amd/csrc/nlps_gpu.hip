@@ -567,7 +567,8 @@ __device__ __forceinline__ void store_block(const PView& P, int f0, int p, const
 // LAZY (the fused explicit step): the hyperelastic laws do not store tau and W -- they are functions of F_n+1 (and J)
 // alone, nothing in the step reads them back, and k_copy_n_to_n1 recomputes them with the same code from the same
 // stored inputs when a level-B stage or a download asks (80 B per particle less to store in K3).
-template <int ND, int LAW = -1, bool CEP = false, bool FRIC = (LAW == NLPS_KLAW_FRICTIONAL), bool LAZY = false>
+// KEEP (with LAZY; the state half of the damage step): tau and W are stored for every law -- the damage hook reads them.
+template <int ND, int LAW = -1, bool CEP = false, bool FRIC = (LAW == NLPS_KLAW_FRICTIONAL), bool LAZY = false, bool KEEP = false>
 __device__ __forceinline__ int stress_update(const PView& P, int p, const MatD* __restrict__ mats, const ParamsD& prm,
                                              const double* Fn1, const double* DF, double J, double* tau, int mat_idx = -1) {
   MatD m = mats[mat_idx >= 0 ? mat_idx : P.mat[p]];  // (mat_idx: the caller has read the particle's material index already)
@@ -606,7 +607,7 @@ __device__ __forceinline__ int stress_update(const PView& P, int p, const MatD* 
   }
 #pragma unroll
   for (int s = 0; s < ND * ND; s++) tau[s] = o.tau[s];
-  if (!(LAZY && (law == NLPS_MAT_NEO_HOOKEAN || law == NLPS_MAT_HENCKY))) {
+  if (!(LAZY && !KEEP && (law == NLPS_MAT_NEO_HOOKEAN || law == NLPS_MAT_HENCKY))) {
     store_block<ND>(P, F_TAU, p, o.tau, o.tau_zz, true);
     PF(P, F_W, p) = o.W;
   }
@@ -676,6 +677,69 @@ __global__ void k_beps_keys0(PView P, unsigned long long* __restrict__ keys, int
   if (p >= P.np) return;
   keys[p] = (unsigned long long)(long long)PF(P, F_I00, p);
   vals[p] = p;
+}
+
+// The same tables without a sort, for the explicit step with the damage hooks (nlps_gpu_set_explicit_damage): three
+// passes, no keys.  (1) every particle takes its rank inside its node from the node's counter; (2) every node takes the
+// run [first, last) of its count from ONE cursor -- a wave scans its 64 counts and asks for their sum with one atomic, so
+// the runs of a wave's nodes are contiguous and the order of the waves' blocks in `sorted` is whatever the atomics made
+// it (nothing reads across runs) -- and puts its counter back to zero; (3) every particle goes to first[node] + rank.
+// SNAP: the key is the closest node of the snapshot (F_I00) instead of the current one.
+// The step's own per-node counters (node_cnt_d / nrank_d of the canonical tile lists) are not used: the search that
+// rides on K5 only counts, and k_fill_orders counts the counters down to zero again while it hands out the ranks
+// (TileCnt::defer), so neither the counts nor a stored rank outlive the list stage; asking K5 for full ranks instead
+// would put the returning atomic back into the kernel it was taken out of.
+template <bool SNAP>
+__device__ __forceinline__ int run_node(const PView& P, int p, int nn) {
+  const int A = SNAP ? (int)PF(P, F_I00, p) : P.I0[p];
+  return (A >= 0 && A < nn) ? A : -1;
+}
+template <bool SNAP>
+__global__ __launch_bounds__(BLK) void k_run_count(PView P, int nn, int* __restrict__ cnt, int* __restrict__ rank,
+                                                   int* __restrict__ cursor) {
+  const int p = blockIdx.x * BLK + threadIdx.x;
+  if (p == 0) *cursor = 0;  // (read by k_run_first only, the next launch of the stream)
+  if (p >= P.np) return;
+  const int A = run_node<SNAP>(P, p, nn);
+  rank[p] = A >= 0 ? atomicAdd(&cnt[A], 1) : -1;
+}
+__global__ __launch_bounds__(BLK) void k_run_first(int nn, int* __restrict__ cnt, int* __restrict__ cursor,
+                                                   int* __restrict__ first, int* __restrict__ last) {
+  const int A = blockIdx.x * BLK + threadIdx.x;  // (no early return: every lane takes part in the wave's scan)
+  const int lane = threadIdx.x & 63;
+  const int c = A < nn ? cnt[A] : 0;
+  int incl = c;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int v = __shfl_up(incl, off);
+    if (lane >= off) incl += v;
+  }
+  const int tot = __shfl(incl, 63);
+  int base = 0;
+  if (lane == 0 && tot > 0) base = atomicAdd(cursor, tot);
+  base = __shfl(base, 0);
+  if (A < nn) {
+    cnt[A] = 0;  // ready for the next count
+    first[A] = base + incl - c;
+    last[A] = base + incl;
+  }
+}
+template <bool SNAP>
+__global__ __launch_bounds__(BLK) void k_run_fill(PView P, int nn, const int* __restrict__ first, const int* __restrict__ rank,
+                                                  int* __restrict__ sorted) {
+  const int p = blockIdx.x * BLK + threadIdx.x;
+  if (p >= P.np) return;
+  const int A = run_node<SNAP>(P, p, nn), r = rank[p];
+  if (A < 0 || r < 0) return;
+  const int s = first[A] + r;
+  if (s < P.np) sorted[s] = p;
+}
+// the damage part of the roll behind K5 (U-Newmark-beta.c:1950-1956; k_roll does it for level B)
+__global__ __launch_bounds__(BLK) void k_damage_roll(PView P) {
+  const int p = blockIdx.x * BLK + threadIdx.x;
+  if (p >= P.np) return;
+  PF(P, F_DMG, p) = PF(P, F_DMG1, p);
+  if (P.softening) PF(P, F_STRF, p) = PF(P, F_STRF1, p);
 }
 
 // first0 / last0 / sorted0: the same tables for the closest nodes of the snapshot (nullptr: no frozen lists)
@@ -908,7 +972,8 @@ __global__ __launch_bounds__(BLK) void k_stress(PView P, const MatD* __restrict_
 // After explicit steps the n+1 slots of F and b_e hold the previous step's values (rolled by renaming);
 // the reference's copy semantics (n+1 == n after the roll) are restored on demand, before any level-B stage
 // or download looks at them.
-template <int ND>
+// KEEP: the last step was an explicit step with the damage hooks, which stored tau (scaled by the hook) and W itself.
+template <int ND, bool KEEP = false>
 __global__ __launch_bounds__(BLK) void k_copy_n_to_n1(PView P, const MatD* __restrict__ mats) {
   int p = blockIdx.x * BLK + threadIdx.x;
   if (p >= P.np) return;
@@ -934,7 +999,7 @@ __global__ __launch_bounds__(BLK) void k_copy_n_to_n1(PView P, const MatD* __res
     // Kirchhoff stress and energy of the hyperelastic laws, which the fused step did not store (stress_update LAZY):
     // the same functions of the same stored F_n+1 and J
     const MatD m = mats[P.mat[p]];
-    if (m.type == NLPS_MAT_NEO_HOOKEAN || m.type == NLPS_MAT_HENCKY) {
+    if (!KEEP && (m.type == NLPS_MAT_NEO_HOOKEAN || m.type == NLPS_MAT_HENCKY)) {
       StressIO<ND> o;
       o.fail = 0;
       if (m.type == NLPS_MAT_NEO_HOOKEAN) law_neo_hookean<ND>(m, Fnew, PF(P, F_JN, p), o);
@@ -1691,6 +1756,15 @@ struct nlps_gpu {
   DevBuf<int> dmg_first_d, dmg_last_d;  // eigenerosion: run of every node in the I0-sorted particle list
   DevBuf<int> dmg_first0_d, dmg_last0_d, dmg_sorted0_d;  // the same for the snapshot's closest nodes
   bool beps_snapshot = false;  // F_X0 / F_I00 hold the configuration of Initialize_Beps = true
+  // the explicit step with the damage hooks (nlps_gpu_set_explicit_damage): node runs without a sort (k_run_count /
+  // k_run_first / k_run_fill), tables of their own -- the level-B force stage rebuilds dmg_* with its sorts every call.
+  // xrun_*0: the tables of the snapshot's closest nodes, made once and again after a re-sort has renumbered the slots
+  bool explicit_damage = false;
+  DevBuf<int> xrun_cnt_d, xrun_cursor_d, xrun_rank_d;              // [nnodes], [1], [npad]
+  DevBuf<int> xrun_first_d, xrun_last_d, xrun_sorted_d;            // [nnodes], [nnodes], [npad]
+  DevBuf<int> xrun_first0_d, xrun_last0_d, xrun_sorted0_d;
+  bool xrun_tables0 = false;
+  bool rolled_keep = false;  // `rolled`, and the last step stored tau and W itself (k_copy_n_to_n1 KEEP)
   DevBuf<double> slab_d;    // P2G window slabs [ntiles][slab_n][1+ND][NW] (TileD::slab), deterministic mode only
   bool deterministic = false;
   int band_lo = -(1 << 30), band_hi = 1 << 30;  // ghost bands: layers <= band_lo and >= band_hi are shared with neighbours
@@ -2435,6 +2509,7 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
   h->steps_since_sort = 0;
   h->rehome = true;  // the slots have new owners: the next search records their tiles
   h->debt = 0.0;
+  h->xrun_tables0 = false;  // (slot numbers)
   return 0;
 }
 
@@ -2584,6 +2659,25 @@ extern "C" int nlps_gpu_set_law_launch_mode(nlps_gpu* h, int mode) {
   h->k3_per_law = mode == 1;
   return 0;
 }
+extern "C" int nlps_gpu_set_explicit_damage(nlps_gpu* h, int on) {
+  if (!h->P.erosion) {
+    h->err = "nlps_gpu_set_explicit_damage: the cloud was created without driver_eigenerosion / driver_eigensoftening "
+             "(nlps_params): it has no damage hooks to run";
+    return 1;
+  }
+  if (on && !h->xrun_cnt_d) {  // every table of the step's node runs, so that a step allocates nothing
+    const size_t nn = (size_t)h->g.nnodes, npad = h->P.npad;
+    if (dev_alloc(h, h->xrun_cnt_d, nn) || dev_alloc(h, h->xrun_cursor_d, 1) || dev_alloc(h, h->xrun_rank_d, npad)) return 1;
+    if (dev_alloc(h, h->xrun_first_d, nn) || dev_alloc(h, h->xrun_last_d, nn) || dev_alloc(h, h->xrun_sorted_d, npad)) return 1;
+    if (!h->P.softening &&
+        (dev_alloc(h, h->xrun_first0_d, nn) || dev_alloc(h, h->xrun_last0_d, nn) || dev_alloc(h, h->xrun_sorted0_d, npad)))
+      return 1;
+    HIPCHK(hipMemsetAsync(h->xrun_cnt_d, 0, nn * sizeof(int), h->stream));  // (k_run_first leaves the counters at zero)
+  }
+  h->explicit_damage = on != 0;
+  return 0;
+}
+
 extern "C" int nlps_gpu_set_deterministic(nlps_gpu* h, int on) {
   h->deterministic = on != 0;
   h->ahead = h->lists_ready = false;
@@ -3661,9 +3755,10 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
 
 static int materialise_roll(nlps_gpu* h) {
   if (!h->rolled) return 0;
-  LAUNCH_ND((k_copy_n_to_n1<2>), (k_copy_n_to_n1<3>), nblk(h->P.np), h->P, h->mats_d);
+  if (h->rolled_keep) LAUNCH_ND((k_copy_n_to_n1<2, true>), (k_copy_n_to_n1<3, true>), nblk(h->P.np), h->P, h->mats_d);
+  else LAUNCH_ND((k_copy_n_to_n1<2>), (k_copy_n_to_n1<3>), nblk(h->P.np), h->P, h->mats_d);
   HIPCHK(hipGetLastError());
-  h->rolled = false;
+  h->rolled = h->rolled_keep = false;
   return 0;
 }
 
@@ -4110,9 +4205,20 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
              "the reference has no working explicit driver that defines it (implicit path only)";
     return 1;
   }
-  if (h->P.erosion) {
+  const bool dmg = h->P.erosion != 0;  // the step with the damage hooks (nlps_gpu_set_explicit_damage)
+  if (dmg && !h->explicit_damage) {
     h->err = "nlps_gpu_explicit_step: the eigenerosion hooks exist in the level-B stages only (the reference defines them in "
              "U-Newmark-beta.c / U-Static.c; its explicit drivers are stubs)";
+    return 1;
+  }
+  if (dmg && (h->halo || h->rccl)) {
+    h->err = "nlps_gpu_explicit_step: the damage hooks inside the explicit step are built for one rank: with a halo callback or "
+             "an RCCL exchange attached, an epsilon-neighbourhood across a slab face would need ghost particles";
+    return 1;
+  }
+  if (dmg && h->deterministic) {
+    h->err = "nlps_gpu_explicit_step: the damage hooks inside the explicit step are not built for the deterministic mode (their "
+             "node runs take ranks and run starts from atomics)";
     return 1;
   }
   if (nbcc > 0 && check_step(h, step, "nlps_gpu_explicit_step")) return 1;
@@ -4181,8 +4287,9 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   // (measured: 3 % faster per step at 1 M particles -- three launches less -- and equal within the noise at 4 M and 8 M,
   // where the window loads of 17 k tiles redo the two divisions per node 16 times over: on below 2 M particles,
   // NLPS_LAZY_NODAL=2 always)
+  // (a step with the damage hooks always runs the non-folded form on the handle's stream: neither lazy nor async_form)
   const bool lazy = (h->lazy_nodal == 2 || (h->lazy_nodal == 1 && h->P.np <= 2000000)) && ride && !det && h->uniform_law >= 0 &&
-                    h->uniform_law <= NLPS_KLAW_FRICTIONAL && nbcc <= NLPS_MAX_BC_INLINE;
+                    h->uniform_law <= NLPS_KLAW_FRICTIONAL && nbcc <= NLPS_MAX_BC_INLINE && !dmg;
   // Async lists: the folded form of ONE rank (no ghost exchange, the whole grid as node window).  Nothing the list stage
   // of the next step needs comes from K5 -- the position K5 writes is x + d_dis, and d_dis is K3's -- so the search
   // leaves K5 for a kernel of its own in front of it (k_search_ahead, full ranks), and the activation and the list
@@ -4246,11 +4353,13 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   const bool one_mat = ND == 3 && h->nmats == 1 && law >= 1 && law <= 3;  // its constants by scalar loads (k3_body, UMAT)
   const dim3 grid3(h->ntw), blk3(K3_BLK);
   const double* const no_dU = nullptr;
-  auto launch_k3 = [&](int cls, bool signal) {
+  // MD = 1: the fused K3; MD = 5: its state half (the step with the damage hooks, never deterministic)
+  auto launch_k3_mode = [&](auto MODE_, int cls, bool signal) {
+    constexpr int MD = CT(MODE_);
     TileD td = tile_view(h, cls);
     const bool per_law = law < 0 && h->k3_per_law;  // one launch of the single-law kernel per law present (FILT)
     if (signal && !per_law) arm_signal(h, td, 1);
-    if (det) {  // one wave per tile and per law present, particles in list order, one slab per (tile, law)
+    if (MD == 1 && det) {  // one wave per tile and per law present, particles in list order, one slab per (tile, law)
       td.slab_n = __builtin_popcount(h->law_present);
       td.slab_slot = -1;
       for_each_law_present(h->law_present, [&](int l, bool) {
@@ -4264,19 +4373,19 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
       });
     } else if (one_mat) {
       with_law_in<1, 3>(law, [&](auto L) {
-        hipLaunchKernelGGL((k3_tile<3, CT(L), 1, false, K3_BLK, true>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
+        hipLaunchKernelGGL((k3_tile<3, CT(L), MD, false, K3_BLK, true>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
                            h->prm, h->gstatus_d, no_dU);
       });
     } else if (law >= 0) {
       with_nd(ND, [&](auto D) {
         with_law(law, [&](auto L) {
-          hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 1>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
+          hipLaunchKernelGGL((k3_tile<CT(D), CT(L), MD>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
                              h->gstatus_d, no_dU);
         });
       });
     } else if (!per_law) {  // several laws, many mixed tiles: the kernel that dispatches on the law at run time
       with_nd(ND, [&](auto D) {
-        hipLaunchKernelGGL((k3_tile<CT(D), -1, 1>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
+        hipLaunchKernelGGL((k3_tile<CT(D), -1, MD>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
                            h->gstatus_d, no_dU);
       });
     } else {  // only the last launch releases the exchange (launches of one stream run in order)
@@ -4284,12 +4393,16 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
         if (signal && last) arm_signal(h, td, 1);
         with_nd(ND, [&](auto D) {
           with_law(l, [&](auto L) {
-            hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 1, true>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
+            hipLaunchKernelGGL((k3_tile<CT(D), CT(L), MD, true>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
                                h->prm, h->gstatus_d, no_dU);
           });
         });
       });
     }
+  };
+  auto launch_k3 = [&](int cls, bool signal) {
+    if (dmg) launch_k3_mode(ic<5>{}, cls, signal);
+    else launch_k3_mode(ic<1>{}, cls, signal);
   };
   auto launch_k3_lazy = [&](int cls, bool signal) {  // (lazy: one law, 0 .. NLPS_KLAW_FRICTIONAL)
     TileD td = tile_view(h, cls);
@@ -4390,6 +4503,40 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     forked = true;
     return 0;
   };
+  // The step with the damage hooks, between the state half of K3 (k3_tile<., ., 5>, launched by k3 above) and the nodal
+  // accelerations: the node runs of this step's closest nodes (and, once per numbering of the slots, of the snapshot's),
+  // the hook, which sets Damage_n1 (Strain_f_n1) and scales every Kirchhoff stress in place, and the force half.  All
+  // on the handle's stream, no sort, no synchronisation, no allocation (nlps_gpu_set_explicit_damage made the tables).
+  auto damage_hook_and_forces = [&]() -> int {
+    const int np = h->P.np, nn = h->g.nnodes;
+    const dim3 gp(nblk(np)), gn(nblk(nn)), blk(BLK);
+    hipLaunchKernelGGL(k_run_count<false>, gp, blk, 0, h->stream, h->P, nn, h->xrun_cnt_d.get(), h->xrun_rank_d.get(), h->xrun_cursor_d.get());
+    hipLaunchKernelGGL(k_run_first, gn, blk, 0, h->stream, nn, h->xrun_cnt_d.get(), h->xrun_cursor_d.get(), h->xrun_first_d.get(), h->xrun_last_d.get());
+    hipLaunchKernelGGL(k_run_fill<false>, gp, blk, 0, h->stream, h->P, nn, (const int*)h->xrun_first_d.get(), (const int*)h->xrun_rank_d.get(),
+                       h->xrun_sorted_d.get());
+    if (h->P.softening) {
+      double* T0 = h->gather_tmp.get();  // [npad] scratch of the re-sort, idle here
+      LAUNCH_ND((k_soften_pass1<2>), (k_soften_pass1<3>), nblk(np), h->P, h->mats_d, T0);
+      // (orig[] = the caller's index of every slot: perm_d travels with the re-sorts)
+      LAUNCH_ND((k_soften_pass2<2>), (k_soften_pass2<3>), nblk(np), h->P, h->g, h->mats_d, h->xrun_first_d, h->xrun_last_d, h->xrun_sorted_d,
+                (const uint8_t*)h->rank1_d, (const int*)h->perm_d, (const double*)T0, h->g.h);
+    } else {
+      if (!h->xrun_tables0) {  // frozen lists (Beps.c:30-36): the runs of the snapshot's closest nodes
+        hipLaunchKernelGGL(k_run_count<true>, gp, blk, 0, h->stream, h->P, nn, h->xrun_cnt_d.get(), h->xrun_rank_d.get(), h->xrun_cursor_d.get());
+        hipLaunchKernelGGL(k_run_first, gn, blk, 0, h->stream, nn, h->xrun_cnt_d.get(), h->xrun_cursor_d.get(), h->xrun_first0_d.get(),
+                           h->xrun_last0_d.get());
+        hipLaunchKernelGGL(k_run_fill<true>, gp, blk, 0, h->stream, h->P, nn, (const int*)h->xrun_first0_d.get(), (const int*)h->xrun_rank_d.get(),
+                           h->xrun_sorted0_d.get());
+        h->xrun_tables0 = true;
+      }
+      LAUNCH_ND((k_damage<2>), (k_damage<3>), nblk(np), h->P, h->g, h->mats_d, h->xrun_first_d, h->xrun_last_d, h->xrun_sorted_d,
+                h->xrun_first0_d, h->xrun_last0_d, h->xrun_sorted0_d, h->g.h);
+    }
+    LAUNCH_ND(k3f_tile<2>, k3f_tile<3>, h->ntw, h->P, h->g, h->N, tile_view(h, 0), h->gstatus_d);
+    HIPCHK(hipGetLastError());
+    return 0;
+  };
+  if (dmg && beps_snapshot(h)) return 1;  // (eigenerosion, first step: before the search moves any closest node)
   h->nodal_stale = false;
   // S1 + S2 (ev[1] is recorded between the search and the lists/Newton/P2G kernel; the nodal accumulators of
   // the node window are reset by k_step_clear inside search_and_lists)
@@ -4436,6 +4583,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     nodal_dU(0);
     if (h->timing) HIPCHK(hipEventRecord(h->ev[3], h->stream));
     k3(0);
+    if (dmg && h->P.np > 0 && damage_hook_and_forces()) return 1;
   }
   HIPCHK(hipGetLastError());
   if (h->timing) HIPCHK(hipEventRecord(h->ev[4], h->stream));
@@ -4455,6 +4603,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     if (async_form && search_next_and_fork()) return 1;
     if (h->timing) HIPCHK(hipEventRecord(h->ev[5], h->stream));
     k5(0);
+    if (dmg && h->P.np > 0) hipLaunchKernelGGL(k_damage_roll, dim3(nblk(h->P.np)), dim3(BLK), 0, h->stream, h->P);
   }
   HIPCHK(hipGetLastError());
   // (anything later on the handle's stream, from any entry of the API, is ordered behind the side work too)
@@ -4462,6 +4611,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   }  // !ov2
   h->P.flip ^= 1;  // F_n <- F_n+1, b_e,n <- b_e,n+1 by renaming
   h->rolled = true;
+  h->rolled_keep = dmg;  // (tau and W of this step are stored: k_copy_n_to_n1 must not re-make them)
   h->searched = ride;  // K5 has updated the closest nodes for the positions it wrote ...
   h->ahead = ride;     // ... and binned the particles for the next step
   h->lists_ready = forked;

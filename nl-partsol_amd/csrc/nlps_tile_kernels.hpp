@@ -871,9 +871,9 @@ static constexpr int K3_WAVES = 2;  // Hencky / Drucker-Prager need > 256 VGPRs 
 template <int ND, int LAW, int MODE>
 struct K3Waves {
   static constexpr int value = ND == 2 ? K3_WAVES_2D
-                               : ((MODE == 1 || MODE == 3) && LAW == NLPS_MAT_NEO_HOOKEAN) ? K3_WAVES_NH
-                               : ((MODE == 1 || MODE == 3) && LAW == NLPS_MAT_HENCKY)      ? K3_WAVES_HENCKY
-                               : ((MODE == 1 || MODE == 3) && LAW == NLPS_MAT_DRUCKER_PRAGER) ? K3_WAVES_DP
+                               : ((MODE == 1 || MODE == 3 || MODE == 5) && LAW == NLPS_MAT_NEO_HOOKEAN) ? K3_WAVES_NH
+                               : ((MODE == 1 || MODE == 3 || MODE == 5) && LAW == NLPS_MAT_HENCKY)      ? K3_WAVES_HENCKY
+                               : ((MODE == 1 || MODE == 3 || MODE == 5) && LAW == NLPS_MAT_DRUCKER_PRAGER) ? K3_WAVES_DP
                                                                                : K3_WAVES;
 };
 // the LDS of k3_tile, owned by the caller of k3_body (the kernels below)
@@ -906,6 +906,12 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN;
   constexpr bool RATES = (MODE == 2 || MODE == 4);
   constexpr bool SCATTER = (MODE == 1 || MODE == 3 || MODE == 4);  // the stress update and the force scatter follow the F update
+  // MODE 5, the state half of the explicit step with the damage hooks (nlps_gpu_set_explicit_damage): MODE 1 up to and
+  // including the stress update -- same gather, same passes, same lists -- and no force scatter: the damage hook scales
+  // the Kirchhoff stress between this kernel and the force half (k3f_tile).  It stores what they read: F_n+1, J (both
+  // slots), DF, tau, W, d_dis; a failed particle (Damage_n == 1) keeps its stress (U-Newmark-beta.c:1218-1224).
+  constexpr bool STATE = (MODE == 5);
+  constexpr bool STRESS = SCATTER || STATE;
   static_assert((MODE == 4) == (LAW == NLPS_KLAW_FLUID), "the rate-carrying residual is the fluid law's, and only its");
   // gather window of dU: {x,y} as one 16-B double2 per node (ds_read_b128) + z as a separate 8-B array
   // (ds_read_b64): with node strides of 16 B and 8 B the tile's 64 I0 positions hit distinct banks; a
@@ -1012,7 +1018,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
     // (requested with the particle's other operands: the constants of its material are then one load away, not two, when
     // the stress update asks for them behind the gather)
-    const int mat_idx = UMAT ? 0 : (SCATTER ? P.mat[p] : -1);
+    const int mat_idx = UMAT ? 0 : (STRESS ? P.mat[p] : -1);
     const int base = window_base<ND>(c.ijk, w0);
     NLPS_YZ_LOCALS(c);
     PH(9)
@@ -1035,7 +1041,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     // which is what lets the elastic laws run at three waves per SIMD; it costs ~350 more VALU instructions a particle.
     // (the level-B modes keep the single pass: with and without rate tensors they must give the same F bit for bit)
     // and the laws that stay at two waves per SIMD keep it too: there the second set of masked weights only costs)
-    constexpr bool TWOPASS = ND == 3 && SCATTER && K3Waves<ND, LAW, MODE>::value >= 3;
+    constexpr bool TWOPASS = ND == 3 && STRESS && K3Waves<ND, LAW, MODE>::value >= 3;
     // (measured and dropped: F_n requested between the two passes -- the moments pass touches no memory and keeps fewer
     // values alive than the gather, so the nine loads would land under it instead of in front of the F update; at 168
     // registers the nine values do not fit beside it: 40 B of scratch, K3 0.213 -> 0.217 ms)
@@ -1127,7 +1133,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
       for (int a = 0; a < ND; a++) Gx[a] = Gy[a] = Gz[a] = Hx[a] = Hy[a] = Hz[a] = 0.0;
       // DIRECT (3-D, no rate tensors): every row goes straight into the totals with its y*z weight -- 15 doubles of
       // plane partials less to keep alive (the kernel then fits three waves per SIMD), for 5 more FMAs per row
-      constexpr bool DIRECT = ND == 3 && SCATTER && LAW == NLPS_MAT_NEO_HOOKEAN;
+      constexpr bool DIRECT = ND == 3 && STRESS && LAW == NLPS_MAT_NEO_HOOKEAN;
       const double zd0 = ez5[k], zd1 = zd0 * (double)(k - 2), zd2 = zd1 * (double)(k - 2);
 #pragma unroll 5  // (as in the two-pass gather)
       for (int j = 0; j < 5; j++) {
@@ -1316,7 +1322,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     double Jn1 = det<ND>(Fn1);
     if (Jn1 <= 0.0) {
       st |= ST_JACOBIAN;  // fatal in the explicit scheme (U-Verlet.c:608-613), clamped in the implicit one
-      if (MODE != 1) Jn1 = 0.0;
+      if (MODE != 1 && !STATE) Jn1 = 0.0;
     }
     // the fused explicit step (MODE 1) keeps DF in registers: nothing reads it before the next step rewrites it, and a
     // level-B stage or a download gets it back as F_n+1 F_n^-1 from the two slots of F (k_copy_n_to_n1): 72 B per
@@ -1326,6 +1332,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     // fused step: J goes straight to its n slot (nothing reads J_n inside the step; J_n+1 = J_n is restored with the
     // roll, k_copy_n_to_n1), so K5 has no copy to make
     PF(P, MODE == 1 ? F_JN : F_JN1, pl) = Jn1;
+    if (STATE) PF(P, F_JN, pl) = Jn1;  // (K5 makes no copy: the n slot as in MODE 1, the n+1 slot for the hook's volumes)
     double dFk[(MODE == 4) ? ND * ND : 1];  // dt_F_n1, kept for the fluid stress (MODE 4)
     if (RATES) {
       double dDF[ND * ND], dFn[ND * ND], dFn1[ND * ND], zz;
@@ -1355,7 +1362,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
         for (int q = 0; q < ND * ND; q++) dFk[q % ((MODE == 4) ? ND * ND : 1)] = dFn1[q];
       }
     }
-    if (!SCATTER) {
+    if (!STRESS) {
       if (st) {
         atomicOr(&P.status[pl], st);
         atomicOr(gstatus, st);
@@ -1363,9 +1370,27 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
       continue;
     }
     // (the density update rho <- rho / det DF of U-Verlet.c:630-632 costs no traffic: rho J is invariant, F_RHOJ)
-    if (MODE == 1) {
+    if (MODE == 1 || STATE) {
 #pragma unroll
       for (int a = 0; a < ND; a++) PF(P, F_DDIS + a, pl) = U[a] * Zinv;  // d_dis_p = sum N dU (used by K5)
+    }
+    if constexpr (STATE) {
+      if (PF(P, F_DMG, pl) == 1.0) {  // failed particle: W = 0, stress and internal variables as they are (k_stress)
+        PF(P, F_W, pl) = 0.0;
+        const int lw = (LAW >= 0) ? LAW : mats[mat_idx].type;
+        if (lw != NLPS_MAT_NEO_HOOKEAN && lw != NLPS_MAT_HENCKY) {  // (b_e rolls by renaming: the slot this step leaves as b_e,n)
+#pragma unroll
+          for (int q = 0; q < ((ND == 2) ? 5 : 9); q++) PF(P, fBEN1(P) + q, pl) = PF(P, fBEN(P) + q, pl);
+        }
+      } else {
+        double tau_s[ND * ND];  // (internal variables to their n slots as in MODE 1, tau and W stored for every law)
+        st |= stress_update<ND, LAW, false, (LAW == NLPS_KLAW_FRICTIONAL), true, true>(P, pl, mats, prm, Fn1, DF, Jn1, tau_s, mat_idx);
+      }
+      if (st) {
+        atomicOr(&P.status[pl], st);
+        atomicOr(gstatus, st);
+      }
+      continue;
     }
     double tau[ND * ND], B[ND * ND];
     // (MODE 3: C_ep kept for the tangent that may follow, everything to the n+1 slots)
@@ -1540,6 +1565,100 @@ __global__ __launch_bounds__(K3_BLK, (K3Waves<ND, LAW, 1>::value)) void k3_tile_
   if (!tile_work_item(td, tw)) return;
   const L lds{dvxy, dvz, duxy, duz, fac, sel, &nsel, wcnt};
   k3_body<ND, LAW, 1, false, K3_BLK, UMAT>(P, g, N, td, mats, prm, gstatus, nullptr, tw, nbnd, lds, &ln.fs);
+}
+
+// The force half of the explicit step with the damage hooks (nlps_gpu_set_explicit_damage): -f_int of every particle
+// from the STORED Kirchhoff stress -- scaled by the damage hook since k3_tile<., ., 5> wrote it -- and DF, into the
+// nodal forces.  K3's scatter in K3's shape: the padded accumulator window (NWA, rows of 12), lds_add, the canonical
+// lists, force_operator with sign -1, one flush per tile; the LME factors are rebuilt from the particle's stored x,
+// lambda, beta and masks (load_lme, as K3's RELOAD path does), J^-1 and Z^-1 from their moments.  One rank, atomic
+// flush: no slabs, no boundary signal.
+template <int ND>
+__global__ __launch_bounds__(K3_BLK, 2) void k3f_tile(PView P, GridD g, NView N, TileD td, int* __restrict__ gstatus) {
+  NLPS_FP_CONTRACT
+  constexpr int KN = Lme<ND>::KN, WA = TileCfg<ND>::WA, PSA = TileCfg<ND>::PSA, NWA = TileCfg<ND>::NWA;
+  __shared__ double fac[ND * NWA];
+  TileWork tw;
+  if (!tile_work_item(td, tw)) return;
+  const int tile = tw.tile, cnt = td.count[tile];
+  int w0[3];
+  tile_origin<ND>(td, tile, w0);
+  for (int idx = threadIdx.x; idx < ND * NWA; idx += K3_BLK) fac[idx] = 0.0;
+  __syncthreads();
+  const int start = td.start[tile];
+  for (int s = threadIdx.x; s < cnt; s += K3_BLK) {
+    const int p = td.order[start + s];
+    Lme<ND> c;
+    double lam[ND], beta;
+    if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
+    double Zinv, r[ND], J[ND * ND], Jm1[ND * ND], tau[ND * ND], DF[ND * ND], B[ND * ND], z;
+    lme_moments_h<ND>(c, Zinv, r, J);
+    load_block<ND>(P, F_TAU, p, tau, z);
+    load_block<ND>(P, F_DF, p, DF, z);
+    if (!(inverse<ND>(Jm1, J) && force_operator<ND>(B, tau, DF, Jm1, PF(P, F_VOL0, p), -1.0))) {
+      atomicOr(&P.status[p], ST_JACOBIAN);
+      atomicOr(gstatus, ST_JACOBIAN);
+      continue;
+    }
+    NLPS_YZ_LOCALS(c);
+    (void)ly5;
+    (void)lz5;
+    // -f_A = p_A * (B l_A) with l = a - h u:  B l = B a - h (B[.][x] u_i + B[.][y] v_j + B[.][z] w_k)   (as k3_body)
+    const double hx = c.lx[2] - c.lx[3];
+    const double al[3] = {c.lx[2], c.ly[2], (ND == 3) ? c.lz[2 % KN] : 0.0};
+    double Ba[ND], hB[ND * ND];
+#pragma unroll
+    for (int a = 0; a < ND; a++) {
+      double v = 0.0;
+#pragma unroll
+      for (int mm = 0; mm < ND; mm++) {
+        v = fma(B[a * ND + mm], al[mm], v);
+        hB[a * ND + mm] = -hx * B[a * ND + mm];
+      }
+      Ba[a] = v;
+    }
+    const int basea = window_base_a<ND>(c.ijk, w0);
+#pragma unroll 1
+    for (int k = 0; k < KN; k++) {
+      const unsigned pb = plane_bits<ND>(c, k);
+      const int basek = basea + (ND == 3 ? PSA * (k - 2) : 0);
+      const double wz = Zinv * ez5[k];
+      const double ck = (double)(k - 2);
+      double cz[ND];
+#pragma unroll
+      for (int a = 0; a < ND; a++) cz[a] = (ND == 3) ? fma(hB[a * ND + (2 % ND)], ck, Ba[a]) : Ba[a];
+      unsigned pbs = pb << 7;  // pop_member: bit 24 (j = 4, i = 4) first
+#pragma unroll
+      for (int j = 4; j >= 0; j--) {
+        const double w = wz * ey5[j];
+        double cr[ND];
+#pragma unroll
+        for (int a = 0; a < ND; a++) cr[a] = fma(hB[a * ND + 1], (double)(j - 2), cz[a]);
+#pragma unroll
+        for (int i = 4; i >= 0; i--)
+          if (pop_member(pbs)) {
+            const int li = basek + (i - 2) + WA * (j - 2);
+            const double we = w * c.ex[i];
+#pragma unroll
+            for (int a = 0; a < ND; a++) lds_add(&fac[a * NWA + li], we * fma(hB[a * ND + 0], (double)(i - 2), cr[a]));
+          }
+      }
+    }
+  }
+  __syncthreads();
+  if (ND == 3) {
+    window_flush3<ND, K3_BLK>(g, w0, fac, N.force);
+  } else {
+    for (int qq = threadIdx.x; qq < NWA * ND; qq += K3_BLK) {
+      const int f = qq % ND, idx = qq / ND;
+      const double v = fac[f * NWA + idx];
+      if (v != 0.0) {
+        bool in;
+        const int node = window_node_a<ND>(g, w0, idx, in);
+        if (in) atomic_add_f64(N.force + (size_t)node * ND + f, v);
+      }
+    }
+  }
 }
 
 // Sums, for every node of two node ranges, the window slabs of the tiles whose window holds the node (<= 2 per axis)

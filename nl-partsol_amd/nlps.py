@@ -105,7 +105,7 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_lumped_mass", "nlps_gpu_nodal_field_n", "nlps_gpu_compatibility", "nlps_gpu_constitutive",
            "nlps_gpu_internal_forces", "nlps_gpu_nodal_traction_forces", "nlps_gpu_roll_state", "nlps_gpu_update_kinetics",
            "nlps_gpu_explicit_step", "nlps_gpu_num_active", "nlps_gpu_explicit_nodal", "nlps_gpu_set_halo_exchange",
-           "nlps_gpu_resort", "nlps_gpu_set_resort_interval", "nlps_gpu_set_adaptive_resort", "nlps_gpu_set_law_launch_mode", "nlps_gpu_set_deterministic",
+           "nlps_gpu_resort", "nlps_gpu_set_resort_interval", "nlps_gpu_set_adaptive_resort", "nlps_gpu_set_law_launch_mode", "nlps_gpu_set_deterministic", "nlps_gpu_set_explicit_damage",
            "nlps_gpu_rccl_unique_id", "nlps_gpu_rccl_attach", "nlps_gpu_rccl_attach_comm", "nlps_gpu_rccl_detach",
            "nlps_gpu_rccl_reduce", "nlps_gpu_rccl_info", "nlps_gpu_rccl_migrate", "nlps_gpu_rccl_selftest_migrate", "nlps_gpu_rccl_selftest_exchange", "nlps_gpu_touched_layers", "nlps_gpu_set_node_window", "nlps_gpu_set_ghost_bands",
            "nlps_gpu_form_initial_guess", "nlps_gpu_nodal_kinetic_increments", "nlps_gpu_nodal_inertial_forces",
@@ -142,6 +142,7 @@ def lib():
         L.nlps_gpu_set_resort_interval.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_set_law_launch_mode.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_set_deterministic.argtypes = [C.c_void_p, C.c_int]
+        L.nlps_gpu_set_explicit_damage.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_rccl_unique_id.argtypes = [C.c_void_p]
         L.nlps_gpu_rccl_attach.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _ip, _ip, C.c_int]
         L.nlps_gpu_rccl_attach_comm.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _ip, _ip, C.c_int]
@@ -553,6 +554,11 @@ class Solver:
 
     def set_deterministic(self, on=True):
         self._chk(self.L.nlps_gpu_set_deterministic(self.h, 1 if on else 0))
+
+    def set_explicit_damage(self, on=True):
+        """The eigenerosion / eigensoftening hooks inside explicit_step (off by default: the step refuses a damage cloud);
+        the definition of such a step is in include/nlps_gpu.h."""
+        self._chk(self.L.nlps_gpu_set_explicit_damage(self.h, 1 if on else 0))
 
     def touched_layers(self):
         lo, hi = C.c_int(0), C.c_int(0)
