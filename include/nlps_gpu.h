@@ -315,10 +315,26 @@ int nlps_gpu_rccl_selftest_exchange(nlps_gpu *h, void *dptr, int nfield, int ele
  * holds Matsuoka-Nakai / Lade-Duncan or Newtonian-Fluid-Compressible: the dispatch kernel does not hold those laws. */
 int nlps_gpu_set_law_launch_mode(nlps_gpu *h, int mode);
 
-/* Run-to-run bit-reproducible results ("race detection"): with on != 0 every nodal sum of the fused
- * explicit step is accumulated in a FIXED order -- the per-tile particle lists are sorted, every wave accumulates into
- * a window of its own, the windows and the tiles are combined in index order (no floating-point atomics between
- * workgroups).  Slower than the default path (atomic accumulation in arrival order); same results to rounding. */
+/* Run-to-run bit-reproducible results ("race detection"): with on != 0 every nodal sum is accumulated in a
+ * FIXED order -- the per-tile particle lists are sorted exactly, one wave per tile accumulates its list into a window of
+ * its own, the windows leave the workgroup as plain copies (slabs) and are combined per node in index order (no
+ * floating-point atomics between workgroups).  Slower than the default path (atomic accumulation in arrival order);
+ * same results to rounding.  Two runs from the same inputs then agree bit for bit, on one rank, with host or device
+ * vectors, in:
+ *   - nlps_gpu_explicit_step (the fused explicit step);
+ *   - the implicit path: nlps_gpu_lumped_mass, nlps_gpu_nodal_field_n, nlps_gpu_internal_forces, the traction sums
+ *     (nlps_gpu_nodal_traction_forces and the loads of the residual: one wave over the contour particles in the
+ *     caller's order), nlps_gpu_lagrangian_evaluation (fused and NLPS_LAGR_SEPARATE), nlps_gpu_tangent_apply,
+ *     nlps_gpu_tangent_block_diagonal, and what is built from them: nlps_gpu_tangent_solve, nlps_gpu_newton_solve,
+ *     nlps_gpu_newmark_step (their norms, dot products and step lengths add per-block partials in a fixed order).
+ * The mode may be switched between calls.  Tile lists that a search built with the mode off are not exact; the first
+ * implicit-path call made with the mode on sorts them exactly before it sums over them (nothing to do for the caller).
+ * The window slabs are allocated at the first call that needs them: 12 x 800 (3-D, per tile of 4^3 closest nodes) or
+ * 8 x 400 (2-D, per tile of 16^2) doubles per tile of the grid.
+ * Outside the contract, on their usual (atomic) path in every mode: the assembled tangent (nlps_gpu_tangent_assemble /
+ * nlps_gpu_tangent_coo); clouds created with driver_eigenerosion / driver_eigensoftening (the damage hooks); handles
+ * with a halo-exchange callback or an RCCL exchange attached; the folded, lazy and async-lists forms of the explicit
+ * step, which the mode does not use. */
 int nlps_gpu_set_deterministic(nlps_gpu *h, int on);
 
 /* ------------------------------------------------------------------ per-dof updates of the implicit driver (a21)
@@ -424,8 +440,8 @@ int nlps_gpu_set_tangent_alpha4(nlps_gpu *h, double alpha_4);
  * (nlps_gpu_resort, periodic or adaptive), a migration, nlps_gpu_update_kinetics, nlps_gpu_roll_state and
  * nlps_gpu_explicit_step.  Several ranks: the scattered K x (and the blocks) pass the halo exchange hook before the
  * nodal epilogue, like the residual call; every rank's x must agree on the shared nodes, as its dU does.
- * Sums use floating-point atomics in every mode (deterministic mode included, like the level-B stage calls): results
- * agree with the assembled matrix times x up to summation order. */
+ * Sums use floating-point atomics, so results agree with the assembled matrix times x up to summation order; in
+ * deterministic mode (nlps_gpu_set_deterministic, one rank) both calls sum in a fixed order and repeat bit for bit. */
 int nlps_gpu_tangent_operator(nlps_gpu *h, double alpha_1, const double *lumped_mass, int apply_dirichlet, size_t *bytes);
 int nlps_gpu_tangent_apply(nlps_gpu *h, const double *x, double *y);
 int nlps_gpu_tangent_block_diagonal(nlps_gpu *h, double *blocks);

@@ -1765,8 +1765,11 @@ struct nlps_gpu {
   DevBuf<int> xrun_first0_d, xrun_last0_d, xrun_sorted0_d;
   bool xrun_tables0 = false;
   bool rolled_keep = false;  // `rolled`, and the last step stored tau and W itself (k_copy_n_to_n1 KEEP)
-  DevBuf<double> slab_d;    // P2G window slabs [ntiles][slab_n][1+ND][NW] (TileD::slab), deterministic mode only
+  DevBuf<double> slab_d;    // P2G window slabs [ntiles][slab_n][fields][NWA] (TileD::slab), deterministic mode only: sized by the
+                            // explicit step and, for the largest user of the implicit path, by det_prepare
   bool deterministic = false;
+  bool lists_exact = false;  // the canonical tile lists are the exact ones (k_tile_order<., true>): a function of the particle
+                             // arrays alone.  Lists built outside the deterministic mode take their ranks from binning atomics.
   int band_lo = -(1 << 30), band_hi = 1 << 30;  // ghost bands: layers <= band_lo and >= band_hi are shared with neighbours
   int overlap = 0;          // halo exchanges: 0 blocking in place; 1 behind the interior tiles of the NEXT stage (split
                             // launches, two-phase callback); 2 behind the interior tiles of the SAME launch (library RCCL only)
@@ -3618,6 +3621,43 @@ static int materialise_nodal(nlps_gpu* h) {
   return 0;
 }
 
+// Deterministic mode on the implicit path (nlps_gpu_set_deterministic): the level-B scatters, the fused residual and the
+// matrix-free tangent run one wave per tile over the exact canonical lists and leave their windows as slabs, which
+// k_slab_gather sums per node in a fixed order.  One rank without a halo callback; a cloud with the damage hooks keeps
+// the atomic path.
+static bool det_implicit(const nlps_gpu* h) { return h->deterministic && !h->halo && !h->rccl && !h->P.erosion && h->P.np > 0; }
+// What a deterministic implicit-path call needs before its tile kernel: the exact lists and room for its slabs.  Lists
+// that a search built with the mode off hold the same particles per tile, in an order that depends on binning
+// atomics: the exact per-tile sort is run over them here (it reads the binned lists, whose CONTENT per tile is
+// exact), so no sum ever runs over a non-exact list.  An exact list is a valid canonical list for every other kernel.
+static int det_prepare(nlps_gpu* h, const char* who) {
+  const int ND = h->nd;
+  if (!h->lists_exact) {
+    if (!h->binned || !h->order2_d) {
+      h->err = std::string(who) + ": deterministic mode needs tile lists: call nlps_gpu_local_search() first";
+      return 1;
+    }
+    LAUNCH_ND_BLK((k_tile_order<2, true>), (k_tile_order<3, true>), h->ntw, 256, h->P, h->g, tile_view(h, 0), (const int*)h->order_d,
+                  h->order2_d);
+    HIPCHK(hipGetLastError());
+    h->lists_exact = true;
+  }
+  // fields per window of the largest user: the explicit step (K2: 1 + d, K3: d per law, sized for four), the block
+  // diagonal (d^2), the nodal field (2 d) and the residual (d per law present)
+  const size_t NWs = ND == 3 ? TileCfg<3>::NWA : TileCfg<2>::NWA;
+  const size_t fields = std::max<size_t>(std::max<size_t>(4 * ND, ND * ND), (size_t)ND * __builtin_popcount(h->law_present));
+  return reserve(h, who, h->slab_d, (size_t)h->ntiles * fields * NWs, "the window slabs of the deterministic mode");
+}
+// out[node][NF] of the whole node window from the slabs (slab_n per tile); nodes outside the window keep what they hold
+#define DET_GATHER(NF2, NF3, slab_count, out)                                                                              \
+  do {                                                                                                                     \
+    const NodeRanges r_ = node_ranges(h, 0);                                                                               \
+    TileD tg_ = tile_view(h, 0);                                                                                           \
+    tg_.slab_n = (slab_count);                                                                                             \
+    if (r_.an + r_.bn > 0)                                                                                                 \
+      LAUNCH_ND((k_slab_gather<2, NF2>), (k_slab_gather<3, NF3>), nblk(r_.an + r_.bn), r_.a0, r_.an, r_.b0, r_.bn, h->g, tg_, (out)); \
+  } while (0)
+
 // arms the boundary-done signal of a single-launch stage (overlap mode 2): stage 0 = K2, 1 = K3
 static void arm_signal(nlps_gpu* h, TileD& td, int stage) {
   RcclHalo* R = h->rccl;
@@ -3697,6 +3737,7 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
   const bool ready = ahead && p2g && h->lists_ready;
   h->lists_ready = false;
   if (ready) adopt_ready_lists(h);
+  if (ready) h->lists_exact = false;
   h->searched = h->ahead = false;  // consumed
   if (!ready) {
   const bool clear_in_dilate = ahead && p2g;  // nothing but the nodal accumulators to reset: k_dilate_scan does it
@@ -3734,6 +3775,7 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
     LAUNCH_ND_BLK((k_tile_order<2, true>), (k_tile_order<3, true>), h->ntw, 256, h->P, h->g, tile_view(h, 0), (const int*)h->order_d,
                   h->order2_d);
   }
+  h->lists_exact = !node_lists(h);
   HIPCHK(hipGetLastError());
   }  // !ready
   if (h->timing) HIPCHK(hipEventRecord(h->ev[1], h->stream));
@@ -3941,7 +3983,12 @@ extern "C" int nlps_gpu_lumped_mass(nlps_gpu* h, double* M) {
   if (need_masks(h, "nlps_gpu_lumped_mass")) return 1;
   int ND = h->nd;
   HIPCHK(hipMemsetAsync(h->gridA, 0, (size_t)h->g.nnodes * sizeof(double), h->stream));
-  {
+  if (det_implicit(h)) {
+    if (det_prepare(h, "nlps_gpu_lumped_mass")) return 1;
+    TileD td = tile_view(h);
+    LAUNCH_ND_BLK((kb_p2g_tile<2, 0, 64>), (kb_p2g_tile<3, 0, 64>), h->ntw, 64, h->P, h->g, td, h->gridA);
+    DET_GATHER(1, 1, 1, h->gridA);
+  } else {
     TileD td = tile_view(h);
     LAUNCH_ND((kb_p2g_tile<2, 0>), (kb_p2g_tile<3, 0>), h->ntw, h->P, h->g, td, h->gridA);
   }
@@ -3954,7 +4001,12 @@ extern "C" int nlps_gpu_nodal_field_n(nlps_gpu* h, double* V, double* A, const d
   if (need_masks(h, "nlps_gpu_nodal_field_n")) return 1;
   int ND = h->nd;
   HIPCHK(hipMemsetAsync(h->gridA, 0, (size_t)h->g.nnodes * 2 * ND * sizeof(double), h->stream));
-  {
+  if (det_implicit(h)) {
+    if (det_prepare(h, "nlps_gpu_nodal_field_n")) return 1;
+    TileD td = tile_view(h);
+    LAUNCH_ND_BLK((kb_p2g_tile<2, 1, 64>), (kb_p2g_tile<3, 1, 64>), h->ntw, 64, h->P, h->g, td, h->gridA);
+    DET_GATHER(4, 6, 1, h->gridA);
+  } else {
     TileD td = tile_view(h);
     LAUNCH_ND((kb_p2g_tile<2, 1>), (kb_p2g_tile<3, 1>), h->ntw, h->P, h->g, td, h->gridA);
   }
@@ -4049,7 +4101,12 @@ extern "C" int nlps_gpu_internal_forces(nlps_gpu* h, double* R) {
   }
   if (materialise_nodal(h)) return 1;  // (the forces of the last explicit step are about to go)
   HIPCHK(hipMemsetAsync(h->N.force, 0, (size_t)h->g.nnodes * ND * sizeof(double), h->stream));
-  {
+  if (det_implicit(h)) {
+    if (det_prepare(h, "nlps_gpu_internal_forces")) return 1;
+    TileD td = tile_view(h);
+    LAUNCH_ND_BLK((kb_fint_tile<2, 64>), (kb_fint_tile<3, 64>), h->ntw, 64, h->P, h->g, td, h->N.force, h->gstatus_d);
+    DET_GATHER(2, 3, 1, h->N.force);
+  } else {
     TileD td = tile_view(h);
     LAUNCH_ND(kb_fint_tile<2>, kb_fint_tile<3>, h->ntw, h->P, h->g, td, h->N.force, h->gstatus_d);
   }
@@ -4084,6 +4141,36 @@ __global__ void k_traction(PView P, GridD g, int n, const int* __restrict__ ids,
         const int node = c.I0 + c.node_offset(g, i, j, k + (ND == 3 ? 0 : 2));
         for (int a = 0; a < ND; a++) atomic_add_f64(out + (size_t)node * ND + a, -Npa * T[(size_t)e * ND + a] * a0);
       }
+}
+
+// Deterministic form (nlps_gpu_set_deterministic): ONE wave walks the contour particles in the caller's order, its lanes
+// over the 5^d stencil slots of the particle -- distinct nodes, so a plain read-add-write per member -- and meets
+// between two particles: every nodal sum is added in list order.  Contours are surface sets; no sort is needed.
+template <int ND>
+__global__ __launch_bounds__(64) void k_traction_serial(PView P, GridD g, int n, const int* __restrict__ ids,
+                                                        const int* __restrict__ inv, const double* __restrict__ T,
+                                                        const double* __restrict__ A0, double thickness, double* out) {
+  constexpr int KN = Lme<ND>::KN, NS = 25 * KN;
+  for (int e = 0; e < n; e++) {  // uniform
+    const int p = inv[ids[e]];
+    Lme<ND> c;
+    double lam[ND], beta;
+    if (load_lme<ND>(P, g, p, c, lam, beta)) {  // (every lane holds the particle's factors)
+      const double a0 = A0 ? A0[e] : PF(P, F_VOL0, p) / thickness;
+      const double zinv = lme_zinv<ND>(c);
+      for (int m = threadIdx.x; m < NS; m += 64) {
+        if (!c.on(m)) continue;
+        const int i = m % 5, j = (m / 5) % 5, k = m / 25;
+        const double Npa = c.ex[i] * c.ey[j] * (ND == 3 ? c.ez[k % KN] : 1.0) * zinv;
+        const int node = c.I0 + c.node_offset(g, i, j, k + (ND == 3 ? 0 : 2));
+        for (int a = 0; a < ND; a++) {
+          double* o = out + (size_t)node * ND + a;
+          *o = *o + (-Npa * T[(size_t)e * ND + a] * a0);
+        }
+      }
+    }
+    __syncthreads();  // the stores of this particle are done before the next one reads the same nodes
+  }
 }
 
 // the traction sums of the Neumann contours in grid numbering: out[nnodes][ND] = - sum N_pA T A0_p (zeroed first);
@@ -4135,7 +4222,10 @@ static int traction_to_grid(nlps_gpu* h, const char* who, double* out, const nlp
   if (ND == 3) HIPCHK(hipMemcpyAsync(A_d, A.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_inverse_perm, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->perm_d, np, h->sval_d);
   HIPCHK(hipMemsetAsync(out, 0, (size_t)h->g.nnodes * ND * sizeof(double), h->stream));
-  LAUNCH_ND(k_traction<2>, k_traction<3>, nblk(n), h->P, h->g, n, ids_d, h->sval_d, T_d, A_d, thickness, out);
+  if (det_implicit(h))
+    LAUNCH_ND_BLK(k_traction_serial<2>, k_traction_serial<3>, 1, 64, h->P, h->g, n, ids_d, h->sval_d, T_d, A_d, thickness, out);
+  else
+    LAUNCH_ND(k_traction<2>, k_traction<3>, nblk(n), h->P, h->g, n, ids_d, h->sval_d, T_d, A_d, thickness, out);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));  // (the host vectors above are about to go)
   return 0;
@@ -4914,9 +5004,31 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
     hipLaunchKernelGGL(k_expand_reset, dim3(nblk(h->g.nnodes)), dim3(BLK), 0, h->stream, h->N.dU, u, h->n2m_d, h->g.nnodes, ND,
                        h->N.force, h->n0, h->nwn);
   if (h->timing) HIPCHK(hipEventRecord(h->ev[2], h->stream));
-  {
+  if (det_implicit(h)) {
+    // deterministic mode: one wave per tile and per law present over the exact lists (ordered compaction), one slab per
+    // (tile, law) -- a tile without a particle of the law writes zeros --, then the fixed-order sum into N.force
+    if (det_prepare(h, "nlps_gpu_lagrangian_evaluation")) return 1;
     TileD td = tile_view(h);
-    td.slab = nullptr;  // (level-B semantics: atomics also in deterministic mode, like kb_fint_tile)
+    td.slab_n = __builtin_popcount(h->law_present);
+    td.slab_slot = -1;
+    for_each_law_present(h->law_present, [&](int l, bool) {
+      td.slab_slot++;
+      with_nd(ND, [&](auto D) {
+        if (l == NLPS_KLAW_FLUID) {
+          hipLaunchKernelGGL((k3_tile<CT(D), NLPS_KLAW_FLUID, 4, true, 64>), dim3(h->ntw), dim3(64), 0, h->stream, h->P, h->g, h->N,
+                             td, h->mats_d, h->prm, h->gstatus_d, (const double*)h->gridB.get());
+          return;
+        }
+        with_law(l, [&](auto L) {
+          hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 3, true, 64>), dim3(h->ntw), dim3(64), 0, h->stream, h->P, h->g, h->N, td,
+                             h->mats_d, h->prm, h->gstatus_d, (const double*)nullptr);
+        });
+      });
+    });
+    DET_GATHER(2, 3, td.slab_n, h->N.force);
+  } else {
+    TileD td = tile_view(h);
+    td.slab = nullptr;  // (the atomic flush: handles outside the deterministic implicit path, see det_implicit)
     const dim3 grid(h->ntw), blk(K3_BLK);
     const int law = h->uniform_law;
     if (law < 0) {
@@ -5168,7 +5280,13 @@ static int tanop_product(nlps_gpu* h, const double* v, double* y, const KspPc* p
     LAUNCH_ND((k_tanop_expand<2>), (k_tanop_expand<3>), nblk(nn), nn, (const int*)h->n2m_d, d2m, v, xg);
     HIPCHK(hipMemsetAsync(yg, 0, (size_t)nn * ND * sizeof(double), h->stream));
   }
-  if (h->top_np > 0) {
+  if (h->top_np > 0 && det_implicit(h)) {
+    if (det_prepare(h, "nlps_gpu_tangent_apply")) return 1;
+    const TileD td = tile_view(h);
+    LAUNCH_ND_BLK((k_tanop_apply<2, 64>), (k_tanop_apply<3, 64>), h->ntw, 64, h->P, h->g, td, (const double*)h->top_d, h->top_np,
+                  (const double*)xg, yg);
+    DET_GATHER(2, 3, 1, yg);
+  } else if (h->top_np > 0) {
     const TileD td = tile_view(h);
     LAUNCH_ND(k_tanop_apply<2>, k_tanop_apply<3>, h->ntw, h->P, h->g, td, (const double*)h->top_d, h->top_np, (const double*)xg, yg);
   }
@@ -5204,7 +5322,14 @@ extern "C" int nlps_gpu_tangent_apply(nlps_gpu* h, const double* x, double* y) {
 static int tanop_bdiag(nlps_gpu* h, double* out) {
   const int ND = h->nd, E = ND * ND, nn = h->g.nnodes;
   int st = hipMemsetAsync(h->top_g, 0, (size_t)nn * E * sizeof(double), h->stream) != hipSuccess;
-  if (!st && h->top_np > 0) {
+  if (!st && h->top_np > 0 && det_implicit(h)) {
+    if (det_prepare(h, "nlps_gpu_tangent_block_diagonal")) return 1;
+    const TileD td = tile_view(h);
+    LAUNCH_ND_BLK((k_tanop_bdiag<2, 64>), (k_tanop_bdiag<3, 64>), h->ntw, 64, h->P, h->g, td, (const double*)h->top_d, h->top_np,
+                  h->top_g.get());
+    DET_GATHER(4, 9, 1, h->top_g.get());
+    st = hipGetLastError() != hipSuccess;
+  } else if (!st && h->top_np > 0) {
     const TileD td = tile_view(h);
     LAUNCH_ND(k_tanop_bdiag<2>, k_tanop_bdiag<3>, h->ntw, h->P, h->g, td, (const double*)h->top_d, h->top_np, h->top_g);
     st = hipGetLastError() != hipSuccess;

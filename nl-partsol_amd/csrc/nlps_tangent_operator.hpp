@@ -12,8 +12,8 @@
 //
 // k_tanop_setup writes Dh per particle, structure of arrays [d^4][np] (the apply reads it coalesced in tile order);
 // k_tanop_apply and k_tanop_bdiag are tile-binned like kb_fint_tile: an LDS gather window of x in grid numbering, the
-// LME factors regenerated in registers, an LDS accumulator window flushed with f64 atomics (level-B semantics: atomics
-// in every mode, run-to-run summation order may differ).  With gn_B = -N_B Jm1 l_B (l_B = x_B - x_p):
+// LME factors regenerated in registers, an LDS accumulator window flushed with f64 atomics (run-to-run summation order
+// may differ) or, in deterministic mode, copied to window slabs that k_slab_gather sums in a fixed order.  With gn_B = -N_B Jm1 l_B (l_B = x_B - x_p):
 //   G = -Jm1 H,  H[b][j] = sum_B N_B l_B[b] x_B[j]     and     (K x)_A[i] = N_A sum_b l_A[b] Q[i][b],  Q = -(Jm1^T T)^T,
 // so both ends are separable sums over the stencil rows.
 #pragma once
@@ -195,8 +195,10 @@ __global__ __launch_bounds__(TANOP_SETUP_NT) void k_tanop_setup(PView P, GridD g
 }
 
 // y_grid += K x_grid over the particles of one tile (x: grid numbering [nnodes][d], Dirichlet dofs already zeroed)
-template <int ND>
-__global__ __launch_bounds__(BLK) void k_tanop_apply(PView P, GridD g, TileD td, const double* __restrict__ Dh, int ld,
+// NT = 64 (here and in k_tanop_bdiag): the deterministic form -- one wave per tile over the exact canonical list, the
+// accumulator window copied to the tile's slab (window_to_slab), y_grid written by k_slab_gather; y is then unused
+template <int ND, int NT = BLK>
+__global__ __launch_bounds__(NT) void k_tanop_apply(PView P, GridD g, TileD td, const double* __restrict__ Dh, int ld,
                                                      const double* __restrict__ x, double* __restrict__ y) {
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN, E = ND * ND;
   __shared__ double win[NW * ND];  // x of the window, node-major
@@ -207,7 +209,7 @@ __global__ __launch_bounds__(BLK) void k_tanop_apply(PView P, GridD g, TileD td,
   const int cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
-  for (int idx = threadIdx.x; idx < NW; idx += BLK) {
+  for (int idx = threadIdx.x; idx < NW; idx += NT) {
     bool in;
     const int node = window_node<ND>(g, w0, idx, in);
 #pragma unroll
@@ -218,8 +220,8 @@ __global__ __launch_bounds__(BLK) void k_tanop_apply(PView P, GridD g, TileD td,
   }
   __syncthreads();
   const int start = td.start[tile];
-  for (int s = threadIdx.x; s < cnt; s += BLK) {
-    const int p = td.order_m[start + s];
+  for (int s = threadIdx.x; s < cnt; s += NT) {
+    const int p = (NT == 64) ? td.order[start + s] : td.order_m[start + s];
     Lme<ND> c;
     double lam[ND], beta;
     if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
@@ -324,7 +326,11 @@ __global__ __launch_bounds__(BLK) void k_tanop_apply(PView P, GridD g, TileD td,
     }
   }
   __syncthreads();
-  for (int q = threadIdx.x; q < NW * ND; q += BLK) {
+  if constexpr (NT == 64) {
+    window_to_slab<ND, ND, NT>(td, tile, acc);
+    return;
+  }
+  for (int q = threadIdx.x; q < NW * ND; q += NT) {
     const int f = q % ND, idx = q / ND;
     const double v = acc[f * NW + idx];
     if (v != 0.0) {
@@ -336,8 +342,8 @@ __global__ __launch_bounds__(BLK) void k_tanop_apply(PView P, GridD g, TileD td,
 }
 
 // out_grid[A][i][j] += sum_p sum_mn gn_A[m] gn_A[n] Dh_p[m][n][i][j]: the diagonal blocks, d^2 accumulator fields per node
-template <int ND>
-__global__ __launch_bounds__(BLK) void k_tanop_bdiag(PView P, GridD g, TileD td, const double* __restrict__ Dh, int ld,
+template <int ND, int NT = BLK>
+__global__ __launch_bounds__(NT) void k_tanop_bdiag(PView P, GridD g, TileD td, const double* __restrict__ Dh, int ld,
                                                      double* __restrict__ out) {
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN, E = ND * ND;
   __shared__ double acc[E * NW];
@@ -347,11 +353,11 @@ __global__ __launch_bounds__(BLK) void k_tanop_bdiag(PView P, GridD g, TileD td,
   const int cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
-  for (int idx = threadIdx.x; idx < NW * E; idx += BLK) acc[idx] = 0.0;
+  for (int idx = threadIdx.x; idx < NW * E; idx += NT) acc[idx] = 0.0;
   __syncthreads();
   const int start = td.start[tile];
-  for (int s = threadIdx.x; s < cnt; s += BLK) {
-    const int p = td.order_m[start + s];
+  for (int s = threadIdx.x; s < cnt; s += NT) {
+    const int p = (NT == 64) ? td.order[start + s] : td.order_m[start + s];
     Lme<ND> c;
     double lam[ND], beta;
     if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
@@ -426,7 +432,11 @@ __global__ __launch_bounds__(BLK) void k_tanop_bdiag(PView P, GridD g, TileD td,
     }
   }
   __syncthreads();
-  for (int q = threadIdx.x; q < NW * E; q += BLK) {
+  if constexpr (NT == 64) {
+    window_to_slab<ND, E, NT>(td, tile, acc);
+    return;
+  }
+  for (int q = threadIdx.x; q < NW * E; q += NT) {
     const int f = q % E, idx = q / E;
     const double v = acc[f * NW + idx];
     if (v != 0.0) {

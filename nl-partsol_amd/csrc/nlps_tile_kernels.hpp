@@ -1485,7 +1485,10 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
   if (!SCATTER) return;
   __syncthreads();
   PH(13)
-  if (td.slab) {
+  // the one-wave residual forms (deterministic mode on the implicit path) are launched with slabs only: the atomic
+  // flush is not part of their code
+  constexpr bool SLAB_ONLY = NT == 64 && (MODE == 3 || MODE == 4);
+  if (SLAB_ONLY || td.slab) {
     double* out = td.slab + ((size_t)tile * td.slab_n + td.slab_slot) * (ND * NWA);
     for (int qq = threadIdx.x; qq < NWA * ND; qq += NT) out[qq] = fac[qq];
     return;
@@ -1868,6 +1871,27 @@ __global__ __launch_bounds__(K5_BLK) void k5_tile_lazy(PView P, GridD g, NView N
 // Level-B stage kernels in tile form (the implicit driver's stage functions)
 // ------------------------------------------------------------------------------------------------
 
+// Deterministic mode of the level-B scatters (NT = 64: one wave per tile, the exact canonical list, see
+// nlps_gpu_set_deterministic): the accumulator window leaves the workgroup as a plain copy into the slab of its tile,
+// which k_slab_gather sums per node in a fixed order.  The level-B accumulators use the gather layout (rows of W,
+// planes of PS); the slab keeps the layout k_slab_gather reads (WA / PSA), so the 3-D copy moves the 8 x 8 x 8 cells
+// (the padding slots of a slab are never read); in 2-D the two layouts are the same.  acc: [NF][NW], field-major.
+template <int ND, int NF, int NT>
+__device__ __forceinline__ void window_to_slab(const TileD& td, int tile, const double* acc) {
+  constexpr int PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW;
+  constexpr int WA = TileCfg<ND>::WA, PSA = TileCfg<ND>::PSA, NWA = TileCfg<ND>::NWA;
+  double* __restrict__ out = td.slab + ((size_t)tile * td.slab_n + td.slab_slot) * (NF * NWA);
+  if (ND == 3) {
+    for (int e = threadIdx.x; e < 512 * NF; e += NT) {
+      const int f = e >> 9, r = e & 511;
+      out[f * NWA + (r & 7) + WA * ((r >> 3) & 7) + PSA * (r >> 6)] = acc[f * NW + (r & 63) + PS * (r >> 6)];
+    }
+  } else {
+    static_assert(ND == 3 || NW == NWA, "2-D: one layout for the gather and the accumulator windows");
+    for (int q = threadIdx.x; q < NF * NW; q += NT) out[q] = acc[q];
+  }
+}
+
 // Z^-1 alone (rows of masked ex, then ey, ez)
 template <int ND>
 __device__ __forceinline__ double lme_zinv(const Lme<ND>& c) {
@@ -1894,8 +1918,9 @@ __device__ __forceinline__ double lme_zinv(const Lme<ND>& c) {
 
 // __compute_nodal_lumped_mass (MODE 0, NF = 1) and the accumulation of __get_nodal_field_n
 // (MODE 1, NF = 2d: m N v, m N a) into out[nnodes][NF]        (U-Newmark-beta.c:528-597, 615-696)
-template <int ND, int MODE>
-__global__ __launch_bounds__(BLK) void kb_p2g_tile(PView P, GridD g, TileD td, double* __restrict__ out) {
+// NT = 64: the deterministic form (window_to_slab)
+template <int ND, int MODE, int NT = BLK>
+__global__ __launch_bounds__(NT) void kb_p2g_tile(PView P, GridD g, TileD td, double* __restrict__ out) {
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN;
   constexpr int NF = MODE == 0 ? 1 : 2 * ND;
   __shared__ double acc[NF * NW];
@@ -1905,11 +1930,11 @@ __global__ __launch_bounds__(BLK) void kb_p2g_tile(PView P, GridD g, TileD td, d
   const int cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
-  for (int idx = threadIdx.x; idx < NW * NF; idx += BLK) acc[idx] = 0.0;
+  for (int idx = threadIdx.x; idx < NW * NF; idx += NT) acc[idx] = 0.0;
   __syncthreads();
   const int start = td.start[tile];
-  for (int s = threadIdx.x; s < cnt; s += BLK) {
-    const int p = td.order_m[start + s];
+  for (int s = threadIdx.x; s < cnt; s += NT) {
+    const int p = (NT == 64) ? td.order[start + s] : td.order_m[start + s];
     Lme<ND> c;
     double lam[ND], beta;
     if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
@@ -1948,7 +1973,11 @@ __global__ __launch_bounds__(BLK) void kb_p2g_tile(PView P, GridD g, TileD td, d
     }
   }
   __syncthreads();
-  for (int q = threadIdx.x; q < NW * NF; q += BLK) {
+  if constexpr (NT == 64) {
+    window_to_slab<ND, NF, NT>(td, tile, acc);
+    return;
+  }
+  for (int q = threadIdx.x; q < NW * NF; q += NT) {
     int f = q % NF, idx = q / NF;
     double v = acc[f * NW + idx];
     if (v != 0.0) {
@@ -1960,8 +1989,9 @@ __global__ __launch_bounds__(BLK) void kb_p2g_tile(PView P, GridD g, TileD td, d
 }
 
 // __nodal_internal_forces (U-Newmark-beta.c:1257-1374): +V0 tau (DF^-T grad N) from the stored tau, DF
-template <int ND>
-__global__ __launch_bounds__(BLK) void kb_fint_tile(PView P, GridD g, TileD td, double* __restrict__ force,
+// NT = 64: the deterministic form (window_to_slab)
+template <int ND, int NT = BLK>
+__global__ __launch_bounds__(NT) void kb_fint_tile(PView P, GridD g, TileD td, double* __restrict__ force,
                                                     int* __restrict__ gstatus) {
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN;
   __shared__ double fac[ND * NW];
@@ -1971,11 +2001,11 @@ __global__ __launch_bounds__(BLK) void kb_fint_tile(PView P, GridD g, TileD td, 
   const int cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
-  for (int idx = threadIdx.x; idx < NW * ND; idx += BLK) fac[idx] = 0.0;
+  for (int idx = threadIdx.x; idx < NW * ND; idx += NT) fac[idx] = 0.0;
   __syncthreads();
   const int start = td.start[tile];
-  for (int s = threadIdx.x; s < cnt; s += BLK) {
-    const int p = td.order_m[start + s];
+  for (int s = threadIdx.x; s < cnt; s += NT) {
+    const int p = (NT == 64) ? td.order[start + s] : td.order_m[start + s];
     Lme<ND> c;
     double lam[ND], beta;
     if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
@@ -2016,7 +2046,11 @@ __global__ __launch_bounds__(BLK) void kb_fint_tile(PView P, GridD g, TileD td, 
     }
   }
   __syncthreads();
-  for (int qq = threadIdx.x; qq < NW * ND; qq += BLK) {
+  if constexpr (NT == 64) {
+    window_to_slab<ND, ND, NT>(td, tile, fac);
+    return;
+  }
+  for (int qq = threadIdx.x; qq < NW * ND; qq += NT) {
     int f = qq % ND, idx = qq / ND;
     double v = fac[f * NW + idx];
     if (v != 0.0) {
