@@ -255,6 +255,31 @@ int nlps_gpu_explicit_step(nlps_gpu *h, const nlps_bcc *bcc, int nbcc, int step,
  * a slab face needs ghost particles), in deterministic mode, and for the fluid law (as above).
  * The setter returns 1 for a cloud created without either driver. */
 int nlps_gpu_set_explicit_damage(nlps_gpu *h, int on);
+/* The damage hooks inside the fused residual (clouds created with driver_eigenerosion or driver_eigensoftening).  Off by
+ * default: nlps_gpu_lagrangian_evaluation then runs the separate stages for such a cloud (nlps_gpu_compatibility,
+ * nlps_gpu_constitutive, nlps_gpu_internal_forces with its two sorts, the traction and inertial calls), exactly as before.
+ * With on != 0 -- and neither NLPS_LAGR_SEPARATE nor NLPS_LAGR_RATES in flags -- the evaluation is the fused damage form,
+ * and so are the evaluations of nlps_gpu_newton_solve and nlps_gpu_newmark_step, which call it.  What it computes, in the
+ * order of U-Newmark-beta.c:1018-1036:
+ *   1. compatibility for every particle: DF, F_n1, J_n1 from the caller's dU, J <= 0 clamped to 0 (:1137-1142);
+ *   2. the constitutive update, which skips failed particles (Damage_n == 1: W = 0, stress and the n+1 internal
+ *      variables untouched, :1218-1224, as the level-B constitutive stage does); every other particle gets tau, W, b_e,n+1,
+ *      kappa_n+1, eps_n+1 and C_ep;
+ *   3. the damage hook (:1313-1331): Damage_n1 (and Strain_f_n1) from the n state, then every Kirchhoff stress scaled in
+ *      place by 1 - Damage_n1; eigensoftening with the reference's sequential semantics (one particle after the other in
+ *      the caller's order);
+ *   4. +f_int from the scaled stress, then the traction and inertial terms, 0 on the Dirichlet dofs.
+ * The n state is never touched: the residual may be evaluated any number of times from it.  nlps_gpu_tangent_operator
+ * scales with 1 - Damage_n1 of the state the evaluation left, nlps_gpu_roll_state rolls Damage and Strain_f, as before.
+ * An evaluation runs on one rank, on the handle's stream, without sorts or allocation and with the one synchronisation
+ * every fused evaluation ends in (inside nlps_gpu_newton_solve its norm arrives with that wait).  The node runs of the
+ * hook are built at the first evaluation and reused until a call that makes the matrix-free operator stale (the list under
+ * nlps_gpu_tangent_apply).
+ * The setter allocates every table (shared with nlps_gpu_set_explicit_damage).  It returns 1, with the reason in
+ * nlps_gpu_last_error, for a cloud created without either driver, for a cloud that holds Newtonian-Fluid-Compressible
+ * (the state half is cut for the solid laws), and when a halo callback or an RCCL exchange is attached (an
+ * epsilon-neighbourhood across a slab face needs ghost particles); an evaluation returns 1 if one is attached later. */
+int nlps_gpu_set_implicit_damage(nlps_gpu *h, int on);
 /* Number of active nodes after the last search (computes Nodes2Mask on the device). */
 int nlps_gpu_num_active(nlps_gpu *h, int *nactive);
 /* Nodal results of the last explicit step in masked numbering (any pointer may be NULL).  On one GPU without a ghost
@@ -332,7 +357,8 @@ int nlps_gpu_set_law_launch_mode(nlps_gpu *h, int mode);
  * The window slabs are allocated at the first call that needs them: 12 x 800 (3-D, per tile of 4^3 closest nodes) or
  * 8 x 400 (2-D, per tile of 16^2) doubles per tile of the grid.
  * Outside the contract, on their usual (atomic) path in every mode: the assembled tangent (nlps_gpu_tangent_assemble /
- * nlps_gpu_tangent_coo); clouds created with driver_eigenerosion / driver_eigensoftening (the damage hooks); handles
+ * nlps_gpu_tangent_coo); clouds created with driver_eigenerosion / driver_eigensoftening (the damage hooks, in the
+ * separate stages and in the fused form of nlps_gpu_set_implicit_damage alike); handles
  * with a halo-exchange callback or an RCCL exchange attached; the folded, lazy and async-lists forms of the explicit
  * step, which the mode does not use. */
 int nlps_gpu_set_deterministic(nlps_gpu *h, int on);

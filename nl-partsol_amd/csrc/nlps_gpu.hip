@@ -1760,6 +1760,11 @@ struct nlps_gpu {
   // k_run_first / k_run_fill), tables of their own -- the level-B force stage rebuilds dmg_* with its sorts every call.
   // xrun_*0: the tables of the snapshot's closest nodes, made once and again after a re-sort has renumbered the slots
   bool explicit_damage = false;
+  // the fused damage residual (nlps_gpu_set_implicit_damage): the same tables; the runs of the current closest nodes are
+  // built at the first evaluation and reused while nothing has moved, reordered or re-listed particles (xrun_gen == tan_gen)
+  bool implicit_damage = false;
+  unsigned long long xrun_gen = 0;
+  int xrun_builds = 0, dmg_fused_evals = 0;  // developer read-out (nlps_gpu_debug_damage_counters)
   DevBuf<int> xrun_cnt_d, xrun_cursor_d, xrun_rank_d;              // [nnodes], [1], [npad]
   DevBuf<int> xrun_first_d, xrun_last_d, xrun_sorted_d;            // [nnodes], [nnodes], [npad]
   DevBuf<int> xrun_first0_d, xrun_last0_d, xrun_sorted0_d;
@@ -2662,13 +2667,9 @@ extern "C" int nlps_gpu_set_law_launch_mode(nlps_gpu* h, int mode) {
   h->k3_per_law = mode == 1;
   return 0;
 }
-extern "C" int nlps_gpu_set_explicit_damage(nlps_gpu* h, int on) {
-  if (!h->P.erosion) {
-    h->err = "nlps_gpu_set_explicit_damage: the cloud was created without driver_eigenerosion / driver_eigensoftening "
-             "(nlps_params): it has no damage hooks to run";
-    return 1;
-  }
-  if (on && !h->xrun_cnt_d) {  // every table of the step's node runs, so that a step allocates nothing
+// every table of the node runs (both damage setters), so that neither a step nor a residual evaluation allocates
+static int xrun_alloc(nlps_gpu* h) {
+  if (!h->xrun_cnt_d) {
     const size_t nn = (size_t)h->g.nnodes, npad = h->P.npad;
     if (dev_alloc(h, h->xrun_cnt_d, nn) || dev_alloc(h, h->xrun_cursor_d, 1) || dev_alloc(h, h->xrun_rank_d, npad)) return 1;
     if (dev_alloc(h, h->xrun_first_d, nn) || dev_alloc(h, h->xrun_last_d, nn) || dev_alloc(h, h->xrun_sorted_d, npad)) return 1;
@@ -2677,7 +2678,39 @@ extern "C" int nlps_gpu_set_explicit_damage(nlps_gpu* h, int on) {
       return 1;
     HIPCHK(hipMemsetAsync(h->xrun_cnt_d, 0, nn * sizeof(int), h->stream));  // (k_run_first leaves the counters at zero)
   }
+  return 0;
+}
+extern "C" int nlps_gpu_set_explicit_damage(nlps_gpu* h, int on) {
+  if (!h->P.erosion) {
+    h->err = "nlps_gpu_set_explicit_damage: the cloud was created without driver_eigenerosion / driver_eigensoftening "
+             "(nlps_params): it has no damage hooks to run";
+    return 1;
+  }
+  if (on && xrun_alloc(h)) return 1;
   h->explicit_damage = on != 0;
+  return 0;
+}
+static const char* implicit_damage_halo_msg =
+    "the fused damage residual is built for one rank: with a halo callback or an RCCL exchange attached, an "
+    "epsilon-neighbourhood across a slab face would need ghost particles";
+extern "C" int nlps_gpu_set_implicit_damage(nlps_gpu* h, int on) {
+  if (!h->P.erosion) {
+    h->err = "nlps_gpu_set_implicit_damage: the cloud was created without driver_eigenerosion / driver_eigensoftening "
+             "(nlps_params): it has no damage hooks to run";
+    return 1;
+  }
+  if (h->law_present & (1 << NLPS_KLAW_FLUID)) {
+    h->err = "nlps_gpu_set_implicit_damage: the cloud holds the Newtonian-Fluid-Compressible law; the state half of the fused "
+             "damage residual is cut for the solid laws";
+    return 1;
+  }
+  if (h->halo || h->rccl) {
+    h->err = std::string("nlps_gpu_set_implicit_damage: ") + implicit_damage_halo_msg;
+    return 1;
+  }
+  if (on && xrun_alloc(h)) return 1;
+  h->implicit_damage = on != 0;
+  h->xrun_gen = 0;
   return 0;
 }
 
@@ -2709,6 +2742,14 @@ extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_displaced(n
   HIPCHK(hipStreamSynchronize(h->stream));  // developer read-out: the count of the last completed search stage
   *count = h->foreign_h.host() ? *(volatile int*)h->foreign_h.host() : 0;
   *debt = h->debt;
+  return 0;
+}
+
+// developer read-out: how often the node runs of the current closest nodes were built, and how many residual evaluations
+// took the fused damage form (tests: the runs are reused inside a solve; NLPS_LAGR_SEPARATE stays on the separate stages)
+extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_damage_counters(nlps_gpu* h, int* run_builds, int* fused_evaluations) {
+  *run_builds = h->xrun_builds;
+  *fused_evaluations = h->dmg_fused_evals;
   return 0;
 }
 
@@ -4286,6 +4327,43 @@ extern "C" int nlps_gpu_update_kinetics(nlps_gpu* h, double alpha_blend, const d
 
 __global__ void k_null_bracket(PView, GridD, NView, TileD, const MatD*, ParamsD, int*, const double*) {}
 
+// The node runs and the damage hook, shared by the explicit step with the damage hooks (nlps_gpu_set_explicit_damage) and
+// the fused damage residual (nlps_gpu_set_implicit_damage): with `rebuild` the runs of the current closest nodes (k_run_*:
+// no sort), once per numbering of the slots those of the snapshot's closest nodes (eigenerosion's frozen lists,
+// Beps.c:30-36), then the hook, which sets Damage_n1 (Strain_f_n1) and scales every Kirchhoff stress in place.  All on the
+// handle's stream, no sort, no synchronisation, no allocation (the setters made the tables).
+static int damage_runs_and_hook(nlps_gpu* h, bool rebuild) {
+  const int np = h->P.np, nn = h->g.nnodes;
+  const dim3 gp(nblk(np)), gn(nblk(nn)), blk(BLK);
+  if (rebuild) {
+    hipLaunchKernelGGL(k_run_count<false>, gp, blk, 0, h->stream, h->P, nn, h->xrun_cnt_d.get(), h->xrun_rank_d.get(), h->xrun_cursor_d.get());
+    hipLaunchKernelGGL(k_run_first, gn, blk, 0, h->stream, nn, h->xrun_cnt_d.get(), h->xrun_cursor_d.get(), h->xrun_first_d.get(), h->xrun_last_d.get());
+    hipLaunchKernelGGL(k_run_fill<false>, gp, blk, 0, h->stream, h->P, nn, (const int*)h->xrun_first_d.get(), (const int*)h->xrun_rank_d.get(),
+                       h->xrun_sorted_d.get());
+    h->xrun_builds++;
+  }
+  if (h->P.softening) {
+    double* T0 = h->gather_tmp.get();  // [npad] scratch of the re-sort, idle here
+    LAUNCH_ND((k_soften_pass1<2>), (k_soften_pass1<3>), nblk(np), h->P, h->mats_d, T0);
+    // (orig[] = the caller's index of every slot: perm_d travels with the re-sorts)
+    LAUNCH_ND((k_soften_pass2<2>), (k_soften_pass2<3>), nblk(np), h->P, h->g, h->mats_d, h->xrun_first_d, h->xrun_last_d, h->xrun_sorted_d,
+              (const uint8_t*)h->rank1_d, (const int*)h->perm_d, (const double*)T0, h->g.h);
+  } else {
+    if (!h->xrun_tables0) {  // frozen lists (Beps.c:30-36): the runs of the snapshot's closest nodes
+      hipLaunchKernelGGL(k_run_count<true>, gp, blk, 0, h->stream, h->P, nn, h->xrun_cnt_d.get(), h->xrun_rank_d.get(), h->xrun_cursor_d.get());
+      hipLaunchKernelGGL(k_run_first, gn, blk, 0, h->stream, nn, h->xrun_cnt_d.get(), h->xrun_cursor_d.get(), h->xrun_first0_d.get(),
+                         h->xrun_last0_d.get());
+      hipLaunchKernelGGL(k_run_fill<true>, gp, blk, 0, h->stream, h->P, nn, (const int*)h->xrun_first0_d.get(), (const int*)h->xrun_rank_d.get(),
+                         h->xrun_sorted0_d.get());
+      h->xrun_tables0 = true;
+    }
+    LAUNCH_ND((k_damage<2>), (k_damage<3>), nblk(np), h->P, h->g, h->mats_d, h->xrun_first_d, h->xrun_last_d, h->xrun_sorted_d,
+              h->xrun_first0_d, h->xrun_last0_d, h->xrun_sorted0_d, h->g.h);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc, int step, double dt, double gamma_nm,
                                       const double* gravity) {
   tan_stale(h, "nlps_gpu_explicit_step");
@@ -4598,30 +4676,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   // the hook, which sets Damage_n1 (Strain_f_n1) and scales every Kirchhoff stress in place, and the force half.  All
   // on the handle's stream, no sort, no synchronisation, no allocation (nlps_gpu_set_explicit_damage made the tables).
   auto damage_hook_and_forces = [&]() -> int {
-    const int np = h->P.np, nn = h->g.nnodes;
-    const dim3 gp(nblk(np)), gn(nblk(nn)), blk(BLK);
-    hipLaunchKernelGGL(k_run_count<false>, gp, blk, 0, h->stream, h->P, nn, h->xrun_cnt_d.get(), h->xrun_rank_d.get(), h->xrun_cursor_d.get());
-    hipLaunchKernelGGL(k_run_first, gn, blk, 0, h->stream, nn, h->xrun_cnt_d.get(), h->xrun_cursor_d.get(), h->xrun_first_d.get(), h->xrun_last_d.get());
-    hipLaunchKernelGGL(k_run_fill<false>, gp, blk, 0, h->stream, h->P, nn, (const int*)h->xrun_first_d.get(), (const int*)h->xrun_rank_d.get(),
-                       h->xrun_sorted_d.get());
-    if (h->P.softening) {
-      double* T0 = h->gather_tmp.get();  // [npad] scratch of the re-sort, idle here
-      LAUNCH_ND((k_soften_pass1<2>), (k_soften_pass1<3>), nblk(np), h->P, h->mats_d, T0);
-      // (orig[] = the caller's index of every slot: perm_d travels with the re-sorts)
-      LAUNCH_ND((k_soften_pass2<2>), (k_soften_pass2<3>), nblk(np), h->P, h->g, h->mats_d, h->xrun_first_d, h->xrun_last_d, h->xrun_sorted_d,
-                (const uint8_t*)h->rank1_d, (const int*)h->perm_d, (const double*)T0, h->g.h);
-    } else {
-      if (!h->xrun_tables0) {  // frozen lists (Beps.c:30-36): the runs of the snapshot's closest nodes
-        hipLaunchKernelGGL(k_run_count<true>, gp, blk, 0, h->stream, h->P, nn, h->xrun_cnt_d.get(), h->xrun_rank_d.get(), h->xrun_cursor_d.get());
-        hipLaunchKernelGGL(k_run_first, gn, blk, 0, h->stream, nn, h->xrun_cnt_d.get(), h->xrun_cursor_d.get(), h->xrun_first0_d.get(),
-                           h->xrun_last0_d.get());
-        hipLaunchKernelGGL(k_run_fill<true>, gp, blk, 0, h->stream, h->P, nn, (const int*)h->xrun_first0_d.get(), (const int*)h->xrun_rank_d.get(),
-                           h->xrun_sorted0_d.get());
-        h->xrun_tables0 = true;
-      }
-      LAUNCH_ND((k_damage<2>), (k_damage<3>), nblk(np), h->P, h->g, h->mats_d, h->xrun_first_d, h->xrun_last_d, h->xrun_sorted_d,
-                h->xrun_first0_d, h->xrun_last0_d, h->xrun_sorted0_d, h->g.h);
-    }
+    if (damage_runs_and_hook(h, true)) return 1;  // (every step has searched: the runs are this step's)
     LAUNCH_ND(k3f_tile<2>, k3f_tile<3>, h->ntw, h->P, h->g, h->N, tile_view(h, 0), h->gstatus_d);
     HIPCHK(hipGetLastError());
     return 0;
@@ -4931,6 +4986,52 @@ __global__ void k_lagrangian_nodal(int nnodes, const int* __restrict__ n2m, cons
 
 static int snes_fnorm_launch(nlps_gpu* h, const double* F);  // (defined with nlps_gpu_newton_solve)
 
+// The fused damage residual (nlps_gpu_set_implicit_damage) between k_expand_reset and the closing nodal
+// kernel: the state half of MODE 3 (k3_tile<., ., 6>: DF, F_n1, J_n1, tau, W, the n+1 internal variables, C_ep; failed
+// particles skipped), the node runs of the current closest nodes -- built once per numbering: nothing between two calls
+// that make the matrix-free operator stale (tan_stale) changes a closest node --, the hook, which sets Damage_n1
+// (Strain_f_n1) and scales every Kirchhoff stress in place, and the force half with the Lagrangian's sign.  All on the
+// handle's stream, no sort, no synchronisation, no allocation (the setter made the tables).  The level-B stages keep
+// tables of their own (dmg_*, the sort buffers): nothing here touches them.
+static int lagrangian_damage_launches(nlps_gpu* h) {
+  const int ND = h->nd;
+  const dim3 grid(h->ntw), blk3(K3_BLK);
+  if (beps_snapshot(h)) return 1;  // (taken by the first search: nothing to do here for a handle that has searched)
+  TileD td = tile_view(h);
+  td.slab = nullptr;  // (the atomic flush: damage clouds are outside the deterministic contract, see det_implicit)
+  const int law = h->uniform_law;
+  const double* const no_dV = nullptr;
+  if (law < 0) {  // one launch per law present, every workgroup compacting its tile's particles of that law first (FILT)
+    for_each_law_present(h->law_present, [&](int l, bool) {
+      with_nd(ND, [&](auto D) {
+        with_law(l, [&](auto L) {
+          hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 6, true>), grid, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
+                             h->gstatus_d, no_dV);
+        });
+      });
+    });
+  } else if (ND == 3 && h->nmats == 1 && law >= 1 && law <= 3) {  // one material (k3_body, UMAT)
+    with_law_in<1, 3>(law, [&](auto L) {
+      hipLaunchKernelGGL((k3_tile<3, CT(L), 6, false, K3_BLK, true>), grid, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
+                         h->prm, h->gstatus_d, no_dV);
+    });
+  } else {
+    with_nd(ND, [&](auto D) {
+      with_law(law, [&](auto L) {
+        hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 6>), grid, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
+                           h->gstatus_d, no_dV);
+      });
+    });
+  }
+  // (built once per numbering: nothing between two calls that make the matrix-free operator stale changes a closest node)
+  if (damage_runs_and_hook(h, h->xrun_gen != h->tan_gen)) return 1;
+  h->xrun_gen = h->tan_gen;
+  h->dmg_fused_evals++;
+  LAUNCH_ND_BLK((k3f_tile<2, true>), (k3f_tile<3, true>), h->ntw, K3_BLK, h->P, h->g, h->N, td, h->gstatus_d);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const double* dU, const double* Un_dt,
                                               const double* Un_dt2, const double* M, const double* alpha,
                                               const double* gravity, const nlps_bcc* loads, int nloads, int step,
@@ -4948,7 +5049,13 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
   // every particle's stress before any force)
   // (a cloud that holds the fluid law always carries the rates: fused in MODE 4, or through the separate stages)
   const bool fluid = (h->law_present & (1 << NLPS_KLAW_FLUID)) != 0;
-  const bool fused = !(flags & NLPS_LAGR_SEPARATE) && (fluid || !(flags & NLPS_LAGR_RATES)) && !h->P.erosion &&
+  // (a damage cloud takes the fused damage form with nlps_gpu_set_implicit_damage on, the separate stages otherwise)
+  const bool dmg = h->P.erosion && h->implicit_damage && !(flags & (NLPS_LAGR_SEPARATE | NLPS_LAGR_RATES)) && h->P.np > 0;
+  if (dmg && (h->halo || h->rccl)) {
+    h->err = std::string("nlps_gpu_lagrangian_evaluation: ") + implicit_damage_halo_msg;
+    return 1;
+  }
+  const bool fused = !(flags & NLPS_LAGR_SEPARATE) && (fluid || !(flags & NLPS_LAGR_RATES)) && (!h->P.erosion || dmg) &&
                      h->uniform_law <= NLPS_KLAW_FLUID && h->P.np > 0;
   if (!fused) {
     DevBuf<double> dV;
@@ -5026,6 +5133,8 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
       });
     });
     DET_GATHER(2, 3, td.slab_n, h->N.force);
+  } else if (dmg) {
+    if (lagrangian_damage_launches(h)) return 1;
   } else {
     TileD td = tile_view(h);
     td.slab = nullptr;  // (the atomic flush: handles outside the deterministic implicit path, see det_implicit)

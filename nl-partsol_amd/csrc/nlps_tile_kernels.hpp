@@ -853,6 +853,9 @@ __global__ __launch_bounds__(NT, NT == 64 ? 1 : (ND == 2 ? K2_WAVES_2D : K2_WAVE
 // constitutive stage stores (tau, W, b_e,n+1, kappa_n+1, eps_n+1, C_ep: the n state stays untouched, the residual is
 // evaluated many times from it) -> P2G of the internal force.  Same registers-only hand-over of DF, tau between the
 // stages as MODE 1, same kernel skeleton and occupancy; what it adds are the stores of the n+1 state.
+// MODE 6: the state half of MODE 3, for the residual of a damage cloud (nlps_gpu_set_implicit_damage): MODE 3 up to and
+// including the stress update, no force scatter -- the damage hook scales the Kirchhoff stress between this kernel and
+// the force half (k3f_tile with sign +1).
 // MODE 2: MODE 0 plus the rate tensors dt_DF = sum dV_A (x) grad N_A and dt_F_n1 = dt_DF F_n + DF dt_F_n
 // (compute-Strains.c:48-72, 176-207) from a second gather window dV.
 // MODE 4 (LAW = NLPS_KLAW_FLUID only): the residual of MODE 3 for the one law that reads the rate tensors -- MODE 3's pass
@@ -871,9 +874,9 @@ static constexpr int K3_WAVES = 2;  // Hencky / Drucker-Prager need > 256 VGPRs 
 template <int ND, int LAW, int MODE>
 struct K3Waves {
   static constexpr int value = ND == 2 ? K3_WAVES_2D
-                               : ((MODE == 1 || MODE == 3 || MODE == 5) && LAW == NLPS_MAT_NEO_HOOKEAN) ? K3_WAVES_NH
-                               : ((MODE == 1 || MODE == 3 || MODE == 5) && LAW == NLPS_MAT_HENCKY)      ? K3_WAVES_HENCKY
-                               : ((MODE == 1 || MODE == 3 || MODE == 5) && LAW == NLPS_MAT_DRUCKER_PRAGER) ? K3_WAVES_DP
+                               : ((MODE == 1 || MODE == 3 || MODE == 5 || MODE == 6) && LAW == NLPS_MAT_NEO_HOOKEAN) ? K3_WAVES_NH
+                               : ((MODE == 1 || MODE == 3 || MODE == 5 || MODE == 6) && LAW == NLPS_MAT_HENCKY)      ? K3_WAVES_HENCKY
+                               : ((MODE == 1 || MODE == 3 || MODE == 5 || MODE == 6) && LAW == NLPS_MAT_DRUCKER_PRAGER) ? K3_WAVES_DP
                                                                                : K3_WAVES;
 };
 // the LDS of k3_tile, owned by the caller of k3_body (the kernels below)
@@ -883,11 +886,12 @@ struct K3Lds {
   static constexpr bool RATES = (MODE == 2 || MODE == 4);
   static constexpr int SELCAP = FILT ? 4096 : 1;
   static constexpr int N_DVXY = RATES ? 2 * NW : 2, N_DVZ = (RATES && ND == 3) ? NW : 1, N_DUZ = (ND == 3) ? NW : 1;
+  static constexpr int N_FAC = (MODE == 6) ? 1 : ND * NWA;  // (MODE 6 scatters nothing: no force accumulator)
   double* dvxy;  // [N_DVXY], 16-byte aligned
   double* dvz;   // [N_DVZ]
   double* duxy;  // [2 NW], 16-byte aligned
   double* duz;   // [N_DUZ]
-  double* fac;   // [ND NWA]
+  double* fac;   // [N_FAC]
   int* sel;      // [SELCAP]
   int* nsel;     // [1]
   int* wcnt;     // [NT / 64]
@@ -911,7 +915,12 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
   // the Kirchhoff stress between this kernel and the force half (k3f_tile).  It stores what they read: F_n+1, J (both
   // slots), DF, tau, W, d_dis; a failed particle (Damage_n == 1) keeps its stress (U-Newmark-beta.c:1218-1224).
   constexpr bool STATE = (MODE == 5);
-  constexpr bool STRESS = SCATTER || STATE;
+  // MODE 6, the implicit sibling (nlps_gpu_set_implicit_damage): MODE 3 up to and including the stress update -- same
+  // gather of the caller's dU, same passes, same lists, the implicit clamp of J <= 0 -- and no force scatter.  Everything
+  // goes to the n+1 slots (DF, F_n+1, J_n+1, tau, W, b_e,n+1, kappa_n+1, eps_n+1, C_ep): the n state stays untouched, the
+  // residual is evaluated many times from it.  A failed particle (Damage_n == 1) gets W = 0 and nothing else (k_stress).
+  constexpr bool STATE_N1 = (MODE == 6);
+  constexpr bool STRESS = SCATTER || STATE || STATE_N1;
   static_assert((MODE == 4) == (LAW == NLPS_KLAW_FLUID), "the rate-carrying residual is the fluid law's, and only its");
   // gather window of dU: {x,y} as one 16-B double2 per node (ds_read_b128) + z as a separate 8-B array
   // (ds_read_b64): with node strides of 16 B and 8 B the tile's 64 I0 positions hit distinct banks; a
@@ -1004,7 +1013,8 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
       if (ND == 3) dvz[(RATES && ND == 3) ? idx : 0] = in ? dVgrid[(size_t)node * ND + (2 % ND)] : 0.0;
     }
   }
-  for (int idx = threadIdx.x; idx < ND * NWA; idx += NT) fac[idx] = 0.0;
+  if (!STATE_N1)
+    for (int idx = threadIdx.x; idx < ND * NWA; idx += NT) fac[idx] = 0.0;
   __syncthreads();
   const double2* du2 = reinterpret_cast<const double2*>(duxy);
   const double2* dv2 = reinterpret_cast<const double2*>(dvxy);
@@ -1392,6 +1402,19 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
       }
       continue;
     }
+    if constexpr (STATE_N1) {
+      if (PF(P, F_DMG, pl) == 1.0) {  // failed particle: U-Newmark-beta.c:1218-1224
+        PF(P, F_W, pl) = 0.0;
+      } else {
+        double tau_s[ND * ND];
+        st |= stress_update<ND, LAW, true, (LAW == NLPS_KLAW_FRICTIONAL), false>(P, pl, mats, prm, Fn1, DF, Jn1, tau_s, mat_idx);
+      }
+      if (st) {
+        atomicOr(&P.status[pl], st);
+        atomicOr(gstatus, st);
+      }
+      continue;
+    }
     double tau[ND * ND], B[ND * ND];
     // (MODE 3: C_ep kept for the tangent that may follow, everything to the n+1 slots)
     if constexpr (MODE == 4) {
@@ -1518,7 +1541,7 @@ __global__ __launch_bounds__(NT, (NT == 64 ? 1 : (K3Waves<ND, LAW, MODE>::value)
   __shared__ double dvz[L::N_DVZ];
   __shared__ __attribute__((aligned(16))) double duxy[2 * L::NW];
   __shared__ double duz[L::N_DUZ];
-  __shared__ double fac[ND * L::NWA];
+  __shared__ double fac[L::N_FAC];
   __shared__ int sel[L::SELCAP];
   __shared__ int nsel;
   __shared__ int wcnt[NT / 64];
@@ -1576,7 +1599,9 @@ __global__ __launch_bounds__(K3_BLK, (K3Waves<ND, LAW, 1>::value)) void k3_tile_
 // lists, force_operator with sign -1, one flush per tile; the LME factors are rebuilt from the particle's stored x,
 // lambda, beta and masks (load_lme, as K3's RELOAD path does), J^-1 and Z^-1 from their moments.  One rank, atomic
 // flush: no slabs, no boundary signal.
-template <int ND>
+// PLUS (nlps_gpu_set_implicit_damage): +f_int, what the Lagrangian of the implicit driver accumulates (MODE 3's sign);
+// the default is the explicit step's kernel, whose code the argument does not change.
+template <int ND, bool PLUS = false>
 __global__ __launch_bounds__(K3_BLK, 2) void k3f_tile(PView P, GridD g, NView N, TileD td, int* __restrict__ gstatus) {
   NLPS_FP_CONTRACT
   constexpr int KN = Lme<ND>::KN, WA = TileCfg<ND>::WA, PSA = TileCfg<ND>::PSA, NWA = TileCfg<ND>::NWA;
@@ -1598,7 +1623,7 @@ __global__ __launch_bounds__(K3_BLK, 2) void k3f_tile(PView P, GridD g, NView N,
     lme_moments_h<ND>(c, Zinv, r, J);
     load_block<ND>(P, F_TAU, p, tau, z);
     load_block<ND>(P, F_DF, p, DF, z);
-    if (!(inverse<ND>(Jm1, J) && force_operator<ND>(B, tau, DF, Jm1, PF(P, F_VOL0, p), -1.0))) {
+    if (!(inverse<ND>(Jm1, J) && force_operator<ND>(B, tau, DF, Jm1, PF(P, F_VOL0, p), PLUS ? 1.0 : -1.0))) {
       atomicOr(&P.status[p], ST_JACOBIAN);
       atomicOr(gstatus, ST_JACOBIAN);
       continue;

@@ -106,6 +106,7 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_internal_forces", "nlps_gpu_nodal_traction_forces", "nlps_gpu_roll_state", "nlps_gpu_update_kinetics",
            "nlps_gpu_explicit_step", "nlps_gpu_num_active", "nlps_gpu_explicit_nodal", "nlps_gpu_set_halo_exchange",
            "nlps_gpu_resort", "nlps_gpu_set_resort_interval", "nlps_gpu_set_adaptive_resort", "nlps_gpu_set_law_launch_mode", "nlps_gpu_set_deterministic", "nlps_gpu_set_explicit_damage",
+           "nlps_gpu_set_implicit_damage",
            "nlps_gpu_rccl_unique_id", "nlps_gpu_rccl_attach", "nlps_gpu_rccl_attach_comm", "nlps_gpu_rccl_detach",
            "nlps_gpu_rccl_reduce", "nlps_gpu_rccl_info", "nlps_gpu_rccl_migrate", "nlps_gpu_rccl_selftest_migrate", "nlps_gpu_rccl_selftest_exchange", "nlps_gpu_touched_layers", "nlps_gpu_set_node_window", "nlps_gpu_set_ghost_bands",
            "nlps_gpu_form_initial_guess", "nlps_gpu_nodal_kinetic_increments", "nlps_gpu_nodal_inertial_forces",
@@ -143,6 +144,8 @@ def lib():
         L.nlps_gpu_set_law_launch_mode.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_set_deterministic.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_set_explicit_damage.argtypes = [C.c_void_p, C.c_int]
+        if hasattr(L, "nlps_gpu_set_implicit_damage"):  # (NLPS_GPU_LIB may name an older build: tools/implicit_damage_bench.py)
+            L.nlps_gpu_set_implicit_damage.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_rccl_unique_id.argtypes = [C.c_void_p]
         L.nlps_gpu_rccl_attach.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _ip, _ip, C.c_int]
         L.nlps_gpu_rccl_attach_comm.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _ip, _ip, C.c_int]
@@ -559,6 +562,20 @@ class Solver:
         """The eigenerosion / eigensoftening hooks inside explicit_step (off by default: the step refuses a damage cloud);
         the definition of such a step is in include/nlps_gpu.h."""
         self._chk(self.L.nlps_gpu_set_explicit_damage(self.h, 1 if on else 0))
+
+    def set_implicit_damage(self, on=True):
+        """The eigenerosion / eigensoftening hooks inside the fused residual (off by default: lagrangian_evaluation runs the
+        separate stages for a damage cloud); newton_solve and newmark_step take it too.  The definition is in
+        include/nlps_gpu.h."""
+        self._chk(self.L.nlps_gpu_set_implicit_damage(self.h, 1 if on else 0))
+
+    def debug_damage_counters(self):
+        """developer read-out: (builds of the node runs of the current closest nodes, residual evaluations that took the fused
+        damage form) since the handle was made"""
+        b, e = C.c_int(0), C.c_int(0)
+        self.L.nlps_gpu_debug_damage_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        self._chk(self.L.nlps_gpu_debug_damage_counters(self.h, C.byref(b), C.byref(e)))
+        return b.value, e.value
 
     def touched_layers(self):
         lo, hi = C.c_int(0), C.c_int(0)
