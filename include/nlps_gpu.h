@@ -250,9 +250,11 @@ int nlps_gpu_explicit_step(nlps_gpu *h, const nlps_bcc *bcc, int nbcc, int step,
  *   6. the roll of the explicit step, and Damage_n <- Damage_n1, Strain_f_n <- Strain_f_n1 (:1950-1956).
  * A download after such a step returns Stress = the scaled stress of that step, W = the unscaled energy (0 for a skipped
  * particle), Damage_n == Damage_n1 and both Strain_f slots, like the level-B roll.
- * The step runs on one rank, on the handle's stream, without sorts, synchronisation or allocation.  It returns 1 with
+ * The step runs on one rank, on the handle's stream, without sorts, synchronisation or allocation (in deterministic mode
+ * with nlps_gpu_set_deterministic_damage one more kernel orders every node run in place).  It returns 1 with
  * the reason in nlps_gpu_last_error when a halo callback or an RCCL exchange is attached (an epsilon-neighbourhood across
- * a slab face needs ghost particles), in deterministic mode, and for the fluid law (as above).
+ * a slab face needs ghost particles), in deterministic mode unless nlps_gpu_set_deterministic_damage is on, and for the
+ * fluid law (as above).
  * The setter returns 1 for a cloud created without either driver. */
 int nlps_gpu_set_explicit_damage(nlps_gpu *h, int on);
 /* The damage hooks inside the fused residual (clouds created with driver_eigenerosion or driver_eigensoftening).  Off by
@@ -274,7 +276,8 @@ int nlps_gpu_set_explicit_damage(nlps_gpu *h, int on);
  * An evaluation runs on one rank, on the handle's stream, without sorts or allocation and with the one synchronisation
  * every fused evaluation ends in (inside nlps_gpu_newton_solve its norm arrives with that wait).  The node runs of the
  * hook are built at the first evaluation and reused until a call that makes the matrix-free operator stale (the list under
- * nlps_gpu_tangent_apply).
+ * nlps_gpu_tangent_apply).  In deterministic mode with nlps_gpu_set_deterministic_damage on, the evaluation sums in a fixed
+ * order (sorted runs, one wave per tile, slabs) and repeats bit for bit; otherwise a damage cloud sums with atomics.
  * The setter allocates every table (shared with nlps_gpu_set_explicit_damage).  It returns 1, with the reason in
  * nlps_gpu_last_error, for a cloud created without either driver, for a cloud that holds Newtonian-Fluid-Compressible
  * (the state half is cut for the solid laws), and when a halo callback or an RCCL exchange is attached (an
@@ -358,10 +361,26 @@ int nlps_gpu_set_law_launch_mode(nlps_gpu *h, int mode);
  * 8 x 400 (2-D, per tile of 16^2) doubles per tile of the grid.
  * Outside the contract, on their usual (atomic) path in every mode: the assembled tangent (nlps_gpu_tangent_assemble /
  * nlps_gpu_tangent_coo); clouds created with driver_eigenerosion / driver_eigensoftening (the damage hooks, in the
- * separate stages and in the fused form of nlps_gpu_set_implicit_damage alike); handles
+ * separate stages and in the fused form of nlps_gpu_set_implicit_damage alike) unless nlps_gpu_set_deterministic_damage
+ * is on -- without it the explicit step refuses such a cloud in the mode; handles
  * with a halo-exchange callback or an RCCL exchange attached; the folded, lazy and async-lists forms of the explicit
- * step, which the mode does not use. */
+ * step, which the mode does not use.
+ * Switching the mode drops the cached node runs of the damage hooks (they are rebuilt by the next step or evaluation). */
 int nlps_gpu_set_deterministic(nlps_gpu *h, int on);
+/* Deterministic mode for clouds created with driver_eigenerosion or driver_eigensoftening.  Off by default: such a cloud
+ * then stays outside the contract above (the explicit step refuses it in the mode, the implicit path sums with atomics).
+ * With on != 0 AND nlps_gpu_set_deterministic on, on one rank, the contract above also holds for a damage cloud in
+ * nlps_gpu_explicit_step (with nlps_gpu_set_explicit_damage), nlps_gpu_lumped_mass, nlps_gpu_nodal_field_n,
+ * nlps_gpu_internal_forces with its hook, nlps_gpu_lagrangian_evaluation (NLPS_LAGR_SEPARATE, the separate stages of
+ * nlps_gpu_set_implicit_damage off, the fused damage form), nlps_gpu_tangent_apply, nlps_gpu_tangent_block_diagonal,
+ * nlps_gpu_tangent_solve, nlps_gpu_newton_solve and nlps_gpu_newmark_step: the particles of every node run of the hooks
+ * are visited in ascending memory slot, so the threshold decisions G_p > Gf and T_eps > ft read sums made in one order,
+ * and the nodal forces under them come from one wave per tile and a fixed-order sum of window slabs.  Damage decisions
+ * and every downloaded array then repeat bit for bit between two runs from the same inputs.
+ * Still refused or outside the contract: a halo callback or an RCCL exchange, the fluid law, the assembled tangent.
+ * The setter allocates the run tables and the window slabs (no step or evaluation allocates) and drops the cached node
+ * runs.  It returns 1, with the reason in nlps_gpu_last_error, for a cloud created without either driver. */
+int nlps_gpu_set_deterministic_damage(nlps_gpu *h, int on);
 
 /* ------------------------------------------------------------------ per-dof updates of the implicit driver (a21)
  * Vectors of N_A*d doubles in masked numbering, host (VecGetArray) or device pointers.  alpha = the six Newmark

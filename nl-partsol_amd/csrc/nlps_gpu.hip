@@ -734,6 +734,34 @@ __global__ __launch_bounds__(BLK) void k_run_fill(PView P, int nn, const int* __
   const int s = first[A] + r;
   if (s < P.np) sorted[s] = p;
 }
+// Deterministic mode with the damage hooks (nlps_gpu_set_deterministic_damage), behind k_run_fill: the order INSIDE every
+// run becomes ascending slot index -- a function of the particle arrays alone, the definition k_tile_order<., true> uses
+// for its exact ranks -- whatever ranks the returning atomic of the count handed out.  Where a run lies in `sorted` still
+// depends on the cursor's atomic; nothing reads across runs.  One thread per node, insertion sort in place: a run holds
+// the particles of one closest node (4 to 8, some tens in a dense cloud) and arrives nearly sorted.  No local array.
+__global__ __launch_bounds__(BLK) void k_run_sort(int nn, int np, const int* __restrict__ first, const int* __restrict__ last,
+                                                  int* __restrict__ sorted) {
+  const int A = blockIdx.x * BLK + threadIdx.x;
+  if (A >= nn) return;
+  const int lo = max(first[A], 0), hi = min(last[A], np);
+  for (int i = lo + 1; i < hi; i++) {
+    const int v = sorted[i];
+    int j = i;
+    while (j > lo) {
+      const int u = sorted[j - 1];
+      if (u <= v) break;
+      sorted[j] = u;
+      j--;
+    }
+    sorted[j] = v;
+  }
+}
+// developer read-out (nlps_gpu_debug_damage_runs): the node every slot is counted under by k_run_count<SNAP>
+template <bool SNAP>
+__global__ __launch_bounds__(BLK) void k_debug_slot_node(PView P, int nn, int* __restrict__ key) {
+  const int p = blockIdx.x * BLK + threadIdx.x;
+  if (p < P.np) key[p] = run_node<SNAP>(P, p, nn);
+}
 // the damage part of the roll behind K5 (U-Newmark-beta.c:1950-1956; k_roll does it for level B)
 __global__ __launch_bounds__(BLK) void k_damage_roll(PView P) {
   const int p = blockIdx.x * BLK + threadIdx.x;
@@ -1769,6 +1797,10 @@ struct nlps_gpu {
   DevBuf<int> xrun_first_d, xrun_last_d, xrun_sorted_d;            // [nnodes], [nnodes], [npad]
   DevBuf<int> xrun_first0_d, xrun_last0_d, xrun_sorted0_d;
   bool xrun_tables0 = false;
+  bool xrun_tables = false;  // the runs of the current closest nodes have been built since the last drop (read-out only)
+  // nlps_gpu_set_deterministic_damage: in deterministic mode the runs are sorted behind k_run_fill (k_run_sort), the force
+  // half runs one wave per tile into slabs (k3f_wave) and det_implicit admits the damage cloud
+  bool det_damage = false;
   bool rolled_keep = false;  // `rolled`, and the last step stored tau and W itself (k_copy_n_to_n1 KEEP)
   DevBuf<double> slab_d;    // P2G window slabs [ntiles][slab_n][fields][NWA] (TileD::slab), deterministic mode only: sized by the
                             // explicit step and, for the largest user of the implicit path, by det_prepare
@@ -2518,6 +2550,7 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
   h->rehome = true;  // the slots have new owners: the next search records their tiles
   h->debt = 0.0;
   h->xrun_tables0 = false;  // (slot numbers)
+  h->xrun_tables = false;   // (read-out: the runs of the current closest nodes hold the old slot numbers until the next build)
   return 0;
 }
 
@@ -2714,8 +2747,31 @@ extern "C" int nlps_gpu_set_implicit_damage(nlps_gpu* h, int on) {
   return 0;
 }
 
+// run tables built in arrival order are never summed over in the deterministic mode, and sorted ones are not kept for
+// the atomic path either: both switches drop every cached table
+static void xrun_drop(nlps_gpu* h) {
+  h->xrun_gen = 0;
+  h->xrun_tables0 = false;
+  h->xrun_tables = false;
+}
+static int det_slab_reserve(nlps_gpu* h, const char* who);  // (defined with det_prepare)
+extern "C" int nlps_gpu_set_deterministic_damage(nlps_gpu* h, int on) {
+  if (!h->P.erosion) {
+    h->err = "nlps_gpu_set_deterministic_damage: the cloud was created without driver_eigenerosion / driver_eigensoftening "
+             "(nlps_params): it has no damage hooks to run";
+    return 1;
+  }
+  // (the run tables, shared with the two damage setters, and the window slabs of the largest user: no step or evaluation
+  // allocates, whichever switch comes first)
+  if (on && (xrun_alloc(h) || det_slab_reserve(h, "nlps_gpu_set_deterministic_damage"))) return 1;
+  h->det_damage = on != 0;
+  xrun_drop(h);
+  return 0;
+}
+
 extern "C" int nlps_gpu_set_deterministic(nlps_gpu* h, int on) {
   h->deterministic = on != 0;
+  xrun_drop(h);
   h->ahead = h->lists_ready = false;
   h->rehome = true;
   h->debt = 0.0;
@@ -2742,6 +2798,30 @@ extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_displaced(n
   HIPCHK(hipStreamSynchronize(h->stream));  // developer read-out: the count of the last completed search stage
   *count = h->foreign_h.host() ? *(volatile int*)h->foreign_h.host() : 0;
   *debt = h->debt;
+  return 0;
+}
+
+// developer read-out: the node runs as the last step or residual evaluation left them -- the tables of the current closest
+// nodes (snapshot = 0) or of the eigenerosion snapshot's (1).  key[np]: the node every slot is counted under (-1: none),
+// first / last [nnodes], sorted[np].  Returns 1 when that table has not been built (or was dropped by a mode switch).
+extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_damage_runs(nlps_gpu* h, int snapshot, int* key, int* first,
+                                                                                 int* last, int* sorted) {
+  const bool have = snapshot ? (h->xrun_tables0 && h->xrun_sorted0_d) : (h->xrun_tables && h->xrun_sorted_d);
+  if (!have || h->P.np <= 0) {
+    h->err = "nlps_gpu_debug_damage_runs: no such run table has been built";
+    return 1;
+  }
+  const size_t np = (size_t)h->P.np, nn = (size_t)h->g.nnodes;
+  DevBuf<int> kd;
+  HIPCHK(kd.reserve(np));
+  if (snapshot) hipLaunchKernelGGL(k_debug_slot_node<true>, dim3(nblk((int)np)), dim3(BLK), 0, h->stream, h->P, (int)nn, kd.get());
+  else hipLaunchKernelGGL(k_debug_slot_node<false>, dim3(nblk((int)np)), dim3(BLK), 0, h->stream, h->P, (int)nn, kd.get());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpy(key, kd.get(), np * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(first, snapshot ? h->xrun_first0_d.get() : h->xrun_first_d.get(), nn * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(last, snapshot ? h->xrun_last0_d.get() : h->xrun_last_d.get(), nn * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(sorted, snapshot ? h->xrun_sorted0_d.get() : h->xrun_sorted_d.get(), np * sizeof(int), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -3665,14 +3745,15 @@ static int materialise_nodal(nlps_gpu* h) {
 // Deterministic mode on the implicit path (nlps_gpu_set_deterministic): the level-B scatters, the fused residual and the
 // matrix-free tangent run one wave per tile over the exact canonical lists and leave their windows as slabs, which
 // k_slab_gather sums per node in a fixed order.  One rank without a halo callback; a cloud with the damage hooks keeps
-// the atomic path.
-static bool det_implicit(const nlps_gpu* h) { return h->deterministic && !h->halo && !h->rccl && !h->P.erosion && h->P.np > 0; }
+// the atomic path unless nlps_gpu_set_deterministic_damage is on.
+static bool det_implicit(const nlps_gpu* h) {
+  return h->deterministic && !h->halo && !h->rccl && (!h->P.erosion || h->det_damage) && h->P.np > 0;
+}
 // What a deterministic implicit-path call needs before its tile kernel: the exact lists and room for its slabs.  Lists
 // that a search built with the mode off hold the same particles per tile, in an order that depends on binning
 // atomics: the exact per-tile sort is run over them here (it reads the binned lists, whose CONTENT per tile is
 // exact), so no sum ever runs over a non-exact list.  An exact list is a valid canonical list for every other kernel.
 static int det_prepare(nlps_gpu* h, const char* who) {
-  const int ND = h->nd;
   if (!h->lists_exact) {
     if (!h->binned || !h->order2_d) {
       h->err = std::string(who) + ": deterministic mode needs tile lists: call nlps_gpu_local_search() first";
@@ -3683,8 +3764,12 @@ static int det_prepare(nlps_gpu* h, const char* who) {
     HIPCHK(hipGetLastError());
     h->lists_exact = true;
   }
-  // fields per window of the largest user: the explicit step (K2: 1 + d, K3: d per law, sized for four), the block
-  // diagonal (d^2), the nodal field (2 d) and the residual (d per law present)
+  return det_slab_reserve(h, who);
+}
+static int det_slab_reserve(nlps_gpu* h, const char* who) {
+  const int ND = h->nd;
+  // fields per window of the largest user: the explicit step (K2: 1 + d, K3: d per law, sized for four; the force half
+  // of a damage step: d), the block diagonal (d^2), the nodal field (2 d) and the residual (d per law present)
   const size_t NWs = ND == 3 ? TileCfg<3>::NWA : TileCfg<2>::NWA;
   const size_t fields = std::max<size_t>(std::max<size_t>(4 * ND, ND * ND), (size_t)ND * __builtin_popcount(h->law_present));
   return reserve(h, who, h->slab_d, (size_t)h->ntiles * fields * NWs, "the window slabs of the deterministic mode");
@@ -4331,16 +4416,23 @@ __global__ void k_null_bracket(PView, GridD, NView, TileD, const MatD*, ParamsD,
 // the fused damage residual (nlps_gpu_set_implicit_damage): with `rebuild` the runs of the current closest nodes (k_run_*:
 // no sort), once per numbering of the slots those of the snapshot's closest nodes (eigenerosion's frozen lists,
 // Beps.c:30-36), then the hook, which sets Damage_n1 (Strain_f_n1) and scales every Kirchhoff stress in place.  All on the
-// handle's stream, no sort, no synchronisation, no allocation (the setters made the tables).
+// handle's stream, no sort call, no synchronisation, no allocation (the setters made the tables).
 static int damage_runs_and_hook(nlps_gpu* h, bool rebuild) {
   const int np = h->P.np, nn = h->g.nnodes;
   const dim3 gp(nblk(np)), gn(nblk(nn)), blk(BLK);
+  // deterministic mode (nlps_gpu_set_deterministic_damage): ascending slot index inside every run, so that the hook's sums
+  // over a neighbourhood run in an order the particle arrays alone decide.  (Both switches drop the cached tables.)
+  const bool sort_runs = h->deterministic && h->det_damage;
   if (rebuild) {
     hipLaunchKernelGGL(k_run_count<false>, gp, blk, 0, h->stream, h->P, nn, h->xrun_cnt_d.get(), h->xrun_rank_d.get(), h->xrun_cursor_d.get());
     hipLaunchKernelGGL(k_run_first, gn, blk, 0, h->stream, nn, h->xrun_cnt_d.get(), h->xrun_cursor_d.get(), h->xrun_first_d.get(), h->xrun_last_d.get());
     hipLaunchKernelGGL(k_run_fill<false>, gp, blk, 0, h->stream, h->P, nn, (const int*)h->xrun_first_d.get(), (const int*)h->xrun_rank_d.get(),
                        h->xrun_sorted_d.get());
+    if (sort_runs)
+      hipLaunchKernelGGL(k_run_sort, gn, blk, 0, h->stream, nn, np, (const int*)h->xrun_first_d.get(), (const int*)h->xrun_last_d.get(),
+                         h->xrun_sorted_d.get());
     h->xrun_builds++;
+    h->xrun_tables = true;
   }
   if (h->P.softening) {
     double* T0 = h->gather_tmp.get();  // [npad] scratch of the re-sort, idle here
@@ -4355,6 +4447,9 @@ static int damage_runs_and_hook(nlps_gpu* h, bool rebuild) {
                          h->xrun_last0_d.get());
       hipLaunchKernelGGL(k_run_fill<true>, gp, blk, 0, h->stream, h->P, nn, (const int*)h->xrun_first0_d.get(), (const int*)h->xrun_rank_d.get(),
                          h->xrun_sorted0_d.get());
+      if (sort_runs)
+        hipLaunchKernelGGL(k_run_sort, gn, blk, 0, h->stream, nn, np, (const int*)h->xrun_first0_d.get(),
+                           (const int*)h->xrun_last0_d.get(), h->xrun_sorted0_d.get());
       h->xrun_tables0 = true;
     }
     LAUNCH_ND((k_damage<2>), (k_damage<3>), nblk(np), h->P, h->g, h->mats_d, h->xrun_first_d, h->xrun_last_d, h->xrun_sorted_d,
@@ -4384,7 +4479,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
              "an RCCL exchange attached, an epsilon-neighbourhood across a slab face would need ghost particles";
     return 1;
   }
-  if (dmg && h->deterministic) {
+  if (dmg && h->deterministic && !h->det_damage) {  // (nlps_gpu_set_deterministic_damage)
     h->err = "nlps_gpu_explicit_step: the damage hooks inside the explicit step are not built for the deterministic mode (their "
              "node runs take ranks and run starts from atomics)";
     return 1;
@@ -4442,7 +4537,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     const NodeRanges r = node_ranges(h, part);
     if (!det || r.an + r.bn == 0) return;
     TileD td = tile_view(h, 0);
-    td.slab_n = __builtin_popcount(h->law_present);
+    td.slab_n = dmg ? 1 : __builtin_popcount(h->law_present);  // (the force half of a damage step: one slab per tile)
     LAUNCH_ND((k_slab_gather<2, 2>), (k_slab_gather<3, 3>), nblk(r.an + r.bn), r.a0, r.an, r.b0, r.bn, h->g, td, h->N.force);
   };
   // the search of the next step rides on K5 (k5_tile<., ., true>, seeds and bins included).  A slab rank that holds no
@@ -4521,7 +4616,8 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   const bool one_mat = ND == 3 && h->nmats == 1 && law >= 1 && law <= 3;  // its constants by scalar loads (k3_body, UMAT)
   const dim3 grid3(h->ntw), blk3(K3_BLK);
   const double* const no_dU = nullptr;
-  // MD = 1: the fused K3; MD = 5: its state half (the step with the damage hooks, never deterministic)
+  // MD = 1: the fused K3; MD = 5: its state half (the step with the damage hooks; a gather and per-particle stores, no
+  // nodal sum: the same launch forms in deterministic mode)
   auto launch_k3_mode = [&](auto MODE_, int cls, bool signal) {
     constexpr int MD = CT(MODE_);
     TileD td = tile_view(h, cls);
@@ -4677,7 +4773,10 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   // on the handle's stream, no sort, no synchronisation, no allocation (nlps_gpu_set_explicit_damage made the tables).
   auto damage_hook_and_forces = [&]() -> int {
     if (damage_runs_and_hook(h, true)) return 1;  // (every step has searched: the runs are this step's)
-    LAUNCH_ND(k3f_tile<2>, k3f_tile<3>, h->ntw, h->P, h->g, h->N, tile_view(h, 0), h->gstatus_d);
+    if (det)  // one wave per tile over the exact list, one slab per tile (slab_n = 1, slot 0); gather_force sums them
+      LAUNCH_ND_BLK((k3f_wave<2, false>), (k3f_wave<3, false>), h->ntw, 64, h->P, h->g, h->N, tile_view(h, 0), h->gstatus_d);
+    else
+      LAUNCH_ND(k3f_tile<2>, k3f_tile<3>, h->ntw, h->P, h->g, h->N, tile_view(h, 0), h->gstatus_d);
     HIPCHK(hipGetLastError());
     return 0;
   };
@@ -4997,8 +5096,12 @@ static int lagrangian_damage_launches(nlps_gpu* h) {
   const int ND = h->nd;
   const dim3 grid(h->ntw), blk3(K3_BLK);
   if (beps_snapshot(h)) return 1;  // (taken by the first search: nothing to do here for a handle that has searched)
+  // deterministic mode with nlps_gpu_set_deterministic_damage: the exact lists, sorted runs, the one-wave force half and
+  // the fixed-order sum of its slabs; the atomic flush otherwise
+  const bool det = det_implicit(h);
+  if (det && det_prepare(h, "nlps_gpu_lagrangian_evaluation")) return 1;
   TileD td = tile_view(h);
-  td.slab = nullptr;  // (the atomic flush: damage clouds are outside the deterministic contract, see det_implicit)
+  if (!det) td.slab = nullptr;
   const int law = h->uniform_law;
   const double* const no_dV = nullptr;
   if (law < 0) {  // one launch per law present, every workgroup compacting its tile's particles of that law first (FILT)
@@ -5027,7 +5130,12 @@ static int lagrangian_damage_launches(nlps_gpu* h) {
   if (damage_runs_and_hook(h, h->xrun_gen != h->tan_gen)) return 1;
   h->xrun_gen = h->tan_gen;
   h->dmg_fused_evals++;
-  LAUNCH_ND_BLK((k3f_tile<2, true>), (k3f_tile<3, true>), h->ntw, K3_BLK, h->P, h->g, h->N, td, h->gstatus_d);
+  if (det) {
+    LAUNCH_ND_BLK((k3f_wave<2, true>), (k3f_wave<3, true>), h->ntw, 64, h->P, h->g, h->N, td, h->gstatus_d);
+    DET_GATHER(2, 3, 1, h->N.force);
+  } else {
+    LAUNCH_ND_BLK((k3f_tile<2, true>), (k3f_tile<3, true>), h->ntw, K3_BLK, h->P, h->g, h->N, td, h->gstatus_d);
+  }
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -5111,7 +5219,9 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
     hipLaunchKernelGGL(k_expand_reset, dim3(nblk(h->g.nnodes)), dim3(BLK), 0, h->stream, h->N.dU, u, h->n2m_d, h->g.nnodes, ND,
                        h->N.force, h->n0, h->nwn);
   if (h->timing) HIPCHK(hipEventRecord(h->ev[2], h->stream));
-  if (det_implicit(h)) {
+  if (dmg) {  // (before the deterministic form below, which does not hold the hook: it has a deterministic form of its own)
+    if (lagrangian_damage_launches(h)) return 1;
+  } else if (det_implicit(h)) {
     // deterministic mode: one wave per tile and per law present over the exact lists (ordered compaction), one slab per
     // (tile, law) -- a tile without a particle of the law writes zeros --, then the fixed-order sum into N.force
     if (det_prepare(h, "nlps_gpu_lagrangian_evaluation")) return 1;
@@ -5133,8 +5243,6 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
       });
     });
     DET_GATHER(2, 3, td.slab_n, h->N.force);
-  } else if (dmg) {
-    if (lagrangian_damage_launches(h)) return 1;
   } else {
     TileD td = tile_view(h);
     td.slab = nullptr;  // (the atomic flush: handles outside the deterministic implicit path, see det_implicit)

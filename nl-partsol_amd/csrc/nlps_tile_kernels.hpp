@@ -1689,6 +1689,90 @@ __global__ __launch_bounds__(K3_BLK, 2) void k3f_tile(PView P, GridD g, NView N,
   }
 }
 
+// The deterministic sibling (nlps_gpu_set_deterministic_damage): ONE wave per tile walks the exact canonical list
+// (k_tile_order<., true>) in list order, accumulates into the same window with the same arithmetic and leaves it as the
+// tile's one slab; k_slab_gather<ND, ND> then sums the slabs per node in a fixed order.  No global atomics on the forces.
+// A kernel of its own rather than a template form of k3f_tile, whose compiled code stays what it was.  Every thread of the
+// wave arrives at both barriers (the work item is uniform, the barriers stand outside the particle loop): a lane without a
+// particle of the list -- or a list of zero particles -- passes them like every other lane.  PLUS: as k3f_tile.
+template <int ND, bool PLUS>
+__global__ __launch_bounds__(64) void k3f_wave(PView P, GridD g, NView N, TileD td, int* __restrict__ gstatus) {
+  NLPS_FP_CONTRACT
+  constexpr int KN = Lme<ND>::KN, WA = TileCfg<ND>::WA, PSA = TileCfg<ND>::PSA, NWA = TileCfg<ND>::NWA;
+  __shared__ double fac[ND * NWA];
+  TileWork tw;
+  if (!tile_work_item(td, tw)) return;
+  const int tile = tw.tile, cnt = td.count[tile];
+  int w0[3];
+  tile_origin<ND>(td, tile, w0);
+  for (int idx = threadIdx.x; idx < ND * NWA; idx += 64) fac[idx] = 0.0;
+  __syncthreads();
+  const int start = td.start[tile];
+  for (int s = threadIdx.x; s < cnt; s += 64) {
+    const int p = td.order[start + s];
+    Lme<ND> c;
+    double lam[ND], beta;
+    if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
+    double Zinv, r[ND], J[ND * ND], Jm1[ND * ND], tau[ND * ND], DF[ND * ND], B[ND * ND], z;
+    lme_moments_h<ND>(c, Zinv, r, J);
+    load_block<ND>(P, F_TAU, p, tau, z);
+    load_block<ND>(P, F_DF, p, DF, z);
+    if (!(inverse<ND>(Jm1, J) && force_operator<ND>(B, tau, DF, Jm1, PF(P, F_VOL0, p), PLUS ? 1.0 : -1.0))) {
+      atomicOr(&P.status[p], ST_JACOBIAN);
+      atomicOr(gstatus, ST_JACOBIAN);
+      continue;
+    }
+    NLPS_YZ_LOCALS(c);
+    (void)ly5;
+    (void)lz5;
+    // -f_A = p_A * (B l_A) with l = a - h u:  B l = B a - h (B[.][x] u_i + B[.][y] v_j + B[.][z] w_k)   (as k3_body)
+    const double hx = c.lx[2] - c.lx[3];
+    const double al[3] = {c.lx[2], c.ly[2], (ND == 3) ? c.lz[2 % KN] : 0.0};
+    double Ba[ND], hB[ND * ND];
+#pragma unroll
+    for (int a = 0; a < ND; a++) {
+      double v = 0.0;
+#pragma unroll
+      for (int mm = 0; mm < ND; mm++) {
+        v = fma(B[a * ND + mm], al[mm], v);
+        hB[a * ND + mm] = -hx * B[a * ND + mm];
+      }
+      Ba[a] = v;
+    }
+    const int basea = window_base_a<ND>(c.ijk, w0);
+#pragma unroll 1
+    for (int k = 0; k < KN; k++) {
+      const unsigned pb = plane_bits<ND>(c, k);
+      const int basek = basea + (ND == 3 ? PSA * (k - 2) : 0);
+      const double wz = Zinv * ez5[k];
+      const double ck = (double)(k - 2);
+      double cz[ND];
+#pragma unroll
+      for (int a = 0; a < ND; a++) cz[a] = (ND == 3) ? fma(hB[a * ND + (2 % ND)], ck, Ba[a]) : Ba[a];
+      unsigned pbs = pb << 7;  // pop_member: bit 24 (j = 4, i = 4) first
+#pragma unroll
+      for (int j = 4; j >= 0; j--) {
+        const double w = wz * ey5[j];
+        double cr[ND];
+#pragma unroll
+        for (int a = 0; a < ND; a++) cr[a] = fma(hB[a * ND + 1], (double)(j - 2), cz[a]);
+#pragma unroll
+        for (int i = 4; i >= 0; i--)
+          if (pop_member(pbs)) {
+            const int li = basek + (i - 2) + WA * (j - 2);
+            const double we = w * c.ex[i];
+#pragma unroll
+            for (int a = 0; a < ND; a++) lds_add(&fac[a * NWA + li], we * fma(hB[a * ND + 0], (double)(i - 2), cr[a]));
+          }
+      }
+    }
+  }
+  __syncthreads();
+  // (fac has the slab's layout already -- rows of WA, planes of PSA --: a plain copy, as k3_body's)
+  double* __restrict__ out = td.slab + ((size_t)tile * td.slab_n + td.slab_slot) * (ND * NWA);
+  for (int qq = threadIdx.x; qq < NWA * ND; qq += 64) out[qq] = fac[qq];
+}
+
 // Sums, for every node of two node ranges, the window slabs of the tiles whose window holds the node (<= 2 per axis)
 // in a fixed order and writes out[node][NF]: the second half of the P2G flush (see TileD::slab).  A tile's slab is
 // valid iff the tile was launched this step (inside [tile0, tile0 + ntw) and count > 0); it then holds td.slab_n slabs.

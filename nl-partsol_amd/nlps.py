@@ -106,7 +106,7 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_internal_forces", "nlps_gpu_nodal_traction_forces", "nlps_gpu_roll_state", "nlps_gpu_update_kinetics",
            "nlps_gpu_explicit_step", "nlps_gpu_num_active", "nlps_gpu_explicit_nodal", "nlps_gpu_set_halo_exchange",
            "nlps_gpu_resort", "nlps_gpu_set_resort_interval", "nlps_gpu_set_adaptive_resort", "nlps_gpu_set_law_launch_mode", "nlps_gpu_set_deterministic", "nlps_gpu_set_explicit_damage",
-           "nlps_gpu_set_implicit_damage",
+           "nlps_gpu_set_implicit_damage", "nlps_gpu_set_deterministic_damage",
            "nlps_gpu_rccl_unique_id", "nlps_gpu_rccl_attach", "nlps_gpu_rccl_attach_comm", "nlps_gpu_rccl_detach",
            "nlps_gpu_rccl_reduce", "nlps_gpu_rccl_info", "nlps_gpu_rccl_migrate", "nlps_gpu_rccl_selftest_migrate", "nlps_gpu_rccl_selftest_exchange", "nlps_gpu_touched_layers", "nlps_gpu_set_node_window", "nlps_gpu_set_ghost_bands",
            "nlps_gpu_form_initial_guess", "nlps_gpu_nodal_kinetic_increments", "nlps_gpu_nodal_inertial_forces",
@@ -144,6 +144,8 @@ def lib():
         L.nlps_gpu_set_law_launch_mode.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_set_deterministic.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_set_explicit_damage.argtypes = [C.c_void_p, C.c_int]
+        if hasattr(L, "nlps_gpu_set_deterministic_damage"):  # (NLPS_GPU_LIB may name an older build)
+            L.nlps_gpu_set_deterministic_damage.argtypes = [C.c_void_p, C.c_int]
         if hasattr(L, "nlps_gpu_set_implicit_damage"):  # (NLPS_GPU_LIB may name an older build: tools/implicit_damage_bench.py)
             L.nlps_gpu_set_implicit_damage.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_rccl_unique_id.argtypes = [C.c_void_p]
@@ -568,6 +570,20 @@ class Solver:
         separate stages for a damage cloud); newton_solve and newmark_step take it too.  The definition is in
         include/nlps_gpu.h."""
         self._chk(self.L.nlps_gpu_set_implicit_damage(self.h, 1 if on else 0))
+
+    def set_deterministic_damage(self, on=True):
+        """Extends set_deterministic to a cloud with the damage hooks (off by default: the explicit step refuses such a
+        cloud in the mode, the implicit path sums with atomics).  The contract is in include/nlps_gpu.h."""
+        self._chk(self.L.nlps_gpu_set_deterministic_damage(self.h, 1 if on else 0))
+
+    def debug_damage_runs(self, snapshot=False):
+        """developer read-out: (key[np], first[nnodes], last[nnodes], sorted[np]) of the node runs the last step or
+        residual evaluation left -- of the current closest nodes, or of the eigenerosion snapshot's"""
+        key, srt = np.zeros(self.np, dtype=np.int32), np.zeros(self.np, dtype=np.int32)
+        first, last = np.zeros(self.nnodes, dtype=np.int32), np.zeros(self.nnodes, dtype=np.int32)
+        self.L.nlps_gpu_debug_damage_runs.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _ip, _ip]
+        self._chk(self.L.nlps_gpu_debug_damage_runs(self.h, 1 if snapshot else 0, _i(key), _i(first), _i(last), _i(srt)))
+        return key, first, last, srt
 
     def debug_damage_counters(self):
         """developer read-out: (builds of the node runs of the current closest nodes, residual evaluations that took the fused

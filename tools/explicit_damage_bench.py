@@ -9,6 +9,9 @@ positive.  Three handles that start from the same cloud, in one process:
 After `warm` steps each, `rounds` alternating rounds of `steps` steps are timed with the host clock around work that ends
 in a synchronise; medians over the rounds.  Prints one JSON line and writes it to the file given as fourth argument.
     python tools/explicit_damage_bench.py [cells=50] [rounds=5] [steps=10] [out.json]
+    python tools/explicit_damage_bench.py [cells] [rounds] [steps] [out.json] --deterministic
+        handle (c) beside a twin with nlps_gpu_set_deterministic and nlps_gpu_set_deterministic_damage on:
+        the same rounds, the ratio of the medians, and whether the two damage fields are equal at the end
     python tools/explicit_damage_bench.py cells steps --trace
         for a kernel trace of its own: `steps` level-B force evaluations of the driver cloud (search, masks,
         compatibility, constitutive update, internal forces with the hook: two sorts, k_node_ranges, k_damage,
@@ -42,7 +45,7 @@ def make_case(Gf):
     return case
 
 
-def solver(Gf, driver, nst):
+def solver(Gf, driver, nst, deterministic=False):
     case = make_case(Gf)
     prm = nlps.default_params()
     if driver:
@@ -51,6 +54,9 @@ def solver(Gf, driver, nst):
     S.initialise_shapefun()
     if driver:
         S.set_explicit_damage(True)
+        if deterministic:
+            S.set_deterministic(True)
+            S.set_deterministic_damage(True)
     else:
         S.debug_option("lazy_nodal", 0)
     return case, S
@@ -95,8 +101,12 @@ if "--trace" in sys.argv:
     sys.exit(0)
 
 Gf = quantile_Gf(none)
-forms = {"plain": solver(1e300, False, 1)[1], "damage_none_fails": solver(1e300, True, 1)[1],
-         "damage_quarter_fails": solver(Gf, True, 1)[1]}
+DET = "--deterministic" in sys.argv
+if DET:
+    forms = {"damage_quarter_fails": solver(Gf, True, 1)[1], "damage_quarter_fails_deterministic": solver(Gf, True, 1, True)[1]}
+else:
+    forms = {"plain": solver(1e300, False, 1)[1], "damage_none_fails": solver(1e300, True, 1)[1],
+             "damage_quarter_fails": solver(Gf, True, 1)[1]}
 for S in forms.values():
     run(S, none, WARM)
 times = {k: [] for k in forms}
@@ -108,6 +118,11 @@ out = {"tool": "explicit_damage_bench", "particles": int(dmg.size), "dt": DT, "r
        "Gf": Gf, "failed_share_at_the_end": round(float(dmg.mean()), 4),
        "ms_per_step": {k: [round(t, 4) for t in v] for k, v in times.items()},
        "median_ms_per_step": {k: round(float(np.median(v)), 4) for k, v in times.items()}}
+if DET:
+    med = out["median_ms_per_step"]
+    twin = forms["damage_quarter_fails_deterministic"].download_state(["Damage_n"])["Damage_n"]
+    out["deterministic_over_atomic"] = round(med["damage_quarter_fails_deterministic"] / med["damage_quarter_fails"], 3)
+    out["damage_fields_equal"] = bool(np.array_equal(dmg, twin))
 for S in forms.values():
     S.close()
 line = json.dumps(out)

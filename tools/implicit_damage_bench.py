@@ -19,6 +19,9 @@ the parent commit, through NLPS_GPU_LIB) only the form that exists there is time
 two forms are, under the names "parent" and "parent_twin".  Prints one
 JSON line and writes it to the file given as fourth argument.
     python tools/implicit_damage_bench.py [cells=50] [rounds=5] [reps=5] [out.json]
+    python tools/implicit_damage_bench.py [cells] [rounds] [reps] [out.json] --deterministic
+        the switch-on handle beside a twin with nlps_gpu_set_deterministic and nlps_gpu_set_deterministic_damage on
+        (DESIGN.md 6b), under the names "on" and "on_deterministic": the same series and the ratios of the medians
     python tools/implicit_damage_bench.py cells steps --trace     (switch on, `steps` steps: for a kernel trace)"""
 import importlib
 import json
@@ -44,6 +47,9 @@ SNES = dict(max_it=50, atol=1e-8, rtol=1e-10, stol=1e-8, linesearch="bt", ksp=di
 HAS_SWITCH = hasattr(nlps.lib(), "nlps_gpu_set_implicit_damage")
 # (without the switch two handles of the one form alternate, as "off" and "on" do: two clouds of 1 M particles share the caches)
 FORMS = ("off", "on") if HAS_SWITCH else ("parent", "parent_twin")
+DET = "--deterministic" in sys.argv
+if DET:
+    FORMS = ("on", "on_deterministic")
 none = nlps.BccSet([])
 
 
@@ -57,8 +63,11 @@ def solver(Gf, form, nst):
     prm.driver_eigenerosion = 1
     S = nlps.Solver(3, case["grid_n"], case["origin"], case["h"], case["cloud"], case["materials"], params=prm, nsteps=nst)
     S.initialise_shapefun()
-    if form == "on":
+    if form in ("on", "on_deterministic"):
         S.set_implicit_damage(True)
+    if form == "on_deterministic":
+        S.set_deterministic(True)
+        S.set_deterministic_damage(True)
     return case, S
 
 
@@ -177,6 +186,10 @@ for label in ("Gf_nobody_reaches", "Gf_q75_of_G_at_the_end_of_the_dry_series"):
         Gf_steps = float(np.quantile(estimate_G(hs[FORMS[0]], made[FORMS[0]][0], "J_n"), 0.75))
     for S in hs.values():
         S.close()
+if DET:
+    ratio = lambda d: round(d["on_deterministic"]["median_ms"] / d["on"]["median_ms"], 3)  # noqa: E731
+    out["deterministic_over_atomic"] = {"residual": ratio(out["residual"]["ms_per_evaluation"]),
+                                        **{k: ratio(v["ms_per_step"]) for k, v in out["newmark_step"].items()}}
 line = json.dumps(out)
 print(line)
 if len(args) > 3:
