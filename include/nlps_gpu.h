@@ -227,7 +227,8 @@ int nlps_gpu_update_kinetics(nlps_gpu *h, double alpha_blend, const double *dU, 
 
 /* Fused explicit predictor-corrector step (stage order and formulas of U-Verlet.c:229-253, 301-367,
  * 455-527, 530-676, 919-1010, 1024-1084; internal force in the Kirchhoff form of
- * U-Newmark-beta.c:1257-1374).  gravity[ndim] may be NULL.  One P2G+stress+G2P particle step.
+ * U-Newmark-beta.c:1257-1374; the contour tractions of :805-902 once nlps_gpu_set_explicit_loads has given them).
+ * gravity[ndim] may be NULL.  One P2G+stress+G2P particle step.
  * A cloud that holds Newtonian-Fluid-Compressible is refused at the start of the call (return 1, the law named in
  * nlps_gpu_last_error): the law reads dt_F_n1 and the reference has no working explicit driver that defines that rate. */
 int nlps_gpu_explicit_step(nlps_gpu *h, const nlps_bcc *bcc, int nbcc, int step, double dt,
@@ -257,6 +258,29 @@ int nlps_gpu_explicit_step(nlps_gpu *h, const nlps_bcc *bcc, int nbcc, int step,
  * fluid law (as above).
  * The setter returns 1 for a cloud created without either driver. */
 int nlps_gpu_set_explicit_damage(nlps_gpu *h, int on);
+/* The Neumann contours inside the explicit step: compute_Nodal_Nominal_traction_Forces (U-Verlet.c:805-902), which
+ * compute_Nodal_Forces calls directly behind the internal forces (:680-699), Forces[A] += N_pA T A0_p over the particles
+ * of MPM_Mesh.Neumann_Contours.  The arguments mean what they mean in nlps_gpu_nodal_traction_forces: loads[l].nodes are
+ * PARTICLE indices in the caller's order, dir / value are [dim][nsteps] with the handle's nsteps, A0_p is Vol_0 / thickness
+ * in 2-D and area0[p] (Phi.Area_0, caller's order, required) in 3-D.  Everything is copied to the device: the caller's
+ * arrays may be freed after the call.  nloads == 0 removes the loads, a second call replaces the first; the loads survive
+ * nlps_gpu_resort, the periodic and the adaptive re-sort (the caller's indices keep addressing the same particles).
+ * From then on every nlps_gpu_explicit_step(.., step, ..) adds the contour tractions of `step` to the nodal force on every
+ * dof, fixed or free, behind the internal forces and in front of the nodal equilibrium (:695): the accelerations of free
+ * dofs and the reactions of fixed dofs (Reactions = Total_Forces, :955) contain them, and nlps_gpu_explicit_nodal returns
+ * force = -f_int + sum N_pA T A0_p, accel and reaction with them.  The traction vector of a step starts at zero; each
+ * contour in turn overwrites the directions whose dir is 1 at that step, a direction switched off keeps the value of the
+ * contour before it (:865-869).  N_pA are the shape functions every other stage of the step uses.
+ * The step stays free of allocation, synchronisation and copies: one more kernel on the handle's stream over the contour
+ * particles, and one over the particles behind a re-sort (the caller's index -> slot map).  In deterministic mode one
+ * wave adds the contributions in the caller's contour order behind the fixed-order sum of the force slabs: the step stays
+ * bit-reproducible.  It works in every one-rank form of the step, nlps_gpu_set_explicit_damage included.
+ * Returns 1, with the reason in nlps_gpu_last_error and nothing stored: a particle index outside the cloud; 3-D without
+ * area0; 2-D with thickness <= 0; a handle with a halo callback or an RCCL exchange attached (slab ranks are not built:
+ * a contour particle near a slab face adds to band nodes, and that sum would have to go in front of the exchange of the
+ * nodal forces in every overlap form) -- a step returns 1 if one is attached later while loads are set; a migrated handle.
+ * With loads set, nlps_gpu_explicit_step returns 1 for a step outside [0, nsteps), with or without Dirichlet sets. */
+int nlps_gpu_set_explicit_loads(nlps_gpu *h, const nlps_bcc *loads, int nloads, double thickness, const double *area0);
 /* The damage hooks inside the fused residual (clouds created with driver_eigenerosion or driver_eigensoftening).  Off by
  * default: nlps_gpu_lagrangian_evaluation then runs the separate stages for such a cloud (nlps_gpu_compatibility,
  * nlps_gpu_constitutive, nlps_gpu_internal_forces with its two sorts, the traction and inertial calls), exactly as before.
@@ -810,7 +834,8 @@ int nlps_host_write_nodes_vtk(const char *path, const nlps_gid_info *info, const
 /* Time (ms, HIP events on the handle's stream) of the kernels of the last explicit step:
  * [0] search+activate, [1] lists+Newton+P2G mass/momentum, [2] G2P grad+F+stress+P2G force,
  * [3] G2P kinematics+roll, [4] nodal/mask kernels, [5] a calibration bracket around a kernel of K3's grid that
- * does nothing (the part of a one-kernel bracket that is not kernel time).  Enabled with nlps_gpu_set_timing(h,1). */
+ * does nothing (the part of a one-kernel bracket that is not kernel time), [7] the bracket around the contour-traction
+ * kernel of nlps_gpu_set_explicit_loads (inside [4]; 0 without loads).  Enabled with nlps_gpu_set_timing(h,1). */
 int nlps_gpu_set_timing(nlps_gpu *h, int on);
 int nlps_gpu_get_timing(nlps_gpu *h, float ms[8]);
 

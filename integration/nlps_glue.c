@@ -311,6 +311,24 @@ int nlps_glue_lagrangian_evaluation_static(const nlps_glue *G, Particle MPM_Mesh
                                          nneumann, TimeStep, 1);
 }
 
+/* compute_Nodal_Nominal_traction_Forces (U-Verlet.c:805-902) of the explicit drivers: call once behind nlps_glue_create
+ * (and again when the contours change); every nlps_gpu_explicit_step then adds Forces[A] += N_pA T A0_p of its TimeStep
+ * behind the internal forces (:695).  neumann[] = MPM_Mesh.Neumann_Contours flattened as for nlps_glue_lagrangian_evaluation
+ * (nodes = particle indices); the library copies it, the caller may free it afterwards.  nneumann = 0 removes the loads. */
+int nlps_glue_set_explicit_loads(const nlps_glue *G, Particle MPM_Mesh, const nlps_bcc *neumann, int nneumann) {
+#if NumberDimensions == 2
+  const double thickness = Thickness_Plain_Stress;
+  const double *area0 = NULL;
+  (void)MPM_Mesh;
+#else
+  const double thickness = 1.0;
+  const double *area0 = MPM_Mesh.Phi.Area_0.nV; /* :851-857 */
+#endif
+  const int STATUS = nlps_gpu_set_explicit_loads(G->gpu, neumann, nneumann, thickness, area0);
+  if (STATUS != EXIT_SUCCESS) fprintf(stderr, "" RED "%s" RESET "\n", nlps_gpu_last_error(G->gpu));
+  return STATUS;
+}
+
 /* __jacobian_evaluation (U-Newmark-beta.c:1646-1830) as a MatShell instead of an assembled MATAIJ: the matrix-free
  * counterpart of nlps_gpu_tangent_assemble + nlps_gpu_tangent_coo.  Call it where the driver assembles the Jacobian
  * (the SNES Jacobian callback): it linearises at the state the last residual evaluation left, with alpha_1 M on the

@@ -1788,6 +1788,16 @@ struct nlps_gpu {
   // k_run_first / k_run_fill), tables of their own -- the level-B force stage rebuilds dmg_* with its sorts every call.
   // xrun_*0: the tables of the snapshot's closest nodes, made once and again after a re-sort has renumbered the slots
   bool explicit_damage = false;
+  // the Neumann contours of the explicit step (nlps_gpu_set_explicit_loads): one entry per contour particle
+  // in the caller's contour order -- caller's index, contour number, A0 (3-D) -- and the traction vector of every
+  // (step, contour) with the carry-over resolved.  xl_inv_d: caller's index -> slot, rebuilt by the first step behind a
+  // re-sort (xl_inv_valid), never per step.  xl_lane_map: developer switch between the two work mappings of the kernel.
+  int xl_n = 0, xl_nloads = 0;
+  double xl_thickness = 1.0;
+  DevBuf<int> xl_ids_d, xl_load_d, xl_inv_d;
+  DevBuf<double> xl_a0_d, xl_T_d;
+  bool xl_inv_valid = false, xl_lane_map = false;
+  hipEvent_t xl_ev[2] = {};  // bracket of the kernel (timing only: slot 7 of nlps_gpu_get_timing)
   // the fused damage residual (nlps_gpu_set_implicit_damage): the same tables; the runs of the current closest nodes are
   // built at the first evaluation and reused while nothing has moved, reordered or re-listed particles (xrun_gen == tan_gen)
   bool implicit_damage = false;
@@ -2551,6 +2561,7 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
   h->debt = 0.0;
   h->xrun_tables0 = false;  // (slot numbers)
   h->xrun_tables = false;   // (read-out: the runs of the current closest nodes hold the old slot numbers until the next build)
+  h->xl_inv_valid = false;  // (the caller's index -> slot map of the explicit loads)
   return 0;
 }
 
@@ -2677,6 +2688,7 @@ extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_option(nlps
   if (k == "lazy_nodal") h->lazy_nodal = (int)value;             // folded explicit step: 0 never, 1 below 2 M particles, 2 always
   else if (k == "async_lists") h->async_lists = value != 0;      // one-rank folded step: next step's lists on the side stream (1) or in front of K2 (0)
   else if (k == "tangent_symmetric") h->tangent_symmetric = value != 0;  // Neo-Hookean clouds: half rows + mirror (1) or every pair (0)
+  else if (k == "loads_lane_map") h->xl_lane_map = value != 0;  // explicit loads: one lane per contour particle (1) or one wave (0)
   else {
     h->err = "nlps_gpu_debug_option: unknown option " + k;
     return 1;
@@ -2839,6 +2851,8 @@ extern "C" int nlps_gpu_destroy(nlps_gpu* h) {
   (void)hipStreamSynchronize(h->stream);
   for (int i = 0; i < 8; i++) (void)hipEventDestroy(h->ev[i]);
   for (hipEvent_t e : h->evw)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : h->xl_ev)
     if (e) (void)hipEventDestroy(e);
   // the members free their memory here: after the synchronise above, before the stream they were used on goes
   const hipStream_t owned = h->own_stream ? h->stream : nullptr;
@@ -4366,6 +4380,189 @@ extern "C" int nlps_gpu_nodal_traction_forces(nlps_gpu* h, double* R, const nlps
   return from_grid(h, R, h->gridA, h->nd, h->nd, 0, 0, 1, nullptr);
 }
 
+// The Neumann contours inside the explicit step (nlps_gpu_set_explicit_loads; compute_Nodal_Nominal_traction_Forces,
+// U-Verlet.c:805-902, called at :695 behind the internal forces): force_A += N_pA T A0_p on every dof, into the nodal
+// force accumulator of the step.  The entries are the contour particles in the caller's contour order; a.T is the row of
+// this step in the table of carried traction vectors ([contour][3]).  Contour particles lie on surfaces: their rows are
+// scattered in memory whatever the mapping, so the mapping is chosen for the atomics:
+//   MAP 0  one wave per entry, its lanes over the (stencil slot, direction) pairs of the particle, direction fastest: every
+//          lane re-forms the factors of the one particle (wave-uniform loads) and a wave-instruction of atomics covers
+//          runs of 5 x d consecutive doubles (one lattice row of the stencil each), 6 instructions in 3-D, 1 in 2-D --
+//          float atomics run at the memory side and are priced per 64-B request, so the shape decides;
+//   MAP 1  one lane per entry (k_traction's mapping, kept behind the developer switch "loads_lane_map" to measure against):
+//          up to 125 x d dependent global atomics per lane, 64 particles' rows per wave-instruction;
+//   MAP 2  deterministic mode: ONE wave walks the entries in order like k_traction_serial, a plain read-add-write per
+//          member (distinct addresses inside one entry) and a barrier between two entries.
+struct XlArgs {
+  const int *ids, *load, *inv;  // [n] caller's index, [n] contour number, [np] caller's index -> slot
+  const double *a0, *T;         // [n] A0 (3-D; 2-D: Vol_0 / thickness), [nloads][3] traction vectors of this step
+  double thickness;
+  int n;
+};
+template <int N>
+__device__ __forceinline__ double pick_factor(const double (&e)[N], int i) {  // e[i] without an indexed (scratch) array
+  double v = e[0];
+#pragma unroll
+  for (int q = 1; q < N; q++) v = i == q ? e[q] : v;
+  return v;
+}
+template <int ND, int MAP>
+__device__ __forceinline__ void explicit_traction_entry(const PView& P, const GridD& g, const XlArgs& a, int e, int lane,
+                                                        double* __restrict__ force) {
+  constexpr int KN = Lme<ND>::KN, NS = 25 * KN;
+  const int p = a.inv[a.ids[e]];
+  Lme<ND> c;
+  double lam[ND], beta;
+  if (!load_lme<ND>(P, g, p, c, lam, beta)) return;
+  const double a0 = ND == 3 ? a.a0[e] : PF(P, F_VOL0, p) / a.thickness;  // U-Verlet.c:851-857
+  const double zinv = lme_zinv<ND>(c);
+  const double* T = a.T + (size_t)a.load[e] * 3;
+  if (MAP == 1) {
+    double Ta[ND];
+#pragma unroll
+    for (int d = 0; d < ND; d++) Ta[d] = T[d];
+    for (int k = 0; k < KN; k++)
+      for (int j = 0; j < 5; j++)
+        for (int i = 0; i < 5; i++) {
+          if (!c.on(i + 5 * j + 25 * k)) continue;
+          const double Npa = c.ex[i] * c.ey[j] * (ND == 3 ? c.ez[k % KN] : 1.0) * zinv;
+          const int node = c.I0 + c.node_offset(g, i, j, k + (ND == 3 ? 0 : 2));
+#pragma unroll
+          for (int d = 0; d < ND; d++) atomic_add_f64(force + (size_t)node * ND + d, Npa * Ta[d] * a0);
+        }
+    return;
+  }
+  for (int q = lane; q < NS * ND; q += 64) {
+    const int m = q / ND, d = q - m * ND;
+    if (!c.on(m)) continue;
+    const int i = m % 5, j = (m / 5) % 5, k = m / 25;
+    const double Npa = pick_factor(c.ex, i) * pick_factor(c.ey, j) * (ND == 3 ? pick_factor(c.ez, k) : 1.0) * zinv;
+    const int node = c.I0 + c.node_offset(g, i, j, k + (ND == 3 ? 0 : 2));
+    double* o = force + (size_t)node * ND + d;
+    const double v = Npa * T[d] * a0;
+    if (MAP == 2) *o = *o + v;
+    else atomic_add_f64(o, v);
+  }
+}
+template <int ND, int MAP>
+__global__ __launch_bounds__(MAP == 2 ? 64 : BLK) void k_explicit_traction(PView P, GridD g, XlArgs a, double* force) {
+  if (MAP == 2) {
+    for (int e = 0; e < a.n; e++) {  // uniform
+      explicit_traction_entry<ND, 2>(P, g, a, e, threadIdx.x, force);
+      __syncthreads();  // the stores of this particle are done before the next one reads the same nodes
+    }
+  } else {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int e = MAP == 1 ? t : t >> 6;
+    if (e < a.n) explicit_traction_entry<ND, MAP>(P, g, a, e, threadIdx.x & 63, force);
+  }
+}
+
+static const char* explicit_loads_halo_msg =
+    "the contour tractions inside the explicit step are built for one rank: with a halo callback or an RCCL exchange "
+    "attached, a contour particle near a slab face would add to band nodes behind the exchange of the nodal forces";
+extern "C" int nlps_gpu_set_explicit_loads(nlps_gpu* h, const nlps_bcc* loads, int nloads, double thickness,
+                                           const double* area0) {
+  const char* who = "nlps_gpu_set_explicit_loads: ";
+  const int ND = h->nd, np = h->P.np, nsteps = h->nsteps;
+  if (nloads < 0 || (nloads > 0 && !loads)) {
+    h->err = std::string(who) + "nloads < 0, or loads is NULL";
+    return 1;
+  }
+  if (nloads > 0) {
+    if (h->halo || h->rccl) {
+      h->err = std::string(who) + explicit_loads_halo_msg;
+      return 1;
+    }
+    if (h->migrated) {
+      h->err = std::string(who) + "not available after a migration (particle order is by global id)";
+      return 1;
+    }
+    if (ND == 3 && !area0) {
+      h->err = std::string(who) + "the 3-D build needs Phi.Area_0 (area0)";
+      return 1;
+    }
+    if (ND == 2 && !(thickness > 0.0)) {
+      h->err = std::string(who) + "the 2-D build needs Thickness_Plain_Stress (thickness) > 0";
+      return 1;
+    }
+  }
+  std::vector<int> ids, lidx;
+  std::vector<double> A;
+  for (int l = 0; l < nloads; l++)
+    for (int q = 0; q < loads[l].nnodes; q++) {
+      const int p = loads[l].nodes[q];
+      if (p < 0 || p >= np) {
+        h->err = std::string(who) + "particle index outside the cloud";
+        return 1;
+      }
+      ids.push_back(p);
+      lidx.push_back(l);
+      if (ND == 3) A.push_back(area0[p]);
+    }
+  const size_t n = ids.size();
+  // the traction vector of every step: zero at the start of the step, each contour in turn overwrites the directions it
+  // switches on and hands the others on to the next contour (U-Verlet.c:865-869)
+  std::vector<double> T(n ? (size_t)nsteps * nloads * 3 : 0, 0.0);
+  if (n)
+    for (int t = 0; t < nsteps; t++) {
+      double Tc[3] = {0.0, 0.0, 0.0};
+      for (int l = 0; l < nloads; l++) {
+        for (int i = 0; i < ND && i < loads[l].dim; i++)
+          if (loads[l].dir[(size_t)i * nsteps + t] == 1) Tc[i] = loads[l].value[(size_t)i * nsteps + t];
+        for (int i = 0; i < 3; i++) T[((size_t)t * nloads + l) * 3 + i] = Tc[i];
+      }
+    }
+  DevBuf<int> ids_d, load_d, inv_d;
+  DevBuf<double> a0_d, T_d;
+  if (n) {
+    HIPCHK(ids_d.reserve(n));
+    HIPCHK(load_d.reserve(n));
+    HIPCHK(T_d.reserve(T.size()));
+    if (ND == 3) HIPCHK(a0_d.reserve(n));
+    HIPCHK(hipMemcpy(ids_d, ids.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(load_d, lidx.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(T_d, T.data(), T.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (ND == 3) HIPCHK(hipMemcpy(a0_d, A.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    if (h->xl_inv_d) inv_d.swap(h->xl_inv_d);  // (sized by the cloud: kept from one set of loads to the next)
+    else HIPCHK(inv_d.reserve((size_t)std::max(np, 1)));
+  }
+  // the copies above are ordered on the default stream only (see ensure_bcs), and a step in flight may still read the
+  // tables this call replaces
+  HIPCHK(hipDeviceSynchronize());
+  h->xl_ids_d = std::move(ids_d);
+  h->xl_load_d = std::move(load_d);
+  h->xl_a0_d = std::move(a0_d);
+  h->xl_T_d = std::move(T_d);
+  h->xl_inv_d = std::move(inv_d);
+  h->xl_n = (int)n;
+  h->xl_nloads = n ? nloads : 0;
+  h->xl_thickness = thickness;
+  h->xl_inv_valid = false;
+  return 0;
+}
+
+// the contour tractions of `step` into the nodal force of the explicit step (xl_n > 0; the checks are the step's)
+static int explicit_loads_launch(nlps_gpu* h, int step) {
+  if (!h->xl_inv_valid) {  // the first step behind a re-sort (or the setter): caller's index -> slot
+    hipLaunchKernelGGL(k_inverse_perm, dim3(nblk(h->P.np)), dim3(BLK), 0, h->stream, h->perm_d, h->P.np, h->xl_inv_d.get());
+    h->xl_inv_valid = true;
+  }
+  const XlArgs a{h->xl_ids_d, h->xl_load_d, h->xl_inv_d, h->xl_a0_d, h->xl_T_d + (size_t)step * h->xl_nloads * 3, h->xl_thickness,
+                 h->xl_n};
+  if (h->timing) {
+    for (hipEvent_t& e : h->xl_ev)
+      if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(h->xl_ev[0], h->stream));
+  }
+  if (h->deterministic) LAUNCH_ND_BLK((k_explicit_traction<2, 2>), (k_explicit_traction<3, 2>), 1, 64, h->P, h->g, a, h->N.force);
+  else if (h->xl_lane_map) LAUNCH_ND((k_explicit_traction<2, 1>), (k_explicit_traction<3, 1>), nblk(h->xl_n), h->P, h->g, a, h->N.force);
+  else LAUNCH_ND((k_explicit_traction<2, 0>), (k_explicit_traction<3, 0>), nblk(h->xl_n, BLK / 64), h->P, h->g, a, h->N.force);
+  HIPCHK(hipGetLastError());
+  if (h->timing) HIPCHK(hipEventRecord(h->xl_ev[1], h->stream));
+  return 0;
+}
+
 extern "C" int nlps_gpu_roll_state(nlps_gpu* h) {
   tan_stale(h, "nlps_gpu_roll_state");
   if (materialise_roll(h)) return 1;
@@ -4484,7 +4681,16 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
              "node runs take ranks and run starts from atomics)";
     return 1;
   }
-  if (nbcc > 0 && check_step(h, step, "nlps_gpu_explicit_step")) return 1;
+  const bool loads = h->xl_n > 0 && h->P.np > 0;  // the Neumann contours (nlps_gpu_set_explicit_loads)
+  if (loads && (h->halo || h->rccl)) {
+    h->err = std::string("nlps_gpu_explicit_step: ") + explicit_loads_halo_msg;
+    return 1;
+  }
+  if (loads && h->migrated) {
+    h->err = "nlps_gpu_explicit_step: the explicit loads are not available after a migration (particle order is by global id)";
+    return 1;
+  }
+  if ((nbcc > 0 || loads) && check_step(h, step, "nlps_gpu_explicit_step")) return 1;
   if (ensure_bcs(h, bcc, nbcc)) return 1;
   if (!h->Pd_alt && h->resort_every > 0 && h->P.np > 0) {
     // the twin block of the periodic re-sort, at the first step of the fused scheme rather than inside the first
@@ -4832,6 +5038,11 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   HIPCHK(hipGetLastError());
   if (h->timing) HIPCHK(hipEventRecord(h->ev[4], h->stream));
   gather_force(ov ? 2 : 0);
+  // the contour tractions (one rank: ov is false): behind K3's atomics -- or the fixed-order sum of its slabs -- in stream
+  // order, in front of the readers of N.force (k_nodal_accel, K5's windows; the folded form keeps N.force for
+  // materialise_nodal).  Nothing resets N.force between k_step_clear / k_dilate_scan at the head of the step and here;
+  // the side stream of the async lists forks behind this launch and resets the twin set only.
+  if (loads && explicit_loads_launch(h, step)) return 1;
   if (halo(h, h->N.force, ND, 8, 0, ov ? 1 : 0)) return 1;
   // nodal acceleration; S5
   if (ov) {
@@ -4881,7 +5092,8 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     h->ms[2] = t34;
     h->ms[3] = t56;
     h->ms[4] = t23 + t45;
-    h->ms[7] = 0.f;
+    h->ms[7] = 0.f;  // the contour-traction kernel (nlps_gpu_set_explicit_loads)
+    if (loads) HIPCHK(hipEventElapsedTime(&h->ms[7], h->xl_ev[0], h->xl_ev[1]));
     h->ms[6] = 0.f;  // time the handle's stream spent in / waiting for the ghost-layer exchanges of this step
     for (int q = 0; q < h->nwait; q++) {
       float tw = 0.f;

@@ -106,6 +106,7 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_internal_forces", "nlps_gpu_nodal_traction_forces", "nlps_gpu_roll_state", "nlps_gpu_update_kinetics",
            "nlps_gpu_explicit_step", "nlps_gpu_num_active", "nlps_gpu_explicit_nodal", "nlps_gpu_set_halo_exchange",
            "nlps_gpu_resort", "nlps_gpu_set_resort_interval", "nlps_gpu_set_adaptive_resort", "nlps_gpu_set_law_launch_mode", "nlps_gpu_set_deterministic", "nlps_gpu_set_explicit_damage",
+           "nlps_gpu_set_explicit_loads",
            "nlps_gpu_set_implicit_damage", "nlps_gpu_set_deterministic_damage",
            "nlps_gpu_rccl_unique_id", "nlps_gpu_rccl_attach", "nlps_gpu_rccl_attach_comm", "nlps_gpu_rccl_detach",
            "nlps_gpu_rccl_reduce", "nlps_gpu_rccl_info", "nlps_gpu_rccl_migrate", "nlps_gpu_rccl_selftest_migrate", "nlps_gpu_rccl_selftest_exchange", "nlps_gpu_touched_layers", "nlps_gpu_set_node_window", "nlps_gpu_set_ghost_bands",
@@ -144,6 +145,8 @@ def lib():
         L.nlps_gpu_set_law_launch_mode.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_set_deterministic.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_set_explicit_damage.argtypes = [C.c_void_p, C.c_int]
+        if hasattr(L, "nlps_gpu_set_explicit_loads"):  # (NLPS_GPU_LIB may name an older build)
+            L.nlps_gpu_set_explicit_loads.argtypes = [C.c_void_p, C.POINTER(Bcc), C.c_int, C.c_double, C.c_void_p]
         if hasattr(L, "nlps_gpu_set_deterministic_damage"):  # (NLPS_GPU_LIB may name an older build)
             L.nlps_gpu_set_deterministic_damage.argtypes = [C.c_void_p, C.c_int]
         if hasattr(L, "nlps_gpu_set_implicit_damage"):  # (NLPS_GPU_LIB may name an older build: tools/implicit_damage_bench.py)
@@ -564,6 +567,14 @@ class Solver:
         """The eigenerosion / eigensoftening hooks inside explicit_step (off by default: the step refuses a damage cloud);
         the definition of such a step is in include/nlps_gpu.h."""
         self._chk(self.L.nlps_gpu_set_explicit_damage(self.h, 1 if on else 0))
+
+    def set_explicit_loads(self, loads, thickness=1.0, area0=None):
+        """The Neumann contours of explicit_step (compute_Nodal_Nominal_traction_Forces): a BccSet whose nodes are particle
+        indices in the caller's order, or None to remove the loads.  Everything is copied to the device.  The contract is
+        in include/nlps_gpu.h."""
+        a0 = None if area0 is None else np.ascontiguousarray(area0, dtype=np.float64)
+        self._chk(self.L.nlps_gpu_set_explicit_loads(self.h, None if loads is None else loads.arr, 0 if loads is None else loads.n,
+                                                     float(thickness), None if a0 is None else a0.ctypes.data))
 
     def set_implicit_damage(self, on=True):
         """The eigenerosion / eigensoftening hooks inside the fused residual (off by default: lagrangian_evaluation runs the
