@@ -281,6 +281,68 @@ int nlps_gpu_set_explicit_damage(nlps_gpu *h, int on);
  * nodal forces in every overlap form) -- a step returns 1 if one is attached later while loads are set; a migrated handle.
  * With loads set, nlps_gpu_explicit_step returns 1 for a step outside [0, nsteps), with or without Dirichlet sets. */
 int nlps_gpu_set_explicit_loads(nlps_gpu *h, const nlps_bcc *loads, int nloads, double thickness, const double *area0);
+/* The step record: one small row of doubles per recorded step, made on the device behind the step and kept in a ring on
+ * the handle -- what a driver watches a run by (energy balance, momenta, min J, the largest velocity of the dynamic Courant
+ * bound of Courant.c:26-45, the reaction on a Dirichlet set, the history of a few particles; the reference's
+ * Energy-Kinetic / Energy-Potential blocks, WriteVtk.c:816-841, and its Out-particles-path-csv events) without
+ * nlps_gpu_download_state.  Inside a step the record adds kernels on the handle's stream and nothing else: no allocation,
+ * no synchronisation, no copy.  With no record set a step launches what it launched before.
+ *
+ * A row is [global block: NLPS_REC_NGLOBAL doubles][reactions: nsets x 3][probes: nprobes x probe_doubles]
+ * (nlps_gpu_step_record_layout gives the offsets).
+ * Global block: every quantity is the reduction over what nlps_gpu_download_state would return at that point --
+ *   mass = sum m, momentum = sum m v, angular = sum m x cross v about the coordinate origin (2-D: slot +2 only), mass_x =
+ *   sum m x, kinetic = 1/2 sum m |v|^2, strain = sum W Vol_0, volume = sum Vol_0 J_n, vmax_comp = max_p max_j |v_pj|,
+ *   vmax_norm = max_p |v_p|, J_min / J_max over J_n, EPS_max over EPS_n, Damage_max over Damage_n, failed = the number of
+ *   particles with Damage_n == 1, status = the handle's failure-flag word read in stream order.  Slots of the third
+ *   dimension are 0 in 2-D.  An empty cloud: sums 0, maxima of non-negative quantities 0, J_min = +inf, J_max = -inf.
+ *   step = the step argument (nlps_gpu_record_now: the tag), kind = NLPS_REC_KIND_*, dt = the step's (NOW: 0), time = the
+ *   sum of the dt of every explicit step and every converged Newmark step since the record was set, recorded or not.
+ *   After a folded explicit step the hyperelastic laws have not stored tau and W: the record re-forms them in registers
+ *   from the stored F_n and J_n with the code the download uses, and writes nothing to the particle arrays; in every other
+ *   state it reads the stored values.  The sums are made without float atomics in a fixed order: a row is bit-reproducible
+ *   for a given memory order of the particles.
+ * Reactions: after an explicit step, for set s < min(nsets, nbcc) and direction k, the sum over the nodes of bcc[s] of the
+ *   reaction nlps_gpu_explicit_nodal would return for dof (node, k), over the dofs with dir[k][step] == 1 (contour tractions
+ *   and gravity enter as they do there); formed from the kept nodal sums without making the lazy nodal arrays.  Slots of
+ *   sets the step did not have, and every reaction slot of a row of another kind, are NaN.
+ * Probes: per probed particle (caller's index; the indices survive every re-sort) the fields selected in probe_fields in
+ *   ascending bit order, laid out as in nlps_gpu_download_state (ndim per vector, 5 or 9 per tensor): x_GC, dis, vel, acc,
+ *   F_n, Stress, J_n, EPS_n, Damage_n, W.
+ * Rows are written at the end of nlps_gpu_explicit_step (every one-rank form; on a slab rank the particle sums are that
+ * rank's share: add the sums and take min / max across the ranks), at the end of a converged nlps_gpu_newmark_step, and
+ * by nlps_gpu_record_now.  The setter returns 1 with the reason in nlps_gpu_last_error and stores nothing for every < 1,
+ * capacity < 1, a negative count, a probe index outside the cloud, nprobes > 0 with probe_fields == 0 (or a bit outside
+ * NLPS_PROBE_*), and nprobes > 0 or nsets > 0 on a handle with a halo callback or an RCCL exchange attached or on a
+ * migrated handle -- a step returns 1 if one is attached later while such a record is set.  A second set replaces the
+ * first (behind a device synchronise) and starts the row count and the time at zero; cfg == NULL switches the record off
+ * and frees it. */
+enum { NLPS_REC_KIND_NOW = 0, NLPS_REC_KIND_EXPLICIT = 1, NLPS_REC_KIND_NEWMARK = 2 };
+enum { /* offsets into the global block of a row, doubles */
+  NLPS_REC_STEP = 0, NLPS_REC_KIND = 1, NLPS_REC_DT = 2, NLPS_REC_TIME = 3, NLPS_REC_NP = 4, NLPS_REC_MASS = 5,
+  NLPS_REC_MOMENTUM = 6 /*3*/, NLPS_REC_ANGULAR = 9 /*3*/, NLPS_REC_MASS_X = 12 /*3*/, NLPS_REC_KINETIC = 15,
+  NLPS_REC_STRAIN = 16, NLPS_REC_VOLUME = 17, NLPS_REC_VMAX_COMP = 18, NLPS_REC_VMAX_NORM = 19, NLPS_REC_J_MIN = 20,
+  NLPS_REC_J_MAX = 21, NLPS_REC_EPS_MAX = 22, NLPS_REC_DAMAGE_MAX = 23, NLPS_REC_FAILED = 24, NLPS_REC_STATUS = 25,
+  NLPS_REC_NGLOBAL = 32 /* 26..31 reserved, 0 */ };
+enum { NLPS_PROBE_X = 1, NLPS_PROBE_DIS = 2, NLPS_PROBE_VEL = 4, NLPS_PROBE_ACC = 8, NLPS_PROBE_F = 16,
+       NLPS_PROBE_STRESS = 32, NLPS_PROBE_J = 64, NLPS_PROBE_EPS = 128, NLPS_PROBE_DAMAGE = 256, NLPS_PROBE_W = 512 };
+typedef struct {
+  int every;            /* >= 1: steps whose `step` argument is a multiple of it are recorded */
+  int capacity;         /* >= 1: rows kept (a ring: the newest `capacity` rows survive) */
+  int nsets;            /* >= 0: reaction totals for the first nsets Dirichlet sets of a step, 3 doubles each */
+  int nprobes; const int *probes;   /* particle indices in the caller's order (copied) */
+  unsigned probe_fields;            /* NLPS_PROBE_*, in ascending bit order inside a probe's block */
+} nlps_record_cfg;
+int nlps_gpu_set_step_record(nlps_gpu *h, const nlps_record_cfg *cfg);      /* NULL: off, frees everything */
+/* doubles per row, offset of the reaction block and of the probe block inside a row, doubles per probe (any pointer may be
+ * NULL); 1 with no record set */
+int nlps_gpu_step_record_layout(nlps_gpu *h, int *row_doubles, int *reaction_offset, int *probe_offset, int *probe_doubles);
+int nlps_gpu_record_now(nlps_gpu *h, int tag);                              /* one row of the state as it stands */
+/* synchronises the handle's stream once.  *total: rows written since the set; *count = min(total, capacity, max_rows);
+ * rows: the newest *count rows, oldest first (rows == NULL: the counts only).  1 with no record set. */
+int nlps_gpu_read_step_records(nlps_gpu *h, long long *total, int *count, double *rows, int max_rows);
+/* the time step of Courant.c: CFL h / Cel, or with a row CFL h / (Cel + row[NLPS_REC_VMAX_COMP]) (DynamicTimeStep) */
+double nlps_host_courant_dt(double CFL, double h, double Cel, const double *row /* or NULL */);
 /* The damage hooks inside the fused residual (clouds created with driver_eigenerosion or driver_eigensoftening).  Off by
  * default: nlps_gpu_lagrangian_evaluation then runs the separate stages for such a cloud (nlps_gpu_compatibility,
  * nlps_gpu_constitutive, nlps_gpu_internal_forces with its two sorts, the traction and inertial calls), exactly as before.

@@ -491,3 +491,33 @@ int nlps_glue_newmark_step(const nlps_glue *G, Particle MPM_Mesh, const nlps_bcc
   if (ksp_iterations) *ksp_iterations = S.linear_iterations;
   return nlps_glue_snes_report(G, STATUS, &S);
 }
+
+/* The step record from one of the reference's particle-path events (Out-particles-path-csv (i_start; i_step; i_end),
+ * NLPS-Out-particle-path-csv.c:62-71, 401-457): the particles of Event.Idx_Path as probes, the Out_csv_particles_path_*
+ * selectors as probe fields, Event.i_step as the interval -- the library records the steps that are multiples of it, so
+ * the reader keeps the rows with i_start <= row[NLPS_REC_STEP] <= i_end.  capacity: rows kept between two reads (the
+ * driver reads when it writes its csv files); nsets: reaction totals for the first nsets Dirichlet sets of
+ * nlps_glue_boundaries (a load-displacement curve), 0 for none.  Energy-Kinetic / Energy-Potential of WriteVtk.c:816-841
+ * are the sums NLPS_REC_KINETIC / NLPS_REC_STRAIN of the same row.  Event == NULL switches the record off. */
+int nlps_glue_set_step_record(const nlps_glue *G, const Event *Out, int capacity, int nsets) {
+  if (Out == NULL) return nlps_gpu_set_step_record(G->gpu, NULL) ? EXIT_FAILURE : EXIT_SUCCESS;
+  nlps_record_cfg cfg;
+  memset(&cfg, 0, sizeof cfg);
+  cfg.every = Out->i_step > 0 ? Out->i_step : 1;
+  cfg.capacity = capacity;
+  cfg.nsets = nsets;
+  cfg.nprobes = Out->Lenght_Path;
+  cfg.probes = Out->Idx_Path;
+  cfg.probe_fields = NLPS_PROBE_X;
+  if (Out->Out_csv_particles_path_Damage) cfg.probe_fields |= NLPS_PROBE_DAMAGE;
+  if (Out->Out_csv_particles_path_Velocity) cfg.probe_fields |= NLPS_PROBE_VEL;
+  if (Out->Out_csv_particles_path_Acceleration) cfg.probe_fields |= NLPS_PROBE_ACC;
+  if (Out->Out_csv_particles_path_Displacement) cfg.probe_fields |= NLPS_PROBE_DIS;
+  if (Out->Out_csv_particles_path_Stress) cfg.probe_fields |= NLPS_PROBE_STRESS;
+  if (Out->Out_csv_particles_path_Deformation_gradient) cfg.probe_fields |= NLPS_PROBE_F;
+  if (nlps_gpu_set_step_record(G->gpu, &cfg) != 0) {
+    fprintf(stderr, "" RED "nlps_glue_set_step_record: %s" RESET "\n", nlps_gpu_last_error(G->gpu));
+    return EXIT_FAILURE;
+  }
+  return EXIT_SUCCESS;
+}

@@ -1472,6 +1472,7 @@ __global__ __launch_bounds__(BLK) void k_fill_orders(int np, const int* __restri
 #include "nlps_tangent_operator.hpp"
 #include "nlps_krylov.hpp"
 #include "nlps_newton.hpp"
+#include "nlps_record.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // physical re-sort of the particle SoA (maintenance, every few dozen steps): restores the
@@ -1798,6 +1799,16 @@ struct nlps_gpu {
   DevBuf<double> xl_a0_d, xl_T_d;
   bool xl_inv_valid = false, xl_lane_map = false;
   hipEvent_t xl_ev[2] = {};  // bracket of the kernel (timing only: slot 7 of nlps_gpu_get_timing)
+  // the step record (nlps_gpu_set_step_record; kernels in nlps_record.hpp).  rec_on is all a step looks at
+  // with no record set.  The ring rec_rows_d holds rec_capacity rows of rec_row doubles; row number g (0-based since the
+  // set) lives in slot g % rec_capacity.  The probes find their particles through xl_inv_d, the map of the explicit loads.
+  int rec_on = 0;
+  int rec_every = 1, rec_capacity = 0, rec_nsets = 0, rec_nprobes = 0, rec_row = 0, rec_probe_doubles = 0;
+  unsigned rec_fields = 0;
+  long long rec_total = 0;
+  double rec_time = 0.0;
+  DevBuf<double> rec_rows_d, rec_part_d;  // [rec_capacity][rec_row], [REC_NQ][blocks of k_rec_particles <= REC_MAX_BLOCKS]
+  DevBuf<int> rec_probes_d;               // [rec_nprobes] caller's indices
   // the fused damage residual (nlps_gpu_set_implicit_damage): the same tables; the runs of the current closest nodes are
   // built at the first evaluation and reused while nothing has moved, reordered or re-listed particles (xrun_gen == tan_gen)
   bool implicit_damage = false;
@@ -4526,6 +4537,8 @@ extern "C" int nlps_gpu_set_explicit_loads(nlps_gpu* h, const nlps_bcc* loads, i
     if (ND == 3) HIPCHK(hipMemcpy(a0_d, A.data(), n * sizeof(double), hipMemcpyHostToDevice));
     if (h->xl_inv_d) inv_d.swap(h->xl_inv_d);  // (sized by the cloud: kept from one set of loads to the next)
     else HIPCHK(inv_d.reserve((size_t)std::max(np, 1)));
+  } else if (h->rec_nprobes > 0) {
+    inv_d.swap(h->xl_inv_d);  // (the probes of the step record read the same map: it stays when the loads go)
   }
   // the copies above are ordered on the default stream only (see ensure_bcs), and a step in flight may still read the
   // tables this call replaces
@@ -4561,6 +4574,200 @@ static int explicit_loads_launch(nlps_gpu* h, int step) {
   HIPCHK(hipGetLastError());
   if (h->timing) HIPCHK(hipEventRecord(h->xl_ev[1], h->stream));
   return 0;
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// The step record (nlps_gpu_set_step_record; kernels: nlps_record.hpp)
+// ------------------------------------------------------------------------------------------------
+static const char* step_record_halo_msg =
+    "reaction totals and probes are built for one rank: not with a halo callback or an RCCL exchange attached, nor after a "
+    "migration (the particle sums alone are allowed there)";
+static int rec_probe_doubles_of(int nd, unsigned fields) {
+  const int T = nd == 2 ? 5 : 9;
+  int n = 0;
+  for (int b = 0; b < 10; b++)
+    if ((fields >> b) & 1u) n += b < 4 ? nd : (b < 6 ? T : 1);
+  return n;
+}
+static void rec_drop(nlps_gpu* h) {
+  h->rec_on = 0;
+  h->rec_capacity = h->rec_nsets = h->rec_nprobes = h->rec_row = h->rec_probe_doubles = 0;
+  h->rec_fields = 0;
+  h->rec_total = 0;
+  h->rec_time = 0.0;
+  h->rec_rows_d.reset();
+  h->rec_part_d.reset();
+  h->rec_probes_d.reset();
+  if (h->xl_n == 0) {  // (the map serves the explicit loads too)
+    h->xl_inv_d.reset();
+    h->xl_inv_valid = false;
+  }
+}
+
+extern "C" int nlps_gpu_set_step_record(nlps_gpu* h, const nlps_record_cfg* cfg) {
+  const char* who = "nlps_gpu_set_step_record: ";
+  if (!cfg) {
+    HIPCHK(hipDeviceSynchronize());  // (a step in flight may still write the ring)
+    rec_drop(h);
+    return 0;
+  }
+  const int np = h->P.np;
+  if (cfg->every < 1 || cfg->capacity < 1) {
+    h->err = std::string(who) + "every >= 1 and capacity >= 1";
+    return 1;
+  }
+  if (cfg->nsets < 0 || cfg->nprobes < 0 || (cfg->nprobes > 0 && !cfg->probes)) {
+    h->err = std::string(who) + "a negative count, or probes is NULL";
+    return 1;
+  }
+  if (cfg->nprobes > 0 && (cfg->probe_fields == 0 || (cfg->probe_fields >> 10) != 0)) {
+    h->err = std::string(who) + "probes need probe_fields (NLPS_PROBE_*)";
+    return 1;
+  }
+  for (int q = 0; q < cfg->nprobes; q++)
+    if (cfg->probes[q] < 0 || cfg->probes[q] >= np) {
+      h->err = std::string(who) + "probe index outside the cloud";
+      return 1;
+    }
+  if ((cfg->nprobes > 0 || cfg->nsets > 0) && (h->halo || h->rccl || h->migrated)) {
+    h->err = std::string(who) + step_record_halo_msg;
+    return 1;
+  }
+  const int pd = cfg->nprobes > 0 ? rec_probe_doubles_of(h->nd, cfg->probe_fields) : 0;
+  const size_t row = (size_t)NLPS_REC_NGLOBAL + (size_t)cfg->nsets * 3 + (size_t)cfg->nprobes * pd;
+  DevBuf<double> rows_d, part_d;
+  DevBuf<int> probes_d, inv_d;
+  HIPCHK(rows_d.reserve(row * (size_t)cfg->capacity));
+  HIPCHK(part_d.reserve((size_t)REC_NQ * REC_MAX_BLOCKS));  // (for any particle count: a migration changes it)
+  if (cfg->nprobes > 0) {
+    HIPCHK(probes_d.reserve((size_t)cfg->nprobes));
+    HIPCHK(hipMemcpy(probes_d, cfg->probes, (size_t)cfg->nprobes * sizeof(int), hipMemcpyHostToDevice));
+    if (!h->xl_inv_d) HIPCHK(inv_d.reserve((size_t)std::max(np, 1)));
+  }
+  HIPCHK(hipMemset(rows_d, 0, row * (size_t)cfg->capacity * sizeof(double)));
+  // the copies above are ordered on the default stream only, and a step in flight may still write the ring this call replaces
+  HIPCHK(hipDeviceSynchronize());
+  h->rec_rows_d = std::move(rows_d);
+  h->rec_part_d = std::move(part_d);
+  h->rec_probes_d = std::move(probes_d);
+  if (inv_d) {
+    h->xl_inv_d = std::move(inv_d);
+    h->xl_inv_valid = false;
+  }
+  h->rec_every = cfg->every;
+  h->rec_capacity = cfg->capacity;
+  h->rec_nsets = cfg->nsets;
+  h->rec_nprobes = cfg->nprobes;
+  h->rec_fields = cfg->nprobes > 0 ? cfg->probe_fields : 0u;
+  h->rec_probe_doubles = pd;
+  h->rec_row = (int)row;
+  h->rec_total = 0;
+  h->rec_time = 0.0;
+  h->rec_on = 1;
+  return 0;
+}
+
+extern "C" int nlps_gpu_step_record_layout(nlps_gpu* h, int* row_doubles, int* reaction_offset, int* probe_offset,
+                                           int* probe_doubles) {
+  if (!h->rec_on) {
+    h->err = "nlps_gpu_step_record_layout: no step record is set";
+    return 1;
+  }
+  if (row_doubles) *row_doubles = h->rec_row;
+  if (reaction_offset) *reaction_offset = NLPS_REC_NGLOBAL;
+  if (probe_offset) *probe_offset = NLPS_REC_NGLOBAL + 3 * h->rec_nsets;
+  if (probe_doubles) *probe_doubles = h->rec_probe_doubles;
+  return 0;
+}
+
+// a record with reaction totals or probes on a handle that has become a slab rank (or migrated) since the set
+static int rec_check(nlps_gpu* h, const char* who) {
+  if ((h->rec_nprobes > 0 || h->rec_nsets > 0) && (h->halo || h->rccl || h->migrated)) {
+    h->err = std::string(who) + ": the step record is set with reaction totals or probes: " + step_record_halo_msg;
+    return 1;
+  }
+  return 0;
+}
+
+// One row of the state as it stands, on the handle's stream: no allocation, no synchronisation, no copy.  bcc / nbcc /
+// step: the Dirichlet sets of the explicit step that has just run (kind NLPS_REC_KIND_EXPLICIT), else nbcc = 0.
+static int rec_write(nlps_gpu* h, int kind, int step, double dt, const nlps_bcc* bcc, int nbcc) {
+  const int np = h->P.np, nb = np > 0 ? std::min(nblk(np, REC_NT), REC_MAX_BLOCKS) : 0;
+  double* row = h->rec_rows_d + (size_t)(h->rec_total % h->rec_capacity) * h->rec_row;
+  const int lazy = (h->rolled && !h->rolled_keep) ? 1 : 0;  // tau and W of the hyperelastic laws are not stored
+  if (np > 0) LAUNCH_ND_BLK(k_rec_particles<2>, k_rec_particles<3>, nb, REC_NT, h->P, h->mats_d, lazy, h->rec_part_d.get(), nb);
+  const RecHead hd{(double)step, (double)kind, dt, h->rec_time, (double)np};
+  hipLaunchKernelGGL(k_rec_finish, dim3(REC_NQ), dim3(REC_NT), 0, h->stream, (const double*)h->rec_part_d.get(), nb, hd,
+                     (const int*)h->gstatus_d.get(), row);
+  for (int s0 = 0; s0 < h->rec_nsets; s0 += REC_SETS_PER_LAUNCH) {
+    const int cnt = std::min(REC_SETS_PER_LAUNCH, h->rec_nsets - s0);
+    RecSets rs;
+    memset(&rs, 0, sizeof rs);
+    rs.nlive = std::max(0, std::min(cnt, nbcc - s0));
+    for (int i = 0; i < rs.nlive; i++) {
+      const BcDev& b = h->bcs[s0 + i];
+      rs.nodes[i] = b.dnodes;
+      rs.n[i] = b.n;
+      rs.dim[i] = bcc[s0 + i].dim;
+      rs.bits[i] = b.n > 0 ? dirbits_of(bcc[s0 + i], step, h->nsteps) : 0;
+    }
+    LAUNCH_ND_BLK(k_rec_reactions<2>, k_rec_reactions<3>, cnt, REC_NT, h->N, rs, h->n0, h->nwn, row + NLPS_REC_NGLOBAL + (size_t)3 * s0);
+  }
+  if (h->rec_nprobes > 0) {
+    if (!h->xl_inv_valid) {  // the first row behind a re-sort (or a setter): caller's index -> slot
+      hipLaunchKernelGGL(k_inverse_perm, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->perm_d, np, h->xl_inv_d.get());
+      h->xl_inv_valid = true;
+    }
+    LAUNCH_ND_BLK(k_rec_probes<2>, k_rec_probes<3>, nblk(h->rec_nprobes * 10, REC_NT), REC_NT, h->P, h->mats_d, lazy,
+                  (const int*)h->rec_probes_d.get(), (const int*)h->xl_inv_d.get(), h->rec_nprobes, h->rec_fields, h->rec_probe_doubles,
+                  row + NLPS_REC_NGLOBAL + (size_t)3 * h->rec_nsets);
+  }
+  HIPCHK(hipGetLastError());
+  h->rec_total++;
+  return 0;
+}
+// the tail of a step (rec_on): the clock runs for every step, a row is written for the steps of the interval
+static int rec_step(nlps_gpu* h, int kind, int step, double dt, const nlps_bcc* bcc, int nbcc) {
+  h->rec_time += dt;
+  if (step % h->rec_every != 0) return 0;
+  return rec_write(h, kind, step, dt, bcc, nbcc);
+}
+
+extern "C" int nlps_gpu_record_now(nlps_gpu* h, int tag) {
+  if (!h->rec_on) {
+    h->err = "nlps_gpu_record_now: no step record is set";
+    return 1;
+  }
+  if (rec_check(h, "nlps_gpu_record_now")) return 1;
+  return rec_write(h, NLPS_REC_KIND_NOW, tag, 0.0, nullptr, 0);
+}
+
+extern "C" int nlps_gpu_read_step_records(nlps_gpu* h, long long* total, int* count, double* rows, int max_rows) {
+  if (!h->rec_on) {
+    h->err = "nlps_gpu_read_step_records: no step record is set";
+    return 1;
+  }
+  if (max_rows < 0) {
+    h->err = "nlps_gpu_read_step_records: max_rows < 0";
+    return 1;
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const long long have = std::min<long long>(h->rec_total, h->rec_capacity);
+  const int n = (int)std::min<long long>(have, max_rows);
+  if (total) *total = h->rec_total;
+  if (count) *count = n;
+  if (!rows) return 0;
+  for (int r = 0; r < n; r++) {  // (row number g lives in slot g % capacity: at most two runs of slots, copied row by row)
+    const long long g = h->rec_total - n + r;
+    HIPCHK(hipMemcpy(rows + (size_t)r * h->rec_row, h->rec_rows_d + (size_t)(g % h->rec_capacity) * h->rec_row,
+                     (size_t)h->rec_row * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+extern "C" double nlps_host_courant_dt(double CFL, double hh, double Cel, const double* row) {
+  return CFL * hh / (row ? Cel + row[NLPS_REC_VMAX_COMP] : Cel);  // U_DeltaT__SolversLib__, Courant.c:26-50
 }
 
 extern "C" int nlps_gpu_roll_state(nlps_gpu* h) {
@@ -4691,6 +4898,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     return 1;
   }
   if ((nbcc > 0 || loads) && check_step(h, step, "nlps_gpu_explicit_step")) return 1;
+  if (h->rec_on && rec_check(h, "nlps_gpu_explicit_step")) return 1;  // (nlps_gpu_set_step_record)
   if (ensure_bcs(h, bcc, nbcc)) return 1;
   if (!h->Pd_alt && h->resort_every > 0 && h->P.np > 0) {
     // the twin block of the periodic re-sort, at the first step of the fused scheme rather than inside the first
@@ -5101,6 +5309,9 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
       h->ms[6] += tw;
     }
   }
+  // the step record: behind the last particle kernel of the step (and the join of the side stream), outside the timing brackets; N.active, N.nm and
+  // N.force of this step are intact in every form (placement table), nothing here writes them
+  if (h->rec_on && rec_step(h, NLPS_REC_KIND_EXPLICIT, step, dt, bcc, nbcc)) return 1;
   return 0;
 }
 
@@ -6272,5 +6483,10 @@ extern "C" int nlps_gpu_newmark_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc,
   if (snes->reason <= 0) return 0;  // (not converged: the particles stay at the last evaluated state, not rolled)
   if (nlps_gpu_nodal_kinetic_increments(h, dV, dA, dU, V, A, alpha)) return 1;          // :380
   if (nlps_gpu_roll_state(h)) return 1;                                                 // :393
-  return nlps_gpu_update_kinetics(h, nm->alpha_blend, dU, V, dV, dA);                   // :396
+  if (nlps_gpu_update_kinetics(h, nm->alpha_blend, dU, V, dV, dA)) return 1;            // :396
+  if (h->rec_on) {  // the step record (nlps_gpu_set_step_record): a converged step, behind the particle update
+    if (rec_check(h, who)) return 1;
+    return rec_step(h, NLPS_REC_KIND_NEWMARK, step, dt, nullptr, 0);
+  }
+  return 0;
 }

@@ -107,6 +107,8 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_explicit_step", "nlps_gpu_num_active", "nlps_gpu_explicit_nodal", "nlps_gpu_set_halo_exchange",
            "nlps_gpu_resort", "nlps_gpu_set_resort_interval", "nlps_gpu_set_adaptive_resort", "nlps_gpu_set_law_launch_mode", "nlps_gpu_set_deterministic", "nlps_gpu_set_explicit_damage",
            "nlps_gpu_set_explicit_loads",
+           "nlps_gpu_set_step_record", "nlps_gpu_step_record_layout", "nlps_gpu_record_now", "nlps_gpu_read_step_records",
+           "nlps_host_courant_dt",
            "nlps_gpu_set_implicit_damage", "nlps_gpu_set_deterministic_damage",
            "nlps_gpu_rccl_unique_id", "nlps_gpu_rccl_attach", "nlps_gpu_rccl_attach_comm", "nlps_gpu_rccl_detach",
            "nlps_gpu_rccl_reduce", "nlps_gpu_rccl_info", "nlps_gpu_rccl_migrate", "nlps_gpu_rccl_selftest_migrate", "nlps_gpu_rccl_selftest_exchange", "nlps_gpu_touched_layers", "nlps_gpu_set_node_window", "nlps_gpu_set_ghost_bands",
@@ -265,6 +267,32 @@ class BccSet:
             v = np.ascontiguousarray(b["value"], dtype=np.float64)
             self.keep += [nodes, d, v]
             self.arr[k] = Bcc(len(nodes), _i(nodes), int(b["dim"]), _i(d), _d(v))
+
+
+class RecordCfg(C.Structure):  # nlps_record_cfg
+    _fields_ = [("every", C.c_int), ("capacity", C.c_int), ("nsets", C.c_int), ("nprobes", C.c_int), ("probes", _ip),
+                ("probe_fields", C.c_uint)]
+
+
+# the global block of a row of the step record (NLPS_REC_*): name -> (offset, doubles)
+REC_KIND_NOW, REC_KIND_EXPLICIT, REC_KIND_NEWMARK = 0, 1, 2
+REC_NGLOBAL = 32
+REC_COLUMNS = {"step": (0, 1), "kind": (1, 1), "dt": (2, 1), "time": (3, 1), "np": (4, 1), "mass": (5, 1), "momentum": (6, 3),
+               "angular": (9, 3), "mass_x": (12, 3), "kinetic": (15, 1), "strain": (16, 1), "volume": (17, 1),
+               "vmax_comp": (18, 1), "vmax_norm": (19, 1), "J_min": (20, 1), "J_max": (21, 1), "EPS_max": (22, 1),
+               "Damage_max": (23, 1), "failed": (24, 1), "status": (25, 1)}
+PROBE_X, PROBE_DIS, PROBE_VEL, PROBE_ACC, PROBE_F, PROBE_STRESS, PROBE_J, PROBE_EPS, PROBE_DAMAGE, PROBE_W = \
+    1, 2, 4, 8, 16, 32, 64, 128, 256, 512
+PROBE_ALL = 1023
+
+
+def courant_dt(CFL, h, Cel, row=None):
+    """CFL h / Cel, or with a row of the step record CFL h / (Cel + vmax_comp) (Courant.c, DynamicTimeStep); host only"""
+    f = lib().nlps_host_courant_dt
+    f.restype = C.c_double
+    f.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
+    r = None if row is None else np.ascontiguousarray(row, dtype=np.float64)
+    return f(float(CFL), float(h), float(Cel), None if r is None else r.ctypes.data_as(C.c_void_p))
 
 
 class NlpsError(RuntimeError):
@@ -575,6 +603,65 @@ class Solver:
         a0 = None if area0 is None else np.ascontiguousarray(area0, dtype=np.float64)
         self._chk(self.L.nlps_gpu_set_explicit_loads(self.h, None if loads is None else loads.arr, 0 if loads is None else loads.n,
                                                      float(thickness), None if a0 is None else a0.ctypes.data))
+
+    def set_step_record(self, every=1, capacity=64, nsets=0, probes=None, probe_fields=0):
+        """The step record: one row per recorded step, made on the device behind explicit_step / newmark_step and kept in a
+        ring of `capacity` rows; every=None switches it off.  `probes`: particle indices in the caller's order,
+        `probe_fields`: PROBE_* bits.  The contract is in include/nlps_gpu.h."""
+        L = self.L
+        L.nlps_gpu_set_step_record.argtypes = [C.c_void_p, C.POINTER(RecordCfg)]
+        if every is None:
+            self._chk(L.nlps_gpu_set_step_record(self.h, None))
+            return
+        ids = np.ascontiguousarray([] if probes is None else probes, dtype=np.int32)
+        cfg = RecordCfg(int(every), int(capacity), int(nsets), int(ids.size), _i(ids) if ids.size else None,
+                        int(probe_fields))
+        self._chk(L.nlps_gpu_set_step_record(self.h, C.byref(cfg)))
+
+    def step_record_layout(self):
+        """-> (doubles per row, offset of the reaction block, offset of the probe block, doubles per probe)"""
+        self.L.nlps_gpu_step_record_layout.argtypes = [C.c_void_p, _ip, _ip, _ip, _ip]
+        v = [C.c_int(0) for _ in range(4)]
+        self._chk(self.L.nlps_gpu_step_record_layout(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def record_now(self, tag=0):
+        self.L.nlps_gpu_record_now.argtypes = [C.c_void_p, C.c_int]
+        self._chk(self.L.nlps_gpu_record_now(self.h, int(tag)))
+
+    def read_step_records(self, max_rows=None, counts_only=False):
+        """The newest rows of the ring, oldest first: a dict with the named columns of the global block (REC_COLUMNS; the
+        vectors as [rows][3]), `reactions` [rows][nsets][3], `probes` [rows][nprobes][doubles per probe] (`probe_slices`
+        gives the slice of every selected field inside a probe's block), `rows` (the raw rows), `total` (rows written since
+        the set) and `count`.  One synchronisation of the handle's stream."""
+        L = self.L
+        L.nlps_gpu_read_step_records.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), _ip, C.c_void_p, C.c_int]
+        row, ro, po, pd = self.step_record_layout()
+        total, count = C.c_longlong(0), C.c_int(0)
+        self._chk(L.nlps_gpu_read_step_records(self.h, C.byref(total), C.byref(count), None,
+                                               2 ** 31 - 1 if max_rows is None else int(max_rows)))
+        out = {"total": total.value, "count": count.value}
+        if counts_only:
+            return out
+        rows = np.zeros((count.value, row))
+        self._chk(L.nlps_gpu_read_step_records(self.h, C.byref(total), C.byref(count), _vp(rows), count.value))
+        out["rows"] = rows
+        for name, (off, n) in REC_COLUMNS.items():
+            out[name] = rows[:, off] if n == 1 else rows[:, off:off + n]
+        nsets = (po - ro) // 3
+        out["reactions"] = rows[:, ro:po].reshape(count.value, nsets, 3)
+        out["probes"] = rows[:, po:].reshape(count.value, -1, pd) if pd else np.zeros((count.value, 0, 0))
+        return out
+
+    def probe_slices(self, probe_fields):
+        """name -> slice inside a probe's block, for the fields selected in `probe_fields` (ascending bit order)"""
+        d, T, off, out = self.ndim, self.T, 0, {}
+        for b, (name, n) in enumerate((("x_GC", d), ("dis", d), ("vel", d), ("acc", d), ("F_n", T), ("Stress", T), ("J_n", 1),
+                                       ("EPS_n", 1), ("Damage_n", 1), ("W", 1))):
+            if (probe_fields >> b) & 1:
+                out[name] = slice(off, off + n)
+                off += n
+        return out
 
     def set_implicit_damage(self, on=True):
         """The eigenerosion / eigensoftening hooks inside the fused residual (off by default: lagrangian_evaluation runs the
