@@ -224,10 +224,19 @@ __device__ __forceinline__ void sym_eigen(double* w, double* v, const double* Ai
       // pair (p,q) and the third index m: r = 0 -> (0,1) m=2 ; r = 1 -> (0,2) m=1 ; r = 2 -> (1,2) m=0
       const int p = (r == 2) ? 1 : 0, q = (r == 0) ? 1 : 2;
       const double apq = o[r];
-      if (apq != 0.0) {
+      // An entry below 1e-145 is passed over, not rotated away.  Its square is a subnormal that has lost bits, or zero,
+      // so beside a df that small (two equal diagonal entries, or a matrix that small altogether: a stress that is
+      // rounding noise) h^2 below is wrong or zero, rh wrong or inf, and the rotation not orthogonal or NaN
+      // (c^2 = 0 * inf, c = inf * 0).  Ignoring it moves the matrix by less than 1e-145, far below the rounding of
+      // anything a caller reads from the result, and every entry that is rotated has h^2 >= 4e-290.  The entry stays
+      // where it is (zeroing it on this path costs the Von-Mises K3 kernels 8 to 12 bytes of scratch): it
+      // adds less than 2e-290 to `off`, so the sweeps end as they would without it, at the latest at the twelfth.
+      // A NaN fails the comparison, is rotated and stays NaN.
+      if (!(fabs(apq) < 1e-145)) {
         const double df = d[q] - d[p];
-        // the small-angle rotation from two reciprocal square roots (no division, no sqrt): with h = sqrt(df^2 + 4 apq^2),
-        // cos 2 theta = |df| / h, so c^2 = (1 + |df| / h) / 2 in [1/2, 1], s = sgn(df) apq / (h c), t = s / c
+        // the rotation (|theta| <= 45 degrees, the inner one) from two reciprocal square roots (no division, no sqrt):
+        // with h = sqrt(df^2 + 4 apq^2), cos 2 theta = |df| / h, so c^2 = (1 + |df| / h) / 2 in [1/2, 1],
+        // s = sgn(df) apq / (h c), t = s / c
         const double rh = rsqrt(fma(df, df, 4.0 * apq * apq));
         const double c2 = fma(0.5 * fabs(df), rh, 0.5), ic = rsqrt(c2);
         const double c = c2 * ic, sn = (df >= 0.0 ? apq : -apq) * rh * ic, t = sn * ic;

@@ -335,7 +335,11 @@ class Solver:
         keymap = {"x_GC": "x", "dis": "dis", "vel": "vel", "acc": "acc", "F_n": "F_n", "b_e_n": "b_e_n",
                   "J_n": "J_n", "rho": "rho", "mass": "mass", "Vol_0": "vol0", "Kappa_n": "kappa_n",
                   "EPS_n": "eps_n", "lambda_": "lambda", "Beta": "beta", "dt_F_n": "dt_F_n",
-                  "Back_stress": "back_stress", "Damage_n": "damage_n", "Strain_f_n": "strain_f_n"}
+                  "Back_stress": "back_stress", "Damage_n": "damage_n", "Strain_f_n": "strain_f_n",
+                  # the n+1 state and the increments, for callers that enter at a per-particle stage (absent: NULL, and
+                  # nlps_gpu_create starts them from the n state / the unit tensor)
+                  "F_n1": "F_n1", "DF": "DF", "J_n1": "J_n1", "b_e_n1": "b_e_n1", "dt_F_n1": "dt_F_n1", "dt_DF": "dt_DF",
+                  "Kappa_n1": "kappa_n1", "EPS_n1": "eps_n1"}
         for ck, k in keymap.items():
             if k in cloud and cloud[k] is not None:
                 a = np.ascontiguousarray(cloud[k], dtype=np.float64)

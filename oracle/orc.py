@@ -486,8 +486,9 @@ class ExplicitStepper:
         return self.bufs[k][: na * self.P.ndim]
 
 
-def stress_one(ndim, mat, prm, F_n1, DF, J, b_e_n, kappa_n, eps_n, back_stress=None):
-    """back_stress: optional array of 3 (Von-Mises), updated in place"""
+def stress_one(ndim, mat, prm, F_n1, DF, J, b_e_n, kappa_n, eps_n, back_stress=None, C_ep=None):
+    """back_stress: optional array of 3 (Von-Mises), updated in place; C_ep: optional array of ndim * ndim, filled where the
+    law stores the moduli"""
     T = 5 if ndim == 2 else 9
     stress = np.zeros(T)
     b1 = np.zeros(T)
@@ -501,7 +502,7 @@ def stress_one(ndim, mat, prm, F_n1, DF, J, b_e_n, kappa_n, eps_n, back_stress=N
     DF = np.ascontiguousarray(DF, dtype=np.float64)
     b_e_n = np.ascontiguousarray(b_e_n, dtype=np.float64)
     st = f(ndim, C.byref(mat), C.byref(prm), _d(F_n1), _d(DF), float(J), _d(b_e_n), float(kappa_n),
-           float(eps_n), _d(stress), C.byref(W), _d(b1), C.byref(k1), C.byref(e1), None,
+           float(eps_n), _d(stress), C.byref(W), _d(b1), C.byref(k1), C.byref(e1), _d(C_ep),
            _d(back_stress) if back_stress is not None else None)
     return st, stress, W.value, b1, k1.value, e1.value
 
