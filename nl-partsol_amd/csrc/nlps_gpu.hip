@@ -3799,22 +3799,122 @@ static int det_slab_reserve(nlps_gpu* h, const char* who) {
   const size_t fields = std::max<size_t>(std::max<size_t>(4 * ND, ND * ND), (size_t)ND * __builtin_popcount(h->law_present));
   return reserve(h, who, h->slab_d, (size_t)h->ntiles * fields * NWs, "the window slabs of the deterministic mode");
 }
-// out[node][NF] of the whole node window from the slabs (slab_n per tile); nodes outside the window keep what they hold
-#define DET_GATHER(NF2, NF3, slab_count, out)                                                                              \
-  do {                                                                                                                     \
-    const NodeRanges r_ = node_ranges(h, 0);                                                                               \
-    TileD tg_ = tile_view(h, 0);                                                                                           \
-    tg_.slab_n = (slab_count);                                                                                             \
-    if (r_.an + r_.bn > 0)                                                                                                 \
-      LAUNCH_ND((k_slab_gather<2, NF2>), (k_slab_gather<3, NF3>), nblk(r_.an + r_.bn), r_.a0, r_.an, r_.b0, r_.bn, h->g, tg_, (out)); \
-  } while (0)
-
 // arms the boundary-done signal of a single-launch stage (overlap mode 2): stage 0 = K2, 1 = K3
 static void arm_signal(nlps_gpu* h, TileD& td, int stage) {
   RcclHalo* R = h->rccl;
   td.sig_cnt = R->sig_cnt + stage;
   td.sig_flag = R->sig_flag[stage];
   td.sig_seq = ++R->sig_seq;
+}
+
+// K3: the one place that names k3_tile<ND, LAW, MODE, FILT, NT, UMAT> (nlps_gpu_compatibility's MODE 0 / 2 apart).
+// Every MODE below exists plain per dimension and law, per law with the tile's particles of that law compacted first
+// (FILT; a cloud of several laws, one launch per law present) and in the one-material form of the 3-D laws 1-3 (UMAT).
+// What only some have is stated here, and launch_k3 instantiates a form only where its flag is set, so the set of
+// kernels in the library is this table:
+//   MODE 1  the fused K3 of the explicit step        + LAW = -1 + one wave per tile (FILT, NT = 64)
+//   MODE 5  its state half (damage hooks)            + LAW = -1   (a deterministic damage step launches these forms too)
+//   MODE 3  the fused residual                       + one wave per tile; the fluid law's particles go to MODE 4
+//   MODE 4  MODE 3 with the rate tensors (dV)          the fluid law only: plain, FILT, one wave per tile
+//   MODE 6  the state half of MODE 3 (damage hooks)    nothing else (tests/test_isa_implicit_damage.py)
+template <int MODE>
+struct K3Forms {
+  static constexpr bool dispatch = MODE == 1 || MODE == 5;  // LAW = -1: the law of every particle looked up at run time
+  static constexpr bool wave = MODE == 1 || MODE == 3;      // the deterministic form
+  static constexpr bool fluid = MODE == 3;                  // NLPS_KLAW_FLUID exists, as MODE 4
+};
+struct K3Launch {
+  bool signal = false;         // arm the boundary-done signal of overlap mode 2 in front of the (last) launch
+  bool wave = false;           // one wave per tile and per law present over the exact lists, one slab per (tile, law)
+  const double* dV = nullptr;  // the nodal rate vector, read by MODE 4 alone
+};
+// 3-D, one material, laws 1-3: its constants by scalar loads (k3_body, UMAT)
+static bool one_material_3d(const nlps_gpu* h) {
+  return h->nd == 3 && h->nmats == 1 && h->uniform_law >= 1 && h->uniform_law <= 3;
+}
+// one workgroup of nt threads per tile; every K3 kernel takes this argument block in front of its own last argument
+template <class K, class X>
+static void k3_go(nlps_gpu* h, K kernel, int nt, const TileD& td, const X& last) {
+  hipLaunchKernelGGL(kernel, dim3(h->ntw), dim3(nt), 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm, h->gstatus_d, last);
+}
+static const double* const no_rates = nullptr;
+// one launch of the kernel of law l (out of range: the last law, with_law_in); MODE 3 hands the fluid law to MODE 4
+template <int MODE, bool FILT, int NT>
+static void launch_k3_law(nlps_gpu* h, const TileD& td, int l, const double* dV) {
+  with_nd(h->nd, [&](auto D) {
+    if constexpr (K3Forms<MODE>::fluid) {
+      if (l == NLPS_KLAW_FLUID) return k3_go(h, k3_tile<CT(D), NLPS_KLAW_FLUID, 4, FILT, NT>, NT, td, dV);
+    }
+    with_law(l, [&](auto L) { k3_go(h, k3_tile<CT(D), CT(L), MODE, FILT, NT>, NT, td, no_rates); });
+  });
+}
+// The launch form of this cloud.  td is the caller's: with or without a slab pointer, for the tile class it wants.
+template <int MODE>
+static void launch_k3(nlps_gpu* h, TileD td, const K3Launch& a) {
+  const int law = h->uniform_law;  // -1: several laws in the cloud (law_present)
+  // one launch of the single-law kernel per law present (FILT); MODE 1 / 5 on request only (nlps_gpu_set_law_launch_mode)
+  const bool per_law = law < 0 && (!K3Forms<MODE>::dispatch || h->k3_per_law);
+  if (a.signal && !per_law) arm_signal(h, td, 1);
+  if constexpr (K3Forms<MODE>::wave) {
+    if (a.wave) {  // (a cloud of one law too: slab_n = 1, slot 0)
+      td.slab_n = __builtin_popcount(h->law_present);
+      td.slab_slot = -1;
+      for_each_law_present(h->law_present, [&](int l, bool) {
+        td.slab_slot++;
+        launch_k3_law<MODE, true, 64>(h, td, l, a.dV);
+      });
+      return;
+    }
+  }
+  if (per_law) {  // only the last launch releases the exchange (launches of one stream run in order)
+    for_each_law_present(h->law_present, [&](int l, bool last) {
+      if (a.signal && last) arm_signal(h, td, 1);
+      launch_k3_law<MODE, true, K3_BLK>(h, td, l, a.dV);
+    });
+  } else if (law < 0) {  // several laws, many mixed tiles: the kernel that dispatches on the law at run time
+    if constexpr (K3Forms<MODE>::dispatch) {
+      with_nd(h->nd, [&](auto D) { k3_go(h, k3_tile<CT(D), -1, MODE>, K3_BLK, td, no_rates); });
+    }
+  } else if (one_material_3d(h)) {
+    with_law_in<1, 3>(law, [&](auto L) { k3_go(h, k3_tile<3, CT(L), MODE, false, K3_BLK, true>, K3_BLK, td, no_rates); });
+  } else {
+    launch_k3_law<MODE, false, K3_BLK>(h, td, law, a.dV);
+  }
+}
+// The folded form of the explicit step (one law, 0 .. NLPS_KLAW_FRICTIONAL): k3_tile_lazy, plain or one-material
+static void launch_k3_lazy(nlps_gpu* h, TileD td, bool signal, const LazyNodal& ln) {
+  if (signal) arm_signal(h, td, 1);
+  if (one_material_3d(h)) {
+    with_law_in<1, 3>(h->uniform_law, [&](auto L) { k3_go(h, k3_tile_lazy<3, CT(L), true>, K3_BLK, td, ln); });
+  } else {
+    with_nd(h->nd, [&](auto D) {
+      with_law(h->uniform_law, [&](auto L) { k3_go(h, k3_tile_lazy<CT(D), CT(L)>, K3_BLK, td, ln); });
+    });
+  }
+}
+
+// One scatter per tile into `out`, which the caller has zeroed and exchanges afterwards.  On the deterministic implicit
+// path (det_implicit) the one-wave form leaves its windows as slab_count slabs per tile and k_slab_gather<ND, NF>
+// sums them per node in a fixed order; otherwise the 256-thread form flushes by atomics.  launch(NT, td) launches either:
+// NT = ic<64> or ic<BLK>, td the tile view to launch on.
+template <int NF2, int NF3>  // out[node][NF] of a part of the node window (node_ranges) from the slabs; other nodes keep theirs
+static void det_gather(nlps_gpu* h, int part, int slab_count, double* out) {
+  const NodeRanges r = node_ranges(h, part);
+  TileD tg = tile_view(h, 0);
+  tg.slab_n = slab_count;
+  if (r.an + r.bn > 0)
+    LAUNCH_ND((k_slab_gather<2, NF2>), (k_slab_gather<3, NF3>), nblk(r.an + r.bn), r.a0, r.an, r.b0, r.bn, h->g, tg, out);
+}
+template <int NF2, int NF3, class F>
+static int scatter_tiles(nlps_gpu* h, const char* who, int slab_count, double* out, F&& launch) {
+  if (!det_implicit(h)) {
+    launch(ic<BLK>{}, tile_view(h));
+    return 0;
+  }
+  if (det_prepare(h, who)) return 1;
+  launch(ic<64>{}, tile_view(h));
+  det_gather<NF2, NF3>(h, 0, slab_count, out);
+  return 0;
 }
 
 static void launch_k2(nlps_gpu* h, bool p2g, int cls, double dt, double gamma_nm, bool signal = false) {
@@ -4041,6 +4141,14 @@ static int dirbits_of(const nlps_bcc& b, int step, int nsteps) {
     if (b.dir[(size_t)k * nsteps + step] == 1) bits |= 1 << k;
   return bits;
 }
+// the values of a Dirichlet set at a step, one per direction it has (0 beyond)
+static void bc_values(const nlps_bcc& b, int step, int nsteps, double v[3]) {
+  for (int k = 0; k < 3; k++) v[k] = k < b.dim ? b.value[(size_t)k * nsteps + step] : 0.0;
+}
+// the caller's gravity[ndim], or NULL, as three components
+static void gravity3(const double* gravity, int nd, double g[3]) {
+  for (int k = 0; k < 3; k++) g[k] = (gravity && k < nd) ? gravity[k] : 0.0;
+}
 
 extern "C" int nlps_gpu_active_masks(nlps_gpu* h, const nlps_bcc* bcc, int nbcc, int step, int* nactive,
                                      int* nfree_dofs, int* nodes2mask, int* dofs2mask) {
@@ -4134,15 +4242,10 @@ extern "C" int nlps_gpu_lumped_mass(nlps_gpu* h, double* M) {
   if (need_masks(h, "nlps_gpu_lumped_mass")) return 1;
   int ND = h->nd;
   HIPCHK(hipMemsetAsync(h->gridA, 0, (size_t)h->g.nnodes * sizeof(double), h->stream));
-  if (det_implicit(h)) {
-    if (det_prepare(h, "nlps_gpu_lumped_mass")) return 1;
-    TileD td = tile_view(h);
-    LAUNCH_ND_BLK((kb_p2g_tile<2, 0, 64>), (kb_p2g_tile<3, 0, 64>), h->ntw, 64, h->P, h->g, td, h->gridA);
-    DET_GATHER(1, 1, 1, h->gridA);
-  } else {
-    TileD td = tile_view(h);
-    LAUNCH_ND((kb_p2g_tile<2, 0>), (kb_p2g_tile<3, 0>), h->ntw, h->P, h->g, td, h->gridA);
-  }
+  if (scatter_tiles<1, 1>(h, "nlps_gpu_lumped_mass", 1, h->gridA, [&](auto NT, TileD td) {
+        LAUNCH_ND_BLK((kb_p2g_tile<2, 0, CT(NT)>), (kb_p2g_tile<3, 0, CT(NT)>), h->ntw, CT(NT), h->P, h->g, td, h->gridA);
+      }))
+    return 1;
   HIPCHK(hipGetLastError());
   if (halo(h, h->gridA, 1, 8, 0)) return 1;
   return from_grid(h, M, h->gridA, ND, 1, 0, 1, 0, nullptr);
@@ -4152,15 +4255,10 @@ extern "C" int nlps_gpu_nodal_field_n(nlps_gpu* h, double* V, double* A, const d
   if (need_masks(h, "nlps_gpu_nodal_field_n")) return 1;
   int ND = h->nd;
   HIPCHK(hipMemsetAsync(h->gridA, 0, (size_t)h->g.nnodes * 2 * ND * sizeof(double), h->stream));
-  if (det_implicit(h)) {
-    if (det_prepare(h, "nlps_gpu_nodal_field_n")) return 1;
-    TileD td = tile_view(h);
-    LAUNCH_ND_BLK((kb_p2g_tile<2, 1, 64>), (kb_p2g_tile<3, 1, 64>), h->ntw, 64, h->P, h->g, td, h->gridA);
-    DET_GATHER(4, 6, 1, h->gridA);
-  } else {
-    TileD td = tile_view(h);
-    LAUNCH_ND((kb_p2g_tile<2, 1>), (kb_p2g_tile<3, 1>), h->ntw, h->P, h->g, td, h->gridA);
-  }
+  if (scatter_tiles<4, 6>(h, "nlps_gpu_nodal_field_n", 1, h->gridA, [&](auto NT, TileD td) {
+        LAUNCH_ND_BLK((kb_p2g_tile<2, 1, CT(NT)>), (kb_p2g_tile<3, 1, CT(NT)>), h->ntw, CT(NT), h->P, h->g, td, h->gridA);
+      }))
+    return 1;
   HIPCHK(hipGetLastError());
   if (halo(h, h->gridA, 2 * ND, 8, 0)) return 1;
   if (from_grid(h, V, h->gridA, ND, 2 * ND, 0, 0, 2, M)) return 1;
@@ -4252,15 +4350,10 @@ extern "C" int nlps_gpu_internal_forces(nlps_gpu* h, double* R) {
   }
   if (materialise_nodal(h)) return 1;  // (the forces of the last explicit step are about to go)
   HIPCHK(hipMemsetAsync(h->N.force, 0, (size_t)h->g.nnodes * ND * sizeof(double), h->stream));
-  if (det_implicit(h)) {
-    if (det_prepare(h, "nlps_gpu_internal_forces")) return 1;
-    TileD td = tile_view(h);
-    LAUNCH_ND_BLK((kb_fint_tile<2, 64>), (kb_fint_tile<3, 64>), h->ntw, 64, h->P, h->g, td, h->N.force, h->gstatus_d);
-    DET_GATHER(2, 3, 1, h->N.force);
-  } else {
-    TileD td = tile_view(h);
-    LAUNCH_ND(kb_fint_tile<2>, kb_fint_tile<3>, h->ntw, h->P, h->g, td, h->N.force, h->gstatus_d);
-  }
+  if (scatter_tiles<2, 3>(h, "nlps_gpu_internal_forces", 1, h->N.force, [&](auto NT, TileD td) {
+        LAUNCH_ND_BLK((kb_fint_tile<2, CT(NT)>), (kb_fint_tile<3, CT(NT)>), h->ntw, CT(NT), h->P, h->g, td, h->N.force, h->gstatus_d);
+      }))
+    return 1;
   HIPCHK(hipGetLastError());
   if (halo(h, h->N.force, ND, 8, 0)) return 1;
   return from_grid(h, R, h->N.force, ND, ND, 0, 0, 1, nullptr);
@@ -4821,20 +4914,22 @@ __global__ void k_null_bracket(PView, GridD, NView, TileD, const MatD*, ParamsD,
 // no sort), once per numbering of the slots those of the snapshot's closest nodes (eigenerosion's frozen lists,
 // Beps.c:30-36), then the hook, which sets Damage_n1 (Strain_f_n1) and scales every Kirchhoff stress in place.  All on the
 // handle's stream, no sort call, no synchronisation, no allocation (the setters made the tables).
-static int damage_runs_and_hook(nlps_gpu* h, bool rebuild) {
+template <bool SNAP>  // the runs of the current (false) or the snapshot's (true) closest nodes
+static void build_runs(nlps_gpu* h, int* first, int* last, int* sorted, bool sort_runs) {
   const int np = h->P.np, nn = h->g.nnodes;
   const dim3 gp(nblk(np)), gn(nblk(nn)), blk(BLK);
+  hipLaunchKernelGGL(k_run_count<SNAP>, gp, blk, 0, h->stream, h->P, nn, h->xrun_cnt_d.get(), h->xrun_rank_d.get(), h->xrun_cursor_d.get());
+  hipLaunchKernelGGL(k_run_first, gn, blk, 0, h->stream, nn, h->xrun_cnt_d.get(), h->xrun_cursor_d.get(), first, last);
+  hipLaunchKernelGGL(k_run_fill<SNAP>, gp, blk, 0, h->stream, h->P, nn, (const int*)first, (const int*)h->xrun_rank_d.get(), sorted);
+  if (sort_runs) hipLaunchKernelGGL(k_run_sort, gn, blk, 0, h->stream, nn, np, (const int*)first, (const int*)last, sorted);
+}
+static int damage_runs_and_hook(nlps_gpu* h, bool rebuild) {
+  const int np = h->P.np;
   // deterministic mode (nlps_gpu_set_deterministic_damage): ascending slot index inside every run, so that the hook's sums
   // over a neighbourhood run in an order the particle arrays alone decide.  (Both switches drop the cached tables.)
   const bool sort_runs = h->deterministic && h->det_damage;
   if (rebuild) {
-    hipLaunchKernelGGL(k_run_count<false>, gp, blk, 0, h->stream, h->P, nn, h->xrun_cnt_d.get(), h->xrun_rank_d.get(), h->xrun_cursor_d.get());
-    hipLaunchKernelGGL(k_run_first, gn, blk, 0, h->stream, nn, h->xrun_cnt_d.get(), h->xrun_cursor_d.get(), h->xrun_first_d.get(), h->xrun_last_d.get());
-    hipLaunchKernelGGL(k_run_fill<false>, gp, blk, 0, h->stream, h->P, nn, (const int*)h->xrun_first_d.get(), (const int*)h->xrun_rank_d.get(),
-                       h->xrun_sorted_d.get());
-    if (sort_runs)
-      hipLaunchKernelGGL(k_run_sort, gn, blk, 0, h->stream, nn, np, (const int*)h->xrun_first_d.get(), (const int*)h->xrun_last_d.get(),
-                         h->xrun_sorted_d.get());
+    build_runs<false>(h, h->xrun_first_d.get(), h->xrun_last_d.get(), h->xrun_sorted_d.get(), sort_runs);
     h->xrun_builds++;
     h->xrun_tables = true;
   }
@@ -4846,14 +4941,7 @@ static int damage_runs_and_hook(nlps_gpu* h, bool rebuild) {
               (const uint8_t*)h->rank1_d, (const int*)h->perm_d, (const double*)T0, h->g.h);
   } else {
     if (!h->xrun_tables0) {  // frozen lists (Beps.c:30-36): the runs of the snapshot's closest nodes
-      hipLaunchKernelGGL(k_run_count<true>, gp, blk, 0, h->stream, h->P, nn, h->xrun_cnt_d.get(), h->xrun_rank_d.get(), h->xrun_cursor_d.get());
-      hipLaunchKernelGGL(k_run_first, gn, blk, 0, h->stream, nn, h->xrun_cnt_d.get(), h->xrun_cursor_d.get(), h->xrun_first0_d.get(),
-                         h->xrun_last0_d.get());
-      hipLaunchKernelGGL(k_run_fill<true>, gp, blk, 0, h->stream, h->P, nn, (const int*)h->xrun_first0_d.get(), (const int*)h->xrun_rank_d.get(),
-                         h->xrun_sorted0_d.get());
-      if (sort_runs)
-        hipLaunchKernelGGL(k_run_sort, gn, blk, 0, h->stream, nn, np, (const int*)h->xrun_first0_d.get(),
-                           (const int*)h->xrun_last0_d.get(), h->xrun_sorted0_d.get());
+      build_runs<true>(h, h->xrun_first0_d.get(), h->xrun_last0_d.get(), h->xrun_sorted0_d.get(), sort_runs);
       h->xrun_tables0 = true;
     }
     LAUNCH_ND((k_damage<2>), (k_damage<3>), nblk(np), h->P, h->g, h->mats_d, h->xrun_first_d, h->xrun_last_d, h->xrun_sorted_d,
@@ -4863,16 +4951,14 @@ static int damage_runs_and_hook(nlps_gpu* h, bool rebuild) {
   return 0;
 }
 
-extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc, int step, double dt, double gamma_nm,
-                                      const double* gravity) {
-  tan_stale(h, "nlps_gpu_explicit_step");
-  int ND = h->nd;
+// The fused explicit step: refuse, re-sort, decide the form (StepForm), search + lists + K2, one of three schedules.
+static int explicit_step_refuse(nlps_gpu* h, int nbcc, int step) {
   if (h->law_present & (1 << NLPS_KLAW_FLUID)) {
     h->err = "nlps_gpu_explicit_step: the cloud holds the Newtonian-Fluid-Compressible law, which reads the rate tensor dt_F_n1; "
              "the reference has no working explicit driver that defines it (implicit path only)";
     return 1;
   }
-  const bool dmg = h->P.erosion != 0;  // the step with the damage hooks (nlps_gpu_set_explicit_damage)
+  const bool dmg = h->P.erosion != 0;
   if (dmg && !h->explicit_damage) {
     h->err = "nlps_gpu_explicit_step: the eigenerosion hooks exist in the level-B stages only (the reference defines them in "
              "U-Newmark-beta.c / U-Static.c; its explicit drivers are stubs)";
@@ -4888,7 +4974,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
              "node runs take ranks and run starts from atomics)";
     return 1;
   }
-  const bool loads = h->xl_n > 0 && h->P.np > 0;  // the Neumann contours (nlps_gpu_set_explicit_loads)
+  const bool loads = h->xl_n > 0 && h->P.np > 0;
   if (loads && (h->halo || h->rccl)) {
     h->err = std::string("nlps_gpu_explicit_step: ") + explicit_loads_halo_msg;
     return 1;
@@ -4899,64 +4985,36 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   }
   if ((nbcc > 0 || loads) && check_step(h, step, "nlps_gpu_explicit_step")) return 1;
   if (h->rec_on && rec_check(h, "nlps_gpu_explicit_step")) return 1;  // (nlps_gpu_set_step_record)
-  if (ensure_bcs(h, bcc, nbcc)) return 1;
-  if (!h->Pd_alt && h->resort_every > 0 && h->P.np > 0) {
-    // the twin block of the periodic re-sort, at the first step of the fused scheme rather than inside the first
-    // re-sort: a hipMalloc of this size (1.3 GB per million particles) takes milliseconds, the re-sort itself 0.3
-    HIPCHK(h->Pd_alt.reserve((size_t)NFD * h->P.npad));
-    HIPCHK(hipMemsetAsync(h->Pd_alt, 0, (size_t)NFD * h->P.npad * sizeof(double), h->stream));
-  }
-  if (!h->rolled && h->P.np > 0) {  // entering the fused scheme: rho J of every particle (see F_RHOJ)
-    hipLaunchKernelGGL(k_init_rhoj, dim3(nblk(h->P.np)), dim3(BLK), 0, h->stream, h->P);
-    HIPCHK(hipGetLastError());
-  }
-  // periodic re-sort; earlier when enough particles have left the tiles their memory slots were sorted into: the count
-  // of a recent step sits in the pinned word (no synchronisation: it may be a step old), its share of the cloud is this
-  // step's cost estimate, and the re-sort comes when the estimates since the last one add up to the budget
-  bool drifted = false;
-  if (h->adaptive_resort > 0.0 && !h->deterministic && h->resort_every > 0 && h->P.np > 0) {  // (a re-sort moment read
-    // from an asynchronous word is not reproducible: the deterministic mode keeps the fixed interval)
-    h->debt += (double)*(volatile int*)h->foreign_h.host() / (double)h->P.np;
-    drifted = h->debt > h->adaptive_resort && h->steps_since_sort >= h->adaptive_min_steps;
-  }
-  if (h->resort_every > 0 && (h->steps_since_sort >= h->resort_every || drifted)) {
-    if (resort(h, nullptr, true)) return 1;
-  }
-  h->steps_since_sort++;
-  h->nwait = 0;
-  if (h->timing) HIPCHK(hipEventRecord(h->ev[0], h->stream));
+  return 0;
+}
+
+// Is a re-sort due: the fixed interval, or earlier when enough particles have left the tiles their memory slots were
+// sorted into (the estimates since the last one, `debt`, add up to the budget).  A re-sort moment read from an
+// asynchronous word is not reproducible: the deterministic mode keeps the fixed interval.  Asked at the head of a step
+// (behind this step's `debt +=`) and by the async fork about the NEXT step; the fork's own spelling left out
+// `!deterministic` and `np > 0`, which hold wherever it runs (the async form is never deterministic and rides, np > 0)
+// and without which `debt` has never grown.
+static bool resort_due(const nlps_gpu* h) {
+  if (h->resort_every <= 0) return false;
+  const bool drifted = h->adaptive_resort > 0.0 && !h->deterministic && h->P.np > 0 && h->debt > h->adaptive_resort &&
+                       h->steps_since_sort >= h->adaptive_min_steps;
+  return h->steps_since_sort >= h->resort_every || drifted;
+}
+
+// What one step runs, decided once in front of its first launch.  (Which K3 kernel: launch_k3 / launch_k3_lazy.)
+struct StepForm {
+  bool dmg;    // the step with the damage hooks (nlps_gpu_set_explicit_damage)
+  bool loads;  // the Neumann contours (nlps_gpu_set_explicit_loads)
+  bool det;    // nlps_gpu_set_deterministic: one wave per tile, slabs, k_slab_gather
   // With a halo callback and ghost bands set, every exchange is started right after the tiles that touch a
   // ghost band have produced their part and is waited for only before those tiles need the result; the tiles
   // (and nodes) away from the bands run in between, on the handle's stream, while the exchange proceeds on the
   // callee's stream.  Without overlap each stage is one pass over all tiles and the exchange blocks in place.
-  const bool ov2 = h->rccl && h->overlap == 2 && !h->deterministic;  // one launch per stage, exchange behind its interior tiles
-  const bool ov = !ov2 && (h->halo || h->rccl) && h->overlap;
-  double gv[3] = {0, 0, 0};
-  if (gravity)
-    for (int a = 0; a < ND; a++) gv[a] = gravity[a];
-  const bool det = h->deterministic;
-  if (det && !h->slab_d) {
-    const size_t NWs = ND == 3 ? TileCfg<3>::NWA : TileCfg<2>::NWA;
-    const size_t per_tile = std::max<size_t>((size_t)(1 + ND), (size_t)4 * ND) * NWs;  // K2: one slab; K3: one per law
-    HIPCHK(h->slab_d.reserve((size_t)h->ntiles * per_tile));
-  }
-  // second half of the P2G flush: per node, the window slabs of the tiles that hold it (part: node ranges as below)
-  auto gather_nm = [&](int part) {
-    const NodeRanges r = node_ranges(h, part);
-    if (!det || r.an + r.bn == 0) return;
-    TileD td = tile_view(h, 0);
-    LAUNCH_ND((k_slab_gather<2, 3>), (k_slab_gather<3, 4>), nblk(r.an + r.bn), r.a0, r.an, r.b0, r.bn, h->g, td, h->N.nm);
-  };
-  auto gather_force = [&](int part) {
-    const NodeRanges r = node_ranges(h, part);
-    if (!det || r.an + r.bn == 0) return;
-    TileD td = tile_view(h, 0);
-    td.slab_n = dmg ? 1 : __builtin_popcount(h->law_present);  // (the force half of a damage step: one slab per tile)
-    LAUNCH_ND((k_slab_gather<2, 2>), (k_slab_gather<3, 3>), nblk(r.an + r.bn), r.a0, r.an, r.b0, r.bn, h->g, td, h->N.force);
-  };
+  bool ov2;  // one launch per stage, exchange behind its interior tiles
+  bool ov;   // boundary tiles, exchange, interior tiles
   // the search of the next step rides on K5 (k5_tile<., ., true>, seeds and bins included).  A slab rank that holds no
   // particles has nothing to search: it launches k5_tile<., ., false> and leaves `searched` / `ahead` false.
-  const bool ride = h->P.np > 0;
+  bool ride;
   // Folded form (k3_tile_lazy / k5_tile_lazy): one law, the Dirichlet sets small enough to travel as kernel arguments:
   // no nodal kernels between the stages (dU, accelerations, reactions are made later if somebody asks).  With a ghost
   // exchange too, in every overlap form: a K3 / K5 launch comes behind the pick-up of the exchange its nodes need (interior
@@ -4965,148 +5023,103 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   // where the window loads of 17 k tiles redo the two divisions per node 16 times over: on below 2 M particles,
   // NLPS_LAZY_NODAL=2 always)
   // (a step with the damage hooks always runs the non-folded form on the handle's stream: neither lazy nor async_form)
-  const bool lazy = (h->lazy_nodal == 2 || (h->lazy_nodal == 1 && h->P.np <= 2000000)) && ride && !det && h->uniform_law >= 0 &&
-                    h->uniform_law <= NLPS_KLAW_FRICTIONAL && nbcc <= NLPS_MAX_BC_INLINE && !dmg;
+  bool lazy;
   // Async lists: the folded form of ONE rank (no ghost exchange, the whole grid as node window).  Nothing the list stage
   // of the next step needs comes from K5 -- the position K5 writes is x + d_dis, and d_dis is K3's -- so the search
   // leaves K5 for a kernel of its own in front of it (k_search_ahead, full ranks), and the activation and the list
   // kernels run on the side stream beside K5, into the twin set (nlps_gpu::side); the handle's stream waits for them at
   // the end of this call.  The multi-rank forms, the deterministic mode, the non-folded form and clouds of several laws
   // keep the riding search and the deferred ranks.
-  const bool async_form = lazy && h->async_lists && !h->halo && !h->rccl && node_lists(h) && h->nwn == h->g.nnodes;
-  const bool inline_bc = nbcc <= NLPS_MAX_BC_INLINE;  // the Dirichlet sets of this step travel as one kernel argument
+  bool async_form;
+  bool inline_bc;      // the Dirichlet sets of this step travel as one kernel argument (bs, bm)
+  int law;             // -1: several laws in the cloud (law_present)
   BcStep bs;
-  memset(&bs, 0, sizeof bs);
-  if (inline_bc) {
-    bs.n = nbcc;
+  const unsigned* bm;  // the bit mask of the sets per node, nullptr without inline sets
+};
+static StepForm step_form(const nlps_gpu* h, const nlps_bcc* bcc, int nbcc, int step) {
+  StepForm f{};
+  f.dmg = h->P.erosion != 0;
+  f.loads = h->xl_n > 0 && h->P.np > 0;
+  f.det = h->deterministic;
+  f.ov2 = h->rccl && h->overlap == 2 && !h->deterministic;
+  f.ov = !f.ov2 && (h->halo || h->rccl) && h->overlap;
+  f.ride = h->P.np > 0;
+  f.lazy = (h->lazy_nodal == 2 || (h->lazy_nodal == 1 && h->P.np <= 2000000)) && f.ride && !f.det && h->uniform_law >= 0 &&
+           h->uniform_law <= NLPS_KLAW_FRICTIONAL && nbcc <= NLPS_MAX_BC_INLINE && !f.dmg;
+  f.async_form = f.lazy && h->async_lists && !h->halo && !h->rccl && node_lists(h) && h->nwn == h->g.nnodes;
+  f.inline_bc = nbcc <= NLPS_MAX_BC_INLINE;
+  f.law = h->uniform_law;
+  if (f.inline_bc) {
+    f.bs.n = nbcc;
     for (int i = 0; i < nbcc; i++) {
-      bs.dim[i] = bcc[i].dim;
-      bs.bits[i] = h->bcs[i].n > 0 ? dirbits_of(bcc[i], step, h->nsteps) : 0;
-      for (int k = 0; k < 3; k++) bs.v[i][k] = (k < bcc[i].dim) ? bcc[i].value[(size_t)k * h->nsteps + step] : 0.0;
+      f.bs.dim[i] = bcc[i].dim;
+      f.bs.bits[i] = h->bcs[i].n > 0 ? dirbits_of(bcc[i], step, h->nsteps) : 0;
+      bc_values(bcc[i], step, h->nsteps, f.bs.v[i]);
     }
   }
-  const unsigned* bm = (inline_bc && nbcc > 0) ? h->bcmask_d : nullptr;
-  LazyNodal ln;
-  if (lazy) {
-    memset(&ln, 0, sizeof ln);
-    ln.fs.bc = bs;
-    ln.fs.bcmask = bm;
-    for (int a = 0; a < 3; a++) ln.fs.gv[a] = gv[a];
-    ln.n0 = h->n0;
-    ln.nwn = h->nwn;
-    ln.node_cnt = node_lists(h) ? h->node_cnt_d : nullptr;
-    ln.ntw = h->ntw;  // (ln.tile_count: after search_and_lists, which swaps the two counter arrays)
-  }
-  auto nodal_dU = [&](int part) {
-    if (lazy) return;  // (K3 makes dU of its window nodes itself)
+  f.bm = (f.inline_bc && nbcc > 0) ? h->bcmask_d.get() : nullptr;
+  return f;
+}
+
+// One step in flight: the stages of the schedules below as methods, what they share as members.
+struct ExplicitStep {
+  nlps_gpu* h;
+  const nlps_bcc* bcc;
+  int nbcc, step;
+  double dt, gamma_nm;
+  StepForm f;
+  double gv[3];
+  LazyNodal ln;  // (lazy)
+  K5Search ks;
+  bool tiles_cleared = false;  // the tile counters of the riding search are reset by the first nodal_accel that runs
+  bool ks_made = false;        // ks.tc is made by the first K5 launch
+  bool forked = false;         // the side stream holds the list kernels of the next step
+
+  // second half of the deterministic flushes: per node, the window slabs of the tiles that hold it (part: node_ranges)
+  void gather_nm(int part) { if (f.det) det_gather<3, 4>(h, part, 1, h->N.nm); }
+  // (one slab per law present; the force half of a damage step: one slab per tile)
+  void gather_force(int part) { if (f.det) det_gather<2, 3>(h, part, f.dmg ? 1 : __builtin_popcount(h->law_present), h->N.force); }
+  // nodal dU = (sum m N dD) / M + Dirichlet values
+  void nodal_dU(int part) {
+    if (f.lazy) return;  // (K3 makes dU of its window nodes itself)
     const NodeRanges r = node_ranges(h, part);
     if (r.an + r.bn == 0) return;
-    LAUNCH_ND(k_nodal_dU<2>, k_nodal_dU<3>, nblk(r.an + r.bn), r.a0, r.an, r.b0, r.bn, h->N, bm, bs);
-    if (inline_bc) return;
+    LAUNCH_ND(k_nodal_dU<2>, k_nodal_dU<3>, nblk(r.an + r.bn), r.a0, r.an, r.b0, r.bn, h->N, f.bm, f.bs);
+    if (f.inline_bc) return;
     // Dirichlet values (nodes of the same range only)
     const NodeRanges in = node_ranges(h, 1);
     for (int i = 0; i < nbcc; i++) {
       if (h->bcs[i].n == 0) continue;
-      double v[3] = {0, 0, 0};
-      for (int k = 0; k < bcc[i].dim && k < 3; k++) v[k] = bcc[i].value[(size_t)k * h->nsteps + step];
-      int bits = dirbits_of(bcc[i], step, h->nsteps);
+      double v[3];
+      bc_values(bcc[i], step, h->nsteps, v);
+      const int bits = dirbits_of(bcc[i], step, h->nsteps);
       const int r0 = part == 0 ? 0 : in.a0, r1 = part == 0 ? h->g.nnodes : in.a0 + in.an, inside = part == 2 ? 0 : 1;
       LAUNCH_ND(k_bc<2>, k_bc<3>, nblk(h->bcs[i].n), h->bcs[i].dnodes, h->bcs[i].n, bcc[i].dim, bits, v[0], v[1], v[2], h->N, r0,
                 r1, inside);
     }
-  };
-  bool tiles_cleared = false;
-  auto nodal_accel = [&](int part) {
-    if (lazy) return;  // (K5 makes the accelerations itself; K3's workgroups have reset the search accumulators)
+  }
+  void nodal_accel(int part) {
+    if (f.lazy) return;  // (K5 makes the accelerations itself; K3's workgroups have reset the search accumulators)
     const NodeRanges r = node_ranges(h, part);
-    int* ctile = (ride && !tiles_cleared) ? h->tile_count2_d + h->tile0 : nullptr;
+    int* ctile = (f.ride && !tiles_cleared) ? h->tile_count2_d + h->tile0 : nullptr;
     if (r.an + r.bn == 0 && !ctile) return;
     tiles_cleared = true;
-    int* cnode = (ride && node_lists(h)) ? h->node_cnt_d : nullptr;
+    int* cnode = (f.ride && node_lists(h)) ? h->node_cnt_d.get() : nullptr;
     LAUNCH_ND(k_nodal_accel<2>, k_nodal_accel<3>, nblk(std::max(1, r.an + r.bn)), r.a0, r.an, r.b0, r.bn, h->N, gv[0], gv[1], gv[2],
-              ride ? 1 : 0, cnode, ctile, h->ntw);
-  };
-  const int law = h->uniform_law;  // -1: several laws in the cloud (law_present)
-  const bool one_mat = ND == 3 && h->nmats == 1 && law >= 1 && law <= 3;  // its constants by scalar loads (k3_body, UMAT)
-  const dim3 grid3(h->ntw), blk3(K3_BLK);
-  const double* const no_dU = nullptr;
-  // MD = 1: the fused K3; MD = 5: its state half (the step with the damage hooks; a gather and per-particle stores, no
+              f.ride ? 1 : 0, cnode, ctile, h->ntw);
+  }
+  // MODE 1: the fused K3; MODE 5: its state half (the step with the damage hooks; a gather and per-particle stores, no
   // nodal sum: the same launch forms in deterministic mode)
-  auto launch_k3_mode = [&](auto MODE_, int cls, bool signal) {
-    constexpr int MD = CT(MODE_);
-    TileD td = tile_view(h, cls);
-    const bool per_law = law < 0 && h->k3_per_law;  // one launch of the single-law kernel per law present (FILT)
-    if (signal && !per_law) arm_signal(h, td, 1);
-    if (MD == 1 && det) {  // one wave per tile and per law present, particles in list order, one slab per (tile, law)
-      td.slab_n = __builtin_popcount(h->law_present);
-      td.slab_slot = -1;
-      for_each_law_present(h->law_present, [&](int l, bool) {
-        td.slab_slot++;
-        with_nd(ND, [&](auto D) {
-          with_law(l, [&](auto L) {
-            hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 1, true, 64>), dim3(h->ntw), dim3(64), 0, h->stream, h->P, h->g, h->N, td,
-                               h->mats_d, h->prm, h->gstatus_d, no_dU);
-          });
-        });
-      });
-    } else if (one_mat) {
-      with_law_in<1, 3>(law, [&](auto L) {
-        hipLaunchKernelGGL((k3_tile<3, CT(L), MD, false, K3_BLK, true>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
-                           h->prm, h->gstatus_d, no_dU);
-      });
-    } else if (law >= 0) {
-      with_nd(ND, [&](auto D) {
-        with_law(law, [&](auto L) {
-          hipLaunchKernelGGL((k3_tile<CT(D), CT(L), MD>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
-                             h->gstatus_d, no_dU);
-        });
-      });
-    } else if (!per_law) {  // several laws, many mixed tiles: the kernel that dispatches on the law at run time
-      with_nd(ND, [&](auto D) {
-        hipLaunchKernelGGL((k3_tile<CT(D), -1, MD>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
-                           h->gstatus_d, no_dU);
-      });
-    } else {  // only the last launch releases the exchange (launches of one stream run in order)
-      for_each_law_present(h->law_present, [&](int l, bool last) {
-        if (signal && last) arm_signal(h, td, 1);
-        with_nd(ND, [&](auto D) {
-          with_law(l, [&](auto L) {
-            hipLaunchKernelGGL((k3_tile<CT(D), CT(L), MD, true>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
-                               h->prm, h->gstatus_d, no_dU);
-          });
-        });
-      });
-    }
-  };
-  auto launch_k3 = [&](int cls, bool signal) {
-    if (dmg) launch_k3_mode(ic<5>{}, cls, signal);
-    else launch_k3_mode(ic<1>{}, cls, signal);
-  };
-  auto launch_k3_lazy = [&](int cls, bool signal) {  // (lazy: one law, 0 .. NLPS_KLAW_FRICTIONAL)
-    TileD td = tile_view(h, cls);
-    if (signal) arm_signal(h, td, 1);
-    ln.tile_count = h->tile_count2_d + h->tile0;  // (after search_and_lists, which swaps the two counter arrays)
-    if (one_mat) {
-      with_law_in<1, 3>(law, [&](auto L) {
-        hipLaunchKernelGGL((k3_tile_lazy<3, CT(L), true>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
-                           h->gstatus_d, ln);
-      });
-    } else {
-      with_nd(ND, [&](auto D) {
-        with_law(law, [&](auto L) {
-          hipLaunchKernelGGL((k3_tile_lazy<CT(D), CT(L)>), grid3, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
-                             h->gstatus_d, ln);
-        });
-      });
-    }
-  };
-  K5Search ks;
-  ks.rank1 = h->rank1_d;
-  ks.bin = 1;
-  bool ks_made = false;
-  auto k5 = [&](int cls) {
+  void k3(int cls, bool signal = false) {
     const TileD td = tile_view(h, cls);
-    if (ride && !ks_made && !async_form) {  // (one TileCnt per step: it consumes the re-home flag of the adaptive re-sort)
+    if (f.lazy) return launch_k3_lazy(h, td, signal, ln);
+    const K3Launch a{signal, f.det && !f.dmg};
+    if (f.dmg) launch_k3<5>(h, td, a);
+    else launch_k3<1>(h, td, a);
+  }
+  void k5(int cls) {
+    const TileD td = tile_view(h, cls);
+    if (f.ride && !ks_made && !f.async_form) {  // (one TileCnt per step: it consumes the re-home flag of the adaptive re-sort)
       ks.tc = tile_cnt(h, true);
       ks.tc.count = h->tile_count2_d;  // (tile_count_d sizes the lists this very launch walks)
       ks.tc.defer = node_lists(h) ? 1 : 0;
@@ -5114,45 +5127,37 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
       ks_made = true;
     }
     const dim3 grid(h->ntw), blk(K5_BLK);
-    with_nd(ND, [&](auto D) {
+    with_nd(h->nd, [&](auto D) {
       // K5 exists in two forms: LAW = 0 serves laws 0 and 1, LAW = 2 every other law and the cloud of several
-      with_bool(law == 0 || law == 1, [&](auto L01) {
+      with_bool(f.law == 0 || f.law == 1, [&](auto L01) {
         constexpr int LAW = CT(L01) ? 0 : 2;
-        if (async_form) {  // (its search has run: search_next_and_fork)
+        if (f.async_form) {  // (its search has run: search_next_and_fork)
           hipLaunchKernelGGL((k5_tile_lazy<CT(D), LAW, false>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, dt, gamma_nm, ks, ln,
                              h->gstatus_d);
-        } else if (lazy) {
+        } else if (f.lazy) {
           hipLaunchKernelGGL((k5_tile_lazy<CT(D), LAW>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, dt, gamma_nm, ks, ln,
                              h->gstatus_d);
         } else {
-          with_bool(ride, [&](auto SEARCH) {
+          with_bool(f.ride, [&](auto SEARCH) {
             hipLaunchKernelGGL((k5_tile<CT(D), LAW, CT(SEARCH)>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, dt, gamma_nm, ks);
           });
         }
       });
     });
-  };
-  auto k3 = [&](int cls, bool signal = false) {
-    if (lazy) launch_k3_lazy(cls, signal);
-    else launch_k3(cls, signal);
-  };
+  }
   // async lists, between K3 and K5: the search of the next step on the handle's stream, then -- unless the brackets of
   // nlps_gpu_set_timing are on, which keep every kernel on the handle's stream and leave the lists to the next step, or
   // the next step starts with a re-sort and has to search again anyway -- its activation and list kernels on the side
   // stream, which K5 then runs beside.  They read what the search wrote (seeds, counters, tile / rank per particle, I0n)
   // and write the twin set only; K5 reads neither.
-  bool forked = false;
-  auto search_next_and_fork = [&]() -> int {
-    const int np = h->P.np;
+  int search_next_and_fork() {
+    const int np = h->P.np, ND = h->nd;
     TileCnt tc = tile_cnt(h, true);  // (one per step: it consumes the re-home flag of the adaptive re-sort)
     tc.count = h->tile_count2_d;     // (tile_count_d sizes the lists K5 walks)
     h->ranks_deferred = false;
     LAUNCH_ND((k_search_ahead<2>), (k_search_ahead<3>), nblk(np), h->P, h->g, h->N, h->rank1_d, tc);
     HIPCHK(hipGetLastError());
-    const bool adaptive = h->adaptive_resort > 0.0 && h->resort_every > 0;
-    const bool resort_next = h->resort_every > 0 && (h->steps_since_sort >= h->resort_every ||
-                                                     (adaptive && h->debt > h->adaptive_resort && h->steps_since_sort >= h->adaptive_min_steps));
-    if (h->timing || resort_next) return 0;
+    if (h->timing || resort_due(h)) return 0;
     if (ensure_list_twins(h)) return 1;
     HIPCHK(h->side.fork(h->stream));
     const hipStream_t ss = h->side.stream();
@@ -5180,35 +5185,28 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     HIPCHK(hipGetLastError());
     forked = true;
     return 0;
-  };
-  // The step with the damage hooks, between the state half of K3 (k3_tile<., ., 5>, launched by k3 above) and the nodal
+  }
+  // The step with the damage hooks, between the state half of K3 (MODE 5, launched by k3 above) and the nodal
   // accelerations: the node runs of this step's closest nodes (and, once per numbering of the slots, of the snapshot's),
   // the hook, which sets Damage_n1 (Strain_f_n1) and scales every Kirchhoff stress in place, and the force half.  All
   // on the handle's stream, no sort, no synchronisation, no allocation (nlps_gpu_set_explicit_damage made the tables).
-  auto damage_hook_and_forces = [&]() -> int {
+  int damage_hook_and_forces() {
     if (damage_runs_and_hook(h, true)) return 1;  // (every step has searched: the runs are this step's)
-    if (det)  // one wave per tile over the exact list, one slab per tile (slab_n = 1, slot 0); gather_force sums them
+    if (f.det)  // one wave per tile over the exact list, one slab per tile (slab_n = 1, slot 0); gather_force sums them
       LAUNCH_ND_BLK((k3f_wave<2, false>), (k3f_wave<3, false>), h->ntw, 64, h->P, h->g, h->N, tile_view(h, 0), h->gstatus_d);
     else
       LAUNCH_ND(k3f_tile<2>, k3f_tile<3>, h->ntw, h->P, h->g, h->N, tile_view(h, 0), h->gstatus_d);
     HIPCHK(hipGetLastError());
     return 0;
-  };
-  if (dmg && beps_snapshot(h)) return 1;  // (eigenerosion, first step: before the search moves any closest node)
-  h->nodal_stale = false;
-  // S1 + S2 (ev[1] is recorded between the search and the lists/Newton/P2G kernel; the nodal accumulators of
-  // the node window are reset by k_step_clear inside search_and_lists)
-  if (search_and_lists(h, false, true, dt, gamma_nm, ov2 ? 2 : (ov ? 1 : 0))) return 1;
-  if (h->timing) HIPCHK(hipEventRecord(h->ev[2], h->stream));
-  if (lazy) {  // (what nlps_gpu_explicit_nodal needs to make the nodal arrays of this step later)
-    h->nodal_stale = true;
-    h->last_bc = ln.fs.bc;
-    h->last_bm = ln.fs.bcmask;
-    for (int a = 0; a < 3; a++) h->last_gv[a] = gv[a];
   }
-  if (ov2) {
-    // mode 2: K2 is in flight as ONE launch; its boundary tiles release the exchange of the shared layers of nm, which
-    // runs beside its interior tiles; the handle's stream picks the result up before the nodal kernel
+
+  // The three schedules, each from behind search_and_lists (K2 is in flight) to the last particle kernel.  ev[3] .. ev[5]
+  // are the timing brackets of nlps_gpu_set_timing.
+  // Overlap mode 2: K2 is in flight as ONE launch; its boundary tiles release the exchange of the shared layers of nm,
+  // which runs beside its interior tiles; the handle's stream picks the result up before the nodal kernel.  (RCCL ranks,
+  // never deterministic: no slab gathers; no damage hooks, no contour loads, no async lists.)
+  int run_overlap2() {
+    const int ND = h->nd;
     if (halo(h, h->N.nm, 1 + ND, 8, 0, 3)) return 1;
     if (halo(h, h->N.nm, 1 + ND, 8, 0, 2)) return 1;
     nodal_dU(0);
@@ -5222,13 +5220,14 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     if (h->timing) HIPCHK(hipEventRecord(h->ev[5], h->stream));
     k5(0);
     HIPCHK(hipGetLastError());
-  } else {
-  // with ghost bands the shared layers are gathered first (only boundary tiles reach them) and go on their way
-  // while the rest is summed
-  gather_nm(ov ? 2 : 0);
-  if (halo(h, h->N.nm, 1 + ND, 8, 0, ov ? 1 : 0)) return 1;
-  // nodal dU = (sum m N dD) / M + Dirichlet values; S3 + S4
-  if (ov) {
+    return 0;
+  }
+  // Overlap mode 1: with ghost bands the shared layers are gathered first (only boundary tiles reach them) and go on
+  // their way while the rest is summed.  (Ranks with an exchange: no damage hooks, no contour loads, no async lists.)
+  int run_overlap1() {
+    const int ND = h->nd;
+    gather_nm(2);
+    if (halo(h, h->N.nm, 1 + ND, 8, 0, 1)) return 1;
     gather_nm(1);
     nodal_dU(1);
     // timing brackets: the K3 bucket starts before the interior tiles (the band nodes' dU then counts as K3 time)
@@ -5237,23 +5236,10 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     if (halo(h, h->N.nm, 1 + ND, 8, 0, 2)) return 1;
     nodal_dU(2);
     k3(1);
-  } else {
-    nodal_dU(0);
-    if (h->timing) HIPCHK(hipEventRecord(h->ev[3], h->stream));
-    k3(0);
-    if (dmg && h->P.np > 0 && damage_hook_and_forces()) return 1;
-  }
-  HIPCHK(hipGetLastError());
-  if (h->timing) HIPCHK(hipEventRecord(h->ev[4], h->stream));
-  gather_force(ov ? 2 : 0);
-  // the contour tractions (one rank: ov is false): behind K3's atomics -- or the fixed-order sum of its slabs -- in stream
-  // order, in front of the readers of N.force (k_nodal_accel, K5's windows; the folded form keeps N.force for
-  // materialise_nodal).  Nothing resets N.force between k_step_clear / k_dilate_scan at the head of the step and here;
-  // the side stream of the async lists forks behind this launch and resets the twin set only.
-  if (loads && explicit_loads_launch(h, step)) return 1;
-  if (halo(h, h->N.force, ND, 8, 0, ov ? 1 : 0)) return 1;
-  // nodal acceleration; S5
-  if (ov) {
+    HIPCHK(hipGetLastError());
+    if (h->timing) HIPCHK(hipEventRecord(h->ev[4], h->stream));
+    gather_force(2);
+    if (halo(h, h->N.force, ND, 8, 0, 1)) return 1;
     gather_force(1);
     nodal_accel(1);
     if (h->timing) HIPCHK(hipEventRecord(h->ev[5], h->stream));
@@ -5261,54 +5247,133 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
     if (halo(h, h->N.force, ND, 8, 0, 2)) return 1;
     nodal_accel(2);
     k5(1);
-  } else {
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  // One pass over all tiles per stage; an exchange, where there is one, blocks in place.
+  int run_one_pass() {
+    const int ND = h->nd, np = h->P.np;
+    gather_nm(0);
+    if (halo(h, h->N.nm, 1 + ND, 8, 0, 0)) return 1;
+    nodal_dU(0);
+    if (h->timing) HIPCHK(hipEventRecord(h->ev[3], h->stream));
+    k3(0);
+    if (f.dmg && np > 0 && damage_hook_and_forces()) return 1;
+    HIPCHK(hipGetLastError());
+    if (h->timing) HIPCHK(hipEventRecord(h->ev[4], h->stream));
+    gather_force(0);
+    // the contour tractions: behind K3's atomics -- or the fixed-order sum of its slabs -- in stream order, in front of
+    // the readers of N.force (k_nodal_accel, K5's windows; the folded form keeps N.force for materialise_nodal).  Nothing
+    // resets N.force between k_step_clear / k_dilate_scan at the head of the step and here; the side stream of the async
+    // lists forks behind this launch and resets the twin set only.
+    if (f.loads && explicit_loads_launch(h, step)) return 1;
+    if (halo(h, h->N.force, ND, 8, 0, 0)) return 1;
     nodal_accel(0);
-    if (async_form && search_next_and_fork()) return 1;
+    if (f.async_form && search_next_and_fork()) return 1;
     if (h->timing) HIPCHK(hipEventRecord(h->ev[5], h->stream));
     k5(0);
-    if (dmg && h->P.np > 0) hipLaunchKernelGGL(k_damage_roll, dim3(nblk(h->P.np)), dim3(BLK), 0, h->stream, h->P);
+    if (f.dmg && np > 0) hipLaunchKernelGGL(k_damage_roll, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->P);
+    HIPCHK(hipGetLastError());
+    // (anything later on the handle's stream, from any entry of the API, is ordered behind the side work too)
+    if (forked) HIPCHK(h->side.join(h->stream));
+    return 0;
   }
-  HIPCHK(hipGetLastError());
-  // (anything later on the handle's stream, from any entry of the API, is ordered behind the side work too)
-  if (forked) HIPCHK(h->side.join(h->stream));
-  }  // !ov2
+};
+
+// The timing brackets of nlps_gpu_set_timing behind a step: ms[0 .. 7] of nlps_gpu_get_timing.  (Synchronises.)
+static int step_timing_read(nlps_gpu* h, bool loads) {
+  HIPCHK(hipEventRecord(h->ev[6], h->stream));
+  // calibration bracket: a kernel of K3's grid and argument block that does nothing; what it reads is the part of
+  // a one-kernel bracket that is not kernel time (records, dispatch, launch of the empty grid)
+  k3_go(h, k_null_bracket, BLK, tile_view(h, 0), no_rates);
+  HIPCHK(hipEventRecord(h->ev[7], h->stream));
+  HIPCHK(hipEventSynchronize(h->ev[7]));
+  float t[7];  // t[q]: from ev[q] to ev[q + 1]
+  for (int q = 0; q < 7; q++) HIPCHK(hipEventElapsedTime(&t[q], h->ev[q], h->ev[q + 1]));
+  h->ms[0] = t[0];  // search
+  h->ms[1] = t[1];  // lists + K2
+  h->ms[2] = t[3];  // K3
+  h->ms[3] = t[5];  // K5
+  h->ms[4] = t[2] + t[4];  // the nodal kernels
+  h->ms[5] = t[6];  // the calibration bracket
+  h->ms[7] = 0.f;  // the contour-traction kernel (nlps_gpu_set_explicit_loads)
+  if (loads) HIPCHK(hipEventElapsedTime(&h->ms[7], h->xl_ev[0], h->xl_ev[1]));
+  h->ms[6] = 0.f;  // time the handle's stream spent in / waiting for the ghost-layer exchanges of this step
+  for (int q = 0; q < h->nwait; q++) {
+    float tw = 0.f;
+    HIPCHK(hipEventElapsedTime(&tw, h->evw[2 * q], h->evw[2 * q + 1]));
+    h->ms[6] += tw;
+  }
+  return 0;
+}
+
+extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc, int step, double dt, double gamma_nm,
+                                      const double* gravity) {
+  tan_stale(h, "nlps_gpu_explicit_step");
+  const int ND = h->nd;
+  if (explicit_step_refuse(h, nbcc, step)) return 1;
+  if (ensure_bcs(h, bcc, nbcc)) return 1;
+  if (!h->Pd_alt && h->resort_every > 0 && h->P.np > 0) {
+    // the twin block of the periodic re-sort, at the first step of the fused scheme rather than inside the first
+    // re-sort: a hipMalloc of this size (1.3 GB per million particles) takes milliseconds, the re-sort itself 0.3
+    HIPCHK(h->Pd_alt.reserve((size_t)NFD * h->P.npad));
+    HIPCHK(hipMemsetAsync(h->Pd_alt, 0, (size_t)NFD * h->P.npad * sizeof(double), h->stream));
+  }
+  if (!h->rolled && h->P.np > 0) {  // entering the fused scheme: rho J of every particle (see F_RHOJ)
+    hipLaunchKernelGGL(k_init_rhoj, dim3(nblk(h->P.np)), dim3(BLK), 0, h->stream, h->P);
+    HIPCHK(hipGetLastError());
+  }
+  // the periodic re-sort (resort_due).  This step's cost estimate first: the count of particles outside their tiles at a
+  // recent step sits in the pinned word (no synchronisation: it may be a step old), its share of the cloud is the estimate
+  if (h->adaptive_resort > 0.0 && !h->deterministic && h->resort_every > 0 && h->P.np > 0)
+    h->debt += (double)*(volatile int*)h->foreign_h.host() / (double)h->P.np;
+  if (resort_due(h) && resort(h, nullptr, true)) return 1;
+  h->steps_since_sort++;
+  h->nwait = 0;
+  if (h->timing) HIPCHK(hipEventRecord(h->ev[0], h->stream));
+
+  ExplicitStep s{h, bcc, nbcc, step, dt, gamma_nm, step_form(h, bcc, nbcc, step)};
+  const StepForm& f = s.f;
+  gravity3(gravity, ND, s.gv);
+  if (f.det && !h->slab_d) {
+    const size_t NWs = ND == 3 ? TileCfg<3>::NWA : TileCfg<2>::NWA;
+    const size_t per_tile = std::max<size_t>((size_t)(1 + ND), (size_t)4 * ND) * NWs;  // K2: one slab; K3: one per law
+    HIPCHK(h->slab_d.reserve((size_t)h->ntiles * per_tile));
+  }
+  if (f.lazy) {
+    s.ln.fs.bc = f.bs;
+    s.ln.fs.bcmask = f.bm;
+    for (int a = 0; a < 3; a++) s.ln.fs.gv[a] = s.gv[a];
+    s.ln.n0 = h->n0;
+    s.ln.nwn = h->nwn;
+    s.ln.node_cnt = node_lists(h) ? h->node_cnt_d.get() : nullptr;
+    s.ln.ntw = h->ntw;  // (ln.tile_count: behind search_and_lists, which swaps the two counter arrays)
+  }
+  s.ks.rank1 = h->rank1_d;
+  s.ks.bin = 1;
+  if (f.dmg && beps_snapshot(h)) return 1;  // (eigenerosion, first step: before the search moves any closest node)
+  h->nodal_stale = false;
+  // S1 + S2 (ev[1] is recorded between the search and the lists/Newton/P2G kernel; the nodal accumulators of
+  // the node window are reset by k_step_clear inside search_and_lists)
+  if (search_and_lists(h, false, true, dt, gamma_nm, f.ov2 ? 2 : (f.ov ? 1 : 0))) return 1;
+  if (h->timing) HIPCHK(hipEventRecord(h->ev[2], h->stream));
+  if (f.lazy) {  // (what nlps_gpu_explicit_nodal needs to make the nodal arrays of this step later)
+    s.ln.tile_count = h->tile_count2_d + h->tile0;
+    h->nodal_stale = true;
+    h->last_bc = s.ln.fs.bc;
+    h->last_bm = s.ln.fs.bcmask;
+    for (int a = 0; a < 3; a++) h->last_gv[a] = s.gv[a];
+  }
+  // S3 + S4 (K3 between the nodal dU and the forces), S5 (nodal acceleration, K5)
+  if (f.ov2 ? s.run_overlap2() : f.ov ? s.run_overlap1() : s.run_one_pass()) return 1;
+
   h->P.flip ^= 1;  // F_n <- F_n+1, b_e,n <- b_e,n+1 by renaming
   h->rolled = true;
-  h->rolled_keep = dmg;  // (tau and W of this step are stored: k_copy_n_to_n1 must not re-make them)
-  h->searched = ride;  // K5 has updated the closest nodes for the positions it wrote ...
-  h->ahead = ride;     // ... and binned the particles for the next step
-  h->lists_ready = forked;
-  if (h->timing) {
-    HIPCHK(hipEventRecord(h->ev[6], h->stream));
-    // calibration bracket: a kernel of K3's grid and argument block that does nothing; what it reads is the part of
-    // a one-kernel bracket that is not kernel time (records, dispatch, launch of the empty grid)
-    hipLaunchKernelGGL(k_null_bracket, dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, h->N,
-                       tile_view(h, 0), h->mats_d, h->prm, h->gstatus_d, (const double*)nullptr);
-    HIPCHK(hipEventRecord(h->ev[7], h->stream));
-    HIPCHK(hipEventSynchronize(h->ev[7]));
-    float t01, t12, t23, t34, t45, t56, t67;
-    HIPCHK(hipEventElapsedTime(&t67, h->ev[6], h->ev[7]));
-    h->ms[5] = t67;
-    HIPCHK(hipEventElapsedTime(&t01, h->ev[0], h->ev[1]));
-    HIPCHK(hipEventElapsedTime(&t12, h->ev[1], h->ev[2]));
-    HIPCHK(hipEventElapsedTime(&t23, h->ev[2], h->ev[3]));
-    HIPCHK(hipEventElapsedTime(&t34, h->ev[3], h->ev[4]));
-    HIPCHK(hipEventElapsedTime(&t45, h->ev[4], h->ev[5]));
-    HIPCHK(hipEventElapsedTime(&t56, h->ev[5], h->ev[6]));
-    h->ms[0] = t01;
-    h->ms[1] = t12;
-    h->ms[2] = t34;
-    h->ms[3] = t56;
-    h->ms[4] = t23 + t45;
-    h->ms[7] = 0.f;  // the contour-traction kernel (nlps_gpu_set_explicit_loads)
-    if (loads) HIPCHK(hipEventElapsedTime(&h->ms[7], h->xl_ev[0], h->xl_ev[1]));
-    h->ms[6] = 0.f;  // time the handle's stream spent in / waiting for the ghost-layer exchanges of this step
-    for (int q = 0; q < h->nwait; q++) {
-      float tw = 0.f;
-      HIPCHK(hipEventElapsedTime(&tw, h->evw[2 * q], h->evw[2 * q + 1]));
-      h->ms[6] += tw;
-    }
-  }
+  h->rolled_keep = f.dmg;  // (tau and W of this step are stored: k_copy_n_to_n1 must not re-make them)
+  h->searched = f.ride;    // K5 has updated the closest nodes for the positions it wrote ...
+  h->ahead = f.ride;       // ... and binned the particles for the next step
+  h->lists_ready = s.forked;
+  if (h->timing && step_timing_read(h, f.loads)) return 1;
   // the step record: behind the last particle kernel of the step (and the join of the side stream), outside the timing brackets; N.active, N.nm and
   // N.force of this step are intact in every form (placement table), nothing here writes them
   if (h->rec_on && rec_step(h, NLPS_REC_KIND_EXPLICIT, step, dt, bcc, nbcc)) return 1;
@@ -5421,8 +5486,8 @@ extern "C" int nlps_gpu_form_initial_guess(nlps_gpu* h, double* dU, const double
   if (n > 0) hipLaunchKernelGGL(k_vec_initial_guess, dim3(nblk(n)), dim3(BLK), 0, h->stream, n, d, v, a, dt, use_explicit_trial);
   for (int i = 0; i < nbcc; i++) {
     if (h->bcs[i].n == 0) continue;
-    double val[3] = {0, 0, 0};
-    for (int k = 0; k < bcc[i].dim && k < 3; k++) val[k] = bcc[i].value[(size_t)k * h->nsteps + step];
+    double val[3];
+    bc_values(bcc[i], step, h->nsteps, val);
     hipLaunchKernelGGL(k_vec_guess_bc, dim3(nblk(h->bcs[i].n)), dim3(BLK), 0, h->stream, h->bcs[i].dnodes, h->bcs[i].n, ND,
                        bcc[i].dim, dirbits_of(bcc[i], step, h->nsteps), val[0], val[1], val[2], h->n2m_d, d);
   }
@@ -5458,9 +5523,8 @@ extern "C" int nlps_gpu_nodal_inertial_forces(nlps_gpu* h, double* R, const doub
   const int n = (int)io.n, ND = h->nd;
   double* r = io.out(R, true);
   const double *m = io.in(M), *u = io.in(dU), *v = io.in(Un_dt), *a = io.in(Un_dt2);
-  double b[3] = {0, 0, 0};
-  if (gravity)
-    for (int k = 0; k < ND; k++) b[k] = gravity[k];
+  double b[3];
+  gravity3(gravity, ND, b);
   if (n > 0)
     hipLaunchKernelGGL(k_vec_inertial, dim3(nblk(n)), dim3(BLK), 0, h->stream, n, ND, r, m, u, v, a, h->d2m_d, alpha[0], alpha[1],
                        alpha[2], b[0], b[1], b[2]);
@@ -5516,49 +5580,24 @@ static int snes_fnorm_launch(nlps_gpu* h, const double* F);  // (defined with nl
 // handle's stream, no sort, no synchronisation, no allocation (the setter made the tables).  The level-B stages keep
 // tables of their own (dmg_*, the sort buffers): nothing here touches them.
 static int lagrangian_damage_launches(nlps_gpu* h) {
-  const int ND = h->nd;
-  const dim3 grid(h->ntw), blk3(K3_BLK);
   if (beps_snapshot(h)) return 1;  // (taken by the first search: nothing to do here for a handle that has searched)
   // deterministic mode with nlps_gpu_set_deterministic_damage: the exact lists, sorted runs, the one-wave force half and
-  // the fixed-order sum of its slabs; the atomic flush otherwise
+  // the fixed-order sum of its slabs; the atomic flush otherwise.  (The lists are made exact in front of the state half
+  // already; scatter_tiles below then finds nothing left to prepare.)
   const bool det = det_implicit(h);
   if (det && det_prepare(h, "nlps_gpu_lagrangian_evaluation")) return 1;
   TileD td = tile_view(h);
   if (!det) td.slab = nullptr;
-  const int law = h->uniform_law;
-  const double* const no_dV = nullptr;
-  if (law < 0) {  // one launch per law present, every workgroup compacting its tile's particles of that law first (FILT)
-    for_each_law_present(h->law_present, [&](int l, bool) {
-      with_nd(ND, [&](auto D) {
-        with_law(l, [&](auto L) {
-          hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 6, true>), grid, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
-                             h->gstatus_d, no_dV);
-        });
-      });
-    });
-  } else if (ND == 3 && h->nmats == 1 && law >= 1 && law <= 3) {  // one material (k3_body, UMAT)
-    with_law_in<1, 3>(law, [&](auto L) {
-      hipLaunchKernelGGL((k3_tile<3, CT(L), 6, false, K3_BLK, true>), grid, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
-                         h->prm, h->gstatus_d, no_dV);
-    });
-  } else {
-    with_nd(ND, [&](auto D) {
-      with_law(law, [&](auto L) {
-        hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 6>), grid, blk3, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
-                           h->gstatus_d, no_dV);
-      });
-    });
-  }
+  launch_k3<6>(h, td, K3Launch{});  // (a cloud of several laws: per law present, FILT)
   // (built once per numbering: nothing between two calls that make the matrix-free operator stale changes a closest node)
   if (damage_runs_and_hook(h, h->xrun_gen != h->tan_gen)) return 1;
   h->xrun_gen = h->tan_gen;
   h->dmg_fused_evals++;
-  if (det) {
-    LAUNCH_ND_BLK((k3f_wave<2, true>), (k3f_wave<3, true>), h->ntw, 64, h->P, h->g, h->N, td, h->gstatus_d);
-    DET_GATHER(2, 3, 1, h->N.force);
-  } else {
-    LAUNCH_ND_BLK((k3f_tile<2, true>), (k3f_tile<3, true>), h->ntw, K3_BLK, h->P, h->g, h->N, td, h->gstatus_d);
-  }
+  if (scatter_tiles<2, 3>(h, "nlps_gpu_lagrangian_evaluation", 1, h->N.force, [&](auto NT, TileD) {  // (on this site's td)
+        if (CT(NT) == 64) LAUNCH_ND_BLK((k3f_wave<2, true>), (k3f_wave<3, true>), h->ntw, 64, h->P, h->g, h->N, td, h->gstatus_d);
+        else LAUNCH_ND_BLK((k3f_tile<2, true>), (k3f_tile<3, true>), h->ntw, K3_BLK, h->P, h->g, h->N, td, h->gstatus_d);
+      }))
+    return 1;
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -5644,67 +5683,18 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
   if (h->timing) HIPCHK(hipEventRecord(h->ev[2], h->stream));
   if (dmg) {  // (before the deterministic form below, which does not hold the hook: it has a deterministic form of its own)
     if (lagrangian_damage_launches(h)) return 1;
-  } else if (det_implicit(h)) {
-    // deterministic mode: one wave per tile and per law present over the exact lists (ordered compaction), one slab per
-    // (tile, law) -- a tile without a particle of the law writes zeros --, then the fixed-order sum into N.force
-    if (det_prepare(h, "nlps_gpu_lagrangian_evaluation")) return 1;
-    TileD td = tile_view(h);
-    td.slab_n = __builtin_popcount(h->law_present);
-    td.slab_slot = -1;
-    for_each_law_present(h->law_present, [&](int l, bool) {
-      td.slab_slot++;
-      with_nd(ND, [&](auto D) {
-        if (l == NLPS_KLAW_FLUID) {
-          hipLaunchKernelGGL((k3_tile<CT(D), NLPS_KLAW_FLUID, 4, true, 64>), dim3(h->ntw), dim3(64), 0, h->stream, h->P, h->g, h->N,
-                             td, h->mats_d, h->prm, h->gstatus_d, (const double*)h->gridB.get());
-          return;
-        }
-        with_law(l, [&](auto L) {
-          hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 3, true, 64>), dim3(h->ntw), dim3(64), 0, h->stream, h->P, h->g, h->N, td,
-                             h->mats_d, h->prm, h->gstatus_d, (const double*)nullptr);
-        });
-      });
-    });
-    DET_GATHER(2, 3, td.slab_n, h->N.force);
   } else {
-    TileD td = tile_view(h);
-    td.slab = nullptr;  // (the atomic flush: handles outside the deterministic implicit path, see det_implicit)
-    const dim3 grid(h->ntw), blk(K3_BLK);
-    const int law = h->uniform_law;
-    if (law < 0) {
-      // a cloud of several laws: one launch per law present of the kernel compiled for that law, every workgroup compacting
-      // its tile's particles of that law first (FILT, as the explicit step's per-law launches)
-      for_each_law_present(h->law_present, [&](int l, bool) {
-        with_nd(ND, [&](auto D) {
-          if (l == NLPS_KLAW_FLUID) {  // the fluid's particles in the rate-carrying mode, the solids' in MODE 3
-            hipLaunchKernelGGL((k3_tile<CT(D), NLPS_KLAW_FLUID, 4, true>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
-                               h->prm, h->gstatus_d, (const double*)h->gridB.get());
-            return;
-          }
-          with_law(l, [&](auto L) {
-            hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 3, true>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
-                               h->gstatus_d, (const double*)nullptr);
-          });
-        });
-      });
-    } else if (law == NLPS_KLAW_FLUID) {
-      with_nd(ND, [&](auto D) {
-        hipLaunchKernelGGL((k3_tile<CT(D), NLPS_KLAW_FLUID, 4>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
-                           h->gstatus_d, (const double*)h->gridB.get());
-      });
-    } else if (ND == 3 && h->nmats == 1 && law >= 1 && law <= 3) {  // one material (k3_body, UMAT)
-      with_law_in<1, 3>(law, [&](auto L) {
-        hipLaunchKernelGGL((k3_tile<3, CT(L), 3, false, K3_BLK, true>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d,
-                           h->prm, h->gstatus_d, (const double*)nullptr);
-      });
-    } else {
-      with_nd(ND, [&](auto D) {
-        with_law(law, [&](auto L) {
-          hipLaunchKernelGGL((k3_tile<CT(D), CT(L), 3>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm,
-                             h->gstatus_d, (const double*)nullptr);
-        });
-      });
-    }
+    // MODE 3, the fluid's particles in the rate-carrying MODE 4 (dV = gridB, k_expand_reset_rates).  Deterministic mode:
+    // one wave per tile and per law present over the exact lists (ordered compaction), one slab per (tile, law) -- a
+    // tile without a particle of the law writes zeros --, then the fixed-order sum into N.force.  Otherwise the atomic
+    // flush, without a slab pointer: one launch, or one per law present (FILT) for a cloud of several laws.
+    const int nlaws = __builtin_popcount(h->law_present);
+    if (scatter_tiles<2, 3>(h, "nlps_gpu_lagrangian_evaluation", nlaws, h->N.force, [&](auto NT, TileD td) {
+          const bool wave = CT(NT) == 64;
+          if (!wave) td.slab = nullptr;
+          launch_k3<3>(h, td, K3Launch{false, wave, h->gridB.get()});
+        }))
+      return 1;
   }
   HIPCHK(hipGetLastError());
   if (h->timing) HIPCHK(hipEventRecord(h->ev[3], h->stream));
@@ -5712,9 +5702,8 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
   int any = 0;
   if (nloads > 0 && traction_to_grid(h, "nlps_gpu_lagrangian_evaluation", h->gridA, loads, nloads, step, thickness, area0, &any))
     return 1;
-  double b[3] = {0, 0, 0};
-  if (gravity)
-    for (int k = 0; k < ND; k++) b[k] = gravity[k];
+  double b[3];
+  gravity3(gravity, ND, b);
   LAUNCH_ND((k_lagrangian_nodal<2>), (k_lagrangian_nodal<3>), nblk(h->g.nnodes), h->g.nnodes, (const int*)h->n2m_d,
             (const int*)h->d2m_d, (const double*)h->N.force, any ? (const double*)h->gridA : (const double*)nullptr, r, m, u, v,
             a, alpha[0], alpha[1], alpha[2], b[0], b[1], b[2], (const int*)h->gstatus_d, h->status_h.alias());
@@ -5920,16 +5909,11 @@ static int tanop_product(nlps_gpu* h, const double* v, double* y, const KspPc* p
     LAUNCH_ND((k_tanop_expand<2>), (k_tanop_expand<3>), nblk(nn), nn, (const int*)h->n2m_d, d2m, v, xg);
     HIPCHK(hipMemsetAsync(yg, 0, (size_t)nn * ND * sizeof(double), h->stream));
   }
-  if (h->top_np > 0 && det_implicit(h)) {
-    if (det_prepare(h, "nlps_gpu_tangent_apply")) return 1;
-    const TileD td = tile_view(h);
-    LAUNCH_ND_BLK((k_tanop_apply<2, 64>), (k_tanop_apply<3, 64>), h->ntw, 64, h->P, h->g, td, (const double*)h->top_d, h->top_np,
-                  (const double*)xg, yg);
-    DET_GATHER(2, 3, 1, yg);
-  } else if (h->top_np > 0) {
-    const TileD td = tile_view(h);
-    LAUNCH_ND(k_tanop_apply<2>, k_tanop_apply<3>, h->ntw, h->P, h->g, td, (const double*)h->top_d, h->top_np, (const double*)xg, yg);
-  }
+  if (h->top_np > 0 && scatter_tiles<2, 3>(h, "nlps_gpu_tangent_apply", 1, yg, [&](auto NT, const TileD td) {
+        LAUNCH_ND_BLK((k_tanop_apply<2, CT(NT)>), (k_tanop_apply<3, CT(NT)>), h->ntw, CT(NT), h->P, h->g, td,
+                      (const double*)h->top_d, h->top_np, (const double*)xg, yg);
+      }))
+    return 1;
   HIPCHK(hipGetLastError());
   if (halo(h, yg, ND, 8, 0)) return 1;
   LAUNCH_ND((k_tanop_nodal<2>), (k_tanop_nodal<3>), nblk(nn), nn, (const int*)h->n2m_d, d2m, (const double*)yg, xin,
@@ -5962,16 +5946,12 @@ extern "C" int nlps_gpu_tangent_apply(nlps_gpu* h, const double* x, double* y) {
 static int tanop_bdiag(nlps_gpu* h, double* out) {
   const int ND = h->nd, E = ND * ND, nn = h->g.nnodes;
   int st = hipMemsetAsync(h->top_g, 0, (size_t)nn * E * sizeof(double), h->stream) != hipSuccess;
-  if (!st && h->top_np > 0 && det_implicit(h)) {
-    if (det_prepare(h, "nlps_gpu_tangent_block_diagonal")) return 1;
-    const TileD td = tile_view(h);
-    LAUNCH_ND_BLK((k_tanop_bdiag<2, 64>), (k_tanop_bdiag<3, 64>), h->ntw, 64, h->P, h->g, td, (const double*)h->top_d, h->top_np,
-                  h->top_g.get());
-    DET_GATHER(4, 9, 1, h->top_g.get());
-    st = hipGetLastError() != hipSuccess;
-  } else if (!st && h->top_np > 0) {
-    const TileD td = tile_view(h);
-    LAUNCH_ND(k_tanop_bdiag<2>, k_tanop_bdiag<3>, h->ntw, h->P, h->g, td, (const double*)h->top_d, h->top_np, h->top_g);
+  if (!st && h->top_np > 0) {
+    if (scatter_tiles<4, 9>(h, "nlps_gpu_tangent_block_diagonal", 1, h->top_g.get(), [&](auto NT, const TileD td) {
+          LAUNCH_ND_BLK((k_tanop_bdiag<2, CT(NT)>), (k_tanop_bdiag<3, CT(NT)>), h->ntw, CT(NT), h->P, h->g, td,
+                        (const double*)h->top_d, h->top_np, h->top_g.get());
+        }))
+      return 1;
     st = hipGetLastError() != hipSuccess;
   }
   if (!st) st = halo(h, h->top_g, E, 8, 0);

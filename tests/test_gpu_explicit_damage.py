@@ -69,8 +69,15 @@ def test_eigenerosion_steps_with_resorts():
 
 
 def test_eigenerosion_steps_interleaved_laws():
-    """Neo-Hookean and Hencky particles in turn: the state half runs once per law (FILT)"""
+    """Neo-Hookean and Hencky particles in turn: the state half of a cloud of several laws (the launch form the library
+    picks for it)"""
     run_erosion(3, (0, 1))
+
+
+def test_eigenerosion_steps_interleaved_laws_per_law_launches():
+    """the same cloud with one launch of the state half per law present (nlps_gpu_set_law_launch_mode 1; the library's own
+    choice for laws in turn is the kernel that dispatches on the law)"""
+    run_erosion(3, (0, 1), prepare=lambda S: S.set_law_launch_mode(1))
 
 
 def test_level_b_force_evaluation_on_top_of_damage_steps():

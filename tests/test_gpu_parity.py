@@ -1510,7 +1510,7 @@ def test_adaptive_resort_only_moves_memory():
         assert_close(a[k], b[k], 1e-10, f"adaptive re-sort on / off: {k}")
 
 
-@pytest.mark.parametrize("ndim,material", [(2, DP), (3, NH)])
+@pytest.mark.parametrize("ndim,material", [(2, DP), (3, NH), (3, DP)])  # (3, DP): the one-material kernels (UMAT) of both forms
 def test_folded_step_matches_the_nodal_kernels(ndim, material):
     """Default on one GPU: K3 and K5 make dU and the accelerations of their window nodes themselves (k3_tile_lazy,
     k5_tile_lazy) and the nodal arrays are only made on request.  Same state, same nodal arrays as the form with the

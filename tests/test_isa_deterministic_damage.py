@@ -1,27 +1,18 @@
 """The ISA of the deterministic mode for clouds with the damage hooks (nlps_gpu_set_deterministic_damage):
 the one-wave force half k3f_wave<ND, PLUS> exists for both dimensions and both signs, holds no global f64 atomic add (its
 window leaves as a plain slab copy) while k3f_tile of the same dimension and sign does, and uses no scratch; the run sort
-k_run_sort exists and uses no scratch.  Compiles the device code to assembly with the product flags, as
-tests/test_isa_deterministic_implicit.py does (hipcc cross-compiles without a GPU)."""
-import os
+k_run_sort exists and uses no scratch.  Reads the device assembly tests/isa_asm.py
+compiles (the product flags, once per process; hipcc cross-compiles without a GPU)."""
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import isa_asm
 
 
 @pytest.mark.timeout(900)
-def test_one_wave_force_half_and_run_sort(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    out = str(tmp_path / "dev.s")
-    subprocess.check_call([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics",
-                           "-fvisibility=hidden", "-fvisibility-inlines-hidden", "--cuda-device-only", "-S", "-o", out,
-                           os.path.join(ROOT, "nl-partsol_amd", "csrc", "nlps_gpu.hip")], stderr=subprocess.DEVNULL)
-    txt = open(out).read()
+def test_one_wave_force_half_and_run_sort():
+    txt = isa_asm.device_asm()
     blocks = dict(re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, re.S))
 
     def scratch(name):

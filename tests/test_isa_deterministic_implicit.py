@@ -1,28 +1,20 @@
 """The ISA of the deterministic mode on the implicit path: the one-wave-per-tile forms of the fused
 residual, the matrix-free tangent and the level-B scatters exist in the library's device code, the slab gather exists
 for their field counts, none of the tile kernels holds a global f64 atomic add (their windows leave as plain slab
-copies), and none uses more scratch than the 256-thread kernel it is cut from.  Compiles the device code to assembly
-with the product flags, as tests/test_isa_explicit_damage.py does (hipcc cross-compiles without a GPU)."""
-import os
+copies), and none uses more scratch than the 256-thread kernel it is cut from.  Reads the device assembly tests/isa_asm.py
+compiles (the product flags, once per process; hipcc cross-compiles without a GPU)."""
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import isa_asm
+
 FLUID = 5  # NLPS_KLAW_FLUID
 
 
 @pytest.mark.timeout(900)
-def test_one_wave_forms_exist_without_global_atomics(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    out = str(tmp_path / "dev.s")
-    subprocess.check_call([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics",
-                           "-fvisibility=hidden", "-fvisibility-inlines-hidden", "--cuda-device-only", "-S", "-o", out,
-                           os.path.join(ROOT, "nl-partsol_amd", "csrc", "nlps_gpu.hip")], stderr=subprocess.DEVNULL)
-    txt = open(out).read()
+def test_one_wave_forms_exist_without_global_atomics():
+    txt = isa_asm.device_asm()
     blocks = dict(re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, re.S))
 
     def scratch(name):

@@ -1,29 +1,21 @@
 """The ISA of the kernels of the explicit step with the damage hooks: they exist in the library's device
 code, the list, roll and force kernels use no scratch memory, and the state half of K3 (k3_tile<., ., 5, ...>) uses no
 more than a few registers' worth beyond the fused kernel of the same law, which it is cut from (it stores tau and W on
-top).  The barrier check of tests/test_isa.py covers every kernel, these included.  Compiles the device code to assembly
-with the product flags, as tests/test_isa_newton.py does (hipcc cross-compiles without a GPU)."""
-import os
+top).  The barrier check of tests/test_isa.py covers every kernel, these included.  Reads the device assembly tests/isa_asm.py
+compiles (the product flags, once per process; hipcc cross-compiles without a GPU)."""
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import isa_asm
+
 # what the state half may spill beyond its fused sibling: eight 4-byte registers per lane
 STATE_HALF_EXTRA_SCRATCH = 32
 
 
 @pytest.mark.timeout(900)
-def test_damage_step_kernels_exist_and_scratch(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    out = str(tmp_path / "dev.s")
-    subprocess.check_call([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics",
-                           "-fvisibility=hidden", "-fvisibility-inlines-hidden", "--cuda-device-only", "-S", "-o", out,
-                           os.path.join(ROOT, "nl-partsol_amd", "csrc", "nlps_gpu.hip")], stderr=subprocess.DEVNULL)
-    txt = open(out).read()
+def test_damage_step_kernels_exist_and_scratch():
+    txt = isa_asm.device_asm()
     blocks = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, re.S)
 
     def scratch(name, body):

@@ -2,29 +2,21 @@
 MODE 3 (k3_tile<., ., 6, ...>) exists in the launch forms the residual's call site has -- plain per dimension and law,
 per-law (FILT), and the one-material form (UMAT) of the 3-D laws 1-3 -- and uses no more than a few registers' worth of
 scratch beyond the fused residual kernel of the same law, which it is cut from; both force halves (k3f_tile<ND, false>, the
-explicit step's, and k3f_tile<ND, true>, the residual's) use no scratch.  Compiles the device code to assembly with the
-product flags, as tests/test_isa_explicit_damage.py does (hipcc cross-compiles without a GPU)."""
-import os
+explicit step's, and k3f_tile<ND, true>, the residual's) use no scratch.  Reads the device assembly tests/isa_asm.py
+compiles (the product flags, once per process; hipcc cross-compiles without a GPU)."""
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import isa_asm
+
 # what a state half may spill beyond its fused sibling: eight 4-byte registers per lane (tests/test_isa_explicit_damage.py)
 STATE_HALF_EXTRA_SCRATCH = 32
 
 
 @pytest.mark.timeout(900)
-def test_fused_damage_residual_kernels_exist_and_scratch(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    out = str(tmp_path / "dev.s")
-    subprocess.check_call([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics",
-                           "-fvisibility=hidden", "-fvisibility-inlines-hidden", "--cuda-device-only", "-S", "-o", out,
-                           os.path.join(ROOT, "nl-partsol_amd", "csrc", "nlps_gpu.hip")], stderr=subprocess.DEVNULL)
-    txt = open(out).read()
+def test_fused_damage_residual_kernels_exist_and_scratch():
+    txt = isa_asm.device_asm()
     blocks = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, re.S)
 
     def scratch(name, body):

@@ -1,25 +1,16 @@
 """The ISA of the Newton solve's kernels (nl-partsol_amd/csrc/nlps_newton.hpp, prefix k_snes_): they exist in the library's
-device code and none of them uses scratch memory.  Compiles the device code to assembly with the product flags, as
-tests/test_isa_krylov.py does (hipcc cross-compiles without a GPU)."""
-import os
+device code and none of them uses scratch memory.  Reads the device assembly tests/isa_asm.py
+compiles (the product flags, once per process; hipcc cross-compiles without a GPU)."""
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import isa_asm
 
 
 @pytest.mark.timeout(900)
-def test_newton_kernels_exist_and_use_no_scratch(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    out = str(tmp_path / "dev.s")
-    subprocess.check_call([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics",
-                           "-fvisibility=hidden", "-fvisibility-inlines-hidden", "--cuda-device-only", "-S", "-o", out,
-                           os.path.join(ROOT, "nl-partsol_amd", "csrc", "nlps_gpu.hip")], stderr=subprocess.DEVNULL)
-    txt = open(out).read()
+def test_newton_kernels_exist_and_use_no_scratch():
+    txt = isa_asm.device_asm()
     blocks = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, re.S)
     snes = {name: body for name, body in blocks if "k_snes_" in name}
     assert snes, "no k_snes_ kernel in the device code"
