@@ -431,15 +431,52 @@ __global__ __launch_bounds__(BLK) void k_search(PView P, GridD g, NView N, const
 // K5 visits -- the particles of this step's lists, P.tile[] >= 0 -- and moves what K5 moves (load_lme: a particle
 // without a neighbourhood stays where it is and keeps its node).  I0n is written for EVERY particle (= I0 for one that is
 // in no list), so the host can adopt the whole array by exchanging the two pointers.
+//
+// The deferred move (nlps_gpu::move_pending).  In the deferred form K5 (k5_tile_lazy<., ., false, true>) leaves x and dis
+// alone, and this kernel records per particle, in moved[], the predicate it has formed anyway: "K5 moves this particle".
+// K2 of the next step applies x += d_dis, dis += d_dis to every marked particle of its lists and clears the mark
+// (k2_body); k_materialise_move does it for every marked particle when somebody else wants x first.
+// Particles the next lists leave out (moved by this step, then outside the node window: status 16, P.tile < 0) are
+// visited by no K2.  The rule: a mark that is still set when the NEXT k_search_ahead comes by -- it visits every
+// particle, behind K2 of its step -- is applied here, before the new predicate is formed; K3 and K5 of that step never
+// touch an unlisted particle, so d_dis is still the one the mark was made for.  A materialise in between takes them like
+// any other mark.  record = 0 (the step keeps the in-place K5): the stale marks are applied, none is made.
 template <int ND>
-__global__ __launch_bounds__(BLK) void k_search_ahead(PView P, GridD g, NView N, const uint8_t* __restrict__ rank1, TileCnt tc) {
+__device__ __forceinline__ void apply_move(const PView& P, int p, double* x) {  // the additions of k5_body
+#pragma unroll
+  for (int a = 0; a < ND; a++) {
+    const double dd = PF(P, F_DDIS + a, p);
+    x[a] = PF(P, F_X + a, p) + dd;
+    PF(P, F_X + a, p) = x[a];
+    PF(P, F_DIS + a, p) = PF(P, F_DIS + a, p) + dd;
+  }
+}
+template <int ND>
+__global__ __launch_bounds__(BLK) void k_materialise_move(PView P, unsigned char* __restrict__ moved) {
+  const int p = blockIdx.x * BLK + threadIdx.x;
+  if (p >= P.np || !moved[p]) return;
+  double x[ND];
+  apply_move<ND>(P, p, x);
+  moved[p] = 0;
+}
+template <int ND>
+__global__ __launch_bounds__(BLK) void k_search_ahead(PView P, GridD g, NView N, const uint8_t* __restrict__ rank1, TileCnt tc,
+                                                      unsigned char* __restrict__ moved, int record) {
   const int p = blockIdx.x * BLK + threadIdx.x;
   int I0n = 0;
   bool binned = false;
   if (p < P.np) {
     I0n = P.I0[p];
     binned = P.tile[p] >= 0;
-    if (binned && (P.mlo[p] | P.mhi[p]) != 0ull) {
+    const bool moves = binned && (P.mlo[p] | P.mhi[p]) != 0ull;
+    if (moved) {
+      if (moved[p]) {  // left out of this step's lists: see above
+        double x[ND];
+        apply_move<ND>(P, p, x);
+      }
+      moved[p] = (record && moves) ? 1 : 0;
+    }
+    if (moves) {
       double xn[ND], dn2 = 0.0;
 #pragma unroll
       for (int a = 0; a < ND; a++) {
@@ -1899,6 +1936,17 @@ struct nlps_gpu {
   DevBuf<int> nwork2_d, tile_start2_d, order_2_d, order2_2_d;
   DevBuf<unsigned char> N_active2, N_fixed2;
   DevBuf<double> N_nm2, N_force2;
+  // The deferred move (k_search_ahead): an async step with the step record off whose successor does not start with a
+  // re-sort runs K5 without the move x += d_dis, dis += d_dis and has the search mark the particles K5 would have moved.
+  // K2 of the next step applies the marks of the particles it lists; while move_pending, everything else that reads or
+  // writes x / dis, reorders the particles or rebuilds lists from them calls materialise_move() first, so x is current
+  // at every boundary of the API.
+  DevBuf<unsigned char> moved_d;  // [npad] marks, all zero while !move_pending
+  bool move_pending = false;
+  // Below this many particles a step keeps the in-place K5: every kernel of the step is then a few microseconds of
+  // launch and latency, and the operands K2 and the search take on cost more than K5 saves (13 824 particles: 0.1272
+  // -> 0.1285 ms per step; equal at 110 000, ahead from 373 000 on).  nlps_gpu_debug_option "defer_move_min".
+  int defer_move_min = 100000;
 
   nlps_halo_fn halo;
   void* halo_ctx;
@@ -1933,6 +1981,16 @@ static inline void tan_stale(nlps_gpu* h, const char* why) {
   h->tan_why = why;
 }
 static int materialise_nodal(nlps_gpu* h);  // the nodal arrays the folded explicit step left unmade (defined with the step)
+
+// The move the last explicit step left to the next K2 (nlps_gpu::move_pending), for every marked particle, on the
+// handle's stream -- behind the join of the side stream, whose search made the marks.
+static int materialise_move(nlps_gpu* h) {
+  if (!h->move_pending) return 0;
+  LAUNCH_ND((k_materialise_move<2>), (k_materialise_move<3>), nblk(h->P.np), h->P, h->moved_d.get());
+  HIPCHK(hipGetLastError());
+  h->move_pending = false;
+  return 0;
+}
 
 static bool is_device_ptr(const void* p) {
   hipPointerAttribute_t a;
@@ -2491,6 +2549,7 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
   tan_stale(h, "a re-sort of the particle arrays");
   const int np = h->P.np;
   if (np == 0) return 0;
+  if (materialise_move(h)) return 1;  // (d_dis does not travel with live_only, and the marks are per slot)
   // The tile lists of the last step in canonical order (order2_d: layer r = the r-th particle of every closest node,
   // nodes in lattice order) ARE the memory order the kernels want -- each wave then reads 64 consecutive slots that hit
   // 64 distinct window rows -- so the periodic re-sort of the fused step takes them as its permutation: no keys, no
@@ -2626,6 +2685,7 @@ extern "C" int nlps_gpu_download_ids(nlps_gpu* h, int* ids) {
 extern "C" int nlps_gpu_migration_select(nlps_gpu* h, int keep_lo, int keep_hi, int* n_down, int* n_up, int* row_words,
                                          void** down_rows, void** up_rows) {
   const int np = h->P.np;
+  if (materialise_move(h)) return 1;
   HIPCHK(hipMemsetAsync(h->mig_cnt_d, 0, 2 * sizeof(int), h->stream));
   HIPCHK(hipMemsetAsync(h->leaving_d, 0, h->P.npad, h->stream));
   if (np > 0) LAUNCH_ND((k_mig_flag<2>), (k_mig_flag<3>), nblk(np), h->P, h->g, keep_lo, keep_hi, h->leaving_d, h->mig_slot_d, h->mig_cnt_d);
@@ -2666,6 +2726,7 @@ extern "C" int nlps_gpu_migration_commit(nlps_gpu* h, const void* rows_a, int n_
   }
   h->mig_selected = false;
   if (n_in == 0 && n_out == 0) return 0;
+  if (materialise_move(h)) return 1;
   const void* src[2] = {rows_a, rows_b};
   const int cnt[2] = {n_a, n_b};
   int first = np;
@@ -2697,6 +2758,7 @@ extern "C" int nlps_gpu_resort(nlps_gpu* h) { return resort(h); }
 extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_option(nlps_gpu* h, const char* name, double value) {
   const std::string k(name ? name : "");
   if (k == "lazy_nodal") h->lazy_nodal = (int)value;             // folded explicit step: 0 never, 1 below 2 M particles, 2 always
+  else if (k == "defer_move_min") h->defer_move_min = (int)value;  // deferred move: the smallest cloud that defers (tests: 0)
   else if (k == "async_lists") h->async_lists = value != 0;      // one-rank folded step: next step's lists on the side stream (1) or in front of K2 (0)
   else if (k == "tangent_symmetric") h->tangent_symmetric = value != 0;  // Neo-Hookean clouds: half rows + mirror (1) or every pair (0)
   else if (k == "loads_lane_map") h->xl_lane_map = value != 0;  // explicit loads: one lane per contour particle (1) or one wave (0)
@@ -2859,6 +2921,7 @@ extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_damage_coun
 extern "C" int nlps_gpu_destroy(nlps_gpu* h) {
   if (!h) return 0;
   (void)nlps_gpu_rccl_detach(h);
+  (void)materialise_move(h);  // (nothing reads it any more; the handle just never dies with a state half written)
   (void)hipStreamSynchronize(h->stream);
   for (int i = 0; i < 8; i++) (void)hipEventDestroy(h->ev[i]);
   for (hipEvent_t e : h->evw)
@@ -3030,6 +3093,7 @@ extern "C" int nlps_gpu_shape_functions(nlps_gpu* h, int first, int count, doubl
     return 1;
   }
   if (count == 0) return 0;
+  if (materialise_move(h)) return 1;
   if (refresh_perm(h)) return 1;
   // device slots of the caller's particles first .. first + count - 1
   std::vector<int> slot_of(np), slots(count), I0(np);
@@ -3497,6 +3561,7 @@ static int rccl_migrate(nlps_gpu* h, int keep_lo, int keep_hi, int* sent_down, i
     h->err = "nlps_gpu_rccl_selftest_migrate: needs an attached communicator of world size 1";
     return 1;
   }
+  if (materialise_move(h)) return 1;  // (steps run before the communicator was attached)
   const int nl = h->g.n[h->nd - 1];
   if (!self_loop) {  // an edge rank has no neighbour on its outer side: nothing may be selected towards it
     if (R->rank == 0) keep_lo = 0;
@@ -3922,13 +3987,17 @@ static void launch_k2(nlps_gpu* h, bool p2g, int cls, double dt, double gamma_nm
   if (signal) arm_signal(h, td, 0);
   if (h->deterministic && p2g) {  // one wave per tile, sorted list, slab flush (nlps_gpu_set_deterministic)
     LAUNCH_ND_BLK((k2_tile<2, true, 64>), (k2_tile<3, true, 64>), h->ntw, 64, h->P, h->g, h->N, td, h->prm, dt, gamma_nm,
-                  h->gstatus_d);
+                  h->gstatus_d, (unsigned char*)nullptr);
     return;
   }
+  // A move still pending here is this K2's to apply: nlps_gpu_explicit_step has left it pending for its async form only
+  // (one launch over all tiles, p2g), and every other caller of search_and_lists has materialised it.  The marks of
+  // particles outside the lists stay set, and move_pending with them, until the search of this step (k_search_ahead).
+  unsigned char* moved = (p2g && h->move_pending) ? h->moved_d.get() : nullptr;
   with_nd(h->nd, [&](auto D) {
     with_bool(p2g, [&](auto P2G) {
       hipLaunchKernelGGL((k2_tile<CT(D), CT(P2G)>), dim3(h->ntw), dim3(BLK), 0, h->stream, h->P, h->g, h->N, td,
-                         h->prm, dt, gamma_nm, h->gstatus_d);
+                         h->prm, dt, gamma_nm, h->gstatus_d, moved);
     });
   });
 }
@@ -3977,6 +4046,7 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
                             bool launch_lists_kernel = true) {
   int np = h->P.np;
   if (!p2g && materialise_nodal(h)) return 1;  // (a level-B search rewrites the active flags the lazy nodal arrays depend on)
+  if (!p2g && materialise_move(h)) return 1;   // (the explicit step decides for itself: K2 below may be the one that moves)
   // ahead: the search of this step was done by the last kernel of the previous one (k5_tile<., ., true>); only the
   // nodal accumulators are reset here
   const bool ahead = h->ahead && !init, searched = h->searched;
@@ -4047,6 +4117,7 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
 }
 
 static int materialise_roll(nlps_gpu* h) {
+  if (materialise_move(h)) return 1;  // (whoever wants the n+1 slots in place wants x and dis in place too)
   if (!h->rolled) return 0;
   if (h->rolled_keep) LAUNCH_ND((k_copy_n_to_n1<2, true>), (k_copy_n_to_n1<3, true>), nblk(h->P.np), h->P, h->mats_d);
   else LAUNCH_ND((k_copy_n_to_n1<2>), (k_copy_n_to_n1<3>), nblk(h->P.np), h->P, h->mats_d);
@@ -4085,6 +4156,7 @@ extern "C" int nlps_gpu_initialize_lme(nlps_gpu* h) {
 // what it sees -- positions and closest nodes -- is kept for the lists that stay frozen afterwards
 static int beps_snapshot(nlps_gpu* h) {
   if (h->beps_snapshot || !h->P.erosion || h->P.softening || h->P.np == 0) return 0;
+  if (materialise_move(h)) return 1;
   hipLaunchKernelGGL(k_beps_snapshot, dim3(nblk(h->P.np)), dim3(BLK), 0, h->stream, h->P, h->nd);
   HIPCHK(hipGetLastError());
   h->beps_snapshot = true;
@@ -4240,6 +4312,7 @@ static int need_masks(nlps_gpu* h, const char* who) {
 
 extern "C" int nlps_gpu_lumped_mass(nlps_gpu* h, double* M) {
   if (need_masks(h, "nlps_gpu_lumped_mass")) return 1;
+  if (materialise_move(h)) return 1;
   int ND = h->nd;
   HIPCHK(hipMemsetAsync(h->gridA, 0, (size_t)h->g.nnodes * sizeof(double), h->stream));
   if (scatter_tiles<1, 1>(h, "nlps_gpu_lumped_mass", 1, h->gridA, [&](auto NT, TileD td) {
@@ -4253,6 +4326,7 @@ extern "C" int nlps_gpu_lumped_mass(nlps_gpu* h, double* M) {
 
 extern "C" int nlps_gpu_nodal_field_n(nlps_gpu* h, double* V, double* A, const double* M) {
   if (need_masks(h, "nlps_gpu_nodal_field_n")) return 1;
+  if (materialise_move(h)) return 1;
   int ND = h->nd;
   HIPCHK(hipMemsetAsync(h->gridA, 0, (size_t)h->g.nnodes * 2 * ND * sizeof(double), h->stream));
   if (scatter_tiles<4, 6>(h, "nlps_gpu_nodal_field_n", 1, h->gridA, [&](auto NT, TileD td) {
@@ -4478,6 +4552,7 @@ static int traction_to_grid(nlps_gpu* h, const char* who, double* out, const nlp
 extern "C" int nlps_gpu_nodal_traction_forces(nlps_gpu* h, double* R, const nlps_bcc* loads, int nloads, int step,
                                               double thickness, const double* area0) {
   if (need_masks(h, "nlps_gpu_nodal_traction_forces")) return 1;
+  if (materialise_move(h)) return 1;
   int any = 0;
   if (traction_to_grid(h, "nlps_gpu_nodal_traction_forces", h->gridA, loads, nloads, step, thickness, area0, &any)) return 1;
   if (!any) return 0;
@@ -4786,6 +4861,7 @@ static int rec_check(nlps_gpu* h, const char* who) {
 // One row of the state as it stands, on the handle's stream: no allocation, no synchronisation, no copy.  bcc / nbcc /
 // step: the Dirichlet sets of the explicit step that has just run (kind NLPS_REC_KIND_EXPLICIT), else nbcc = 0.
 static int rec_write(nlps_gpu* h, int kind, int step, double dt, const nlps_bcc* bcc, int nbcc) {
+  if (materialise_move(h)) return 1;  // (nlps_gpu_record_now between two steps; a step with the record on defers nothing)
   const int np = h->P.np, nb = np > 0 ? std::min(nblk(np, REC_NT), REC_MAX_BLOCKS) : 0;
   double* row = h->rec_rows_d + (size_t)(h->rec_total % h->rec_capacity) * h->rec_row;
   const int lazy = (h->rolled && !h->rolled_keep) ? 1 : 0;  // tau and W of the hyperelastic laws are not stored
@@ -4875,6 +4951,7 @@ extern "C" int nlps_gpu_update_kinetics(nlps_gpu* h, double alpha_blend, const d
                                         const double* dU_dt, const double* dU_dt2) {
   tan_stale(h, "nlps_gpu_update_kinetics");
   if (need_masks(h, "nlps_gpu_update_kinetics")) return 1;
+  if (materialise_move(h)) return 1;
   h->searched = h->ahead = h->lists_ready = false;  // the particles move: the next search is a search
   int ND = h->nd;
   size_t st = (size_t)h->g.nnodes * ND;
@@ -5074,6 +5151,7 @@ struct ExplicitStep {
   bool tiles_cleared = false;  // the tile counters of the riding search are reset by the first nodal_accel that runs
   bool ks_made = false;        // ks.tc is made by the first K5 launch
   bool forked = false;         // the side stream holds the list kernels of the next step
+  bool deferred = false;       // K5 of this step leaves the move to the next K2 (nlps_gpu::move_pending)
 
   // second half of the deterministic flushes: per node, the window slabs of the tiles that hold it (part: node_ranges)
   void gather_nm(int part) { if (f.det) det_gather<3, 4>(h, part, 1, h->N.nm); }
@@ -5131,7 +5209,10 @@ struct ExplicitStep {
       // K5 exists in two forms: LAW = 0 serves laws 0 and 1, LAW = 2 every other law and the cloud of several
       with_bool(f.law == 0 || f.law == 1, [&](auto L01) {
         constexpr int LAW = CT(L01) ? 0 : 2;
-        if (f.async_form) {  // (its search has run: search_next_and_fork)
+        if (deferred) {  // (its search is in flight beside it, or has run: search_next_and_fork)
+          hipLaunchKernelGGL((k5_tile_lazy<CT(D), LAW, false, true>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, dt, gamma_nm,
+                             ks, ln, h->gstatus_d);
+        } else if (f.async_form) {  // (its search has run: search_next_and_fork)
           hipLaunchKernelGGL((k5_tile_lazy<CT(D), LAW, false>), grid, blk, 0, h->stream, h->P, h->g, h->N, td, dt, gamma_nm, ks, ln,
                              h->gstatus_d);
         } else if (f.lazy) {
@@ -5150,17 +5231,45 @@ struct ExplicitStep {
   // the next step starts with a re-sort and has to search again anyway -- its activation and list kernels on the side
   // stream, which K5 then runs beside.  They read what the search wrote (seeds, counters, tile / rank per particle, I0n)
   // and write the twin set only; K5 reads neither.
+  // The deferred form (step record off, no re-sort at the head of the next step: nlps_gpu::move_pending) runs K5 without
+  // the move, so nothing K5 writes is read by the search, and the fork comes in front of the search: the whole chain
+  // k_search_ahead, k_dilate_scan, k_fill_orders runs beside K5.  Who touches what between the fork and the join:
+  //   k5_tile_lazy<., ., false, true>  reads   x, lambda, beta, I0, mlo, mhi, vel of the particles of this step's lists
+  //                                            (td.order_m, tile_start / tile_count of the set in use), nm, force, active
+  //                                            and fixed of the set in use, the Dirichlet sets;   writes acc, vel, gstatus (or)
+  //   k_search_ahead                   reads   I0, tile, mlo, mhi, x, dis, d_dis, moved, rank1;   writes I0n, tile, rank, nrank,
+  //                                            seed, tile_count2, node_cnt, home / foreign, moved, status / gstatus (or), and
+  //                                            x, dis of a particle whose mark K2 did not take -- one in no list, which K5
+  //                                            never visits
+  //   k_dilate_scan<., 256>            reads   seed, tile_count2, node_cnt;   writes active, fixed, nm, force of the TWIN set,
+  //                                            tile_start2, work1_2, nwork2, the layer tables (tile_tab), foreign_h
+  //   k_fill_orders                    reads   tile, rank, nrank, I0n, tile_start2, the layer tables;   writes order_2, order2_2
+  // tile_count2, node_cnt and the seeds are reset by K3's workgroups (LazyNodal), so the fork stands behind K3.  With the
+  // timing brackets on, the same K5 runs behind the search on the handle's stream and the lists are left to the next step.
   int search_next_and_fork() {
     const int np = h->P.np, ND = h->nd;
     TileCnt tc = tile_cnt(h, true);  // (one per step: it consumes the re-home flag of the adaptive re-sort)
     tc.count = h->tile_count2_d;     // (tile_count_d sizes the lists K5 walks)
     h->ranks_deferred = false;
-    LAUNCH_ND((k_search_ahead<2>), (k_search_ahead<3>), nblk(np), h->P, h->g, h->N, h->rank1_d, tc);
-    HIPCHK(hipGetLastError());
-    if (h->timing || resort_due(h)) return 0;
-    if (ensure_list_twins(h)) return 1;
-    HIPCHK(h->side.fork(h->stream));
+    const bool next_sorts = resort_due(h);
+    deferred = !h->rec_on && !next_sorts && np >= h->defer_move_min;
+    const bool lists = !h->timing && !next_sorts;
+    if (deferred && !h->moved_d) {
+      HIPCHK(h->moved_d.reserve(h->P.npad));
+      HIPCHK(hipMemsetAsync(h->moved_d, 0, h->P.npad, h->stream));
+    }
+    if (lists && ensure_list_twins(h)) return 1;
+    const bool side_search = deferred && lists;  // (nothing K5 writes is read by the search any more: the whole chain beside K5)
+    if (side_search) HIPCHK(h->side.fork(h->stream));
     const hipStream_t ss = h->side.stream();
+    with_nd(ND, [&](auto D) {
+      hipLaunchKernelGGL(k_search_ahead<CT(D)>, dim3(nblk(np)), dim3(BLK), 0, side_search ? ss : h->stream, h->P, h->g, h->N,
+                         h->rank1_d.get(), tc, h->moved_d.get(), deferred ? 1 : 0);
+    });
+    HIPCHK(hipGetLastError());
+    if (h->moved_d) h->move_pending = deferred;  // (stale marks are gone either way; new ones exist in the deferred form)
+    if (!lists) return 0;
+    if (!side_search) HIPCHK(h->side.fork(h->stream));
     const int TB = ND == 3 ? TileCfg<3>::TB : TileCfg<2>::TB;
     TileScanArgs ts{h->tile_count2_d + h->tile0, h->tile_start2_d + h->tile0, h->ntw, h->tile0, h->ntiles / h->nt[ND - 1], TB,
                     h->band_lo, h->band_hi, h->work1_2_d, h->nwork2_d, nullptr};
@@ -5334,6 +5443,11 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
 
   ExplicitStep s{h, bcc, nbcc, step, dt, gamma_nm, step_form(h, bcc, nbcc, step)};
   const StepForm& f = s.f;
+  // A move the last step left pending is applied by K2 of this step where the step goes from here straight to its one K2
+  // launch: the async form, on lists from the search done ahead -- nothing in front of that K2 reads x or dis (a re-sort
+  // above has materialised it).  Every other form has it applied now; so has a step with contour loads, whose traction
+  // kernel reads x of every contour particle between K2 and the search, one left out of the lists included.
+  if (!(f.async_form && h->ahead && !f.loads) && materialise_move(h)) return 1;
   gravity3(gravity, ND, s.gv);
   if (f.det && !h->slab_d) {
     const size_t NWs = ND == 3 ? TileCfg<3>::NWA : TileCfg<2>::NWA;
@@ -5607,6 +5721,7 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
                                               const double* gravity, const nlps_bcc* loads, int nloads, int step,
                                               double thickness, const double* area0, int flags) {
   if (need_masks(h, "nlps_gpu_lagrangian_evaluation")) return 1;
+  if (materialise_move(h)) return 1;
   if (!R || !dU || !Un_dt || !Un_dt2 || !M || !alpha) {
     h->err = "nlps_gpu_lagrangian_evaluation: R, dU, Un_dt, Un_dt2, M and alpha are required";
     return 1;
@@ -5793,6 +5908,7 @@ extern "C" int nlps_gpu_tangent_coo(nlps_gpu* h, double alpha_1, const double* l
     return 1;
   }
   if (need_masks(h, "nlps_gpu_tangent_coo")) return 1;
+  if (materialise_move(h)) return 1;
   const int ND = h->nd, nn = h->g.nnodes;
   const size_t ne = (size_t)h->knnz_blocks * ND * ND;
   if (ne == 0) return 0;
@@ -5830,6 +5946,7 @@ extern "C" int nlps_gpu_sparsity_pattern(nlps_gpu* h, int* nnz_per_row) {
     return 1;
   }
   if (need_masks(h, "nlps_gpu_sparsity_pattern")) return 1;
+  if (materialise_move(h)) return 1;
   const int ND = h->nd, nn = h->g.nnodes;
   DevBuf<int> pat_d;
   HIPCHK(pat_d.reserve((size_t)h->nactive * ND + 4));

@@ -579,10 +579,12 @@ __device__ __forceinline__ void fused_nodal_accel(const NView& N, const NodalFol
 // ------------------------------------------------------------------------------------------------
 // body of k2_tile for one work item; acc [NF * NWA] doubles and actrow [NROWS] words of LDS are the caller's.
 // fs: unused by K2 (kept so that the three stage bodies share one signature)
+// moved: the marks of a pending deferred move (nlps_gpu::move_pending), or null
 template <int ND, bool P2G, int NT>
 __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NView& N, const TileD& td, const ParamsD& prm,
                                         double dt, double gamma_nm, int* __restrict__ gstatus, const TileWork& tw, int nbnd,
-                                        double* acc, unsigned* actrow, const NodalFold* fs) {
+                                        double* acc, unsigned* actrow, const NodalFold* fs,
+                                        unsigned char* __restrict__ moved) {
   constexpr int W = TileCfg<ND>::W, NW = TileCfg<ND>::NW, NF = 1 + ND, NROWS = WinRows<ND>::NROWS;
   constexpr int WA = TileCfg<ND>::WA, PSA = TileCfg<ND>::PSA, NWA = TileCfg<ND>::NWA;
   constexpr int KN = Lme<ND>::KN;
@@ -618,6 +620,31 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
     for (int a = 0; a < ND; a++) {
       x[a] = PF(P, F_X + a, p);
       lam[a] = PF(P, F_LAM + a, p);
+    }
+    // The deferred move (k_search_ahead): the last step's K5 left x and dis of the marked particles alone; they move here,
+    // by the additions of k5_body.  `moved` is a kernel argument, so the test is wave-uniform; every other step passes null.
+    // The operands are requested for every particle, beside x and lambda, and only the stores wait for the mark: with
+    // the loads behind the test, each trip of this loop waited for two more round trips to memory in a row (K2 +14 us
+    // at 1 M particles, all that K5 had saved).
+    if (moved != nullptr) {
+      double dd[ND], dis[ND];
+#pragma unroll
+      for (int a = 0; a < ND; a++) {
+        dd[a] = PF(P, F_DDIS + a, p);
+        dis[a] = PF(P, F_DIS + a, p);
+      }
+      const unsigned char mark = moved[p];
+#pragma unroll
+      for (int a = 0; a < ND; a++) asm volatile("" : "+v"(dd[a]), "+v"(dis[a]));  // (keeps the loads in front of the test)
+      if (mark) {
+#pragma unroll
+        for (int a = 0; a < ND; a++) {
+          x[a] = x[a] + dd[a];
+          PF(P, F_X + a, p) = x[a];
+          PF(P, F_DIS + a, p) = dis[a] + dd[a];
+        }
+        moved[p] = 0;
+      }
     }
     const int I0 = P.I0[p];
     c.geom(g, x, I0);
@@ -833,14 +860,14 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
 static constexpr int K2_WAVES = 3, K2_WAVES_2D = 3;
 template <int ND, bool P2G, int NT = BLK>
 __global__ __launch_bounds__(NT, NT == 64 ? 1 : (ND == 2 ? K2_WAVES_2D : K2_WAVES)) void k2_tile(PView P, GridD g, NView N, TileD td, ParamsD prm, double dt,
-                                               double gamma_nm, int* __restrict__ gstatus) {
+                                               double gamma_nm, int* __restrict__ gstatus, unsigned char* __restrict__ moved) {
   __shared__ double acc[(1 + ND) * TileCfg<ND>::NWA];
   __shared__ unsigned actrow[WinRows<ND>::NROWS];
   const int nbnd = tile_boundary_count(td);
   tile_signal_empty(td, nbnd);
   TileWork tw;
   if (!tile_work_item(td, tw)) return;
-  k2_body<ND, P2G, NT>(P, g, N, td, prm, dt, gamma_nm, gstatus, tw, nbnd, acc, actrow, nullptr);
+  k2_body<ND, P2G, NT>(P, g, N, td, prm, dt, gamma_nm, gstatus, tw, nbnd, acc, actrow, nullptr, moved);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1826,10 +1853,13 @@ struct K5Search {
   int bin;  // 0: closest-node update only (I0n); the seeds and bins are left to k_search in its adopt form.  (The host always
             // sets 1 now; the field goes with a later change of the kernels that read it.)
 };
-template <int ND, int LAW, bool SEARCH>
+// DEFER (SEARCH = false only): the deferred move.  x and dis are neither loaded for the corrector nor stored: K2 of the
+// next step moves the particle (k_search_ahead has marked it), and this kernel writes acc and vel alone.
+template <int ND, int LAW, bool SEARCH, bool DEFER = false>
 __device__ __forceinline__ void k5_body(const PView& P, const GridD& g, const NView& N, const TileD& td, double dt,
                                         double gamma_nm, const K5Search& ks, const TileWork& tw, double* axy, double* az,
                                         const NodalFold* fs, int* __restrict__ gstatus) {
+  static_assert(!(SEARCH && DEFER), "the riding search needs the position this kernel writes");
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN;
   const int tile = tw.tile;
   const int cnt = td.count[tile];
@@ -1891,9 +1921,9 @@ __device__ __forceinline__ void k5_body(const PView& P, const GridD& g, const NV
       double dd_[ND], vel_[ND], dis_[ND];
 #pragma unroll
       for (int a = 0; a < ND; a++) {
-        dd_[a] = PF(P, F_DDIS + a, p);
+        if (!DEFER) dd_[a] = PF(P, F_DDIS + a, p);
         vel_[a] = PF(P, F_VEL + a, p);
-        dis_[a] = PF(P, F_DIS + a, p);
+        if (!DEFER) dis_[a] = PF(P, F_DIS + a, p);
       }
 #pragma unroll 1  // real plane loop: unrolled it measured +14 %
       for (int k = 0; k < KN; k++) {
@@ -1927,9 +1957,11 @@ __device__ __forceinline__ void k5_body(const PView& P, const GridD& g, const NV
       double xn[ND], dn2 = 0.0;
 #pragma unroll
       for (int a = 0; a < ND; a++) {
-        const double dd = dd_[a], av = sv[a] * Zinv;
+        const double av = sv[a] * Zinv;
         PF(P, F_ACC + a, p) = av;
         PF(P, F_VEL + a, p) = vel_[a] + gamma_nm * dt * av;
+        if (DEFER) continue;
+        const double dd = dd_[a];
         xn[a] = PF(P, F_X + a, p) + dd;
         PF(P, F_X + a, p) = xn[a];
         const double dn = dis_[a] + dd;
@@ -1966,14 +1998,15 @@ __global__ __launch_bounds__(K5_BLK) void k5_tile(PView P, GridD g, NView N, Til
 
 // SEARCH = false: the one-rank form whose search is a kernel of its own in front of this one (k_search_ahead), so that
 // the lists of the next step can be built on a second stream while this kernel runs
-template <int ND, int LAW, bool SEARCH = true>
+// DEFER: the deferred move (k5_body)
+template <int ND, int LAW, bool SEARCH = true, bool DEFER = false>
 __global__ __launch_bounds__(K5_BLK) void k5_tile_lazy(PView P, GridD g, NView N, TileD td, double dt, double gamma_nm, K5Search ks,
                                                        LazyNodal ln, int* __restrict__ gstatus) {
   __shared__ __attribute__((aligned(16))) double axy[2 * TileCfg<ND>::NW];
   __shared__ double az[(ND == 3) ? TileCfg<ND>::NW : 1];
   TileWork tw;
   if (!tile_work_item(td, tw)) return;
-  k5_body<ND, LAW, SEARCH>(P, g, N, td, dt, gamma_nm, ks, tw, axy, az, &ln.fs, gstatus);
+  k5_body<ND, LAW, SEARCH, DEFER>(P, g, N, td, dt, gamma_nm, ks, tw, axy, az, &ln.fs, gstatus);
 }
 
 // ------------------------------------------------------------------------------------------------
