@@ -343,6 +343,59 @@ int nlps_gpu_record_now(nlps_gpu *h, int tag);                              /* o
 int nlps_gpu_read_step_records(nlps_gpu *h, long long *total, int *count, double *rows, int max_rows);
 /* the time step of Courant.c: CFL h / Cel, or with a row CFL h / (Cel + row[NLPS_REC_VMAX_COMP]) (DynamicTimeStep) */
 double nlps_host_courant_dt(double CFL, double h, double Cel, const double *row /* or NULL */);
+/* The particle snapshot: what a driver WRITES a run out by (the particle VTK every N steps of GramsOutputs (i=N), the
+ * state a restart starts from) without nlps_gpu_download_state and its stall.  nlps_gpu_snapshot_begin launches one pack
+ * kernel on the handle's stream, which gathers the selected fields into a staging block on the device, and queues one
+ * asynchronous copy of that block to pinned host memory on a stream of the snapshot's own; the steps that follow run
+ * beside the copy.  The caller picks the snapshot up later with nlps_gpu_snapshot_wait.
+ *
+ * Values: the selected arrays are bit for bit what nlps_gpu_download_state would have returned, had it been called in
+ *   place of nlps_gpu_snapshot_begin, in the same layout ([np][ndim] vectors, [np][5 | 9] tensors, Back_stress [np][3],
+ *   caller's particle order) -- in every state the handle can be in between two calls: after an explicit step of any
+ *   form (non-folded, folded, async lists, deferred move, deterministic, with the damage hooks, with contour loads),
+ *   after the level-B stages, after nlps_gpu_newmark_step, after any re-sort, right after create.  The field set is the
+ *   n state and the kinematics (what an output reads and what nlps_gpu_create takes back); the n+1 slots, DF, the rate
+ *   tensors and C_ep stay with nlps_gpu_download_state.  Damage_n and Strain_f_n are defined for every cloud, as they
+ *   are there (0, or what was uploaded, on a cloud without the damage drivers).
+ * No writes: begin reads through the pending state and writes nothing to the particle arrays -- x + d_dis and dis +
+ *   d_dis of the particles a deferred move has marked, tau and W of the hyperelastic laws after a folded step and rho =
+ *   (rho J) / J_n inside the fused scheme are formed in registers with the expressions the download's kernels use, and the
+ *   n slots of F and b_e are read under the current renaming.  The steps behind it launch exactly what they would have
+ *   launched without it.
+ * Cost of begin: the pack kernel and an event record on the handle's stream (in front of the first pack behind a re-sort,
+ *   one more kernel that inverts the permutation of the slots), a wait for that event and ONE device-to-host copy on the
+ *   snapshot stream.  No allocation (the setter makes every buffer), no synchronisation, no host copy.  The handle's
+ *   stream never waits for the snapshot stream, which is not the side stream of the async lists.
+ * nlps_gpu_snapshot_wait blocks on that slot's copy alone (not on the handle's stream), sets view->np and the pointers of
+ *   the selected fields into the slot's pinned block (every other member NULL) and returns the tag; the pointers are
+ *   valid until nlps_gpu_snapshot_release, which frees the slot for the next begin (and, for a slot nobody has waited
+ *   for, waits for its copy first).  nlps_host_write_particles_vtk takes them as they are.  A slot may be waited for
+ *   more than once.
+ * Memory (nlps_gpu_snapshot_bytes): pinned = slots x max(8, np x (8 D + 4 I)) bytes, device = pinned + 4 max(np, 1) (the
+ *   inverse permutation), np the particle count at the set, D the doubles per particle of the selected fields (ndim for
+ *   x, dis, vel, acc, lambda; 5 | 9 for F_n, Stress, b_e_n; 3 for Back_stress; 1 for the others), I = 1 with
+ *   NLPS_SNAP_I0.  A slot's block holds the selected fields one after the other in ascending bit order, the ints of I0
+ *   last.
+ * Returns 1 with the reason in nlps_gpu_last_error, stores and launches nothing, and leaves the handle usable: the setter
+ *   for slots outside [1, NLPS_SNAP_MAX_SLOTS], fields == 0 or a bit outside NLPS_SNAP_*, a failed allocation (the
+ *   snapshots set before stay), a migrated handle (its rows are by global id); begin / wait / release / bytes with no
+ *   snapshots set; begin with every slot in flight or unreleased, or on a handle that has migrated since the set; wait or
+ *   release on a slot that was not begun.  A halo callback or an RCCL exchange changes nothing: the pack is rank-local.
+ * A second set replaces the first; cfg == NULL switches the snapshots off.  Both, and nlps_gpu_destroy, wait for the
+ * copies in flight before they free. */
+enum { NLPS_SNAP_X = 1 << 0, NLPS_SNAP_DIS = 1 << 1, NLPS_SNAP_VEL = 1 << 2, NLPS_SNAP_ACC = 1 << 3,
+       NLPS_SNAP_F_N = 1 << 4, NLPS_SNAP_STRESS = 1 << 5, NLPS_SNAP_B_E_N = 1 << 6, NLPS_SNAP_J_N = 1 << 7,
+       NLPS_SNAP_RHO = 1 << 8, NLPS_SNAP_MASS = 1 << 9, NLPS_SNAP_VOL0 = 1 << 10, NLPS_SNAP_W = 1 << 11,
+       NLPS_SNAP_KAPPA_N = 1 << 12, NLPS_SNAP_EPS_N = 1 << 13, NLPS_SNAP_BACK_STRESS = 1 << 14,
+       NLPS_SNAP_DAMAGE_N = 1 << 15, NLPS_SNAP_STRAIN_F_N = 1 << 16, NLPS_SNAP_LAMBDA = 1 << 17,
+       NLPS_SNAP_BETA = 1 << 18, NLPS_SNAP_I0 = 1 << 19 };
+#define NLPS_SNAP_MAX_SLOTS 4
+typedef struct { unsigned fields; int slots; } nlps_snapshot_cfg;       /* slots: snapshots that may be in flight or unreleased */
+int nlps_gpu_set_snapshots(nlps_gpu *h, const nlps_snapshot_cfg *cfg);  /* NULL: off, waits for copies in flight, frees */
+int nlps_gpu_snapshot_begin(nlps_gpu *h, int tag, int *slot);
+int nlps_gpu_snapshot_wait(nlps_gpu *h, int slot, nlps_particles *view, int *tag);
+int nlps_gpu_snapshot_release(nlps_gpu *h, int slot);
+int nlps_gpu_snapshot_bytes(nlps_gpu *h, size_t *device, size_t *pinned);
 /* The damage hooks inside the fused residual (clouds created with driver_eigenerosion or driver_eigensoftening).  Off by
  * default: nlps_gpu_lagrangian_evaluation then runs the separate stages for such a cloud (nlps_gpu_compatibility,
  * nlps_gpu_constitutive, nlps_gpu_internal_forces with its two sorts, the traction and inertial calls), exactly as before.

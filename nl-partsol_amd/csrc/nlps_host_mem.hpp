@@ -79,6 +79,7 @@ class Pinned {
     }
     return hipSuccess;
   }
+  void swap(Pinned& o) noexcept { std::swap(p_, o.p_), std::swap(alias_, o.alias_); }
   T* host() const { return p_; }
   T* alias() const { return alias_; }
 };
@@ -133,6 +134,7 @@ class SideStream {
     if (e != hipSuccess) reset();
     return e;
   }
+  void swap(SideStream& o) noexcept { std::swap(s_, o.s_), std::swap(fork_, o.fork_), std::swap(join_, o.join_); }
   hipStream_t stream() const { return s_; }
   hipError_t fork(hipStream_t from) {
     const hipError_t e = hipEventRecord(fork_, from);

@@ -96,8 +96,9 @@ VTK_X_GC, VTK_P, VTK_ENERGY = 1, 2, 4
 
 def write_particles_vtk(path, results_time_step, state, flags=0):
     """The particle file of particle_results_vtk__InOutFun__ (InOutFun/Outputs/WriteVtk.c:95-266) from a dict in the
-    layout of Solver.download_state(): keys x (required), mass, rho, I0, matidx, vel, acc, dis, Stress, F_n, W, EPS_n;
-    missing keys leave their block out."""
+    layout of Solver.download_state() -- or the dict of Solver.snapshot_wait(), as it is, views of the pinned block
+    included (nlps.SNAP_VTK selects what is read here) --: keys x (required), mass, rho, I0, matidx, vel, acc, dis, Stress,
+    F_n, W, EPS_n; missing keys leave their block out."""
     x = np.ascontiguousarray(state["x"], dtype=np.float64)
     npart, nd = x.shape
     keep = [x]

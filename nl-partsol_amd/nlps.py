@@ -109,6 +109,8 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_set_explicit_loads",
            "nlps_gpu_set_step_record", "nlps_gpu_step_record_layout", "nlps_gpu_record_now", "nlps_gpu_read_step_records",
            "nlps_host_courant_dt",
+           "nlps_gpu_set_snapshots", "nlps_gpu_snapshot_begin", "nlps_gpu_snapshot_wait", "nlps_gpu_snapshot_release",
+           "nlps_gpu_snapshot_bytes",
            "nlps_gpu_set_implicit_damage", "nlps_gpu_set_deterministic_damage",
            "nlps_gpu_rccl_unique_id", "nlps_gpu_rccl_attach", "nlps_gpu_rccl_attach_comm", "nlps_gpu_rccl_detach",
            "nlps_gpu_rccl_reduce", "nlps_gpu_rccl_info", "nlps_gpu_rccl_migrate", "nlps_gpu_rccl_selftest_migrate", "nlps_gpu_rccl_selftest_exchange", "nlps_gpu_touched_layers", "nlps_gpu_set_node_window", "nlps_gpu_set_ghost_bands",
@@ -284,6 +286,30 @@ REC_COLUMNS = {"step": (0, 1), "kind": (1, 1), "dt": (2, 1), "time": (3, 1), "np
 PROBE_X, PROBE_DIS, PROBE_VEL, PROBE_ACC, PROBE_F, PROBE_STRESS, PROBE_J, PROBE_EPS, PROBE_DAMAGE, PROBE_W = \
     1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 PROBE_ALL = 1023
+
+
+class SnapshotCfg(C.Structure):  # nlps_snapshot_cfg
+    _fields_ = [("fields", C.c_uint), ("slots", C.c_int)]
+
+
+# the fields of a particle snapshot (NLPS_SNAP_*) in bit order: the names download_state() uses, the member of Particles
+# and the columns of a row (d = ndim, T = 5 | 9)
+SNAP_FIELDS = (("x_GC", "d"), ("dis", "d"), ("vel", "d"), ("acc", "d"), ("F_n", "T"), ("Stress", "T"), ("b_e_n", "T"),
+               ("J_n", 1), ("rho", 1), ("mass", 1), ("Vol_0", 1), ("W", 1), ("Kappa_n", 1), ("EPS_n", 1), ("Back_stress", 3),
+               ("Damage_n", 1), ("Strain_f_n", 1), ("lambda_", "d"), ("Beta", 1), ("I0", 1))
+SNAP_BITS = {name: 1 << b for b, (name, _) in enumerate(SNAP_FIELDS)}
+SNAP_ALL = (1 << len(SNAP_FIELDS)) - 1
+SNAP_MAX_SLOTS = 4
+# what gid.write_particles_vtk reads of a state
+SNAP_VTK = sum(SNAP_BITS[k] for k in ("x_GC", "dis", "vel", "acc", "F_n", "Stress", "rho", "mass", "W", "EPS_n", "I0"))
+
+
+def snapshot_mask(fields):
+    """NLPS_SNAP_* bits from an int or from names as download_state() takes them (x, lambda, beta are aliases)"""
+    if isinstance(fields, (int, np.integer)):
+        return int(fields)
+    alias = {"x": "x_GC", "lambda": "lambda_", "beta": "Beta"}
+    return sum({SNAP_BITS[alias.get(k, k)] for k in fields})
 
 
 def courant_dt(CFL, h, Cel, row=None):
@@ -666,6 +692,62 @@ class Solver:
                 out[name] = slice(off, off + n)
                 off += n
         return out
+
+    def set_snapshots(self, fields, slots=2):
+        """The particle snapshot: `fields` is a mask of SNAP_BITS or a list of names as download_state() takes them, `slots`
+        the number of snapshots that may be in flight or unreleased; fields=None switches it off (waits for the copies
+        in flight, frees).  The contract is in include/nlps_gpu.h."""
+        L = self.L
+        L.nlps_gpu_set_snapshots.argtypes = [C.c_void_p, C.POINTER(SnapshotCfg)]
+        if fields is None:
+            self._chk(L.nlps_gpu_set_snapshots(self.h, None))
+            return
+        cfg = SnapshotCfg(snapshot_mask(fields) & 0xFFFFFFFF, int(slots))
+        self._chk(L.nlps_gpu_set_snapshots(self.h, C.byref(cfg)))
+
+    def snapshot_begin(self, tag=0):
+        """Packs the selected fields of the state as it stands on the handle's stream and queues their copy to pinned
+        memory on the snapshot stream; returns the slot at once (no synchronisation)."""
+        self.L.nlps_gpu_snapshot_begin.argtypes = [C.c_void_p, C.c_int, _ip]
+        slot = C.c_int(-1)
+        self._chk(self.L.nlps_gpu_snapshot_begin(self.h, int(tag), C.byref(slot)))
+        return slot.value
+
+    def snapshot_wait(self, slot, copy=True):
+        """Waits for that slot's copy alone; -> the dict download_state(fields) would have returned in place of
+        snapshot_begin (same names, aliases included), with `tag`.  copy=False: the arrays are views of the slot's pinned
+        block, valid until snapshot_release(slot) / set_snapshots / close()."""
+        self.L.nlps_gpu_snapshot_wait.argtypes = [C.c_void_p, C.c_int, C.POINTER(Particles), _ip]
+        hp, tag = Particles(), C.c_int(0)
+        self._chk(self.L.nlps_gpu_snapshot_wait(self.h, int(slot), C.byref(hp), C.byref(tag)))
+        n, o = hp.np, {}
+        for name, w in SNAP_FIELDS:
+            ptr = getattr(hp, name)
+            if not ptr:
+                continue
+            w = {"d": self.ndim, "T": self.T}.get(w, w)
+            shape = (n,) if w == 1 else (n, w)
+            if n == 0:
+                a = np.zeros(shape, dtype=np.int32 if name == "I0" else np.float64)
+            else:
+                a = np.ctypeslib.as_array(ptr, shape=shape)
+            o[name] = a.copy() if copy else a
+        for short, full in (("x", "x_GC"), ("lambda", "lambda_"), ("beta", "Beta")):
+            if full in o:
+                o[short] = o[full]
+        o["tag"] = tag.value
+        return o
+
+    def snapshot_release(self, slot):
+        self.L.nlps_gpu_snapshot_release.argtypes = [C.c_void_p, C.c_int]
+        self._chk(self.L.nlps_gpu_snapshot_release(self.h, int(slot)))
+
+    def snapshot_bytes(self):
+        """-> (device bytes, pinned bytes) the snapshots hold"""
+        self.L.nlps_gpu_snapshot_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        dev, pin = C.c_size_t(0), C.c_size_t(0)
+        self._chk(self.L.nlps_gpu_snapshot_bytes(self.h, C.byref(dev), C.byref(pin)))
+        return dev.value, pin.value
 
     def set_implicit_damage(self, on=True):
         """The eigenerosion / eigensoftening hooks inside the fused residual (off by default: lagrangian_evaluation runs the
