@@ -45,8 +45,9 @@ enum {
   NLPS_MAT_VON_MISES = 3,      /* "Von-Mises",           Plasticity/Von-Mises.c:212-392 */
   NLPS_MAT_MATSUOKA_NAKAI = 4, /* "Matsuoka-Nakai",      Plasticity/Matsuoka-Nakai.c:300-700 */
   NLPS_MAT_LADE_DUNCAN = 5,    /* "Lade-Duncan",         Plasticity/Lade-Duncan.c:290-692 */
-  NLPS_MAT_NEWTONIAN_FLUID = 6 /* "Newtonian-Fluid-Compressible", Fluid/Newtonian-Fluid.c:17-79: implicit path only, reads the
-                                  rate tensor dt_F_n1 (nlps_gpu_explicit_step refuses a cloud that holds it) */
+  NLPS_MAT_NEWTONIAN_FLUID = 6 /* "Newtonian-Fluid-Compressible", Fluid/Newtonian-Fluid.c:17-79: reads the rate tensor dt_F_n1.
+                                  Implicit path; nlps_gpu_explicit_step refuses a cloud that holds it unless
+                                  nlps_gpu_set_explicit_fluid is on, which defines the rate of that step */
 };
 
 /* Structured background grid (GramsBox mesh, InOutFun/Read_GramsBox.c:54): Q4 / H8 lattice, nodes
@@ -230,9 +231,40 @@ int nlps_gpu_update_kinetics(nlps_gpu *h, double alpha_blend, const double *dU, 
  * U-Newmark-beta.c:1257-1374; the contour tractions of :805-902 once nlps_gpu_set_explicit_loads has given them).
  * gravity[ndim] may be NULL.  One P2G+stress+G2P particle step.
  * A cloud that holds Newtonian-Fluid-Compressible is refused at the start of the call (return 1, the law named in
- * nlps_gpu_last_error): the law reads dt_F_n1 and the reference has no working explicit driver that defines that rate. */
+ * nlps_gpu_last_error): the law reads dt_F_n1 and the reference has no working explicit driver that defines that rate.
+ * nlps_gpu_set_explicit_fluid (below) defines it and lifts the refusal for the handle it is set on. */
 int nlps_gpu_explicit_step(nlps_gpu *h, const nlps_bcc *bcc, int nbcc, int step, double dt,
                            double gamma, const double *gravity);
+/* The explicit step of a cloud that holds Newtonian-Fluid-Compressible.  Off by default: nlps_gpu_explicit_step then
+ * refuses such a cloud, as above.  With on != 0 the step of such a cloud is the explicit composition above (stage order
+ * of U-Verlet.c) with the rate tensors of the reference's own formulas (compute-Strains.c:48-72, 176-207) under two
+ * choices:
+ *   - the nodal rate vector is the increment's mean rate over the step, dV_A = dU_A / dt;
+ *   - the rate carried over from the last step is zero.
+ * That gives
+ *   dt_DF   = sum_A (dU_A / dt) (x) grad N_A   = (DF - I) / dt,
+ *   dt_F_n1 = dt_DF F_n                        = (F_n1 - F_n) / dt,
+ *   L       = dt_F_n1 F_n1^-1                  = (I - DF^-1) / dt.
+ * The carried term DF dt_F_n of the Newmark path is dropped on purpose: there dV is a velocity INCREMENT and the term
+ * accumulates it; here dV is the full mean velocity of the step, and keeping the term would make the viscous stress grow
+ * step by step.
+ * The fluid stress is Newtonian-Fluid.c:17-79 from F_n1, dt_F_n1, J_n1 (in 2-D the trace is xx + yx, as upstream).  The
+ * density update rho / det DF, the internal forces, gravity, the Dirichlet sets, the contour loads, the equilibrium, G2P
+ * and the corrector are the step's own, shared with the solid laws of a mixed cloud (one K3 launch per law present).
+ * The roll includes dt_F_n <- dt_F_n1: a download after the step returns the step's rate in both dt_F_n and dt_F_n1 for
+ * the fluid particles, and a nlps_gpu_newmark_step that follows explicit steps starts from that rate; particles of other
+ * laws keep what they had.  The step does not write dt_DF: a download returns for it what it returned before the step.
+ * W of a fluid particle is not touched (Constitutive.c:84-108 writes Stress and nothing else).
+ * A particle with J_n1 <= 0 raises the Jacobian flag as in every explicit step; one whose F_n1 does not invert raises the
+ * constitutive flag and contributes neither stress nor force.
+ * With the switch on a step returns 1 with the reason in nlps_gpu_last_error, launches nothing and leaves the handle
+ * usable when a halo callback or an RCCL exchange is attached (one rank only), for a cloud created with
+ * driver_eigenerosion / driver_eigensoftening (the state half of the damage step is cut for the solid laws), and for
+ * dt <= 0 (the rate is the increment over dt).
+ * nlps_gpu_set_law_launch_mode(2) stays refused for such a cloud.  The step runs the non-folded form on the handle's
+ * stream, in deterministic mode too.
+ * The setter returns 1, with the reason in nlps_gpu_last_error, for a cloud that holds no fluid material. */
+int nlps_gpu_set_explicit_fluid(nlps_gpu *h, int on);
 /* The damage hooks inside the explicit step (clouds created with driver_eigenerosion or driver_eigensoftening).  Off
  * by default: nlps_gpu_explicit_step then refuses such a cloud (the hooks of the level-B stages are its only form).
  * With on != 0 the step of such a cloud is the composition of the explicit step above with the hooks of the maintained

@@ -1110,6 +1110,17 @@ __global__ __launch_bounds__(BLK) void k_roll(PView P) {
   }
 }
 
+// After explicit steps of a fluid cloud (nlps_gpu_set_explicit_fluid) the step's rate sits in dt_F_n alone, where K3 put
+// it: the reference's copy semantics (dt_F_n1 == dt_F_n after the roll) are restored on demand, with k_copy_n_to_n1, for
+// the fluid particles; those of other laws keep what they had.
+template <int ND>
+__global__ __launch_bounds__(BLK) void k_roll_rate(PView P, const MatD* __restrict__ mats) {
+  int p = blockIdx.x * BLK + threadIdx.x;
+  if (p >= P.np || mats[P.mat[p]].type != NLPS_KLAW_FLUID) return;
+#pragma unroll
+  for (int s = 0; s < ND * ND; s++) PF(P, F_DTFN1 + s, p) = PF(P, F_DTFN + s, p);
+}
+
 // ------------------------------------------------------------------------------------------------
 // nodal kernels (grid numbering)
 // ------------------------------------------------------------------------------------------------
@@ -1827,6 +1838,7 @@ struct nlps_gpu {
   // k_run_first / k_run_fill), tables of their own -- the level-B force stage rebuilds dmg_* with its sorts every call.
   // xrun_*0: the tables of the snapshot's closest nodes, made once and again after a re-sort has renumbered the slots
   bool explicit_damage = false;
+  bool explicit_fluid = false;  // nlps_gpu_set_explicit_fluid: the explicit step of a cloud that holds the fluid law
   // the Neumann contours of the explicit step (nlps_gpu_set_explicit_loads): one entry per contour particle
   // in the caller's contour order -- caller's index, contour number, A0 (3-D) -- and the traction vector of every
   // (step, contour) with the carry-over resolved.  xl_inv_d: caller's index -> slot, rebuilt by the first step behind a
@@ -1882,6 +1894,7 @@ struct nlps_gpu {
   // half runs one wave per tile into slabs (k3f_wave) and det_implicit admits the damage cloud
   bool det_damage = false;
   bool rolled_keep = false;  // `rolled`, and the last step stored tau and W itself (k_copy_n_to_n1 KEEP)
+  bool rolled_rate = false;  // `rolled`, and the last step left the fluid particles' rate in dt_F_n alone (k_roll_rate)
   DevBuf<double> slab_d;    // P2G window slabs [ntiles][slab_n][fields][NWA] (TileD::slab), deterministic mode only: sized by the
                             // explicit step and, for the largest user of the implicit path, by det_prepare
   bool deterministic = false;
@@ -2820,6 +2833,14 @@ static int xrun_alloc(nlps_gpu* h) {
       return 1;
     HIPCHK(hipMemsetAsync(h->xrun_cnt_d, 0, nn * sizeof(int), h->stream));  // (k_run_first leaves the counters at zero)
   }
+  return 0;
+}
+extern "C" int nlps_gpu_set_explicit_fluid(nlps_gpu* h, int on) {
+  if (!(h->law_present & (1 << NLPS_KLAW_FLUID))) {
+    h->err = "nlps_gpu_set_explicit_fluid: the cloud holds no Newtonian-Fluid-Compressible material";
+    return 1;
+  }
+  h->explicit_fluid = on != 0;
   return 0;
 }
 extern "C" int nlps_gpu_set_explicit_damage(nlps_gpu* h, int on) {
@@ -3908,16 +3929,19 @@ static void arm_signal(nlps_gpu* h, TileD& td, int stage) {
 //   MODE 3  the fused residual                       + one wave per tile; the fluid law's particles go to MODE 4
 //   MODE 4  MODE 3 with the rate tensors (dV)          the fluid law only: plain, FILT, one wave per tile
 //   MODE 6  the state half of MODE 3 (damage hooks)    nothing else (tests/test_isa_implicit_damage.py)
+//   MODE 7  MODE 1 with the step's mean rate (dt)      the fluid law only: plain, FILT, one wave per tile
+//                                                      (nlps_gpu_set_explicit_fluid; MODE 1 hands the law's particles to it)
 template <int MODE>
 struct K3Forms {
   static constexpr bool dispatch = MODE == 1 || MODE == 5;  // LAW = -1: the law of every particle looked up at run time
   static constexpr bool wave = MODE == 1 || MODE == 3;      // the deterministic form
-  static constexpr bool fluid = MODE == 3;                  // NLPS_KLAW_FLUID exists, as MODE 4
+  static constexpr int fluid = MODE == 3 ? 4 : MODE == 1 ? 7 : 0;  // NLPS_KLAW_FLUID exists, as MODE 4 / MODE 7
 };
 struct K3Launch {
   bool signal = false;         // arm the boundary-done signal of overlap mode 2 in front of the (last) launch
   bool wave = false;           // one wave per tile and per law present over the exact lists, one slab per (tile, law)
   const double* dV = nullptr;  // the nodal rate vector, read by MODE 4 alone
+  double dt = 0.0;             // the step, read by MODE 7 alone
 };
 // 3-D, one material, laws 1-3: its constants by scalar loads (k3_body, UMAT)
 static bool one_material_3d(const nlps_gpu* h) {
@@ -3929,12 +3953,17 @@ static void k3_go(nlps_gpu* h, K kernel, int nt, const TileD& td, const X& last)
   hipLaunchKernelGGL(kernel, dim3(h->ntw), dim3(nt), 0, h->stream, h->P, h->g, h->N, td, h->mats_d, h->prm, h->gstatus_d, last);
 }
 static const double* const no_rates = nullptr;
-// one launch of the kernel of law l (out of range: the last law, with_law_in); MODE 3 hands the fluid law to MODE 4
+// one launch of the kernel of law l (out of range: the last law, with_law_in); MODE 3 hands the fluid law to MODE 4,
+// MODE 1 to MODE 7, whose kernel is the k3_tile overload that takes dt
+using K3StepKernel = void (*)(PView, GridD, NView, TileD, const MatD*, ParamsD, int*, double);
 template <int MODE, bool FILT, int NT>
-static void launch_k3_law(nlps_gpu* h, const TileD& td, int l, const double* dV) {
+static void launch_k3_law(nlps_gpu* h, const TileD& td, int l, const K3Launch& a) {
   with_nd(h->nd, [&](auto D) {
-    if constexpr (K3Forms<MODE>::fluid) {
-      if (l == NLPS_KLAW_FLUID) return k3_go(h, k3_tile<CT(D), NLPS_KLAW_FLUID, 4, FILT, NT>, NT, td, dV);
+    if constexpr (K3Forms<MODE>::fluid == 4) {
+      if (l == NLPS_KLAW_FLUID) return k3_go(h, k3_tile<CT(D), NLPS_KLAW_FLUID, 4, FILT, NT>, NT, td, a.dV);
+    }
+    if constexpr (K3Forms<MODE>::fluid == 7) {
+      if (l == NLPS_KLAW_FLUID) return k3_go(h, K3StepKernel(k3_tile<CT(D), NLPS_KLAW_FLUID, 7, FILT, NT>), NT, td, a.dt);
     }
     with_law(l, [&](auto L) { k3_go(h, k3_tile<CT(D), CT(L), MODE, FILT, NT>, NT, td, no_rates); });
   });
@@ -3952,7 +3981,7 @@ static void launch_k3(nlps_gpu* h, TileD td, const K3Launch& a) {
       td.slab_slot = -1;
       for_each_law_present(h->law_present, [&](int l, bool) {
         td.slab_slot++;
-        launch_k3_law<MODE, true, 64>(h, td, l, a.dV);
+        launch_k3_law<MODE, true, 64>(h, td, l, a);
       });
       return;
     }
@@ -3960,7 +3989,7 @@ static void launch_k3(nlps_gpu* h, TileD td, const K3Launch& a) {
   if (per_law) {  // only the last launch releases the exchange (launches of one stream run in order)
     for_each_law_present(h->law_present, [&](int l, bool last) {
       if (a.signal && last) arm_signal(h, td, 1);
-      launch_k3_law<MODE, true, K3_BLK>(h, td, l, a.dV);
+      launch_k3_law<MODE, true, K3_BLK>(h, td, l, a);
     });
   } else if (law < 0) {  // several laws, many mixed tiles: the kernel that dispatches on the law at run time
     if constexpr (K3Forms<MODE>::dispatch) {
@@ -3969,7 +3998,7 @@ static void launch_k3(nlps_gpu* h, TileD td, const K3Launch& a) {
   } else if (one_material_3d(h)) {
     with_law_in<1, 3>(law, [&](auto L) { k3_go(h, k3_tile<3, CT(L), MODE, false, K3_BLK, true>, K3_BLK, td, no_rates); });
   } else {
-    launch_k3_law<MODE, false, K3_BLK>(h, td, law, a.dV);
+    launch_k3_law<MODE, false, K3_BLK>(h, td, law, a);
   }
 }
 // The folded form of the explicit step (one law, 0 .. NLPS_KLAW_FRICTIONAL): k3_tile_lazy, plain or one-material
@@ -4147,8 +4176,9 @@ static int materialise_roll(nlps_gpu* h) {
   if (!h->rolled) return 0;
   if (h->rolled_keep) LAUNCH_ND((k_copy_n_to_n1<2, true>), (k_copy_n_to_n1<3, true>), nblk(h->P.np), h->P, h->mats_d);
   else LAUNCH_ND((k_copy_n_to_n1<2>), (k_copy_n_to_n1<3>), nblk(h->P.np), h->P, h->mats_d);
+  if (h->rolled_rate) LAUNCH_ND(k_roll_rate<2>, k_roll_rate<3>, nblk(h->P.np), h->P, h->mats_d);
   HIPCHK(hipGetLastError());
-  h->rolled = h->rolled_keep = false;
+  h->rolled = h->rolled_keep = h->rolled_rate = false;
   return 0;
 }
 
@@ -5230,9 +5260,20 @@ static int damage_runs_and_hook(nlps_gpu* h, bool rebuild) {
 
 // The fused explicit step: refuse, re-sort, decide the form (StepForm), search + lists + K2, one of three schedules.
 static int explicit_step_refuse(nlps_gpu* h, int nbcc, int step) {
-  if (h->law_present & (1 << NLPS_KLAW_FLUID)) {
+  const bool fluid = (h->law_present & (1 << NLPS_KLAW_FLUID)) != 0;
+  if (fluid && !h->explicit_fluid) {
     h->err = "nlps_gpu_explicit_step: the cloud holds the Newtonian-Fluid-Compressible law, which reads the rate tensor dt_F_n1; "
              "the reference has no working explicit driver that defines it (implicit path only)";
+    return 1;
+  }
+  if (fluid && (h->halo || h->rccl)) {  // (nlps_gpu_set_explicit_fluid)
+    h->err = "nlps_gpu_explicit_step: the explicit step of the Newtonian-Fluid-Compressible law is built for one rank: not with "
+             "a halo callback or an RCCL exchange attached";
+    return 1;
+  }
+  if (fluid && h->P.erosion) {
+    h->err = "nlps_gpu_explicit_step: the cloud holds the Newtonian-Fluid-Compressible law and was created with "
+             "driver_eigenerosion / driver_eigensoftening; the state half of the damage step is cut for the solid laws";
     return 1;
   }
   const bool dmg = h->P.erosion != 0;
@@ -5391,7 +5432,7 @@ struct ExplicitStep {
   void k3(int cls, bool signal = false) {
     const TileD td = tile_view(h, cls);
     if (f.lazy) return launch_k3_lazy(h, td, signal, ln);
-    const K3Launch a{signal, f.det && !f.dmg};
+    const K3Launch a{signal, f.det && !f.dmg, nullptr, dt};
     if (f.dmg) launch_k3<5>(h, td, a);
     else launch_k3<1>(h, td, a);
   }
@@ -5621,6 +5662,10 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   tan_stale(h, "nlps_gpu_explicit_step");
   const int ND = h->nd;
   if (explicit_step_refuse(h, nbcc, step)) return 1;
+  if ((h->law_present & (1 << NLPS_KLAW_FLUID)) && !(dt > 0.0)) {  // (the rate of such a step is dU / dt: nlps_gpu_set_explicit_fluid)
+    h->err = "nlps_gpu_explicit_step: the cloud holds the Newtonian-Fluid-Compressible law, whose rate is the increment over dt: dt must be positive";
+    return 1;
+  }
   if (ensure_bcs(h, bcc, nbcc)) return 1;
   if (!h->Pd_alt && h->resort_every > 0 && h->P.np > 0) {
     // the twin block of the periodic re-sort, at the first step of the fused scheme rather than inside the first
@@ -5684,6 +5729,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   h->P.flip ^= 1;  // F_n <- F_n+1, b_e,n <- b_e,n+1 by renaming
   h->rolled = true;
   h->rolled_keep = f.dmg;  // (tau and W of this step are stored: k_copy_n_to_n1 must not re-make them)
+  h->rolled_rate = (h->law_present & (1 << NLPS_KLAW_FLUID)) != 0;  // (K3 wrote the step's rate into dt_F_n: k_roll_rate)
   h->searched = f.ride;    // K5 has updated the closest nodes for the positions it wrote ...
   h->ahead = f.ride;       // ... and binned the particles for the next step
   h->lists_ready = s.forked;

@@ -889,6 +889,12 @@ __global__ __launch_bounds__(NT, NT == 64 ? 1 : (ND == 2 ? K2_WAVES_2D : K2_WAVE
 // with MODE 2's second gather window: G and Gv from one member loop, DF, F_n1, J_n1, dt_DF, dt_F_n1, the fluid stress
 // (Newtonian-Fluid.c:17-79) from F_n1, dt_F_n1, J_n1 still in registers, the force scatter; stores what MODE 3 stores
 // plus the two rate tensors (the separate stages pass DF, F_n1, tau and both rate tensors through HBM between three launches).
+// MODE 7 (LAW = NLPS_KLAW_FLUID only): MODE 1 for the one law that reads the rate (nlps_gpu_set_explicit_fluid, DESIGN.md
+// 5m).  One gather window, dU, as MODE 1; the rate is the increment's mean rate over the step, dt_DF = sum (dU_A / dt) (x)
+// grad N_A -- the sum that already forms DF, divided by dt, not (DF - I) / dt, which cancels -- and dt_F_n1 = dt_DF F_n,
+// without the carried term DF dt_F_n of MODE 2 / 4: no second window, no load of dt_F_n.  The fluid stress from F_n1,
+// dt_F_n1, J_n1 in registers; stores what MODE 1 stores (F_n+1, J to its n slot, d_dis; DF stays in registers), tau, and
+// dt_F_n1 once, into the slot that is dt_F_n after the step.  dt is the kernel's last argument (the k3_tile overload below).
 // FILT (clouds with several laws): the launch handles only the tile's particles whose material follows LAW; they are
 // compacted into an LDS list first, so every lane works and the kernel is the single-law specialisation (one launch per
 // law present; the run-time dispatch over all laws in one kernel needed 436 B of scratch per lane and 0.51 ms).
@@ -932,11 +938,13 @@ template <int ND, int LAW, int MODE, bool FILT, int NT, bool UMAT = false>
 __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NView& N, const TileD& td,
                                         const MatD* __restrict__ mats, const ParamsD& prm, int* __restrict__ gstatus,
                                         const double* __restrict__ dVgrid, const TileWork& tw, int nbnd,
-                                        const K3Lds<ND, MODE, FILT>& lds, const NodalFold* fs) {
+                                        const K3Lds<ND, MODE, FILT>& lds, const NodalFold* fs, double dt = 0.0) {
   NLPS_FP_CONTRACT
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN;
   constexpr bool RATES = (MODE == 2 || MODE == 4);
-  constexpr bool SCATTER = (MODE == 1 || MODE == 3 || MODE == 4);  // the stress update and the force scatter follow the F update
+  constexpr bool SCATTER = (MODE == 1 || MODE == 3 || MODE == 4 || MODE == 7);  // the stress update and the force scatter follow the F update
+  constexpr bool XSTEP = (MODE == 1 || MODE == 7);  // the fused K3 of the explicit step: -f_int, J to its n slot, DF not stored
+  constexpr bool FLUID = (MODE == 4 || MODE == 7);  // the stress is law_newtonian_fluid's, from a rate tensor kept in registers
   // MODE 5, the state half of the explicit step with the damage hooks (nlps_gpu_set_explicit_damage): MODE 1 up to and
   // including the stress update -- same gather, same passes, same lists -- and no force scatter: the damage hook scales
   // the Kirchhoff stress between this kernel and the force half (k3f_tile).  It stores what they read: F_n+1, J (both
@@ -948,7 +956,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
   // residual is evaluated many times from it.  A failed particle (Damage_n == 1) gets W = 0 and nothing else (k_stress).
   constexpr bool STATE_N1 = (MODE == 6);
   constexpr bool STRESS = SCATTER || STATE || STATE_N1;
-  static_assert((MODE == 4) == (LAW == NLPS_KLAW_FLUID), "the rate-carrying residual is the fluid law's, and only its");
+  static_assert(FLUID == (LAW == NLPS_KLAW_FLUID), "the rate-carrying modes are the fluid law's, and only its");
   // gather window of dU: {x,y} as one 16-B double2 per node (ds_read_b128) + z as a separate 8-B array
   // (ds_read_b64): with node strides of 16 B and 8 B the tile's 64 I0 positions hit distinct banks; a
   // padded 32-B AoS row put every second node on the same banks (41 % conflict cycles measured).
@@ -1337,6 +1345,8 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     if (!inverse<ND>(Jm1, J)) st |= ST_NEWTON;
     // DF = I + sum_A dU_A (x) grad N_A = I - (G/Z) J^-T            (compute-Strains.c:20-44)
     double DF[ND * ND], Fn1[ND * ND];
+    constexpr int NK = FLUID ? ND * ND : 1;
+    double dFk[NK];  // dt_F_n1, kept for the fluid stress (MODE 4, 7); MODE 7: dt_DF until F_n is here
 #pragma unroll
     for (int i = 0; i < ND; i++)
 #pragma unroll
@@ -1345,6 +1355,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
 #pragma unroll
         for (int m = 0; m < ND; m++) v = fma(G[i * ND + m] * Zinv, Jm1[j * ND + m], v);
         DF[i * ND + j] = ((i == j) ? 1.0 : 0.0) - v;
+        if (MODE == 7) dFk[(i * ND + j) % NK] = -v / dt;  // dt_DF = sum (dU_A / dt) (x) grad N_A
       }
     load_block<ND>(P, fFN(P), pl, Fn, fzz);
 #pragma unroll
@@ -1356,21 +1367,35 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
         for (int k2 = 0; k2 < ND; k2++) a2 += DF[i * ND + k2] * Fn[k2 * ND + j];
         Fn1[i * ND + j] = a2;
       }
+    if constexpr (MODE == 7) {  // dt_F_n1 = dt_DF F_n (compute-Strains.c:176-207 with dt_F_n = 0)
+      double dFn1[ND * ND];
+#pragma unroll
+      for (int i = 0; i < ND; i++)
+#pragma unroll
+        for (int j = 0; j < ND; j++) {
+          double a2 = 0.0;
+#pragma unroll
+          for (int k2 = 0; k2 < ND; k2++) a2 += dFk[(i * ND + k2) % NK] * Fn[k2 * ND + j];
+          dFn1[i * ND + j] = a2;
+        }
+#pragma unroll
+      for (int q = 0; q < ND * ND; q++) dFk[q % NK] = dFn1[q];
+      store_block<ND>(P, F_DTFN, pl, dFn1, 0.0, false);  // (nothing in the step reads dt_F_n: the roll is this store)
+    }
     double Jn1 = det<ND>(Fn1);
     if (Jn1 <= 0.0) {
       st |= ST_JACOBIAN;  // fatal in the explicit scheme (U-Verlet.c:608-613), clamped in the implicit one
-      if (MODE != 1 && !STATE) Jn1 = 0.0;
+      if (!XSTEP && !STATE) Jn1 = 0.0;
     }
     // the fused explicit step (MODE 1) keeps DF in registers: nothing reads it before the next step rewrites it, and a
     // level-B stage or a download gets it back as F_n+1 F_n^-1 from the two slots of F (k_copy_n_to_n1): 72 B per
     // particle less to store (K3 0.260 -> 0.251 ms at 1 M particles)
-    if (MODE != 1) store_block<ND>(P, F_DF, pl, DF, 0.0, false);
+    if (!XSTEP) store_block<ND>(P, F_DF, pl, DF, 0.0, false);
     store_block<ND>(P, fFN1(P), pl, Fn1, 0.0, false);
     // fused step: J goes straight to its n slot (nothing reads J_n inside the step; J_n+1 = J_n is restored with the
     // roll, k_copy_n_to_n1), so K5 has no copy to make
-    PF(P, MODE == 1 ? F_JN : F_JN1, pl) = Jn1;
+    PF(P, XSTEP ? F_JN : F_JN1, pl) = Jn1;
     if (STATE) PF(P, F_JN, pl) = Jn1;  // (K5 makes no copy: the n slot as in MODE 1, the n+1 slot for the hook's volumes)
-    double dFk[(MODE == 4) ? ND * ND : 1];  // dt_F_n1, kept for the fluid stress (MODE 4)
     if (RATES) {
       double dDF[ND * ND], dFn[ND * ND], dFn1[ND * ND], zz;
 #pragma unroll
@@ -1396,7 +1421,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
       store_block<ND>(P, F_DTFN1, pl, dFn1, 0.0, false);
       if (MODE == 4) {
 #pragma unroll
-        for (int q = 0; q < ND * ND; q++) dFk[q % ((MODE == 4) ? ND * ND : 1)] = dFn1[q];
+        for (int q = 0; q < ND * ND; q++) dFk[q % NK] = dFn1[q];
       }
     }
     if (!STRESS) {
@@ -1407,7 +1432,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
       continue;
     }
     // (the density update rho <- rho / det DF of U-Verlet.c:630-632 costs no traffic: rho J is invariant, F_RHOJ)
-    if (MODE == 1 || STATE) {
+    if (XSTEP || STATE) {
 #pragma unroll
       for (int a = 0; a < ND; a++) PF(P, F_DDIS + a, pl) = U[a] * Zinv;  // d_dis_p = sum N dU (used by K5)
     }
@@ -1444,7 +1469,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     }
     double tau[ND * ND], B[ND * ND];
     // (MODE 3: C_ep kept for the tangent that may follow, everything to the n+1 slots)
-    if constexpr (MODE == 4) {
+    if constexpr (FLUID) {
       double tzz = 0.0;
       if (law_newtonian_fluid<ND>(mats[mat_idx], Fn1, dFk, Jn1, tau, tzz)) {
         store_block<ND>(P, F_TAU, pl, tau, tzz, true);
@@ -1459,7 +1484,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     // (MODE 1 accumulates -f_int, what the explicit scheme divides by the mass; MODE 3 the +f_int of the Lagrangian, :1359)
     // (measured and dropped, round 4: DF^-T J^-1 formed BEFORE the stress update so that DF and J^-1 need not live through
     // it -- the allocator then spills more, not less: Drucker-Prager at three waves 152 -> 192 B of scratch, Hencky 8 -> 44)
-    const bool fo_ok = force_operator<ND>(B, tau, DF, Jm1, PF(P, F_VOL0, pl), MODE >= 3 ? 1.0 : -1.0);
+    const bool fo_ok = force_operator<ND>(B, tau, DF, Jm1, PF(P, F_VOL0, pl), XSTEP ? -1.0 : 1.0);
     PH(11)
     if (fo_ok) {
       // RELOAD (the laws whose stress update sets the register budget): the LME factors are rebuilt from the particle's
@@ -1578,6 +1603,27 @@ __global__ __launch_bounds__(NT, (NT == 64 ? 1 : (K3Waves<ND, LAW, MODE>::value)
   if (!tile_work_item(td, tw)) return;
   const L lds{dvxy, dvz, duxy, duz, fac, sel, &nsel, wcnt};
   k3_body<ND, LAW, MODE, FILT, NT, UMAT>(P, g, N, td, mats, prm, gstatus, dVgrid, tw, nbnd, lds, nullptr);
+}
+// MODE 7: the same kernel with dt in the slot of dV (an overload, so that the name and the code of every other
+// instantiation stay what they were; the launcher picks it by its signature, launch_k3_law)
+template <int ND, int LAW, int MODE, bool FILT = false, int NT = K3_BLK, bool UMAT = false, std::enable_if_t<MODE == 7, int> = 0>
+__global__ __launch_bounds__(NT, (NT == 64 ? 1 : (K3Waves<ND, LAW, MODE>::value))) void k3_tile(PView P, GridD g, NView N, TileD td, const MatD* __restrict__ mats,
+                                               ParamsD prm, int* __restrict__ gstatus, double dt) {
+  using L = K3Lds<ND, MODE, FILT>;
+  __shared__ __attribute__((aligned(16))) double dvxy[L::N_DVXY];
+  __shared__ double dvz[L::N_DVZ];
+  __shared__ __attribute__((aligned(16))) double duxy[2 * L::NW];
+  __shared__ double duz[L::N_DUZ];
+  __shared__ double fac[L::N_FAC];
+  __shared__ int sel[L::SELCAP];
+  __shared__ int nsel;
+  __shared__ int wcnt[NT / 64];
+  const int nbnd = tile_boundary_count(td);
+  tile_signal_empty(td, nbnd);
+  TileWork tw;
+  if (!tile_work_item(td, tw)) return;
+  const L lds{dvxy, dvz, duxy, duz, fac, sel, &nsel, wcnt};
+  k3_body<ND, LAW, MODE, FILT, NT, UMAT>(P, g, N, td, mats, prm, gstatus, nullptr, tw, nbnd, lds, nullptr, dt);
 }
 
 // The explicit step of one GPU without a ghost exchange, "folded" form: the nodal kernels between the stages are gone.

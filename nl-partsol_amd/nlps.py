@@ -106,6 +106,7 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_internal_forces", "nlps_gpu_nodal_traction_forces", "nlps_gpu_roll_state", "nlps_gpu_update_kinetics",
            "nlps_gpu_explicit_step", "nlps_gpu_num_active", "nlps_gpu_explicit_nodal", "nlps_gpu_set_halo_exchange",
            "nlps_gpu_resort", "nlps_gpu_set_resort_interval", "nlps_gpu_set_adaptive_resort", "nlps_gpu_set_law_launch_mode", "nlps_gpu_set_deterministic", "nlps_gpu_set_explicit_damage",
+           "nlps_gpu_set_explicit_fluid",
            "nlps_gpu_set_explicit_loads",
            "nlps_gpu_set_step_record", "nlps_gpu_step_record_layout", "nlps_gpu_record_now", "nlps_gpu_read_step_records",
            "nlps_host_courant_dt",
@@ -149,6 +150,8 @@ def lib():
         L.nlps_gpu_set_law_launch_mode.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_set_deterministic.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_set_explicit_damage.argtypes = [C.c_void_p, C.c_int]
+        if hasattr(L, "nlps_gpu_set_explicit_fluid"):  # (NLPS_GPU_LIB may name an older build: tools/explicit_fluid_bench.py)
+            L.nlps_gpu_set_explicit_fluid.argtypes = [C.c_void_p, C.c_int]
         if hasattr(L, "nlps_gpu_set_explicit_loads"):  # (NLPS_GPU_LIB may name an older build)
             L.nlps_gpu_set_explicit_loads.argtypes = [C.c_void_p, C.POINTER(Bcc), C.c_int, C.c_double, C.c_void_p]
         if hasattr(L, "nlps_gpu_set_deterministic_damage"):  # (NLPS_GPU_LIB may name an older build)
@@ -625,6 +628,11 @@ class Solver:
         """The eigenerosion / eigensoftening hooks inside explicit_step (off by default: the step refuses a damage cloud);
         the definition of such a step is in include/nlps_gpu.h."""
         self._chk(self.L.nlps_gpu_set_explicit_damage(self.h, 1 if on else 0))
+
+    def set_explicit_fluid(self, on=True):
+        """explicit_step for a cloud that holds the compressible Newtonian fluid (off by default: the step refuses such a
+        cloud); the rate of such a step, dt_F_n1 = (F_n1 - F_n) / dt, is defined in include/nlps_gpu.h."""
+        self._chk(self.L.nlps_gpu_set_explicit_fluid(self.h, 1 if on else 0))
 
     def set_explicit_loads(self, loads, thickness=1.0, area0=None):
         """The Neumann contours of explicit_step (compute_Nodal_Nominal_traction_Forces): a BccSet whose nodes are particle
