@@ -708,6 +708,71 @@ typedef struct {
 } nlps_ksp;
 int nlps_gpu_tangent_solve(nlps_gpu *h, const double *b, double *x, nlps_ksp *ksp);
 
+/* nlps_gpu_tangent_lambda_max: the largest Ritz value theta of the pencil (K, M) on the free dofs, by Lanczos on the
+ * device -- the omega_max^2 that bounds the explicit step's stable dt (nlps_host_critical_dt), where the deck's
+ * CFL h / Cel (nlps_host_courant_dt, Courant.c:6-56) knows nothing of the cloud's gradients or its light rim nodes.
+ * K is the operator of the last nlps_gpu_tangent_operator, whatever alpha_1 and mass that was built with: with
+ * alpha_1 != 0 and the same mass the result is omega^2 + alpha_1.  lumped_mass and v0 are masked [N_A*d], host or device
+ * pointers, neither is touched; mode (masked [N_A*d], host or device, may be NULL) is written.
+ * A = P S K S P, S = diag(M^-1/2), P zeroes the dofs the operator's Dirichlet snapshot fixes (apply_dirichlet = 0: P = I).
+ *   1. q_1 = P v0 / ||P v0||.  v0 is used as it is, in the scaled space.  v0 == NULL: component i (i = masked node * d +
+ *      direction) is 2 u - 1 in [-1, 1) with u = (z >> 11) * 2^-53 and z the splitmix64 output of 64-bit wrapping arithmetic
+ *        z = seed + (i + 1) * 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *        z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31).
+ *   2. For j = 1 .. max_it:  w = A q_j;  alpha_j = q_j . w;  w is orthogonalised against every q_i, i <= j, by classical
+ *      Gram-Schmidt with one more pass when ||w|| drops below 1/sqrt 2 of its value (DGKS, the rule and the kernels of
+ *      nlps_gpu_tangent_solve);  beta_j = ||w||;  T_j = tridiag(alpha_1..alpha_j ; beta_1..beta_{j-1}) and (theta_j, s) its
+ *      largest eigenpair, ||s|| = 1 (one wave on the device: Sturm-count multisection to the last bits of ||T||, the
+ *      vector by the twisted factorisation);  est_j = beta_j |s_j|;  history[j-1] = theta_j.  Stop, in this order: a
+ *      non-finite value NLPS_EIG_DIVERGED_NANORINF; est_j <= rtol |theta_j| (beta_j == 0 included) NLPS_EIG_CONVERGED;
+ *      j == max_it NLPS_EIG_DIVERGED_ITS.  q_{j+1} = w / beta_j.  One host wait per step.
+ *   3. y = Q s and resid = ||A y - theta y|| from one more product: the TRUE residual.  For a symmetric K an eigenvalue
+ *      of the pencil lies within resid of theta, and theta <= lambda_max: pass theta + resid to nlps_host_critical_dt.
+ *   4. mode = S y: M-normalised (mode^T M mode = 1) and exactly 0 on the fixed dofs.  Not a converged run
+ *      (NLPS_EIG_DIVERGED_ITS) still returns its theta, resid and mode; NLPS_EIG_DIVERGED_NANORINF (resid = NaN) and
+ *      NLPS_EIG_EMPTY write a zero mode.
+ * asymmetry = max over j of sqrt(sum_{i<j-1} (q_i . w)^2 + ((q_{j-1} . w) - beta_{j-1})^2) / |theta_j|, from the first
+ *   Gram-Schmidt pass of step j: what a symmetric A makes zero.  Rounding noise for a symmetric tangent (Neo-Hookean); of
+ *   the order of the tangent's own asymmetry for the laws whose assembled tangent is not symmetric (Hencky,
+ *   Drucker-Prager: max|K - K^T| / max|K| of a few 1e-3).  The iteration treats A as symmetric all the same: for such
+ *   laws theta is the Ritz value of the symmetric recurrence, close to the largest eigenvalue of A's symmetric part, and
+ *   the bracket of 3. does not hold to the letter.
+ * No free dof, or P v0 == 0: returns 0 with reason NLPS_EIG_EMPTY, iterations 0, theta 0.
+ * Returns 1, with the reason in nlps_gpu_last_error and the handle usable, where nlps_gpu_tangent_solve does (no
+ * operator, a stale operator, a halo callback or an RCCL world > 1) and for lumped_mass == NULL, max_it outside
+ * 1 .. NLPS_KSP_MAX_RESTART, rtol < 0, eig == NULL, and a mass entry <= 0 or not finite on a free dof (found by the kernel
+ * that builds S, ahead of any product; the message names the masked node).
+ * bytes = 8 * ((max_it + 4) n + (max_it + 2) nb + nbg + 5 (max_it + 2) + 8) with n = N_A d, nb = ceil(n / 512) and
+ *   nbg = ceil(nnodes / 256): the basis, S P, two work vectors, per-block partial sums and T's state.  The buffers are the
+ *   ones of nlps_gpu_tangent_solve (shared, kept on the handle and only grown): no allocation once a call has sized them.
+ * In deterministic mode (nlps_gpu_set_deterministic) the call repeats bit for bit: the product does, and every sum here
+ * is taken in a fixed order (no float atomics of its own). */
+enum {
+  NLPS_EIG_CONVERGED = 1,          /* est_j <= rtol |theta_j| */
+  NLPS_EIG_EMPTY = 2,              /* no free dof or P v0 == 0: nothing to iterate on */
+  NLPS_EIG_DIVERGED_ITS = -3,      /* max_it steps without convergence (rtol = 0: the run asked for) */
+  NLPS_EIG_DIVERGED_NANORINF = -9  /* a non-finite value */
+};
+typedef struct {
+  /* in */
+  int max_it;              /* Lanczos steps, 1 .. NLPS_KSP_MAX_RESTART */
+  double rtol;             /* stop when est_j <= rtol |theta_j|; 0: run max_it steps */
+  unsigned long long seed; /* start vector when v0 == NULL */
+  double *history;         /* host array of max_it values theta_j, or NULL */
+  /* out */
+  int reason, iterations;  /* NLPS_EIG_*: > 0 converged or empty, < 0 not; Lanczos steps taken */
+  double theta;            /* largest Ritz value of the pencil (K, M) on the free dofs */
+  double resid;            /* ||A y - theta y||, the true residual, from one product */
+  double asymmetry;        /* see above */
+  size_t bytes;            /* device workspace this call holds, by the formula above */
+} nlps_eig;
+int nlps_gpu_tangent_lambda_max(nlps_gpu *h, const double *lumped_mass, const double *v0 /* or NULL */, nlps_eig *eig,
+                                double *mode /* or NULL */);
+/* The stable step of the explicit scheme (K2 / K5: the Newmark family at beta = 0) from omega2 = omega_max^2:
+ * safety * sqrt(2 / gamma) / sqrt(omega2), the undamped limit Omega_crit = (gamma / 2 - beta)^-1/2; 2 / omega at
+ * gamma = 1/2.  +inf for omega2 <= 0, -1 for gamma < 0.5.  Callers pass theta + resid.  Host only. */
+double nlps_host_critical_dt(double omega2, double gamma, double safety);
+
 /* ------------------------------------------------------------------ nonlinear solve and the implicit time step
  * nlps_gpu_newton_solve: the SNESSolve of the maintained driver (U-Newmark-beta.c:270-356) in one call -- Newton with a
  * line search around nlps_gpu_lagrangian_evaluation (the residual R), nlps_gpu_tangent_operator and

@@ -1519,6 +1519,7 @@ __global__ __launch_bounds__(BLK) void k_fill_orders(int np, const int* __restri
 #include "nlps_tangent_kernels.hpp"
 #include "nlps_tangent_operator.hpp"
 #include "nlps_krylov.hpp"
+#include "nlps_eigen.hpp"
 #include "nlps_newton.hpp"
 #include "nlps_record.hpp"
 #include "nlps_snapshot.hpp"
@@ -1943,6 +1944,7 @@ struct nlps_gpu {
   DevBuf<double> ksp_s;     // the cycle's small state (KspSmall)
   DevBuf<int> ksp_bad_d;    // first masked node whose PC block does not invert
   Mirrored<KspHost> ksp_h;  // what the host reads per step
+  Mirrored<EigHost> eig_h;  // the same for nlps_gpu_tangent_lambda_max (nlps_eigen.hpp), which shares ksp_v / ksp_part / ksp_s
   // Newton solve (nlps_gpu_newton_solve, nlps_newton.hpp), allocated on first use and kept (they only grow)
   DevBuf<double> snes_v;     // [8 n]: X, Y, W, F, K Y and the device copies of Un_dt, Un_dt2, M
   DevBuf<double> snes_part;  // [5 nb]: per-block partials of the trial update (3 columns) and the dots (2)
@@ -6562,6 +6564,188 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
   ksp->bnorm = bnorm;
   if (io.finish()) {
     h->err = "nlps_gpu_tangent_solve: HIP error";
+    return 1;
+  }
+  if (io.back.empty()) HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// device Lanczos on the matrix-free tangent (nlps_eigen.hpp): the stable step of the explicit scheme
+// ------------------------------------------------------------------------------------------------
+extern "C" double nlps_host_critical_dt(double omega2, double gamma, double safety) {
+  if (gamma < 0.5) return -1.0;
+  if (!(omega2 > 0.0)) return INFINITY;
+  return safety * sqrt(2.0 / gamma) / sqrt(omega2);  // Omega_crit = (gamma / 2 - beta)^-1/2 at beta = 0
+}
+
+// w = A q = ps (K (ps q)) on device masked vectors (xs: the scaled input, kept for the mass term); apart: the block
+// partial sums of q . w, or nullptr
+static int eig_product(nlps_gpu* h, const double* ps, const double* q, double* xs, double* w, double* apart) {
+  const int ND = h->nd, nn = h->g.nnodes;
+  double *xg = h->top_g, *yg = h->top_g + (size_t)nn * ND;
+  LAUNCH_ND((k_eig_expand<2>), (k_eig_expand<3>), nblk(nn), nn, (const int*)h->n2m_d, ps, q, xs, xg, yg);
+  if (h->top_np > 0 && scatter_tiles<2, 3>(h, "nlps_gpu_tangent_lambda_max", 1, yg, [&](auto NT, const TileD td) {
+        LAUNCH_ND_BLK((k_tanop_apply<2, CT(NT)>), (k_tanop_apply<3, CT(NT)>), h->ntw, CT(NT), h->P, h->g, td,
+                      (const double*)h->top_d, h->top_np, (const double*)xg, yg);
+      }))
+    return 1;
+  HIPCHK(hipGetLastError());
+  LAUNCH_ND_BLK((k_eig_nodal<2>), (k_eig_nodal<3>), nblk(nn, KSP_NT), KSP_NT, nn, (const int*)h->n2m_d, (const double*)yg,
+                (const double*)xs, h->top_mass ? (const double*)h->top_m : (const double*)nullptr, ps,
+                apart ? q : (const double*)nullptr, w, apart);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+static int eig_wait(nlps_gpu* h) {
+  HIPCHK(h->eig_h.fetch(h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int nlps_gpu_tangent_lambda_max(nlps_gpu* h, const double* lumped_mass, const double* v0, nlps_eig* eig,
+                                           double* mode) {
+  const char* who = "nlps_gpu_tangent_lambda_max";
+  if (!eig) {
+    h->err = "nlps_gpu_tangent_lambda_max: eig is required";
+    return 1;
+  }
+  eig->reason = 0;
+  eig->iterations = 0;
+  eig->theta = eig->resid = eig->asymmetry = 0.0;
+  eig->bytes = 0;
+  if (tanop_valid(h, who)) return 1;
+  if (h->halo || (h->rccl && h->rccl->world > 1)) {
+    h->err = "nlps_gpu_tangent_lambda_max: single rank only: this handle exchanges halos (a halo callback or an RCCL world "
+             "> 1), and dot products across ranks would need an owner mask and an allreduce";
+    return 1;
+  }
+  if (!lumped_mass) {
+    h->err = "nlps_gpu_tangent_lambda_max: lumped_mass is required";
+    return 1;
+  }
+  const int m = eig->max_it;
+  if (m < 1 || m > NLPS_KSP_MAX_RESTART) {
+    h->err = "nlps_gpu_tangent_lambda_max: max_it must be 1 .. NLPS_KSP_MAX_RESTART";
+    return 1;
+  }
+  if (!(eig->rtol >= 0.0)) {
+    h->err = "nlps_gpu_tangent_lambda_max: rtol must be >= 0";
+    return 1;
+  }
+  VecIO io;
+  if (vec_begin(h, who, io)) return 1;
+  const size_t n = io.n;
+  const int nA = h->nactive, nn = h->g.nnodes, nb = (int)((n + KSP_TILE - 1) / KSP_TILE), nbg = nblk(nn, KSP_NT);
+  const EigSmall L{m};
+  eig->bytes = sizeof(double) * ((size_t)(m + 4) * n + (size_t)(m + 2) * nb + nbg + L.size());
+  if (n == 0) {
+    eig->reason = NLPS_EIG_EMPTY;
+    return 0;
+  }
+  if (reserve(h, who, h->ksp_v, (size_t)(m + 4) * n, "the Lanczos basis") ||
+      reserve(h, who, h->ksp_part, (size_t)(m + 2) * nb + nbg, "the partial sums") ||
+      reserve(h, who, h->ksp_s, L.size(), "the tridiagonal state") ||
+      reserve(h, who, h->ksp_bad_d, 1, "the mass check"))
+    return 1;
+  if (!h->eig_h.host()) {
+    HIPCHK(h->eig_h.alloc());
+    memset(h->eig_h.host(), 0, sizeof(EigHost));
+  }
+  const double* md = io.in(lumped_mass);
+  const double* v0d = io.in(v0);
+  double* moded = io.out(mode, false);
+  double* const Q = h->ksp_v;  // Q[c] at Q + c n, c <= m
+  double* const ps = Q + (size_t)(m + 1) * n;
+  double* const xs = ps + n;
+  double* const y = xs + n;
+  double* const part = h->ksp_part;
+  double* const apart = part + (size_t)(m + 2) * nb;
+  double* const s = h->ksp_s;
+  EigHost* const hw = h->eig_h.target();
+  EigHost* const hh = h->eig_h.host();
+  const dim3 gs(nb), bs(KSP_NT);
+  const double* const nul = nullptr;
+  double* const nulw = nullptr;
+  // ps = P S, q_1 = P v0 / ||P v0||; the one wait ahead of the loop brings the norm and the mass check
+  HIPCHK(hipMemsetAsync(h->ksp_bad_d, 0x7f, sizeof(int), h->stream));  // (0x7f7f7f7f: no node failed)
+  hipLaunchKernelGGL(k_eig_start, gs, bs, 0, h->stream, (int)n, h->nd, h->top_dir ? (const int*)h->d2m_d : (const int*)nullptr,
+                     md, v0d, eig->seed, ps, Q, part, h->ksp_bad_d.get());
+  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, s + L.n2(), &hw->n2, nul, nulw, nul);
+  hipLaunchKernelGGL(k_ksp_scale, gs, bs, 0, h->stream, (int)n, (const double*)Q, Q, 1.0, (const double*)(s + L.n2()));
+  HIPCHK(hipGetLastError());
+  HIPCHK(h->eig_h.fetch(h->stream));
+  HIPCHK(hipMemcpyAsync(&hh->bad, h->ksp_bad_d, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const int bad = *(volatile int*)&hh->bad;
+  if (bad < nA) {
+    char buf[240];
+    snprintf(buf, sizeof buf,
+             "nlps_gpu_tangent_lambda_max: the lumped mass of masked node %d is not positive and finite on a free dof: "
+             "M^-1/2 does not exist there",
+             bad);
+    h->err = buf;
+    return 1;
+  }
+  const double n2 = hh->n2;
+  int its = 0, reason = 0;
+  double theta = 0.0, asym = 0.0;
+  if (n2 == 0.0) reason = NLPS_EIG_EMPTY;
+  else if (!std::isfinite(n2)) reason = NLPS_EIG_DIVERGED_NANORINF;
+  for (int j = 0; !reason; j++) {
+    double* const w = Q + (size_t)(j + 1) * n;
+    double* const refine = s + L.refine();
+    if (eig_product(h, ps, Q + (size_t)j * n, xs, w, apart)) return 1;
+    hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)apart, nbg, s + L.aj(), nulw, nul, nulw, nul);
+    // classical Gram-Schmidt against q_1 .. q_j, pass 1 (with w.w for DGKS), then pass 2 when the refine word says so
+    hipLaunchKernelGGL(k_ksp_mdot, gs, bs, 0, h->stream, (int)n, (const double*)Q, n, j + 1, 1, (const double*)w, part, nb, nul);
+    hipLaunchKernelGGL(k_ksp_finish, dim3(j + 2), bs, 0, h->stream, (const double*)part, nb, s + L.h1(), nulw, nul, nulw, nul);
+    hipLaunchKernelGGL(k_ksp_maxpy, gs, bs, 0, h->stream, (int)n, (const double*)Q, n, j + 1, (const double*)(s + L.h1()), w,
+                       part, nul);
+    hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, s + L.wn2(), nulw, nul, refine,
+                       (const double*)(s + L.h1() + j + 1));
+    hipLaunchKernelGGL(k_ksp_mdot, gs, bs, 0, h->stream, (int)n, (const double*)Q, n, j + 1, 0, (const double*)w, part, nb,
+                       (const double*)refine);
+    hipLaunchKernelGGL(k_ksp_finish, dim3(j + 1), bs, 0, h->stream, (const double*)part, nb, s + L.h2(), nulw,
+                       (const double*)refine, nulw, nul);
+    hipLaunchKernelGGL(k_ksp_maxpy, gs, bs, 0, h->stream, (int)n, (const double*)Q, n, j + 1, (const double*)(s + L.h2()), w,
+                       part, (const double*)refine);
+    hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, s + L.wn2(), nulw,
+                       (const double*)refine, nulw, nul);
+    hipLaunchKernelGGL(k_eig_ritz, dim3(1), dim3(64), 0, h->stream, L, s, j, hw);
+    hipLaunchKernelGGL(k_ksp_scale, gs, bs, 0, h->stream, (int)n, (const double*)w, w, 1.0, (const double*)(s + L.wn2()));
+    HIPCHK(hipGetLastError());
+    if (eig_wait(h)) return 1;
+    theta = hh->theta;
+    asym = hh->asym;
+    const double est = hh->est;
+    its = j + 1;
+    if (eig->history) eig->history[j] = theta;
+    if ((hh->flags & EIG_FLAG_NONFINITE) || !std::isfinite(theta) || !std::isfinite(est)) reason = NLPS_EIG_DIVERGED_NANORINF;
+    else if (est <= eig->rtol * fabs(theta)) reason = NLPS_EIG_CONVERGED;  // (beta_j == 0 gives est == 0)
+    else if (its == m) reason = NLPS_EIG_DIVERGED_ITS;
+  }
+  eig->reason = reason;
+  eig->iterations = its;
+  eig->theta = theta;
+  eig->asymmetry = asym;
+  if (its > 0 && reason != NLPS_EIG_DIVERGED_NANORINF) {  // y = Q s, the true residual from one product, mode = S y
+    double* const t = Q + (size_t)its * n;
+    hipLaunchKernelGGL(k_eig_ritzvec, gs, bs, 0, h->stream, (int)n, (const double*)Q, n, its, (const double*)(s + L.s()), y);
+    if (eig_product(h, ps, y, xs, t, nullptr)) return 1;
+    hipLaunchKernelGGL(k_eig_resid, gs, bs, 0, h->stream, (int)n, (const double*)t, (const double*)y,
+                       (const double*)(s + L.theta()), (const double*)ps, moded, part);
+    hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, nulw, &hw->rn2, nul, nulw, nul);
+    HIPCHK(hipGetLastError());
+    if (eig_wait(h)) return 1;
+    eig->resid = sqrt(hh->rn2);
+  } else {
+    if (moded) HIPCHK(hipMemsetAsync(moded, 0, n * sizeof(double), h->stream));
+    if (reason == NLPS_EIG_DIVERGED_NANORINF) eig->resid = NAN;
+  }
+  if (io.finish()) {
+    h->err = "nlps_gpu_tangent_lambda_max: HIP error";
     return 1;
   }
   if (io.back.empty()) HIPCHK(hipStreamSynchronize(h->stream));

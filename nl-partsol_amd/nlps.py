@@ -63,6 +63,13 @@ class Ksp(C.Structure):  # nlps_ksp (include/nlps_gpu.h): nlps_gpu_tangent_solve
                 ("bytes", C.c_size_t)]
 
 
+class Eig(C.Structure):  # nlps_eig: nlps_gpu_tangent_lambda_max's settings and results
+    _fields_ = [("max_it", C.c_int), ("rtol", C.c_double), ("seed", C.c_ulonglong), ("history", _dp),
+                ("reason", C.c_int), ("iterations", C.c_int), ("theta", C.c_double), ("resid", C.c_double),
+                ("asymmetry", C.c_double), ("bytes", C.c_size_t)]
+
+
+EIG_REASONS = {1: "converged", 2: "empty", -3: "diverged_its", -9: "diverged_nanorinf"}  # NLPS_EIG_*
 PC_KINDS = {"none": 0, "jacobi": 1, "pbjacobi": 2}  # NLPS_PC_NONE / _JACOBI / _PBJACOBI
 KSP_REASONS = {1: "converged_bzero", 2: "converged_rtol", 3: "converged_atol", -3: "diverged_its", -4: "diverged_dtol",
                -5: "diverged_breakdown", -9: "diverged_nanorinf"}
@@ -118,7 +125,8 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_form_initial_guess", "nlps_gpu_nodal_kinetic_increments", "nlps_gpu_nodal_inertial_forces",
            "nlps_gpu_tangent_assemble", "nlps_gpu_tangent_set_grouped", "nlps_gpu_set_tangent_alpha4", "nlps_gpu_tangent_coo",
            "nlps_gpu_sparsity_pattern", "nlps_gpu_tangent_operator", "nlps_gpu_tangent_apply",
-           "nlps_gpu_tangent_block_diagonal", "nlps_gpu_tangent_solve", "nlps_gpu_newton_solve", "nlps_gpu_newmark_step",
+           "nlps_gpu_tangent_block_diagonal", "nlps_gpu_tangent_solve", "nlps_gpu_tangent_lambda_max",
+           "nlps_host_critical_dt", "nlps_gpu_newton_solve", "nlps_gpu_newmark_step",
            "nlps_gpu_migration_select", "nlps_gpu_migration_commit", "nlps_gpu_num_particles",
            "nlps_gpu_set_particle_ids", "nlps_gpu_download_ids",
            "nlps_gpu_set_timing", "nlps_gpu_get_timing", "nlps_host_stencil_tables",
@@ -183,6 +191,10 @@ def lib():
         L.nlps_gpu_tangent_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.nlps_gpu_tangent_block_diagonal.argtypes = [C.c_void_p, C.c_void_p]
         L.nlps_gpu_tangent_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Ksp)]
+        if hasattr(L, "nlps_gpu_tangent_lambda_max"):  # (NLPS_GPU_LIB may name an older build)
+            L.nlps_gpu_tangent_lambda_max.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Eig), C.c_void_p]
+            L.nlps_host_critical_dt.restype = C.c_double
+            L.nlps_host_critical_dt.argtypes = [C.c_double, C.c_double, C.c_double]
         L.nlps_gpu_newton_solve.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [_dp, _dp, C.POINTER(Bcc), C.c_int, C.c_int,
                                             C.c_double, C.c_void_p, C.POINTER(Snes)]
         L.nlps_gpu_newmark_step.argtypes = [C.c_void_p, C.POINTER(Bcc), C.c_int, C.c_int, C.POINTER(Newmark), _dp,
@@ -322,6 +334,12 @@ def courant_dt(CFL, h, Cel, row=None):
     f.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
     r = None if row is None else np.ascontiguousarray(row, dtype=np.float64)
     return f(float(CFL), float(h), float(Cel), None if r is None else r.ctypes.data_as(C.c_void_p))
+
+
+def critical_dt(omega2, gamma=0.5, safety=0.9):
+    """safety * sqrt(2 / gamma) / sqrt(omega2): the explicit scheme's stable step from omega_max^2 (pass theta + resid of
+    Solver.tangent_lambda_max); +inf for omega2 <= 0, -1 for gamma < 0.5 (nlps_host_critical_dt); host only"""
+    return lib().nlps_host_critical_dt(float(omega2), float(gamma), float(safety))
 
 
 class NlpsError(RuntimeError):
@@ -913,6 +931,28 @@ class Solver:
                     rnorm=k.rnorm, bnorm=k.bnorm, bytes=int(k.bytes),
                     history=hist[: k.iterations + 1].copy() if hist is not None else None)
         return out, info
+
+    def tangent_lambda_max(self, mass, v0=None, max_it=64, rtol=1e-6, seed=0, mode=False, history=False):
+        """The largest Ritz value of the pencil (K, M) on the free dofs of the last tangent_operator, by Lanczos on the
+        device (nlps_gpu_tangent_lambda_max).  mass, v0: numpy arrays (host) or torch tensors (device), masked
+        [nactive*ndim]; v0 None: the hash vector of seed.  mode: True for a new vector of mass's kind, or the vector to
+        write.  Returns info = dict(theta, resid, asymmetry, iterations, reason (an NLPS_EIG_* value), reason_name, bytes,
+        history (iterations values theta_j, or None), mode (or None))."""
+        out = None
+        if mode is True:
+            if isinstance(mass, np.ndarray):
+                out = np.empty(self.nactive * self.ndim)
+            else:
+                import torch
+                out = torch.empty(self.nactive * self.ndim, dtype=torch.float64, device=mass.device)
+        elif mode is not False and mode is not None:
+            out = mode
+        hist = np.zeros(max(int(max_it), 1)) if history else None
+        e = Eig(max_it=int(max_it), rtol=float(rtol), seed=int(seed), history=_d(hist) if hist is not None else None)
+        self._chk(self.L.nlps_gpu_tangent_lambda_max(self.h, _vp(mass), _vp(v0), C.byref(e), _vp(out)))
+        return dict(theta=e.theta, resid=e.resid, asymmetry=e.asymmetry, iterations=e.iterations, reason=e.reason,
+                    reason_name=EIG_REASONS.get(e.reason, str(e.reason)), bytes=int(e.bytes),
+                    history=hist[: e.iterations].copy() if hist is not None else None, mode=out)
 
     @staticmethod
     def _snes(max_it, max_funcs, atol, rtol, stol, divtol, linesearch, ls_alpha, ls_steptol, ls_maxstep, ls_max_it,
