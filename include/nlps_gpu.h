@@ -530,8 +530,10 @@ int nlps_gpu_set_law_launch_mode(nlps_gpu *h, int mode);
  * implicit-path call made with the mode on sorts them exactly before it sums over them (nothing to do for the caller).
  * The window slabs are allocated at the first call that needs them: 12 x 800 (3-D, per tile of 4^3 closest nodes) or
  * 8 x 400 (2-D, per tile of 16^2) doubles per tile of the grid.
- * Outside the contract, on their usual (atomic) path in every mode: the assembled tangent (nlps_gpu_tangent_assemble /
- * nlps_gpu_tangent_coo); clouds created with driver_eigenerosion / driver_eigensoftening (the damage hooks, in the
+ * The assembled tangent is inside the contract in its CSR form (nlps_gpu_tangent_csr_pattern / nlps_gpu_tangent_csr,
+ * which hold no floating-point atomic in any mode).
+ * Outside the contract, on their usual (atomic) path in every mode: the COO form of the assembled tangent
+ * (nlps_gpu_tangent_assemble / nlps_gpu_tangent_coo); clouds created with driver_eigenerosion / driver_eigensoftening (the damage hooks, in the
  * separate stages and in the fused form of nlps_gpu_set_implicit_damage alike) unless nlps_gpu_set_deterministic_damage
  * is on -- without it the explicit step refuses such a cloud in the mode; handles
  * with a halo-exchange callback or an RCCL exchange attached; the folded, lazy and async-lists forms of the explicit
@@ -548,7 +550,9 @@ int nlps_gpu_set_deterministic(nlps_gpu *h, int on);
  * are visited in ascending memory slot, so the threshold decisions G_p > Gf and T_eps > ft read sums made in one order,
  * and the nodal forces under them come from one wave per tile and a fixed-order sum of window slabs.  Damage decisions
  * and every downloaded array then repeat bit for bit between two runs from the same inputs.
- * Still refused or outside the contract: a halo callback or an RCCL exchange, the fluid law, the assembled tangent.
+ * nlps_gpu_tangent_csr_pattern / nlps_gpu_tangent_csr repeat bit for bit for a damage cloud as well.
+ * Still refused or outside the contract: a halo callback or an RCCL exchange, the fluid law, the COO form of the
+ * assembled tangent (nlps_gpu_tangent_assemble / nlps_gpu_tangent_coo).
  * The setter allocates the run tables and the window slabs (no step or evaluation allocates) and drops the cached node
  * runs.  It returns 1, with the reason in nlps_gpu_last_error, for a cloud created without either driver. */
 int nlps_gpu_set_deterministic_damage(nlps_gpu *h, int on);
@@ -858,6 +862,37 @@ typedef struct { double beta, gamma, dt, alpha_blend; int use_explicit_trial; } 
 int nlps_gpu_newmark_step(nlps_gpu *h, const nlps_bcc *bcc, int nbcc, int step, const nlps_newmark *nm,
                           const double *gravity, const nlps_bcc *loads, int nloads, double thickness,
                           const double *area0, nlps_snes *snes, int *nactive, double *dU_out /* or NULL */);
+
+/* ------------------------------------------------------------------ the tangent in CSR (MatCreateSeqAIJWithArrays)
+ * The matrix of nlps_gpu_tangent_assemble + nlps_gpu_tangent_coo as sorted CSR, assembled row by row: every entry has one
+ * owner, which adds the particles' contributions in a fixed order (closest nodes around the row node in grid order, the
+ * particles of one closest node by ascending memory slot) with plain adds and writes the finished row once.  No kernel
+ * of the path holds a floating-point atomic, and no dense stencil array is allocated.
+ * Both calls work on the linearisation of the last successful nlps_gpu_tangent_operator, whose snapshot supplies Dh,
+ * alpha_1 M and the Dirichlet choice; they fail with the messages and under the staleness rules of
+ * nlps_gpu_tangent_apply (before any operator; after a search, nlps_gpu_active_masks, a re-sort, a migration,
+ * nlps_gpu_update_kinetics, nlps_gpu_roll_state or nlps_gpu_explicit_step).  One rank: both are refused, with the reason,
+ * while a halo callback or an RCCL exchange is attached.  A failed allocation returns 1 with the reason.
+ * nlps_gpu_tangent_csr_pattern: the structure -- all d x d entries of a node pair (A, B) are present iff some particle
+ * holds both nodes in its list (__create_sparsity_pattern, U-Newmark-beta.c:1568-1632; the set nlps_gpu_tangent_coo
+ * emits).  *nnz (may be NULL) = the stored entries, equal to nlps_gpu_tangent_assemble's; nnz > INT_MAX returns 1 with a
+ * message naming nnz.  *bytes (may be NULL) = the device memory the CSR path keeps on the handle for this
+ * linearisation, by the formula
+ *   8 np (d^4 + 6 d + 2) + 4 (nnodes + 1) + 8 w nnodes + 8 (N_A + 1),   w = 2 in 2-D, 12 in 3-D
+ * -- per particle, in the order by closest node, the tensor E = Jm1^T Dh Jm1, the 5 d separable shape-function factors,
+ * the position and the membership mask; the run starts and a bit mask of the visited column offsets per grid node
+ * (81 / 729 bits); block counts and offsets per active node.  (The atomic path: 8 d^2 (9^d nnodes + nnz / d^2) bytes and more.)  The buffers are kept and
+ * only grow.  Staging for host destinations and the scan's workspace live for one call and are not counted.
+ * nlps_gpu_tangent_csr: row_ptr[N_A*d + 1], cols[nnz], vals[nnz], host or device pointers (all three on the device, or
+ * staged).  Rows and columns in masked dof numbering; columns strictly ascending within each row, also under
+ * nlps_gpu_set_node_numbering; every structural entry present even when its value is 0 (the zeroed entries of the
+ * Dirichlet rows and columns included, which keep a 1 on the diagonal), as in nlps_gpu_tangent_coo.  Requires
+ * nlps_gpu_tangent_csr_pattern since the current operator.  np == 0 or N_A == 0: nnz = 0, row_ptr all zero, return 0
+ * (cols and vals may then be NULL).
+ * Two calls on one linearisation return the same bits in any mode; with nlps_gpu_set_deterministic on (and
+ * nlps_gpu_set_deterministic_damage for a damage cloud) two runs from the same inputs return bit-identical arrays. */
+int nlps_gpu_tangent_csr_pattern(nlps_gpu *h, long long *nnz, size_t *bytes);
+int nlps_gpu_tangent_csr(nlps_gpu *h, int *row_ptr, int *cols, double *vals);
 
 /* ------------------------------------------------------------------ multi-GPU hooks */
 

@@ -340,6 +340,44 @@ int nlps_glue_tangent_operator(const nlps_glue *G, double alpha_1, const double 
   return STATUS;
 }
 
+/* __create_sparsity_pattern + __jacobian_evaluation (U-Newmark-beta.c:1568-1830; the PCCHOLESKY / CHOLMOD branch of
+ * U-Static.c:229-241) as the three arrays of MatCreateSeqAIJWithArrays(PETSC_COMM_SELF, n, n, *row_ptr, *cols, *vals, &K),
+ * n = nactive * NumberDimensions: sorted CSR of the linearisation of the last nlps_glue_tangent_operator, assembled on the
+ * device row by row without float atomics (it repeats bit for bit), columns ascending in every row.  The arrays are
+ * malloc()ed here and belong to the caller (free() them after MatDestroy: the matrix does not copy them); *nnz = the
+ * stored entries.  PetscInt must be a 32-bit int (the default configuration); nnz > INT_MAX is refused by the library. */
+int nlps_glue_jacobian_csr(const nlps_glue *G, int nactive, int **row_ptr, int **cols, double **vals, long long *nnz) {
+  long long n = 0;
+  *row_ptr = NULL;
+  *cols = NULL;
+  *vals = NULL;
+  int STATUS = nlps_gpu_tangent_csr_pattern(G->gpu, &n, NULL);
+  if (STATUS == EXIT_SUCCESS) {
+    *row_ptr = (int *)malloc(((size_t)nactive * NumberDimensions + 1) * sizeof(int));
+    *cols = (int *)malloc((size_t)(n > 0 ? n : 1) * sizeof(int));
+    *vals = (double *)malloc((size_t)(n > 0 ? n : 1) * sizeof(double));
+    if (*row_ptr == NULL || *cols == NULL || *vals == NULL) {
+      fprintf(stderr, "" RED "nlps_glue_jacobian_csr: out of memory for %lld entries" RESET "\n", n);
+      STATUS = EXIT_FAILURE;
+    } else {
+      STATUS = nlps_gpu_tangent_csr(G->gpu, *row_ptr, *cols, *vals);
+      if (STATUS != EXIT_SUCCESS) fprintf(stderr, "" RED "%s" RESET "\n", nlps_gpu_last_error(G->gpu));
+    }
+  } else {
+    fprintf(stderr, "" RED "%s" RESET "\n", nlps_gpu_last_error(G->gpu));
+  }
+  if (STATUS != EXIT_SUCCESS) {
+    free(*row_ptr);
+    free(*cols);
+    free(*vals);
+    *row_ptr = NULL;
+    *cols = NULL;
+    *vals = NULL;
+  }
+  if (nnz) *nnz = n;
+  return STATUS;
+}
+
 /* The body of the MatShell's MATOP_MULT after VecGetArrayRead(x, &x_ptr) / VecGetArray(y, &y_ptr): y = K x. */
 int nlps_glue_tangent_mult(const nlps_glue *G, const double *x_ptr, double *y_ptr) {
   const int STATUS = nlps_gpu_tangent_apply(G->gpu, x_ptr, y_ptr);

@@ -22,6 +22,7 @@
 #include <rccl/rccl.h>  // types and prototypes only: the library is dlopen()ed when a communicator is attached
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1518,6 +1519,7 @@ __global__ __launch_bounds__(BLK) void k_fill_orders(int np, const int* __restri
 }
 #include "nlps_tangent_kernels.hpp"
 #include "nlps_tangent_operator.hpp"
+#include "nlps_tangent_csr.hpp"
 #include "nlps_krylov.hpp"
 #include "nlps_eigen.hpp"
 #include "nlps_newton.hpp"
@@ -1932,6 +1934,16 @@ struct nlps_gpu {
   bool top_mass = false, top_dir = false;
   unsigned long long tan_gen = 1, top_gen = 0;  // top_gen 0: no operator yet
   const char* tan_why = "";
+  // the tangent in CSR (nlps_gpu_tangent_csr_pattern / nlps_gpu_tangent_csr, nlps_tangent_csr.hpp), allocated on first
+  // use.  The pattern belongs to one linearisation: csr_serial is the top_serial it was built from (0: none).
+  DevBuf<double> csr_e;      // E [np][d^4], particles in the order by closest node (like csr_f and csr_mk)
+  DevBuf<double> csr_f;      // separable factors and position [np][6 d]
+  DevBuf<unsigned long long> csr_mk;  // membership masks [np][2]
+  DevBuf<int> csr_run;       // run starts [nnodes + 1]
+  DevBuf<unsigned long long> csr_mask;  // visited column offsets of every row node [nnodes][2 | 12]
+  DevBuf<int> csr_cnt, csr_off;         // blocks per masked node and their exclusive scan [N_A + 1]
+  unsigned long long csr_serial = 0;
+  long long csr_blocks = 0;
   // device GMRES (nlps_gpu_tangent_solve, nlps_krylov.hpp), allocated on first use and kept (they only grow).  The
   // preconditioner belongs to one linearisation: top_serial counts the successful nlps_gpu_tangent_operator calls
   // (top_gen does not move when the caller re-linearises without moving particles), ksp_pc_serial says which one
@@ -6349,6 +6361,131 @@ extern "C" int nlps_gpu_tangent_block_diagonal(nlps_gpu* h, double* blocks) {
   if (st && h->err.find("nlps_gpu_tangent_block_diagonal") == std::string::npos)
     h->err = "nlps_gpu_tangent_block_diagonal: HIP error (or halo exchange failure)";
   return st;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the tangent in CSR, assembled row by row without float atomics (nlps_tangent_csr.hpp)
+// ------------------------------------------------------------------------------------------------
+static size_t tancsr_bytes(int nd, size_t np, size_t nnodes, size_t nactive) {
+  const size_t E = (size_t)nd * nd, mw = nd == 3 ? 12 : 2;
+  return 8 * np * (E * E + 6 * (size_t)nd + 2) + 4 * (nnodes + 1) + 8 * mw * nnodes + 8 * (nactive + 1);
+}
+
+static int tancsr_one_rank(nlps_gpu* h, const char* who) {
+  if (h->halo || h->rccl) {
+    h->err = std::string(who) + ": the CSR assembly is built for one rank: not with a halo callback or an RCCL exchange "
+             "attached (a row's owner would need the particles of the neighbouring rank that hold its node)";
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int nlps_gpu_tangent_csr_pattern(nlps_gpu* h, long long* nnz, size_t* bytes) {
+  const char* who = "nlps_gpu_tangent_csr_pattern";
+  if (tanop_valid(h, who)) return 1;
+  if (tancsr_one_rank(h, who)) return 1;
+  h->csr_serial = 0;  // (no pattern until this call succeeds)
+  const int ND = h->nd, E = ND * ND, np = h->top_np, nn = h->g.nnodes, na = h->nactive;
+  const int mw = ND == 3 ? CsrCfg<3>::MW : CsrCfg<2>::MW;
+  if (bytes) *bytes = tancsr_bytes(ND, (size_t)np, (size_t)nn, (size_t)na);
+  h->csr_blocks = 0;
+  if (np > 0 && na > 0) {
+    if (reserve(h, who, h->csr_e, (size_t)np * E * E, ND == 3 ? "81 doubles per particle" : "16 doubles per particle")) return 1;
+    if (reserve(h, who, h->csr_f, (size_t)np * 6 * ND, "the shape-function factors")) return 1;
+    if (reserve(h, who, h->csr_mk, (size_t)np * 2, "the membership masks")) return 1;
+    if (reserve(h, who, h->csr_run, (size_t)nn + 1, "the run starts")) return 1;
+    if (reserve(h, who, h->csr_mask, (size_t)nn * mw, "the visited-offset masks")) return 1;
+    if (reserve(h, who, h->csr_cnt, (size_t)na + 1, "the block counts")) return 1;
+    if (reserve(h, who, h->csr_off, (size_t)na + 1, "the block offsets")) return 1;
+    DevBuf<char> scan_tmp;  // (of this call only)
+    size_t scan_bytes = 0;
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, h->csr_cnt.get(), h->csr_off.get(), na + 1, h->stream));
+    if (reserve(h, who, scan_tmp, scan_bytes + 16, "the scan")) return 1;
+    // particles grouped by closest node: the (I0, p) sort of the atomic assembly (a stable radix sort of slots in
+    // ascending order, so a run holds its particles by ascending memory slot)
+    hipLaunchKernelGGL(k_tangent_keys, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->P, h->skey_d, h->sval_d);
+    size_t sort_bytes = h->cub_tmp_bytes;
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(h->cub_tmp.get(), sort_bytes, h->skey_d.get(), h->skey2_d.get(), h->sval_d.get(),
+                                              h->sval2_d.get(), np, 0, 32, h->stream));
+    hipLaunchKernelGGL(k_tancsr_runs, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, nn, (const unsigned long long*)h->skey2_d,
+                       h->csr_run.get());
+    // (the records of E, factors and masks in that order: the sorted list itself is not kept)
+    LAUNCH_ND_BLK(k_tancsr_setup<2>, k_tancsr_setup<3>, (np + 63) / 64, 64, h->P, h->g, (const double*)h->top_d, np,
+                  (const int*)h->sval2_d, h->csr_e.get(), h->csr_f.get(), h->csr_mk.get(), h->gstatus_d);
+    HIPCHK(hipMemsetAsync(h->csr_cnt, 0, ((size_t)na + 1) * sizeof(int), h->stream));
+    LAUNCH_ND((k_tancsr_pattern<2>), (k_tancsr_pattern<3>), (nn + 3) / 4, h->g, (const int*)h->csr_run,
+              (const unsigned long long*)h->csr_mk, (const int*)h->n2m_d, h->csr_mask.get(), h->csr_cnt.get());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(scan_tmp.get(), scan_bytes, h->csr_cnt.get(), h->csr_off.get(), na + 1, h->stream));
+    int total = 0;
+    HIPCHK(hipMemcpyAsync(&total, h->csr_off + na, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (check_status(h, ST_NEWTON, "nlps_gpu_tangent_csr_pattern()")) return 1;  // (synchronises)
+    h->csr_blocks = total;
+  }
+  const long long n = h->csr_blocks * E;
+  if (nnz) *nnz = n;
+  if (n > (long long)INT_MAX) {
+    char buf[200];
+    snprintf(buf, sizeof buf, "%s: nnz = %lld does not fit the int row_ptr and cols of the CSR arrays (INT_MAX = %d)", who, n,
+             INT_MAX);
+    h->err = buf;
+    return 1;
+  }
+  h->csr_serial = h->top_serial;
+  return 0;
+}
+
+extern "C" int nlps_gpu_tangent_csr(nlps_gpu* h, int* row_ptr, int* cols, double* vals) {
+  const char* who = "nlps_gpu_tangent_csr";
+  if (tanop_valid(h, who)) return 1;
+  if (tancsr_one_rank(h, who)) return 1;
+  if (h->csr_serial == 0 || h->csr_serial != h->top_serial) {
+    h->err = std::string(who) + ": call nlps_gpu_tangent_csr_pattern() after nlps_gpu_tangent_operator() first";
+    return 1;
+  }
+  const int ND = h->nd, E = ND * ND, nn = h->g.nnodes, na = h->nactive;
+  const size_t nr = (size_t)na * ND + 1, ne = (size_t)h->csr_blocks * E;
+  if (!row_ptr || (ne > 0 && (!cols || !vals))) {
+    h->err = std::string(who) + ": row_ptr, cols and vals are required";
+    return 1;
+  }
+  if (ne == 0) {
+    if (is_device_ptr(row_ptr)) {
+      HIPCHK(hipMemsetAsync(row_ptr, 0, nr * sizeof(int), h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+    } else {
+      memset(row_ptr, 0, nr * sizeof(int));
+    }
+    return 0;
+  }
+  const bool dev = is_device_ptr(row_ptr) && is_device_ptr(cols) && is_device_ptr(vals);
+  DevBuf<int> row_d, cols_d;  // staging of host destinations, of this call only
+  DevBuf<double> vals_d;
+  int *rp = row_ptr, *cp = cols;
+  double* vp = vals;
+  if (!dev) {
+    if (reserve(h, who, row_d, nr, "the staging of row_ptr") || reserve(h, who, cols_d, ne, "the staging of cols") ||
+        reserve(h, who, vals_d, ne, "the staging of vals"))
+      return 1;
+    rp = row_d.get();
+    cp = cols_d.get();
+    vp = vals_d.get();
+  }
+  LAUNCH_ND((k_tancsr_rowptr<2>), (k_tancsr_rowptr<3>), nblk((int)nr), na, (const int*)h->csr_cnt, (const int*)h->csr_off, rp);
+  const int* d2m = h->top_dir ? (const int*)h->d2m_d : nullptr;
+  const double* aM = h->top_mass ? (const double*)h->top_m : nullptr;
+  LAUNCH_ND_BLK((k_tancsr_rows<2>), (k_tancsr_rows<3>), nn, (ND == 3 ? CsrCfg<3>::NT : CsrCfg<2>::NT), h->g,
+                (const int*)h->csr_run, (const double*)h->csr_e, (const double*)h->csr_f,
+                (const unsigned long long*)h->csr_mk, (const unsigned long long*)h->csr_mask, (const int*)h->n2m_d, d2m, aM, (const int*)h->csr_cnt,
+                (const int*)h->csr_off, cp, vp);
+  HIPCHK(hipGetLastError());
+  if (!dev) {
+    HIPCHK(hipMemcpyAsync(row_ptr, rp, nr * sizeof(int), hipMemcpyDefault, h->stream));
+    HIPCHK(hipMemcpyAsync(cols, cp, ne * sizeof(int), hipMemcpyDefault, h->stream));
+    HIPCHK(hipMemcpyAsync(vals, vp, ne * sizeof(double), hipMemcpyDefault, h->stream));
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));  // (the copies land in the caller's memory before the staging goes)
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -127,6 +127,7 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_sparsity_pattern", "nlps_gpu_tangent_operator", "nlps_gpu_tangent_apply",
            "nlps_gpu_tangent_block_diagonal", "nlps_gpu_tangent_solve", "nlps_gpu_tangent_lambda_max",
            "nlps_host_critical_dt", "nlps_gpu_newton_solve", "nlps_gpu_newmark_step",
+           "nlps_gpu_tangent_csr_pattern", "nlps_gpu_tangent_csr",
            "nlps_gpu_migration_select", "nlps_gpu_migration_commit", "nlps_gpu_num_particles",
            "nlps_gpu_set_particle_ids", "nlps_gpu_download_ids",
            "nlps_gpu_set_timing", "nlps_gpu_get_timing", "nlps_host_stencil_tables",
@@ -200,6 +201,9 @@ def lib():
         L.nlps_gpu_newmark_step.argtypes = [C.c_void_p, C.POINTER(Bcc), C.c_int, C.c_int, C.POINTER(Newmark), _dp,
                                             C.POINTER(Bcc), C.c_int, C.c_double, C.c_void_p, C.POINTER(Snes), _ip,
                                             C.c_void_p]
+        if hasattr(L, "nlps_gpu_tangent_csr"):  # (NLPS_GPU_LIB may name an older build: tools/tangent_csr_bench.py)
+            L.nlps_gpu_tangent_csr_pattern.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_size_t)]
+            L.nlps_gpu_tangent_csr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nlps_gpu_migration_select.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_void_p)]
         L.nlps_gpu_migration_commit.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -900,6 +904,31 @@ class Solver:
             out = np.empty(shape)
         self._chk(self.L.nlps_gpu_tangent_block_diagonal(self.h, _vp(out)))
         return out
+
+    def tangent_csr_pattern(self):
+        """The sparsity structure of the tangent of the last tangent_operator, for tangent_csr
+        (nlps_gpu_tangent_csr_pattern).  Returns (nnz, bytes): the stored entries and the device bytes the CSR path keeps
+        on the handle."""
+        nnz, nb = C.c_longlong(0), C.c_size_t(0)
+        self._chk(self.L.nlps_gpu_tangent_csr_pattern(self.h, C.byref(nnz), C.byref(nb)))
+        self._csr_nnz = int(nnz.value)
+        return self._csr_nnz, int(nb.value)
+
+    def tangent_csr(self, on_device=False):
+        """(row_ptr, cols, vals) of the tangent of the last tangent_operator in CSR, masked dof numbering, columns ascending
+        in every row (nlps_gpu_tangent_csr; what MatCreateSeqAIJWithArrays takes).  Assembled row by row without float
+        atomics: two calls return the same bits.  Needs tangent_csr_pattern() since the operator.  on_device: torch tensors
+        on the GPU, written by the row kernel itself."""
+        n, nr = getattr(self, "_csr_nnz", 0), self.nactive * self.ndim + 1
+        if on_device:
+            import torch
+            row_ptr = torch.empty(nr, dtype=torch.int32, device="cuda")
+            cols = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+            vals = torch.empty(max(n, 1), dtype=torch.float64, device="cuda")[:n]
+        else:
+            row_ptr, cols, vals = np.zeros(nr, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n)
+        self._chk(self.L.nlps_gpu_tangent_csr(self.h, _vp(row_ptr), _vp(cols), _vp(vals)))
+        return row_ptr, cols, vals
 
     def tangent_solve(self, b, x=None, pc="pbjacobi", restart=30, max_it=10000, rtol=1e-5, atol=0.0, dtol=1e5,
                       history=False, out=None):
