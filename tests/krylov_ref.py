@@ -1,7 +1,9 @@
 """Reference GMRES for nlps_gpu_tangent_solve (tests only): right-preconditioned restarted GMRES(m) in numpy on a dense K,
 classical Gram-Schmidt with the same DGKS second pass (when ||w|| drops below 1/sqrt 2 of its value), Givens rotations,
 and the same stopping rules: the estimate |g[j+1]| ends a cycle, the true residual b - K x at the end of every cycle
-confirms it or starts the next one.  history[0] = ||b - K x0||, history[k] = the estimate after Arnoldi step k."""
+confirms it or starts the next one.  history[0] = ||b - K x0||, history[k] = the estimate after Arnoldi step k.
+Beside the device's outputs the returned dict says what the device cannot: refined[k] whether step k + 1 took the DGKS second
+pass (refinements: how many did) and happy_ratio[k] = hn / sqrt(w . w), what the happy-breakdown gate compares with HAPPY."""
 import numpy as np
 
 CONVERGED_BZERO, CONVERGED_RTOL, CONVERGED_ATOL = 1, 2, 3
@@ -28,12 +30,14 @@ def gmres(K, b, Minv, restart=30, max_it=10000, rtol=1e-5, atol=0.0, dtol=1e5, x
     bnorm = float(np.linalg.norm(b))
     x = np.zeros(n) if x0 is None else np.array(x0, dtype=np.float64)
     if bnorm == 0.0:
-        return np.zeros(n), dict(iterations=0, reason=CONVERGED_BZERO, rnorm=0.0, bnorm=0.0, history=np.zeros(1))
+        return np.zeros(n), dict(iterations=0, reason=CONVERGED_BZERO, rnorm=0.0, bnorm=0.0, history=np.zeros(1),
+                                 refinements=0, refined=np.zeros(0, dtype=bool), happy_ratio=np.zeros(0))
     r = b - K @ x
     rnorm = float(np.linalg.norm(r))
     tol = max(rtol * bnorm, atol)
     hist = [rnorm]
     its, broke, reason = 0, False, 0
+    refined, ratio = [], []  # per Arnoldi step: did the DGKS second pass run, and hn / sqrt(ww) (what the happy gate sees)
     m = restart
     while True:
         if not (np.isfinite(rnorm) and np.isfinite(bnorm)):
@@ -60,12 +64,14 @@ def gmres(K, b, Minv, restart=30, max_it=10000, rtol=1e-5, atol=0.0, dtol=1e5, x
             ww = w @ w
             w = w - V[: j + 1].T @ h
             wn2 = w @ w
+            refined.append(bool(wn2 < 0.5 * ww))
             if wn2 < 0.5 * ww:  # DGKS: one more pass
                 h2 = V[: j + 1] @ w
                 w = w - V[: j + 1].T @ h2
                 wn2 = w @ w
                 h = h + h2
             hn = np.sqrt(wn2)
+            ratio.append(hn / np.sqrt(ww) if ww > 0.0 else 0.0)
             col = np.append(h, hn)
             for i in range(j):
                 a, bb = col[i], col[i + 1]
@@ -104,4 +110,5 @@ def gmres(K, b, Minv, restart=30, max_it=10000, rtol=1e-5, atol=0.0, dtol=1e5, x
             x = x + Minv(V[:k].T @ y)
         r = b - K @ x
         rnorm = float(np.linalg.norm(r))
-    return x, dict(iterations=its, reason=reason, rnorm=rnorm, bnorm=bnorm, history=np.array(hist))
+    return x, dict(iterations=its, reason=reason, rnorm=rnorm, bnorm=bnorm, history=np.array(hist),
+                   refinements=int(np.sum(refined)), refined=np.array(refined, dtype=bool), happy_ratio=np.array(ratio))
