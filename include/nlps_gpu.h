@@ -894,6 +894,40 @@ int nlps_gpu_newmark_step(nlps_gpu *h, const nlps_bcc *bcc, int nbcc, int step, 
 int nlps_gpu_tangent_csr_pattern(nlps_gpu *h, long long *nnz, size_t *bytes);
 int nlps_gpu_tangent_csr(nlps_gpu *h, int *row_ptr, int *cols, double *vals);
 
+/* ------------------------------------------------------------------ the tangent in block CSR (MatCreateSeq[S]BAIJWithArrays)
+ * The matrix of nlps_gpu_tangent_csr with one column index and d x d contiguous values per node pair: block rows of the
+ * N_A masked nodes, bs = d.  kind = NLPS_BSR_FULL keeps every block (MATSEQBAIJ), NLPS_BSR_UPPER the blocks (A, B) with
+ * B >= A in masked numbering, the diagonal block whole (MATSEQSBAIJ, what a Cholesky factorisation takes).
+ * Both calls work on the linearisation of the last successful nlps_gpu_tangent_operator and are refused exactly like
+ * nlps_gpu_tangent_csr_pattern / nlps_gpu_tangent_csr: before any operator, when it is stale, with a halo callback or an
+ * RCCL exchange attached, on a failed allocation; a refusal leaves the handle usable.  A block-CSR pattern and a CSR
+ * pattern may both exist on one linearisation, neither invalidates the other, and the per-particle records, the runs
+ * and the visited-offset masks are built once and shared.
+ * nlps_gpu_tangent_bsr_pattern: block (A, B) is present iff the CSR pattern holds the entries of that node pair.
+ * *nblocks (may be NULL): for FULL the nnz of nlps_gpu_tangent_csr_pattern divided by d^2; the pattern is structurally
+ * symmetric, so FULL = 2 UPPER - (diagonal blocks present).  nblocks > INT_MAX returns 1 with a message naming nblocks;
+ * a kind other than the two returns 1.  NLPS_BSR_UPPER is accepted for a cloud whose particles are all Neo-Hookean
+ * (with or without the damage factor, alpha_1 M and the Dirichlet choice: all keep K symmetric), the rule of the half
+ * rows of nlps_gpu_tangent_assemble; any other cloud -- the spectral and plastic laws, the fluid law, a mixed cloud
+ * that holds another law -- is refused with the laws named, since its assembled tangent is not symmetric.  *bytes (may
+ * be NULL) = the device memory the CSR / block-CSR path keeps on the handle for this linearisation, the same for both
+ * kinds and whether or not a CSR pattern exists beside it:
+ *   8 np (d^4 + 6 d + 2) + 4 (nnodes + 1) + 8 w nnodes + 8 (N_A + 1)  [the CSR formula]  + 8 (N_A + 1) + 4
+ * -- the counts and offsets of the upper block rows and one flag (the full form reads those of the CSR pattern).
+ * Nothing of the order 9^d nnodes doubles.
+ * nlps_gpu_tangent_bsr: brow_ptr[N_A + 1], bcols[nblocks], vals[nblocks * d * d] of the kind of the last
+ * nlps_gpu_tangent_bsr_pattern since the current operator (refused without one); host or device pointers (all three
+ * on the device, or staged).  bcols strictly ascending within each block row, also under nlps_gpu_set_node_numbering,
+ * where "upper" is decided by the masked numbers, not by the lattice offset.  vals[q][i][j] is row-major inside a block
+ * like nlps_gpu_tangent_block_diagonal; col_major != 0 stores vals[q][j][i] (PETSc's values(bs,bs,nnz)).  Every value
+ * has the bits of the entry (A d + i, B d + j) nlps_gpu_tangent_csr returns for this linearisation: the same sums in the
+ * same order, alpha_1 M and the identity rows and columns of the Dirichlet choice included (zeroed entries kept).  No
+ * floating-point atomic on the path; two calls return the same bits.  np == 0 or N_A == 0: nblocks = 0, brow_ptr all
+ * zero, return 0 (bcols and vals may then be NULL). */
+enum { NLPS_BSR_FULL = 0, NLPS_BSR_UPPER = 1 };
+int nlps_gpu_tangent_bsr_pattern(nlps_gpu *h, int kind, long long *nblocks, size_t *bytes);
+int nlps_gpu_tangent_bsr(nlps_gpu *h, int col_major, int *brow_ptr, int *bcols, double *vals);
+
 /* ------------------------------------------------------------------ multi-GPU hooks */
 
 /* Halo exchange callback, invoked by explicit_step / the P2G stages after a nodal scatter, on the

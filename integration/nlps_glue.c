@@ -378,6 +378,54 @@ int nlps_glue_jacobian_csr(const nlps_glue *G, int nactive, int **row_ptr, int *
   return STATUS;
 }
 
+/* The same tangent as the three arrays of MatCreateSeqSBAIJWithArrays / MatCreateSeqBAIJWithArrays(PETSC_COMM_SELF, bs, n,
+ * n, *brow_ptr, *bcols, *vals, &K) with bs = NumberDimensions, n = nactive * bs: block rows per masked node, bcols
+ * ascending, every block in PETSc's column-major values(bs,bs,nblocks) (col_major = 1).  kind = NLPS_BSR_UPPER: the blocks
+ * B >= A of a Neo-Hookean cloud's symmetric tangent, what the Cholesky factorisations and CHOLMOD take without the AIJ ->
+ * SBAIJ conversion of every Newton iterate (refused by the library for a cloud of another law).  Ownership and
+ * PetscInt as in nlps_glue_jacobian_csr; *nblocks = the stored blocks. */
+static int nlps_glue_jacobian_blocks(const nlps_glue *G, int kind, const char *who, int nactive, int **brow_ptr, int **bcols,
+                                     double **vals, long long *nblocks) {
+  const size_t bs2 = (size_t)NumberDimensions * NumberDimensions;
+  long long n = 0;
+  *brow_ptr = NULL;
+  *bcols = NULL;
+  *vals = NULL;
+  int STATUS = nlps_gpu_tangent_bsr_pattern(G->gpu, kind, &n, NULL);
+  if (STATUS == EXIT_SUCCESS) {
+    *brow_ptr = (int *)malloc(((size_t)nactive + 1) * sizeof(int));
+    *bcols = (int *)malloc((size_t)(n > 0 ? n : 1) * sizeof(int));
+    *vals = (double *)malloc((size_t)(n > 0 ? n : 1) * bs2 * sizeof(double));
+    if (*brow_ptr == NULL || *bcols == NULL || *vals == NULL) {
+      fprintf(stderr, "" RED "%s: out of memory for %lld blocks" RESET "\n", who, n);
+      STATUS = EXIT_FAILURE;
+    } else {
+      STATUS = nlps_gpu_tangent_bsr(G->gpu, 1, *brow_ptr, *bcols, *vals);
+      if (STATUS != EXIT_SUCCESS) fprintf(stderr, "" RED "%s" RESET "\n", nlps_gpu_last_error(G->gpu));
+    }
+  } else {
+    fprintf(stderr, "" RED "%s" RESET "\n", nlps_gpu_last_error(G->gpu));
+  }
+  if (STATUS != EXIT_SUCCESS) {
+    free(*brow_ptr);
+    free(*bcols);
+    free(*vals);
+    *brow_ptr = NULL;
+    *bcols = NULL;
+    *vals = NULL;
+  }
+  if (nblocks) *nblocks = n;
+  return STATUS;
+}
+
+int nlps_glue_jacobian_sbaij(const nlps_glue *G, int nactive, int **brow_ptr, int **bcols, double **vals, long long *nblocks) {
+  return nlps_glue_jacobian_blocks(G, NLPS_BSR_UPPER, "nlps_glue_jacobian_sbaij", nactive, brow_ptr, bcols, vals, nblocks);
+}
+
+int nlps_glue_jacobian_baij(const nlps_glue *G, int nactive, int **brow_ptr, int **bcols, double **vals, long long *nblocks) {
+  return nlps_glue_jacobian_blocks(G, NLPS_BSR_FULL, "nlps_glue_jacobian_baij", nactive, brow_ptr, bcols, vals, nblocks);
+}
+
 /* The body of the MatShell's MATOP_MULT after VecGetArrayRead(x, &x_ptr) / VecGetArray(y, &y_ptr): y = K x. */
 int nlps_glue_tangent_mult(const nlps_glue *G, const double *x_ptr, double *y_ptr) {
   const int STATUS = nlps_gpu_tangent_apply(G->gpu, x_ptr, y_ptr);

@@ -6,7 +6,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "nlps_gpu.hip")
 IO_SRC = os.path.join(HERE, "csrc", "nlps_io.cpp")  # host-only input formats (GiD meshes, lattice, particles)
 DEPS = [SRC, IO_SRC] + [os.path.join(HERE, "csrc", f) for f in ("nlps_device.hpp", "nlps_tables.hpp", "nlps_tile_kernels.hpp",
-                                                         "nlps_tangent_kernels.hpp", "nlps_tangent_operator.hpp", "nlps_tangent_csr.hpp", "nlps_krylov.hpp",
+                                                         "nlps_tangent_kernels.hpp", "nlps_tangent_operator.hpp", "nlps_tangent_csr.hpp", "nlps_tangent_bsr.hpp", "nlps_krylov.hpp",
                                                          "nlps_eigen.hpp", "nlps_newton.hpp", "nlps_record.hpp", "nlps_snapshot.hpp",
                                                          "nlps_host_mem.hpp")] + \
        [os.path.join(HERE, "..", "include", "nlps_gpu.h")]

@@ -1520,6 +1520,7 @@ __global__ __launch_bounds__(BLK) void k_fill_orders(int np, const int* __restri
 #include "nlps_tangent_kernels.hpp"
 #include "nlps_tangent_operator.hpp"
 #include "nlps_tangent_csr.hpp"
+#include "nlps_tangent_bsr.hpp"
 #include "nlps_krylov.hpp"
 #include "nlps_eigen.hpp"
 #include "nlps_newton.hpp"
@@ -1944,6 +1945,16 @@ struct nlps_gpu {
   DevBuf<int> csr_cnt, csr_off;         // blocks per masked node and their exclusive scan [N_A + 1]
   unsigned long long csr_serial = 0;
   long long csr_blocks = 0;
+  // the same tangent in block CSR (nlps_gpu_tangent_bsr_pattern / nlps_gpu_tangent_bsr, nlps_tangent_bsr.hpp): the records,
+  // runs and masks above are shared (csr_rec_serial: the top_serial they were built from, whichever pattern call built
+  // them); of its own only the counts of the kind asked for
+  unsigned long long csr_rec_serial = 0, bsr_serial = 0;
+  DevBuf<int> bsr_cnt, bsr_off;  // the upper form: blocks per masked node's block row (and, behind them, one flag: some
+                                 // row's upper blocks are not its offsets >= 0, a caller's numbering) [N_A + 2]; their
+                                 // exclusive scan [N_A + 1].  The full form reads csr_cnt and csr_off
+  long long bsr_blocks = 0;
+  int bsr_kind = 0;
+  bool bsr_half = false;         // the upper form walks the kept half only (k_tanbsr_rows<ND, true>)
   // device GMRES (nlps_gpu_tangent_solve, nlps_krylov.hpp), allocated on first use and kept (they only grow).  The
   // preconditioner belongs to one linearisation: top_serial counts the successful nlps_gpu_tangent_operator calls
   // (top_gen does not move when the caller re-linearises without moving particles), ksp_pc_serial says which one
@@ -6380,14 +6391,13 @@ static int tancsr_one_rank(nlps_gpu* h, const char* who) {
   return 0;
 }
 
-extern "C" int nlps_gpu_tangent_csr_pattern(nlps_gpu* h, long long* nnz, size_t* bytes) {
-  const char* who = "nlps_gpu_tangent_csr_pattern";
-  if (tanop_valid(h, who)) return 1;
-  if (tancsr_one_rank(h, who)) return 1;
-  h->csr_serial = 0;  // (no pattern until this call succeeds)
+// the records, runs, masks and block counts of the current linearisation, shared by the CSR and the block-CSR form:
+// built by the first pattern call of either kind since the operator (they depend on the linearisation alone)
+static int tancsr_records(nlps_gpu* h, const char* who) {
+  if (h->csr_rec_serial != 0 && h->csr_rec_serial == h->top_serial) return 0;
+  h->csr_rec_serial = 0;  // (no records until this call succeeds)
   const int ND = h->nd, E = ND * ND, np = h->top_np, nn = h->g.nnodes, na = h->nactive;
   const int mw = ND == 3 ? CsrCfg<3>::MW : CsrCfg<2>::MW;
-  if (bytes) *bytes = tancsr_bytes(ND, (size_t)np, (size_t)nn, (size_t)na);
   h->csr_blocks = 0;
   if (np > 0 && na > 0) {
     if (reserve(h, who, h->csr_e, (size_t)np * E * E, ND == 3 ? "81 doubles per particle" : "16 doubles per particle")) return 1;
@@ -6419,9 +6429,21 @@ extern "C" int nlps_gpu_tangent_csr_pattern(nlps_gpu* h, long long* nnz, size_t*
     HIPCHK(hipcub::DeviceScan::ExclusiveSum(scan_tmp.get(), scan_bytes, h->csr_cnt.get(), h->csr_off.get(), na + 1, h->stream));
     int total = 0;
     HIPCHK(hipMemcpyAsync(&total, h->csr_off + na, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (check_status(h, ST_NEWTON, "nlps_gpu_tangent_csr_pattern()")) return 1;  // (synchronises)
+    if (check_status(h, ST_NEWTON, (std::string(who) + "()").c_str())) return 1;  // (synchronises)
     h->csr_blocks = total;
   }
+  h->csr_rec_serial = h->top_serial;
+  return 0;
+}
+
+extern "C" int nlps_gpu_tangent_csr_pattern(nlps_gpu* h, long long* nnz, size_t* bytes) {
+  const char* who = "nlps_gpu_tangent_csr_pattern";
+  if (tanop_valid(h, who)) return 1;
+  if (tancsr_one_rank(h, who)) return 1;
+  h->csr_serial = 0;  // (no pattern until this call succeeds)
+  const int ND = h->nd, E = ND * ND;
+  if (bytes) *bytes = tancsr_bytes(ND, (size_t)h->top_np, (size_t)h->g.nnodes, (size_t)h->nactive);
+  if (tancsr_records(h, who)) return 1;
   const long long n = h->csr_blocks * E;
   if (nnz) *nnz = n;
   if (n > (long long)INT_MAX) {
@@ -6483,6 +6505,136 @@ extern "C" int nlps_gpu_tangent_csr(nlps_gpu* h, int* row_ptr, int* cols, double
     HIPCHK(hipMemcpyAsync(row_ptr, rp, nr * sizeof(int), hipMemcpyDefault, h->stream));
     HIPCHK(hipMemcpyAsync(cols, cp, ne * sizeof(int), hipMemcpyDefault, h->stream));
     HIPCHK(hipMemcpyAsync(vals, vp, ne * sizeof(double), hipMemcpyDefault, h->stream));
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));  // (the copies land in the caller's memory before the staging goes)
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the tangent in block CSR, every block or the upper blocks of a symmetric tangent (nlps_tangent_bsr.hpp)
+// ------------------------------------------------------------------------------------------------
+static size_t tanbsr_bytes(int nd, size_t np, size_t nnodes, size_t nactive) {
+  return tancsr_bytes(nd, np, nnodes, nactive) + 8 * (nactive + 1) + 4;
+}
+
+extern "C" int nlps_gpu_tangent_bsr_pattern(nlps_gpu* h, int kind, long long* nblocks, size_t* bytes) {
+  const char* who = "nlps_gpu_tangent_bsr_pattern";
+  if (tanop_valid(h, who)) return 1;
+  if (tancsr_one_rank(h, who)) return 1;
+  h->bsr_serial = 0;  // (no pattern until this call succeeds)
+  if (kind != NLPS_BSR_FULL && kind != NLPS_BSR_UPPER) {
+    h->err = std::string(who) + ": kind " + std::to_string(kind) + " is neither NLPS_BSR_FULL (0) nor NLPS_BSR_UPPER (1)";
+    return 1;
+  }
+  if (kind == NLPS_BSR_UPPER && h->uniform_law != NLPS_MAT_NEO_HOOKEAN) {
+    // (the rule of the atomic path's half rows: nlps_gpu_tangent_assemble)
+    static const char* const names[] = {"Neo-Hookean", "Hencky", "Drucker-Prager", "Von-Mises", "Matsuoka-Nakai / Lade-Duncan",
+                                        "Newtonian-Fluid-Compressible"};
+    std::string laws;
+    for (int k = 1; k <= NLPS_KLAW_FLUID; k++)
+      if (h->law_present & (1 << k)) laws += (laws.empty() ? "" : ", ") + std::string(names[k]);
+    h->err = std::string(who) + ": NLPS_BSR_UPPER needs a symmetric tangent, which only a cloud of Neo-Hookean particles "
+             "has; this cloud holds " + (laws.empty() ? "no material" : laws) + " (use NLPS_BSR_FULL)";
+    return 1;
+  }
+  const int ND = h->nd, nn = h->g.nnodes, na = h->nactive;
+  if (bytes) *bytes = tanbsr_bytes(ND, (size_t)h->top_np, (size_t)nn, (size_t)na);
+  if (tancsr_records(h, who)) return 1;
+  h->bsr_blocks = h->csr_blocks;  // (every block: the counts and offsets of the CSR pattern serve as they stand)
+  h->bsr_half = false;
+  if (h->csr_blocks > 0) {
+    // [0, N_A]: the counts of the upper block rows; [N_A + 1]: some row's upper blocks are not its offsets >= 0
+    if (reserve(h, who, h->bsr_cnt, (size_t)na + 2, "the block counts")) return 1;
+    if (reserve(h, who, h->bsr_off, (size_t)na + 1, "the block offsets")) return 1;
+  }
+  if (h->csr_blocks > 0 && kind == NLPS_BSR_UPPER) {
+    size_t scan_bytes = 0;
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, h->bsr_cnt.get(), h->bsr_off.get(), na + 1, h->stream));
+    DevBuf<char> scan_own;  // (the sort's workspace serves the scan; one of this call only where it is too small)
+    void* scan_tmp = h->cub_tmp.get();
+    if (scan_bytes > h->cub_tmp_bytes) {
+      if (reserve(h, who, scan_own, scan_bytes + 16, "the scan")) return 1;
+      scan_tmp = scan_own.get();
+    }
+    HIPCHK(hipMemsetAsync(h->bsr_cnt, 0, ((size_t)na + 2) * sizeof(int), h->stream));
+    LAUNCH_ND((k_tanbsr_count<2>), (k_tanbsr_count<3>), (nn + 3) / 4, h->g, (const unsigned long long*)h->csr_mask,
+              (const int*)h->n2m_d, h->bsr_cnt.get(), h->bsr_cnt.get() + na + 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, h->bsr_cnt.get(), h->bsr_off.get(), na + 1, h->stream));
+    int total = 0, mixed = 0;
+    HIPCHK(hipMemcpyAsync(&total, h->bsr_off + na, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&mixed, h->bsr_cnt + na + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->bsr_blocks = total;
+    h->bsr_half = !mixed;
+  }
+  if (nblocks) *nblocks = h->bsr_blocks;
+  if (h->bsr_blocks > (long long)INT_MAX) {
+    char buf[200];
+    snprintf(buf, sizeof buf, "%s: nblocks = %lld does not fit the int brow_ptr and bcols of the arrays (INT_MAX = %d)", who,
+             h->bsr_blocks, INT_MAX);
+    h->err = buf;
+    return 1;
+  }
+  h->bsr_kind = kind;
+  h->bsr_serial = h->top_serial;
+  return 0;
+}
+
+extern "C" int nlps_gpu_tangent_bsr(nlps_gpu* h, int col_major, int* brow_ptr, int* bcols, double* vals) {
+  const char* who = "nlps_gpu_tangent_bsr";
+  if (tanop_valid(h, who)) return 1;
+  if (tancsr_one_rank(h, who)) return 1;
+  if (h->bsr_serial == 0 || h->bsr_serial != h->top_serial) {
+    h->err = std::string(who) + ": call nlps_gpu_tangent_bsr_pattern() after nlps_gpu_tangent_operator() first";
+    return 1;
+  }
+  const int ND = h->nd, E = ND * ND, nn = h->g.nnodes, na = h->nactive;
+  const size_t nr = (size_t)na + 1, nb = (size_t)h->bsr_blocks;
+  if (!brow_ptr || (nb > 0 && (!bcols || !vals))) {
+    h->err = std::string(who) + ": brow_ptr, bcols and vals are required";
+    return 1;
+  }
+  if (nb == 0) {
+    if (is_device_ptr(brow_ptr)) {
+      HIPCHK(hipMemsetAsync(brow_ptr, 0, nr * sizeof(int), h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+    } else {
+      memset(brow_ptr, 0, nr * sizeof(int));
+    }
+    return 0;
+  }
+  const bool dev = is_device_ptr(brow_ptr) && is_device_ptr(bcols) && is_device_ptr(vals);
+  DevBuf<int> cols_d;  // staging of host destinations, of this call only
+  DevBuf<double> vals_d;
+  int* cp = bcols;
+  double* vp = vals;
+  if (!dev) {
+    if (reserve(h, who, cols_d, nb, "the staging of bcols") || reserve(h, who, vals_d, nb * E, "the staging of vals")) return 1;
+    cp = cols_d.get();
+    vp = vals_d.get();
+  }
+  const int* d2m = h->top_dir ? (const int*)h->d2m_d : nullptr;
+  const double* aM = h->top_mass ? (const double*)h->top_m : nullptr;
+  const int upper = h->bsr_kind == NLPS_BSR_UPPER ? 1 : 0, nt = ND == 3 ? CsrCfg<3>::NT : CsrCfg<2>::NT;
+  const int* cnt = upper ? (const int*)h->bsr_cnt : (const int*)h->csr_cnt;
+  const int* off = upper ? (const int*)h->bsr_off : (const int*)h->csr_off;
+#define TANBSR_ROWS(HALF)                                                                                                   \
+  LAUNCH_ND_BLK((k_tanbsr_rows<2, HALF>), (k_tanbsr_rows<3, HALF>), nn, nt, h->g, (const int*)h->csr_run,                   \
+                (const double*)h->csr_e, (const double*)h->csr_f, (const unsigned long long*)h->csr_mk,                     \
+                (const unsigned long long*)h->csr_mask, (const int*)h->n2m_d, d2m, aM, cnt, off, upper,                     \
+                col_major ? 1 : 0, cp, vp)
+  if (h->bsr_half)
+    TANBSR_ROWS(true);
+  else
+    TANBSR_ROWS(false);
+#undef TANBSR_ROWS
+  HIPCHK(hipGetLastError());
+  // brow_ptr is the scan of the block counts as it stands
+  HIPCHK(hipMemcpyAsync(brow_ptr, off, nr * sizeof(int), hipMemcpyDefault, h->stream));
+  if (!dev) {
+    HIPCHK(hipMemcpyAsync(bcols, cp, nb * sizeof(int), hipMemcpyDefault, h->stream));
+    HIPCHK(hipMemcpyAsync(vals, vp, nb * E * sizeof(double), hipMemcpyDefault, h->stream));
   }
   HIPCHK(hipStreamSynchronize(h->stream));  // (the copies land in the caller's memory before the staging goes)
   return 0;

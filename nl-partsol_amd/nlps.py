@@ -128,6 +128,7 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_tangent_block_diagonal", "nlps_gpu_tangent_solve", "nlps_gpu_tangent_lambda_max",
            "nlps_host_critical_dt", "nlps_gpu_newton_solve", "nlps_gpu_newmark_step",
            "nlps_gpu_tangent_csr_pattern", "nlps_gpu_tangent_csr",
+           "nlps_gpu_tangent_bsr_pattern", "nlps_gpu_tangent_bsr",
            "nlps_gpu_migration_select", "nlps_gpu_migration_commit", "nlps_gpu_num_particles",
            "nlps_gpu_set_particle_ids", "nlps_gpu_download_ids",
            "nlps_gpu_set_timing", "nlps_gpu_get_timing", "nlps_host_stencil_tables",
@@ -204,6 +205,9 @@ def lib():
         if hasattr(L, "nlps_gpu_tangent_csr"):  # (NLPS_GPU_LIB may name an older build: tools/tangent_csr_bench.py)
             L.nlps_gpu_tangent_csr_pattern.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_size_t)]
             L.nlps_gpu_tangent_csr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "nlps_gpu_tangent_bsr"):  # (the same hook: tools/tangent_bsr_bench.py)
+            L.nlps_gpu_tangent_bsr_pattern.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_size_t)]
+            L.nlps_gpu_tangent_bsr.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nlps_gpu_migration_select.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_void_p)]
         L.nlps_gpu_migration_commit.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -929,6 +933,34 @@ class Solver:
             row_ptr, cols, vals = np.zeros(nr, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n)
         self._chk(self.L.nlps_gpu_tangent_csr(self.h, _vp(row_ptr), _vp(cols), _vp(vals)))
         return row_ptr, cols, vals
+
+    def tangent_bsr_pattern(self, kind="full"):
+        """The block structure of the tangent of the last tangent_operator, for tangent_bsr
+        (nlps_gpu_tangent_bsr_pattern).  kind: "full" (every d x d block, MATSEQBAIJ) or "upper" (the blocks B >= A of a
+        Neo-Hookean cloud's symmetric tangent, MATSEQSBAIJ).  Returns (nblocks, bytes): the stored blocks and the device
+        bytes the CSR / block-CSR path keeps on the handle."""
+        kinds = {"full": 0, "upper": 1}
+        nblk, nb = C.c_longlong(0), C.c_size_t(0)
+        self._chk(self.L.nlps_gpu_tangent_bsr_pattern(self.h, kinds.get(kind, kind), C.byref(nblk), C.byref(nb)))
+        self._bsr_nblocks = int(nblk.value)
+        return self._bsr_nblocks, int(nb.value)
+
+    def tangent_bsr(self, col_major=False, on_device=False):
+        """(brow_ptr, bcols, vals) of the tangent of the last tangent_operator in block CSR, masked node numbering, bcols
+        ascending in every block row, vals shaped (nblocks, ndim, ndim) (nlps_gpu_tangent_bsr; what
+        MatCreateSeqBAIJWithArrays / MatCreateSeqSBAIJWithArrays take).  The values are the bits of tangent_csr's.
+        col_major: vals[q] holds the transposed block (PETSc's Fortran-ordered blocks).  Needs tangent_bsr_pattern()
+        since the operator.  on_device: torch tensors on the GPU, written by the row kernel itself."""
+        n, nr, d = getattr(self, "_bsr_nblocks", 0), self.nactive + 1, self.ndim
+        if on_device:
+            import torch
+            brow_ptr = torch.empty(nr, dtype=torch.int32, device="cuda")
+            bcols = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
+            vals = torch.empty((max(n, 1), d, d), dtype=torch.float64, device="cuda")[:n]
+        else:
+            brow_ptr, bcols, vals = np.zeros(nr, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros((n, d, d))
+        self._chk(self.L.nlps_gpu_tangent_bsr(self.h, 1 if col_major else 0, _vp(brow_ptr), _vp(bcols), _vp(vals)))
+        return brow_ptr, bcols, vals
 
     def tangent_solve(self, b, x=None, pc="pbjacobi", restart=30, max_it=10000, rtol=1e-5, atol=0.0, dtol=1e5,
                       history=False, out=None):
