@@ -692,6 +692,7 @@ enum {
   NLPS_KSP_DIVERGED_ITS = -3,       /* max_it steps without convergence */
   NLPS_KSP_DIVERGED_DTOL = -4,      /* ||b - K x|| > dtol ||b|| */
   NLPS_KSP_DIVERGED_BREAKDOWN = -5, /* the Hessenberg matrix is singular (K M^-1 singular on the Krylov space) */
+  NLPS_KSP_DIVERGED_INDEFINITE_PC = -8, /* MINRES only: v . M^-1 v < 0 (<= 0 at r0), M^-1 is not positive definite */
   NLPS_KSP_DIVERGED_NANORINF = -9   /* a non-finite value: x is the one of the last finished cycle */
 };
 #define NLPS_KSP_MAX_RESTART 256
@@ -711,6 +712,54 @@ typedef struct {
   size_t bytes;   /* device workspace this solve holds, by the formula above */
 } nlps_ksp;
 int nlps_gpu_tangent_solve(nlps_gpu *h, const double *b, double *x, nlps_ksp *ksp);
+
+/* nlps_gpu_set_linear_solver: which Krylov method nlps_gpu_tangent_solve runs on this handle, and with it
+ * nlps_gpu_newton_solve and nlps_gpu_newmark_step, which call it.  NLPS_KSP_TYPE_GMRES (the default) is the solve above,
+ * unchanged.  NLPS_KSP_TYPE_MINRES is a preconditioned MINRES for a SYMMETRIC tangent: a short recurrence, one product
+ * per step, no basis and no restart, and no need for K to be positive definite (the Neo-Hookean tangent at a general
+ * Newton iterate is not).  The setter returns 1, names the cloud's laws in nlps_gpu_last_error and leaves the handle on
+ * its previous solver unless every particle is Neo-Hookean (the rule of NLPS_BSR_UPPER; damage, alpha_1 M and the
+ * Dirichlet choice keep K symmetric); it also returns 1 for a type other than the two.
+ * With MINRES selected ksp->restart is not read; pc, max_it, x_is_guess, rtol, atol, dtol, history, reason, iterations,
+ * rnorm, bnorm and bytes mean what they mean for GMRES, and the call refuses what the GMRES form refuses (no operator, a
+ * stale operator, a halo callback or an RCCL world > 1, missing arguments, negative tolerances), with the same messages.
+ * M^-1 is none, the reciprocal diagonal or the inverted diagonal blocks of the GMRES form (built once per linearisation
+ * and shared with it); it must be positive definite.  tol = max(rtol ||b||, atol).  The algorithm:
+ *
+ *   x = x0 (0 unless x_is_guess);  r0 = b - K x (no product for x0 = 0);  rnorm = ||r0||;  history[0] = rnorm
+ *   ahead of the first step, in GMRES's order: ||b|| == 0 -> BZERO, x = 0;  non-finite -> NANORINF;  rnorm <= tol ->
+ *     ATOL / RTOL;  rnorm > dtol ||b|| -> DTOL;  max_it == 0 -> ITS
+ *   v_prev = 0, v = r0, z = M^-1 v, g = sqrt(v.z)  (v.z <= 0: INDEFINITE_PC, not finite: NANORINF, 0 iterations)
+ *   g_prev = 1, eta = g, scale = rnorm / g, c_prev = c = 1, s_prev = s = 0, w_prev = w = 0
+ *   step k = 1, 2, ...:
+ *     q = z / g;  p = K q;  d = p.q
+ *     v_new = p - (d / g) v - (g / g_prev) v_prev;   z_new = M^-1 v_new;   gg = v_new.z_new
+ *     gg < 0 -> INDEFINITE_PC;  d, gg not finite -> NANORINF   (in both the step's update of x is NOT applied)
+ *     g_new = sqrt(gg)
+ *     a0 = c d - c_prev s g;  a1 = sqrt(a0^2 + gg);  a2 = s d + c_prev c g;  a3 = s_prev g
+ *     a1 == 0 -> BREAKDOWN (no update)
+ *     (c_prev, c) = (c, a0 / a1);  (s_prev, s) = (s, g_new / a1)
+ *     w_new = (q - a3 w_prev - a2 w) / a1;   x += c eta w_new;   eta = -s eta
+ *     shift (v_prev, v, z, g_prev, g, w_prev, w);   iterations = k;   est = scale |eta|;   history[k] = est
+ *     est not finite -> NANORINF
+ *     if est <= tol or k == max_it or g_new == 0:           -- confirmation, one product, read-only for the recurrence
+ *        rnorm = ||b - K x||;  not finite -> NANORINF;  rnorm <= tol -> ATOL (rnorm < atol) / RTOL;
+ *        rnorm > dtol ||b|| -> DTOL;  k == max_it -> ITS;  g_new == 0 -> BREAKDOWN;
+ *        otherwise scale = rnorm / |eta| and the SAME recurrence goes on
+ *
+ * est is the preconditioned residual norm ||r||_{M^-1}, which MINRES minimises and which never grows, calibrated to the
+ * true norm at r0 and at every confirmation that did not end the solve (the history steps up there).  The recurrence is never restarted.  ksp->rnorm
+ * is always the true residual ||b - K x|| of the returned x, from one product, also where a step ends the solve without a
+ * confirmation (INDEFINITE_PC, BREAKDOWN and NANORINF inside a step); iterations counts the steps whose update x holds.
+ * One host wait per step and one per confirmation; the rotation's coefficients stay on the device.
+ * bytes = 8 * (7 n + nb + nbn + 16 + [pc] N_A d^2) with n = N_A d, nb = ceil(n / 512) and nbn = ceil(N_A / 256): two
+ *   Lanczos vectors, z, q, p, two direction vectors, the per-block partial sums of the element and of the node kernels,
+ *   the rotation state and the preconditioner.  The buffers are the ones of the GMRES form (shared, kept on the handle
+ *   and only grown): for the same n less than GMRES(restart) from restart = 5 on.
+ * Every sum is taken over per-block partials in a fixed order (no float atomics of its own): in deterministic mode
+ * (nlps_gpu_set_deterministic) a solve repeats bit for bit. */
+enum { NLPS_KSP_TYPE_GMRES = 0, NLPS_KSP_TYPE_MINRES = 1 };
+int nlps_gpu_set_linear_solver(nlps_gpu *h, int type);
 
 /* nlps_gpu_tangent_lambda_max: the largest Ritz value theta of the pencil (K, M) on the free dofs, by Lanczos on the
  * device -- the omega_max^2 that bounds the explicit step's stable dt (nlps_host_critical_dt), where the deck's

@@ -1522,6 +1522,7 @@ __global__ __launch_bounds__(BLK) void k_fill_orders(int np, const int* __restri
 #include "nlps_tangent_csr.hpp"
 #include "nlps_tangent_bsr.hpp"
 #include "nlps_krylov.hpp"
+#include "nlps_minres.hpp"
 #include "nlps_eigen.hpp"
 #include "nlps_newton.hpp"
 #include "nlps_record.hpp"
@@ -1961,6 +1962,7 @@ struct nlps_gpu {
   // ksp_pc was built from.
   unsigned long long top_serial = 0, ksp_pc_serial = 0;
   int ksp_pc_kind = -1;
+  int ksp_type = NLPS_KSP_TYPE_GMRES;  // nlps_gpu_set_linear_solver: which Krylov method nlps_gpu_tangent_solve runs
   DevBuf<double> ksp_pc;    // [N_A d^2]: the inverted blocks (PBJACOBI) or reciprocals on the block diagonals (JACOBI)
   DevBuf<double> ksp_v;     // [(m + 3) n]: the basis V[0..m], z = M^-1 v, t = K x
   DevBuf<double> ksp_part;  // [(m + 2) nb]: per-block partial sums
@@ -6685,6 +6687,170 @@ static int ksp_pc_build(nlps_gpu* h, int kind) {
   return 0;
 }
 
+static size_t minres_nbn(size_t nA) { return (nA + KSP_NT - 1) / KSP_NT; }
+
+// nlps_gpu_tangent_solve with NLPS_KSP_TYPE_MINRES (nlps_minres.hpp), after the checks the two solvers share: the
+// algorithm of include/nlps_gpu.h, one host wait per step (|eta| and the flags) and one per confirmation
+static int minres_solve(nlps_gpu* h, VecIO& io, const double* b, double* x, nlps_ksp* ksp) {
+  const char* who = "nlps_gpu_tangent_solve";
+  const size_t n = io.n;
+  const int ND = h->nd, nA = h->nactive, kind = ksp->pc, max_it = ksp->max_it;
+  const int nb = (int)((n + KSP_TILE - 1) / KSP_TILE), nbn = (int)minres_nbn((size_t)nA);
+  ksp->bytes = sizeof(double) * ((size_t)7 * n + (size_t)nb + (size_t)nbn + MINRES_SMALL +
+                                 (kind != NLPS_PC_NONE ? (size_t)nA * ND * ND : 0));
+  double* hist = ksp->history;
+  if (n == 0) {
+    ksp->reason = NLPS_KSP_CONVERGED_BZERO;
+    if (hist) hist[0] = 0.0;
+    return 0;
+  }
+  if (reserve(h, who, h->ksp_v, (size_t)7 * n, "the MINRES vectors") ||
+      reserve(h, who, h->ksp_part, (size_t)nb + nbn, "the partial sums") ||
+      reserve(h, who, h->ksp_s, (size_t)MINRES_SMALL, "the rotation state"))
+    return 1;
+  if (!h->ksp_h.host()) {
+    HIPCHK(h->ksp_h.alloc());
+    memset(h->ksp_h.host(), 0, sizeof(KspHost));
+  }
+  if (ksp_pc_build(h, kind)) return 1;
+  const double* bd = io.in(b);
+  double* xd = io.out(x, ksp->x_is_guess != 0);
+  double* const base = h->ksp_v;
+  double *vp = base, *v = base + n, *wp = base + 2 * n, *w = base + 3 * n;  // (the pairs that rotate)
+  double *const z = base + 4 * n, *const q = base + 5 * n, *const p = base + 6 * n;
+  double* const part = h->ksp_part;    // [nb]: p . q and the residual norms
+  double* const partn = part + nb;     // [nbn]: v_new . z
+  double* const s = h->ksp_s;
+  const double* const Minv = h->ksp_pc;
+  KspHost* const hw = h->ksp_h.target();
+  const dim3 gs(nb), gn(nbn), bs(KSP_NT);
+  const double* const nul = nullptr;
+  double* const nulw = nullptr;
+  // rn2 of the host word = ||b - K x||^2 of the current x, through p
+  auto true_residual = [&](double* rnorm) -> int {
+    if (tanop_product(h, xd, p, nullptr)) return 1;
+    hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, (const double*)p, nulw, part);
+    hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, nulw, &hw->rn2, nul, nulw, nul);
+    HIPCHK(hipGetLastError());
+    if (ksp_wait(h)) return 1;
+    *rnorm = sqrt(h->ksp_h.host()->rn2);
+    return 0;
+  };
+  // ||b|| and r0 = b - K x0 into v
+  hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, nul, nulw, part);
+  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, nulw, &hw->bn2, nul, nulw, nul);
+  if (ksp->x_is_guess) {
+    if (tanop_product(h, xd, p, nullptr)) return 1;
+    hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, (const double*)p, v, part);
+  } else {
+    HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(double), h->stream));
+    hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, nul, v, part);
+  }
+  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, nulw, &hw->rn2, nul, nulw, nul);
+  HIPCHK(hipGetLastError());
+  if (ksp_wait(h)) return 1;
+  const double bnorm = sqrt(h->ksp_h.host()->bn2);
+  double rnorm = sqrt(h->ksp_h.host()->rn2);
+  const double tol = std::max(ksp->rtol * bnorm, ksp->atol);
+  if (hist) hist[0] = rnorm;
+  int its = 0, reason = 0;
+  if (bnorm == 0.0) {  // x = 0 (also over a guess), as KSPSolve
+    HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(double), h->stream));
+    rnorm = 0.0;
+    if (hist) hist[0] = 0.0;
+    reason = NLPS_KSP_CONVERGED_BZERO;
+  } else if (!std::isfinite(rnorm) || !std::isfinite(bnorm)) reason = NLPS_KSP_DIVERGED_NANORINF;
+  else if (rnorm <= tol) reason = rnorm < ksp->atol ? NLPS_KSP_CONVERGED_ATOL : NLPS_KSP_CONVERGED_RTOL;
+  else if (rnorm > ksp->dtol * bnorm) reason = NLPS_KSP_DIVERGED_DTOL;
+  else if (max_it == 0) reason = NLPS_KSP_DIVERGED_ITS;
+  double scale = 0.0;
+  if (!reason) {  // z = M^-1 r0, g = sqrt(r0 . z), q = z / g; v_prev = w_prev = w = 0
+    HIPCHK(hipMemsetAsync(vp, 0, n * sizeof(double), h->stream));
+    HIPCHK(hipMemsetAsync(wp, 0, 2 * n * sizeof(double), h->stream));
+    LAUNCH_ND_BLK((k_minres_lanczos<2>), (k_minres_lanczos<3>), nbn, KSP_NT, nA, kind, Minv, 1, (const double*)v,
+                  (const double*)v, vp, z, (const double*)part, nb, s, partn);
+    hipLaunchKernelGGL(k_minres_rotate, dim3(1), dim3(64), 0, h->stream, 1, (const double*)partn, nbn, s, hw);
+    hipLaunchKernelGGL(k_minres_update, gs, bs, 0, h->stream, (int)n, 1, (const double*)s, (const double*)z, q, wp,
+                       (const double*)w, xd);
+    HIPCHK(hipGetLastError());
+    if (ksp_wait(h)) return 1;
+    const int flags = h->ksp_h.host()->flags;
+    if (flags & MINRES_FLAG_INDEFINITE) reason = NLPS_KSP_DIVERGED_INDEFINITE_PC;
+    else if (flags & KSP_FLAG_NONFINITE) reason = NLPS_KSP_DIVERGED_NANORINF;
+    else scale = rnorm / h->ksp_h.host()->est;
+  }
+  while (!reason) {
+    if (tanop_product(h, q, p, nullptr)) return 1;
+    hipLaunchKernelGGL(k_minres_dot, gs, bs, 0, h->stream, (int)n, (const double*)p, (const double*)q, part);
+    LAUNCH_ND_BLK((k_minres_lanczos<2>), (k_minres_lanczos<3>), nbn, KSP_NT, nA, kind, Minv, 0, (const double*)p,
+                  (const double*)v, vp, z, (const double*)part, nb, s, partn);
+    hipLaunchKernelGGL(k_minres_rotate, dim3(1), dim3(64), 0, h->stream, 0, (const double*)partn, nbn, s, hw);
+    hipLaunchKernelGGL(k_minres_update, gs, bs, 0, h->stream, (int)n, 0, (const double*)s, (const double*)z, q, wp,
+                       (const double*)w, xd);
+    HIPCHK(hipGetLastError());
+    if (ksp_wait(h)) return 1;
+    const int flags = h->ksp_h.host()->flags;
+    const double eta = h->ksp_h.host()->est;  // (|eta|: the estimate is scale |eta|)
+    if (flags & (MINRES_FLAG_INDEFINITE | KSP_FLAG_NONFINITE | KSP_FLAG_SINGULAR)) {  // (x is the one of step its)
+      reason = (flags & MINRES_FLAG_INDEFINITE) ? NLPS_KSP_DIVERGED_INDEFINITE_PC
+               : (flags & KSP_FLAG_NONFINITE)   ? NLPS_KSP_DIVERGED_NANORINF
+                                                : NLPS_KSP_DIVERGED_BREAKDOWN;
+      if (true_residual(&rnorm)) return 1;
+      break;
+    }
+    std::swap(vp, v);  // (v_new and w_new were written over v_prev and w_prev)
+    std::swap(wp, w);
+    its++;
+    const double est = scale * eta;
+    if (hist) hist[its] = est;
+    if (!std::isfinite(est)) {
+      reason = NLPS_KSP_DIVERGED_NANORINF;
+      if (true_residual(&rnorm)) return 1;
+      break;
+    }
+    const bool gzero = (flags & MINRES_FLAG_GZERO) != 0;
+    if (est <= tol || its >= max_it || gzero) {  // the confirmation: read-only for the recurrence
+      if (true_residual(&rnorm)) return 1;
+      if (!std::isfinite(rnorm)) reason = NLPS_KSP_DIVERGED_NANORINF;
+      else if (rnorm <= tol) reason = rnorm < ksp->atol ? NLPS_KSP_CONVERGED_ATOL : NLPS_KSP_CONVERGED_RTOL;
+      else if (rnorm > ksp->dtol * bnorm) reason = NLPS_KSP_DIVERGED_DTOL;
+      else if (its >= max_it) reason = NLPS_KSP_DIVERGED_ITS;
+      else if (gzero) reason = NLPS_KSP_DIVERGED_BREAKDOWN;
+      else scale = rnorm / eta;
+    }
+  }
+  ksp->reason = reason;
+  ksp->iterations = its;
+  ksp->rnorm = rnorm;
+  ksp->bnorm = bnorm;
+  if (io.finish()) {
+    h->err = "nlps_gpu_tangent_solve: HIP error";
+    return 1;
+  }
+  if (io.back.empty()) HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int nlps_gpu_set_linear_solver(nlps_gpu* h, int type) {
+  const char* who = "nlps_gpu_set_linear_solver";
+  if (type != NLPS_KSP_TYPE_GMRES && type != NLPS_KSP_TYPE_MINRES) {
+    h->err = std::string(who) + ": type " + std::to_string(type) + " is neither NLPS_KSP_TYPE_GMRES (0) nor NLPS_KSP_TYPE_MINRES (1)";
+    return 1;
+  }
+  if (type == NLPS_KSP_TYPE_MINRES && h->uniform_law != NLPS_MAT_NEO_HOOKEAN) {  // (the rule of NLPS_BSR_UPPER)
+    static const char* const names[] = {"Neo-Hookean", "Hencky", "Drucker-Prager", "Von-Mises", "Matsuoka-Nakai / Lade-Duncan",
+                                        "Newtonian-Fluid-Compressible"};
+    std::string laws;
+    for (int k = 0; k <= NLPS_KLAW_FLUID; k++)
+      if (h->law_present & (1 << k)) laws += (laws.empty() ? "" : ", ") + std::string(names[k]);
+    h->err = std::string(who) + ": NLPS_KSP_TYPE_MINRES needs a symmetric tangent, which only a cloud of Neo-Hookean particles "
+             "has; this cloud holds " + (laws.empty() ? "no material" : laws) + " (the handle stays on its previous solver)";
+    return 1;
+  }
+  h->ksp_type = type;
+  return 0;
+}
+
 extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, nlps_ksp* ksp) {
   const char* who = "nlps_gpu_tangent_solve";
   if (!ksp) {
@@ -6710,7 +6876,8 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
     h->err = "nlps_gpu_tangent_solve: pc must be NLPS_PC_NONE, NLPS_PC_JACOBI or NLPS_PC_PBJACOBI";
     return 1;
   }
-  if (m < 1 || m > NLPS_KSP_MAX_RESTART || max_it < 0) {
+  const bool minres = h->ksp_type == NLPS_KSP_TYPE_MINRES;  // (restart is not read)
+  if ((!minres && (m < 1 || m > NLPS_KSP_MAX_RESTART)) || max_it < 0) {
     h->err = "nlps_gpu_tangent_solve: restart must be 1 .. NLPS_KSP_MAX_RESTART and max_it >= 0";
     return 1;
   }
@@ -6720,6 +6887,7 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
   }
   VecIO io;
   if (vec_begin(h, who, io)) return 1;
+  if (minres) return minres_solve(h, io, b, x, ksp);
   const size_t n = io.n;
   const int ND = h->nd, nA = h->nactive, nb = (int)((n + KSP_TILE - 1) / KSP_TILE);
   const KspSmall L{m};

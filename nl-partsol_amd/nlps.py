@@ -72,7 +72,8 @@ class Eig(C.Structure):  # nlps_eig: nlps_gpu_tangent_lambda_max's settings and 
 EIG_REASONS = {1: "converged", 2: "empty", -3: "diverged_its", -9: "diverged_nanorinf"}  # NLPS_EIG_*
 PC_KINDS = {"none": 0, "jacobi": 1, "pbjacobi": 2}  # NLPS_PC_NONE / _JACOBI / _PBJACOBI
 KSP_REASONS = {1: "converged_bzero", 2: "converged_rtol", 3: "converged_atol", -3: "diverged_its", -4: "diverged_dtol",
-               -5: "diverged_breakdown", -9: "diverged_nanorinf"}
+               -5: "diverged_breakdown", -8: "diverged_indefinite_pc", -9: "diverged_nanorinf"}
+KSP_TYPES = {"gmres": 0, "minres": 1}  # NLPS_KSP_TYPE_GMRES / _MINRES
 
 
 class Snes(C.Structure):  # nlps_snes: nlps_gpu_newton_solve's settings and results
@@ -125,7 +126,8 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_form_initial_guess", "nlps_gpu_nodal_kinetic_increments", "nlps_gpu_nodal_inertial_forces",
            "nlps_gpu_tangent_assemble", "nlps_gpu_tangent_set_grouped", "nlps_gpu_set_tangent_alpha4", "nlps_gpu_tangent_coo",
            "nlps_gpu_sparsity_pattern", "nlps_gpu_tangent_operator", "nlps_gpu_tangent_apply",
-           "nlps_gpu_tangent_block_diagonal", "nlps_gpu_tangent_solve", "nlps_gpu_tangent_lambda_max",
+           "nlps_gpu_tangent_block_diagonal", "nlps_gpu_tangent_solve", "nlps_gpu_set_linear_solver",
+           "nlps_gpu_tangent_lambda_max",
            "nlps_host_critical_dt", "nlps_gpu_newton_solve", "nlps_gpu_newmark_step",
            "nlps_gpu_tangent_csr_pattern", "nlps_gpu_tangent_csr",
            "nlps_gpu_tangent_bsr_pattern", "nlps_gpu_tangent_bsr",
@@ -160,6 +162,8 @@ def lib():
         L.nlps_gpu_set_law_launch_mode.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_set_deterministic.argtypes = [C.c_void_p, C.c_int]
         L.nlps_gpu_set_explicit_damage.argtypes = [C.c_void_p, C.c_int]
+        if hasattr(L, "nlps_gpu_set_linear_solver"):  # (NLPS_GPU_LIB may name an older build)
+            L.nlps_gpu_set_linear_solver.argtypes = [C.c_void_p, C.c_int]
         if hasattr(L, "nlps_gpu_set_explicit_fluid"):  # (NLPS_GPU_LIB may name an older build: tools/explicit_fluid_bench.py)
             L.nlps_gpu_set_explicit_fluid.argtypes = [C.c_void_p, C.c_int]
         if hasattr(L, "nlps_gpu_set_explicit_loads"):  # (NLPS_GPU_LIB may name an older build)
@@ -962,9 +966,18 @@ class Solver:
         self._chk(self.L.nlps_gpu_tangent_bsr(self.h, 1 if col_major else 0, _vp(brow_ptr), _vp(bcols), _vp(vals)))
         return brow_ptr, bcols, vals
 
+    def set_linear_solver(self, kind):
+        """The Krylov method of tangent_solve, newton_solve and newmark_step on this handle: "gmres" (the default) or
+        "minres" (symmetric tangents: refused, naming the laws, unless every particle is Neo-Hookean)."""
+        if kind not in KSP_TYPES:
+            raise ValueError(f"kind must be one of {sorted(KSP_TYPES)}")
+        self._chk(self.L.nlps_gpu_set_linear_solver(self.h, KSP_TYPES[kind]))
+
     def tangent_solve(self, b, x=None, pc="pbjacobi", restart=30, max_it=10000, rtol=1e-5, atol=0.0, dtol=1e5,
                       history=False, out=None):
-        """K x = b on the device by GMRES(restart), right-preconditioned (nlps_gpu_tangent_solve; the driver's KSPSolve).
+        """K x = b on the device by GMRES(restart), right-preconditioned (nlps_gpu_tangent_solve; the driver's KSPSolve),
+        or, after set_linear_solver("minres") on a Neo-Hookean cloud, by preconditioned MINRES (restart is then not read;
+        reason may be -8, diverged_indefinite_pc).
         b: numpy array (host) or torch tensor (device), masked [nactive*ndim]; the result is of the same kind.  x: an
         initial guess (left as it is unless it is also out), None for x0 = 0.  out: the vector to write (default: a new
         one).  pc: "none", "jacobi" or "pbjacobi".  Returns (x, info), info = dict(iterations, reason (an NLPS_KSP_*
