@@ -6393,6 +6393,36 @@ static int tancsr_one_rank(nlps_gpu* h, const char* who) {
   return 0;
 }
 
+// off = the exclusive scan of the N_A + 1 counts cnt, *total = its last entry (synchronises).  The sort's workspace
+// serves the scan; one of this call only where it is too small
+static int tancsr_scan(nlps_gpu* h, const char* who, int* cnt, int* off, int* total) {
+  const int n = h->nactive + 1;
+  size_t bytes = 0;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, off, n, h->stream));
+  DevBuf<char> own;
+  void* tmp = h->cub_tmp.get();
+  if (bytes > h->cub_tmp_bytes) {
+    if (reserve(h, who, own, bytes + 16, "the scan")) {
+      (void)hipStreamSynchronize(h->stream);  // (a copy the caller queued into a variable of its own lands first)
+      return 1;
+    }
+    tmp = own.get();
+  }
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, cnt, off, n, h->stream));
+  HIPCHK(hipMemcpyAsync(total, off + n - 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// the row pointer and the indices of the arrays are int
+static int tancsr_fits_int(nlps_gpu* h, const char* who, const char* what, long long n, const char* arrays) {
+  if (n <= (long long)INT_MAX) return 0;
+  char buf[200];
+  snprintf(buf, sizeof buf, "%s: %s = %lld does not fit the int %s (INT_MAX = %d)", who, what, n, arrays, INT_MAX);
+  h->err = buf;
+  return 1;
+}
+
 // the records, runs, masks and block counts of the current linearisation, shared by the CSR and the block-CSR form:
 // built by the first pattern call of either kind since the operator (they depend on the linearisation alone)
 static int tancsr_records(nlps_gpu* h, const char* who) {
@@ -6409,10 +6439,6 @@ static int tancsr_records(nlps_gpu* h, const char* who) {
     if (reserve(h, who, h->csr_mask, (size_t)nn * mw, "the visited-offset masks")) return 1;
     if (reserve(h, who, h->csr_cnt, (size_t)na + 1, "the block counts")) return 1;
     if (reserve(h, who, h->csr_off, (size_t)na + 1, "the block offsets")) return 1;
-    DevBuf<char> scan_tmp;  // (of this call only)
-    size_t scan_bytes = 0;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, h->csr_cnt.get(), h->csr_off.get(), na + 1, h->stream));
-    if (reserve(h, who, scan_tmp, scan_bytes + 16, "the scan")) return 1;
     // particles grouped by closest node: the (I0, p) sort of the atomic assembly (a stable radix sort of slots in
     // ascending order, so a run holds its particles by ascending memory slot)
     hipLaunchKernelGGL(k_tangent_keys, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->P, h->skey_d, h->sval_d);
@@ -6428,9 +6454,8 @@ static int tancsr_records(nlps_gpu* h, const char* who) {
     LAUNCH_ND((k_tancsr_pattern<2>), (k_tancsr_pattern<3>), (nn + 3) / 4, h->g, (const int*)h->csr_run,
               (const unsigned long long*)h->csr_mk, (const int*)h->n2m_d, h->csr_mask.get(), h->csr_cnt.get());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(scan_tmp.get(), scan_bytes, h->csr_cnt.get(), h->csr_off.get(), na + 1, h->stream));
     int total = 0;
-    HIPCHK(hipMemcpyAsync(&total, h->csr_off + na, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (tancsr_scan(h, who, h->csr_cnt.get(), h->csr_off.get(), &total)) return 1;
     if (check_status(h, ST_NEWTON, (std::string(who) + "()").c_str())) return 1;  // (synchronises)
     h->csr_blocks = total;
   }
@@ -6448,68 +6473,92 @@ extern "C" int nlps_gpu_tangent_csr_pattern(nlps_gpu* h, long long* nnz, size_t*
   if (tancsr_records(h, who)) return 1;
   const long long n = h->csr_blocks * E;
   if (nnz) *nnz = n;
-  if (n > (long long)INT_MAX) {
-    char buf[200];
-    snprintf(buf, sizeof buf, "%s: nnz = %lld does not fit the int row_ptr and cols of the CSR arrays (INT_MAX = %d)", who, n,
-             INT_MAX);
-    h->err = buf;
+  if (tancsr_fits_int(h, who, "nnz", n, "row_ptr and cols of the CSR arrays")) return 1;
+  h->csr_serial = h->top_serial;
+  return 0;
+}
+
+// The three arrays of an assembled form as the caller gave them: the row pointer [nr], the indices [ni], the values
+// [nv].  Destinations on the device are written in place, host ones through staging of this call only.
+struct TanOut {
+  nlps_gpu* h;
+  int *row_ptr, *idx;
+  double* vals;
+  size_t nr, ni, nv;
+  bool dev = false;
+  DevBuf<int> row_d, idx_d;
+  DevBuf<double> vals_d;
+  int *rp = nullptr, *ip = nullptr;  // what the kernels write
+  double* vp = nullptr;
+  // after the caller's launches.  row_src: the device array that is the row pointer as it stands (nullptr: a kernel
+  // wrote rp)
+  int finish(const int* row_src) {
+    HIPCHK(hipGetLastError());
+    if (row_src || !dev) HIPCHK(hipMemcpyAsync(row_ptr, row_src ? row_src : rp, nr * sizeof(int), hipMemcpyDefault, h->stream));
+    if (!dev) {
+      HIPCHK(hipMemcpyAsync(idx, ip, ni * sizeof(int), hipMemcpyDefault, h->stream));
+      HIPCHK(hipMemcpyAsync(vals, vp, nv * sizeof(double), hipMemcpyDefault, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));  // (the copies land in the caller's memory before the staging goes)
+    return 0;
+  }
+};
+// Refuses the call (returns 1) or readies io for the launches.  serial: the pattern's, of the call `pattern`; rname and
+// iname: what the caller's header calls the row pointer and the indices; stage_row: a kernel writes the row pointer.
+// An empty matrix is finished here (the row pointer zeroed): the caller returns 0 where io.ni == 0.
+static int tanout_begin(nlps_gpu* h, const char* who, unsigned long long serial, const char* pattern, const char* rname,
+                        const char* iname, bool stage_row, TanOut& io) {
+  if (tanop_valid(h, who)) return 1;
+  if (tancsr_one_rank(h, who)) return 1;
+  if (serial == 0 || serial != h->top_serial) {
+    h->err = std::string(who) + ": call " + pattern + "() after nlps_gpu_tangent_operator() first";
     return 1;
   }
-  h->csr_serial = h->top_serial;
+  if (!io.row_ptr || (io.ni > 0 && (!io.idx || !io.vals))) {
+    h->err = std::string(who) + ": " + rname + ", " + iname + " and vals are required";
+    return 1;
+  }
+  if (io.ni == 0) {
+    if (is_device_ptr(io.row_ptr)) {
+      HIPCHK(hipMemsetAsync(io.row_ptr, 0, io.nr * sizeof(int), h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+    } else {
+      memset(io.row_ptr, 0, io.nr * sizeof(int));
+    }
+    return 0;
+  }
+  io.dev = is_device_ptr(io.row_ptr) && is_device_ptr(io.idx) && is_device_ptr(io.vals);
+  io.rp = io.row_ptr;
+  io.ip = io.idx;
+  io.vp = io.vals;
+  if (!io.dev) {
+    const std::string stage = "the staging of ";
+    if ((stage_row && reserve(h, who, io.row_d, io.nr, (stage + rname).c_str())) ||
+        reserve(h, who, io.idx_d, io.ni, (stage + iname).c_str()) || reserve(h, who, io.vals_d, io.nv, "the staging of vals"))
+      return 1;
+    io.rp = io.row_d.get();
+    io.ip = io.idx_d.get();
+    io.vp = io.vals_d.get();
+  }
   return 0;
 }
 
 extern "C" int nlps_gpu_tangent_csr(nlps_gpu* h, int* row_ptr, int* cols, double* vals) {
   const char* who = "nlps_gpu_tangent_csr";
-  if (tanop_valid(h, who)) return 1;
-  if (tancsr_one_rank(h, who)) return 1;
-  if (h->csr_serial == 0 || h->csr_serial != h->top_serial) {
-    h->err = std::string(who) + ": call nlps_gpu_tangent_csr_pattern() after nlps_gpu_tangent_operator() first";
-    return 1;
-  }
   const int ND = h->nd, E = ND * ND, nn = h->g.nnodes, na = h->nactive;
-  const size_t nr = (size_t)na * ND + 1, ne = (size_t)h->csr_blocks * E;
-  if (!row_ptr || (ne > 0 && (!cols || !vals))) {
-    h->err = std::string(who) + ": row_ptr, cols and vals are required";
-    return 1;
-  }
-  if (ne == 0) {
-    if (is_device_ptr(row_ptr)) {
-      HIPCHK(hipMemsetAsync(row_ptr, 0, nr * sizeof(int), h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));
-    } else {
-      memset(row_ptr, 0, nr * sizeof(int));
-    }
-    return 0;
-  }
-  const bool dev = is_device_ptr(row_ptr) && is_device_ptr(cols) && is_device_ptr(vals);
-  DevBuf<int> row_d, cols_d;  // staging of host destinations, of this call only
-  DevBuf<double> vals_d;
-  int *rp = row_ptr, *cp = cols;
-  double* vp = vals;
-  if (!dev) {
-    if (reserve(h, who, row_d, nr, "the staging of row_ptr") || reserve(h, who, cols_d, ne, "the staging of cols") ||
-        reserve(h, who, vals_d, ne, "the staging of vals"))
-      return 1;
-    rp = row_d.get();
-    cp = cols_d.get();
-    vp = vals_d.get();
-  }
-  LAUNCH_ND((k_tancsr_rowptr<2>), (k_tancsr_rowptr<3>), nblk((int)nr), na, (const int*)h->csr_cnt, (const int*)h->csr_off, rp);
+  const size_t ne = (size_t)h->csr_blocks * E;
+  TanOut io{h, row_ptr, cols, vals, (size_t)na * ND + 1, ne, ne};
+  if (tanout_begin(h, who, h->csr_serial, "nlps_gpu_tangent_csr_pattern", "row_ptr", "cols", true, io)) return 1;
+  if (ne == 0) return 0;
+  LAUNCH_ND((k_tancsr_rowptr<2>), (k_tancsr_rowptr<3>), nblk((int)io.nr), na, (const int*)h->csr_cnt, (const int*)h->csr_off,
+            io.rp);
   const int* d2m = h->top_dir ? (const int*)h->d2m_d : nullptr;
   const double* aM = h->top_mass ? (const double*)h->top_m : nullptr;
   LAUNCH_ND_BLK((k_tancsr_rows<2>), (k_tancsr_rows<3>), nn, (ND == 3 ? CsrCfg<3>::NT : CsrCfg<2>::NT), h->g,
                 (const int*)h->csr_run, (const double*)h->csr_e, (const double*)h->csr_f,
                 (const unsigned long long*)h->csr_mk, (const unsigned long long*)h->csr_mask, (const int*)h->n2m_d, d2m, aM, (const int*)h->csr_cnt,
-                (const int*)h->csr_off, cp, vp);
-  HIPCHK(hipGetLastError());
-  if (!dev) {
-    HIPCHK(hipMemcpyAsync(row_ptr, rp, nr * sizeof(int), hipMemcpyDefault, h->stream));
-    HIPCHK(hipMemcpyAsync(cols, cp, ne * sizeof(int), hipMemcpyDefault, h->stream));
-    HIPCHK(hipMemcpyAsync(vals, vp, ne * sizeof(double), hipMemcpyDefault, h->stream));
-  }
-  HIPCHK(hipStreamSynchronize(h->stream));  // (the copies land in the caller's memory before the staging goes)
-  return 0;
+                (const int*)h->csr_off, io.ip, io.vp);
+  return io.finish(nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -6550,34 +6599,18 @@ extern "C" int nlps_gpu_tangent_bsr_pattern(nlps_gpu* h, int kind, long long* nb
     if (reserve(h, who, h->bsr_off, (size_t)na + 1, "the block offsets")) return 1;
   }
   if (h->csr_blocks > 0 && kind == NLPS_BSR_UPPER) {
-    size_t scan_bytes = 0;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, h->bsr_cnt.get(), h->bsr_off.get(), na + 1, h->stream));
-    DevBuf<char> scan_own;  // (the sort's workspace serves the scan; one of this call only where it is too small)
-    void* scan_tmp = h->cub_tmp.get();
-    if (scan_bytes > h->cub_tmp_bytes) {
-      if (reserve(h, who, scan_own, scan_bytes + 16, "the scan")) return 1;
-      scan_tmp = scan_own.get();
-    }
     HIPCHK(hipMemsetAsync(h->bsr_cnt, 0, ((size_t)na + 2) * sizeof(int), h->stream));
     LAUNCH_ND((k_tanbsr_count<2>), (k_tanbsr_count<3>), (nn + 3) / 4, h->g, (const unsigned long long*)h->csr_mask,
               (const int*)h->n2m_d, h->bsr_cnt.get(), h->bsr_cnt.get() + na + 1);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, h->bsr_cnt.get(), h->bsr_off.get(), na + 1, h->stream));
     int total = 0, mixed = 0;
-    HIPCHK(hipMemcpyAsync(&total, h->bsr_off + na, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(&mixed, h->bsr_cnt + na + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if (tancsr_scan(h, who, h->bsr_cnt.get(), h->bsr_off.get(), &total)) return 1;
     h->bsr_blocks = total;
     h->bsr_half = !mixed;
   }
   if (nblocks) *nblocks = h->bsr_blocks;
-  if (h->bsr_blocks > (long long)INT_MAX) {
-    char buf[200];
-    snprintf(buf, sizeof buf, "%s: nblocks = %lld does not fit the int brow_ptr and bcols of the arrays (INT_MAX = %d)", who,
-             h->bsr_blocks, INT_MAX);
-    h->err = buf;
-    return 1;
-  }
+  if (tancsr_fits_int(h, who, "nblocks", h->bsr_blocks, "brow_ptr and bcols of the arrays")) return 1;
   h->bsr_kind = kind;
   h->bsr_serial = h->top_serial;
   return 0;
@@ -6585,37 +6618,11 @@ extern "C" int nlps_gpu_tangent_bsr_pattern(nlps_gpu* h, int kind, long long* nb
 
 extern "C" int nlps_gpu_tangent_bsr(nlps_gpu* h, int col_major, int* brow_ptr, int* bcols, double* vals) {
   const char* who = "nlps_gpu_tangent_bsr";
-  if (tanop_valid(h, who)) return 1;
-  if (tancsr_one_rank(h, who)) return 1;
-  if (h->bsr_serial == 0 || h->bsr_serial != h->top_serial) {
-    h->err = std::string(who) + ": call nlps_gpu_tangent_bsr_pattern() after nlps_gpu_tangent_operator() first";
-    return 1;
-  }
-  const int ND = h->nd, E = ND * ND, nn = h->g.nnodes, na = h->nactive;
-  const size_t nr = (size_t)na + 1, nb = (size_t)h->bsr_blocks;
-  if (!brow_ptr || (nb > 0 && (!bcols || !vals))) {
-    h->err = std::string(who) + ": brow_ptr, bcols and vals are required";
-    return 1;
-  }
-  if (nb == 0) {
-    if (is_device_ptr(brow_ptr)) {
-      HIPCHK(hipMemsetAsync(brow_ptr, 0, nr * sizeof(int), h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));
-    } else {
-      memset(brow_ptr, 0, nr * sizeof(int));
-    }
-    return 0;
-  }
-  const bool dev = is_device_ptr(brow_ptr) && is_device_ptr(bcols) && is_device_ptr(vals);
-  DevBuf<int> cols_d;  // staging of host destinations, of this call only
-  DevBuf<double> vals_d;
-  int* cp = bcols;
-  double* vp = vals;
-  if (!dev) {
-    if (reserve(h, who, cols_d, nb, "the staging of bcols") || reserve(h, who, vals_d, nb * E, "the staging of vals")) return 1;
-    cp = cols_d.get();
-    vp = vals_d.get();
-  }
+  const int ND = h->nd, E = ND * ND, nn = h->g.nnodes;
+  const size_t nb = (size_t)h->bsr_blocks;
+  TanOut io{h, brow_ptr, bcols, vals, (size_t)h->nactive + 1, nb, nb * E};
+  if (tanout_begin(h, who, h->bsr_serial, "nlps_gpu_tangent_bsr_pattern", "brow_ptr", "bcols", false, io)) return 1;
+  if (nb == 0) return 0;
   const int* d2m = h->top_dir ? (const int*)h->d2m_d : nullptr;
   const double* aM = h->top_mass ? (const double*)h->top_m : nullptr;
   const int upper = h->bsr_kind == NLPS_BSR_UPPER ? 1 : 0, nt = ND == 3 ? CsrCfg<3>::NT : CsrCfg<2>::NT;
@@ -6625,21 +6632,13 @@ extern "C" int nlps_gpu_tangent_bsr(nlps_gpu* h, int col_major, int* brow_ptr, i
   LAUNCH_ND_BLK((k_tanbsr_rows<2, HALF>), (k_tanbsr_rows<3, HALF>), nn, nt, h->g, (const int*)h->csr_run,                   \
                 (const double*)h->csr_e, (const double*)h->csr_f, (const unsigned long long*)h->csr_mk,                     \
                 (const unsigned long long*)h->csr_mask, (const int*)h->n2m_d, d2m, aM, cnt, off, upper,                     \
-                col_major ? 1 : 0, cp, vp)
+                col_major ? 1 : 0, io.ip, io.vp)
   if (h->bsr_half)
     TANBSR_ROWS(true);
   else
     TANBSR_ROWS(false);
 #undef TANBSR_ROWS
-  HIPCHK(hipGetLastError());
-  // brow_ptr is the scan of the block counts as it stands
-  HIPCHK(hipMemcpyAsync(brow_ptr, off, nr * sizeof(int), hipMemcpyDefault, h->stream));
-  if (!dev) {
-    HIPCHK(hipMemcpyAsync(bcols, cp, nb * sizeof(int), hipMemcpyDefault, h->stream));
-    HIPCHK(hipMemcpyAsync(vals, vp, nb * E * sizeof(double), hipMemcpyDefault, h->stream));
-  }
-  HIPCHK(hipStreamSynchronize(h->stream));  // (the copies land in the caller's memory before the staging goes)
-  return 0;
+  return io.finish(off);  // (brow_ptr is the scan of the block counts as it stands)
 }
 
 // ------------------------------------------------------------------------------------------------

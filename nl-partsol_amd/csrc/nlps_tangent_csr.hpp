@@ -10,7 +10,8 @@
 // are column nodes of the row, no lane idles on an offset outside the stencil --, the finished run passes through LDS
 // as plain stores and each offset's owner adds it to its accumulator.  Every sum has one thread and one order; the
 // finished rows are written once.  No kernel of this file holds a float atomic, so the matrix repeats bit for bit
-// whenever the particle arrays do.
+// whenever the particle arrays do.  That walk is tancsr_walk below; k_tancsr_rows stores its blocks as scalar CSR rows,
+// k_tanbsr_rows (nlps_tangent_bsr.hpp) stores the same blocks as block CSR.
 //
 // Kept per linearisation (nlps_gpu_tangent_csr_pattern, counted in its `bytes`), one record per particle IN THE ORDER BY
 // CLOSEST NODE, so that a row reads its runs as contiguous memory at addresses that depend on the run starts alone (no
@@ -37,6 +38,21 @@ struct CsrCfg {
   static constexpr int GS = (ND == 3) ? 128 : 32;    // threads of a worker group: one per member
   static constexpr int NG = NT / GS;                 // worker groups, each sums its share of a block's d^2 components: 4 / 2
   static constexpr int NPT = (E + NG - 1) / NG;      // components per worker: 1 / 5
+};
+
+// how the walk deals offsets and members where it keeps the upper blocks only (tancsr_walk<ND, true>)
+template <int ND>
+struct BsrCfg {
+  using C = CsrCfg<ND>;
+  static constexpr int SC = (C::S - 1) / 2;                  // the centre offset: 40 / 364
+  static constexpr int SH = C::S - SC;                       // offsets >= 0: 41 / 365
+  static constexpr int OPTH = (SH + C::NT - 1) / C::NT;      // offsets an owner holds in the upper form: 1 / 2
+  // worker groups of a run with few kept members: 4 groups of 16 lanes (one wave) / 3 groups of 64 lanes (three waves)
+  static constexpr int GSS = (ND == 3) ? 64 : 16;
+  static constexpr int NGS = (ND == 3) ? 3 : 4;
+  static constexpr int LGS = (ND == 3) ? 6 : 4;              // log2 GSS, and of CsrCfg::GS
+  static constexpr int LG = (ND == 3) ? 7 : 5;
+  static_assert((1 << LGS) == GSS && (1 << LG) == C::GS, "worker groups are powers of two");
 };
 
 __device__ __forceinline__ bool tancsr_bit(u64 lo, u64 hi, int b) {
@@ -181,19 +197,25 @@ __global__ void k_tancsr_rowptr(int nactive, const int* __restrict__ cntm, const
   row_ptr[idx] = off[m] * ND * ND + i * cntm[m] * ND;
 }
 
-// the d rows of row node A: columns and values, one workgroup per row node
-template <int ND>
-__global__ __launch_bounds__(CsrCfg<ND>::NT) void k_tancsr_rows(GridD g, const int* __restrict__ run,
-                                                                 const double* __restrict__ Ep, const double* __restrict__ Fp,
-                                                                 const u64* __restrict__ Mk, const u64* __restrict__ mask,
-                                                                 const int* __restrict__ n2m, const int* __restrict__ d2m,
-                                                                 const double* __restrict__ aM, const int* __restrict__ cntm,
-                                                                 const int* __restrict__ off, int* __restrict__ cols,
-                                                                 double* __restrict__ vals) {
+// axis `ax` of a column offset packed by tancsr_walk: 0 .. 8 in one byte each, here as -4 .. 4
+__device__ __forceinline__ int tancsr_dof(int packed, int ax) { return (int)((packed >> (8 * ax)) & 0xff) - 4; }
+
+// The walk of row node A = blockIdx.x by one workgroup of CsrCfg::NT threads: the blocks K_AB of A's visited column
+// offsets, summed as the header says, finished (alpha_1 M on the diagonal, Dirichlet rows and columns) and handed to
+// emit(off[mA], cntm[mA], pos, mB, o) by the thread that owns the offset: pos is the block's place among the row's kept
+// blocks in ascending order of masked number, mB its masked column node, o its d^2 values row-major.  Every form of the
+// assembled tangent is this function with another emit, so every form stores the same bits.  HALF and `upper` (cntm
+// and off are then those of the kept blocks): nlps_tangent_bsr.hpp.
+template <int ND, bool HALF, class Emit>
+__device__ __forceinline__ void tancsr_walk(
+    const GridD& g, const int* __restrict__ run, const double* __restrict__ Ep, const double* __restrict__ Fp,
+    const u64* __restrict__ Mk, const u64* __restrict__ mask, const int* __restrict__ n2m, const int* __restrict__ d2m,
+    const double* __restrict__ aM, const int* __restrict__ cntm, const int* __restrict__ off, int upper, const Emit& emit) {
   using Cfg = CsrCfg<ND>;
-  constexpr int S = Cfg::S, NT = Cfg::NT, OPT = Cfg::OPT, MW = Cfg::MW, E = Cfg::E, E4 = Cfg::E4, NWV = Cfg::NWV, NF = Cfg::NF,
-                NFX = Cfg::NFX, CH = Cfg::CH, MAXM = Cfg::MAXM, GS = Cfg::GS, NG = Cfg::NG, NPT = Cfg::NPT,
-                NC = (ND == 3) ? 125 : 25;
+  using Bfg = BsrCfg<ND>;
+  constexpr int S = Cfg::S, NT = Cfg::NT, MW = Cfg::MW, E = Cfg::E, E4 = Cfg::E4, NWV = Cfg::NWV, NF = Cfg::NF,
+                NFX = Cfg::NFX, CH = Cfg::CH, MAXM = Cfg::MAXM, NPT = Cfg::NPT, NC = (ND == 3) ? 125 : 25,
+                S0 = HALF ? Bfg::SC : 0, OPT = HALF ? Bfg::OPTH : Cfg::OPT;
   // the staged particles, in two buffers (a pass fills one while slower waves still read the other: one barrier per pass)
   __shared__ double sh_w[2][CH][NWV];     // w[b][ij] = N_A sum_a l_A[a] E[a][b][ij]
   __shared__ double sh_f[2][CH][2 * NF];  // factors (x, y, z), then l per axis and stencil index
@@ -203,28 +225,23 @@ __global__ __launch_bounds__(CsrCfg<ND>::NT) void k_tancsr_rows(GridD g, const i
   __shared__ double sh_part[MAXM][E];     // the blocks of one closest node's run, by member of its stencil
   __shared__ u64 sh_mask[MW];
   __shared__ int sh_pref[MW];
-  __shared__ int sh_key[S];               // masked node of the q-th visited offset
+  __shared__ int sh_key[S];               // masked node of the q-th listed offset
   const int A = blockIdx.x, t = threadIdx.x;
   const int mA = n2m[A];
   if (mA < 0) return;  // (uniform)
   const int cnt = cntm[mA];
   if (cnt == 0) return;
   const int Ai[3] = {A % g.n[0], (A / g.n[0]) % g.n[1], ND == 3 ? A / (g.n[0] * g.n[1]) : 0};
-  int dof[OPT][3];  // owner role: the column offsets of this thread, each axis in -4 .. 4
+  // owner role: the column offsets S0 + t + k NT of this thread, each axis 0 .. 8 in one byte of dofp (a register each)
+  int dofp[OPT];
   double acc[OPT][E];
 #pragma unroll
   for (int k = 0; k < OPT; k++) {
-    const int s = t + k * NT;
-    dof[k][0] = s % 9 - 4;
-    dof[k][1] = (s / 9) % 9 - 4;
-    dof[k][2] = ND == 3 ? s / 81 - 4 : 0;
+    const int s = S0 + t + k * NT;
+    dofp[k] = s % 9 | ((s / 9) % 9) << 8 | (ND == 3 ? s / 81 : 4) << 16;
 #pragma unroll
     for (int ij = 0; ij < E; ij++) acc[k][ij] = 0.0;
   }
-  // worker role: member wm of the closest node's stencil, components ij = wg + n NG of its block
-  const int wg = t / GS, wm = t % GS;
-  const bool worker = wm < MAXM;
-  const int wb[3] = {wm % 5, (wm / 5) % 5, ND == 3 ? (wm / 25) % 5 : 0};
   int buf = 0;
   if (t < NC) {
     const int Cc[3] = {Ai[0] + t % 5 - 2, Ai[1] + (t / 5) % 5 - 2, ND == 3 ? Ai[2] + t / 25 - 2 : 0};
@@ -242,6 +259,14 @@ __global__ __launch_bounds__(CsrCfg<ND>::NT) void k_tancsr_rows(GridD g, const i
     const int Cc[3] = {Ai[0] + e[0], Ai[1] + e[1], Ai[2] + e[2]};
     const int a[3] = {2 - e[0], 2 - e[1], ND == 3 ? 2 - e[2] : 0};  // stencil index of A around C
     const int sA = a[0] + 5 * a[1] + 25 * a[2];
+    // worker role: member wm of the closest node's stencil, components ij = wg + n ng of its block.  The kept members
+    // are first .. NC - 1; few of them take the narrow groups (uniform over the workgroup: sA is)
+    const int first = HALF ? sA : 0;
+    const bool narrow = HALF && NC - first <= Bfg::GSS;
+    const int lg = narrow ? Bfg::LGS : Bfg::LG, ng = narrow ? Bfg::NGS : Cfg::NG;
+    const int wg = t >> lg, wm = first + (t & ((1 << lg) - 1));
+    const bool worker = wg < ng && wm < NC;
+    const int wb[3] = {wm % 5, (wm / 5) % 5, ND == 3 ? (wm / 25) % 5 : 0};
     double part[NPT];
 #pragma unroll
     for (int n = 0; n < NPT; n++) part[n] = 0.0;
@@ -299,7 +324,7 @@ __global__ __launch_bounds__(CsrCfg<ND>::NT) void k_tancsr_rows(GridD g, const i
           const double* w = sh_w[buf][q];
 #pragma unroll
           for (int n = 0; n < NPT; n++) {
-            const int ij = wg + n * NG;
+            const int ij = wg + n * ng;
             if (ij < E) {
               double v = l0 * w[ij];
               v = fma(l1, w[E + ij], v);
@@ -312,26 +337,29 @@ __global__ __launch_bounds__(CsrCfg<ND>::NT) void k_tancsr_rows(GridD g, const i
       buf ^= 1;
     }
     // the run's blocks go from the member that summed them to the thread that owns the column offset.  (sh_part is
-    // rewritten behind at least one more barrier, the next run's first pass, which every thread reaches after these reads)
+    // rewritten behind at least one more barrier, the next run's first pass, which every thread reaches after these
+    // reads.)  Every kept member of the run is written, also one no particle holds (a zero); an owner of the upper
+    // form reads kept members only: offset >= 0 is member code >= sA
     if (worker) {
 #pragma unroll
       for (int n = 0; n < NPT; n++) {
-        const int ij = wg + n * NG;
+        const int ij = wg + n * ng;
         if (ij < E) sh_part[wm][ij] = part[n];
       }
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < OPT; k++) {
-      const int b0 = dof[k][0] + a[0], b1 = dof[k][1] + a[1], b2 = ND == 3 ? dof[k][2] + a[2] : 0;
-      if (t + k * NT < S && (unsigned)b0 < 5u && (unsigned)b1 < 5u && (unsigned)b2 < 5u) {
+      const int b0 = tancsr_dof(dofp[k], 0) + a[0], b1 = tancsr_dof(dofp[k], 1) + a[1];
+      const int b2 = ND == 3 ? tancsr_dof(dofp[k], 2) + a[2] : 0;
+      if (S0 + t + k * NT < S && (unsigned)b0 < 5u && (unsigned)b1 < 5u && (unsigned)b2 < 5u) {
         const double* src = sh_part[b0 + 5 * b1 + 25 * b2];
 #pragma unroll
         for (int ij = 0; ij < E; ij++) acc[k][ij] += src[ij];
       }
     }
   }
-  // the visited offsets in lexicographic order; position of an offset = visited offsets before it
+  // the visited offsets in lexicographic order; listed position of an offset = visited offsets from S0 before it
   __syncthreads();
   if (t < MW) sh_mask[t] = mask[(size_t)A * MW + t];
   __syncthreads();
@@ -343,50 +371,83 @@ __global__ __launch_bounds__(CsrCfg<ND>::NT) void k_tancsr_rows(GridD g, const i
     }
   }
   __syncthreads();
+  const int skip = HALF ? sh_pref[S0 >> 6] + (int)__popcll(sh_mask[S0 >> 6] & ((1ull << (S0 & 63)) - 1ull)) : 0;
+  // (cnt, but for the walk of every member with `upper`: then cnt <= listed)
+  const int listed = sh_pref[MW - 1] + (int)__popcll(sh_mask[MW - 1]) - skip;
   int pos[OPT], mB[OPT];
 #pragma unroll
   for (int k = 0; k < OPT; k++) {
-    const int s = t + k * NT;
+    const int s = S0 + t + k * NT;
     pos[k] = -1;
     mB[k] = -1;
     if (s < S && ((sh_mask[s >> 6] >> (s & 63)) & 1ull)) {
-      pos[k] = sh_pref[s >> 6] + (int)__popcll(sh_mask[s >> 6] & ((1ull << (s & 63)) - 1ull));
-      mB[k] = n2m[A + dof[k][0] + g.n[0] * (dof[k][1] + g.n[1] * dof[k][2])];
+      pos[k] = sh_pref[s >> 6] + (int)__popcll(sh_mask[s >> 6] & ((1ull << (s & 63)) - 1ull)) - skip;
+      mB[k] = n2m[A + tancsr_dof(dofp[k], 0) + g.n[0] * (tancsr_dof(dofp[k], 1) + g.n[1] * tancsr_dof(dofp[k], 2))];
       sh_key[pos[k]] = mB[k];
     }
   }
   __syncthreads();
   // masked numbers that ascend with the grid order (the default numbering) leave the columns ascending as they stand;
-  // under a caller's numbering the row's keys are ranked in LDS (keys of one row are distinct)
-  int bad = 0;
-  for (int q = t; q + 1 < cnt; q += NT) bad |= sh_key[q] >= sh_key[q + 1];
+  // under a caller's numbering the row's keys are ranked in LDS (keys of one row are distinct), among the keys >= mA
+  // where the upper blocks are picked by number
+  const int least = (!HALF && upper) ? mA : -1;
+  int bad = (!HALF && upper) ? 1 : 0;
+  for (int q = t; q + 1 < listed; q += NT) bad |= sh_key[q] >= sh_key[q + 1];
   if (__syncthreads_or(bad)) {
 #pragma unroll
     for (int k = 0; k < OPT; k++) {
       if (pos[k] < 0) continue;
       int rk = 0;
-      for (int q = 0; q < cnt; q++) rk += sh_key[q] < mB[k];
-      pos[k] = rk;
+      for (int q = 0; q < listed; q++) rk += sh_key[q] >= least && sh_key[q] < mB[k];
+      pos[k] = mB[k] >= least ? rk : -1;
     }
   }
-  const size_t base = (size_t)off[mA] * E;
+  const size_t base = (size_t)off[mA];
 #pragma unroll
   for (int k = 0; k < OPT; k++) {
     if (pos[k] < 0) continue;
-    const bool centre = dof[k][0] == 0 && dof[k][1] == 0 && dof[k][2] == 0;
+    const bool centre = dofp[k] == 0x040404;
+    double o[E];
 #pragma unroll
     for (int i = 0; i < ND; i++) {
       const int ra = mA * ND + i;
-      const size_t at = base + (size_t)i * cnt * ND + (size_t)pos[k] * ND;
 #pragma unroll
       for (int j = 0; j < ND; j++) {
         const int cb = mB[k] * ND + j;
         double v = acc[k][i * ND + j];
         if (centre && i == j && aM) v += aM[ra];
         if (d2m && (d2m[ra] == -1 || d2m[cb] == -1)) v = (ra == cb) ? 1.0 : 0.0;
-        cols[at + j] = cb;
-        vals[at + j] = v;
+        o[i * ND + j] = v;
+      }
+    }
+    emit(base, cnt, pos[k], mB[k], o);
+  }
+}
+
+// scalar CSR: the d rows of the row node lie behind one another, each with the row's cnt d columns
+template <int ND>
+struct EmitCsr {
+  int* __restrict__ cols;
+  double* __restrict__ vals;
+  __device__ __forceinline__ void operator()(size_t base, int cnt, int pos, int mB, const double (&o)[ND * ND]) const {
+#pragma unroll
+    for (int i = 0; i < ND; i++) {
+      const size_t at = base * (ND * ND) + (size_t)i * cnt * ND + (size_t)pos * ND;
+#pragma unroll
+      for (int j = 0; j < ND; j++) {
+        cols[at + j] = mB * ND + j;
+        vals[at + j] = o[i * ND + j];
       }
     }
   }
+};
+
+// the d rows of row node A: columns and values, one workgroup per row node
+template <int ND>
+__global__ __launch_bounds__(CsrCfg<ND>::NT) void k_tancsr_rows(
+    GridD g, const int* __restrict__ run, const double* __restrict__ Ep, const double* __restrict__ Fp,
+    const u64* __restrict__ Mk, const u64* __restrict__ mask, const int* __restrict__ n2m, const int* __restrict__ d2m,
+    const double* __restrict__ aM, const int* __restrict__ cntm, const int* __restrict__ off, int* __restrict__ cols,
+    double* __restrict__ vals) {
+  tancsr_walk<ND, false>(g, run, Ep, Fp, Mk, mask, n2m, d2m, aM, cntm, off, 0, EmitCsr<ND>{cols, vals});
 }

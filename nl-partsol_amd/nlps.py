@@ -283,6 +283,17 @@ def _vp(a):
     return C.c_void_p(int(a))
 
 
+def _csr_arrays(nr, n, block, on_device):
+    """(row pointer [nr] int32, indices [n] int32, values [n, *block] float64) for tangent_csr / tangent_bsr to fill: numpy
+    arrays, or torch tensors on the GPU (an empty matrix still gets a valid device pointer: one entry, sliced to none)."""
+    if on_device:
+        import torch
+        return (torch.empty(nr, dtype=torch.int32, device="cuda"),
+                torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n],
+                torch.empty((max(n, 1),) + tuple(block), dtype=torch.float64, device="cuda")[:n])
+    return np.zeros(nr, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros((n,) + tuple(block))
+
+
 class BccSet:
     """FEM_Mesh.Bounds: list of dicts {nodes, dim, dir[dim][nsteps], value[dim][nsteps]}."""
 
@@ -927,14 +938,8 @@ class Solver:
         in every row (nlps_gpu_tangent_csr; what MatCreateSeqAIJWithArrays takes).  Assembled row by row without float
         atomics: two calls return the same bits.  Needs tangent_csr_pattern() since the operator.  on_device: torch tensors
         on the GPU, written by the row kernel itself."""
-        n, nr = getattr(self, "_csr_nnz", 0), self.nactive * self.ndim + 1
-        if on_device:
-            import torch
-            row_ptr = torch.empty(nr, dtype=torch.int32, device="cuda")
-            cols = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
-            vals = torch.empty(max(n, 1), dtype=torch.float64, device="cuda")[:n]
-        else:
-            row_ptr, cols, vals = np.zeros(nr, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n)
+        n = getattr(self, "_csr_nnz", 0)
+        row_ptr, cols, vals = _csr_arrays(self.nactive * self.ndim + 1, n, (), on_device)
         self._chk(self.L.nlps_gpu_tangent_csr(self.h, _vp(row_ptr), _vp(cols), _vp(vals)))
         return row_ptr, cols, vals
 
@@ -955,14 +960,8 @@ class Solver:
         MatCreateSeqBAIJWithArrays / MatCreateSeqSBAIJWithArrays take).  The values are the bits of tangent_csr's.
         col_major: vals[q] holds the transposed block (PETSc's Fortran-ordered blocks).  Needs tangent_bsr_pattern()
         since the operator.  on_device: torch tensors on the GPU, written by the row kernel itself."""
-        n, nr, d = getattr(self, "_bsr_nblocks", 0), self.nactive + 1, self.ndim
-        if on_device:
-            import torch
-            brow_ptr = torch.empty(nr, dtype=torch.int32, device="cuda")
-            bcols = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
-            vals = torch.empty((max(n, 1), d, d), dtype=torch.float64, device="cuda")[:n]
-        else:
-            brow_ptr, bcols, vals = np.zeros(nr, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros((n, d, d))
+        n = getattr(self, "_bsr_nblocks", 0)
+        brow_ptr, bcols, vals = _csr_arrays(self.nactive + 1, n, (self.ndim, self.ndim), on_device)
         self._chk(self.L.nlps_gpu_tangent_bsr(self.h, 1 if col_major else 0, _vp(brow_ptr), _vp(bcols), _vp(vals)))
         return brow_ptr, bcols, vals
 

@@ -9,7 +9,7 @@ after one warm-up round.  Prints one JSON line and, with out=, writes it to a fi
 
     python tools/tangent_bsr_bench.py [cells=50] [reps=5] [out=profiles/r21_tangent_bsr_bench.json] [parent=<libnlps_gpu.so>]
 
-cells=50: 1 M particles.  parent= names a build of the PARENT commit's library: its CSR path and its atomic path are then
+cells=50: 1 M particles.  parent= names a build of the PARENT commit's library: every path it has is then
 timed in a fresh child process of this tool (NLPS_GPU_LIB), inside the same run, and the ratios are taken against those.
 --profile [only=full|upper]: one warm-up round and one round only (for rocprofv3 --kernel-trace --stats, or counters)."""
 import importlib
@@ -135,9 +135,13 @@ if "parent" in opts and not os.environ.get("NLPS_GPU_LIB"):
     for law in ("nh", "dp"):
         r = res[law]
         assert parent[law]["nnz"] == r["nnz"]
-        for k in ("csr", "atomic"):
+        for k in ("csr", "atomic", "bsr_full", "bsr_upper"):
+            if k + "_ms" not in parent[law]:  # (a parent without the block forms; the upper form: Neo-Hookean only)
+                continue
             r["parent_%s_ms" % k] = parent[law][k + "_ms"]
             r["parent_%s_ms_rounds" % k] = parent[law][k + "_ms_rounds"]
+            if k != "atomic":  # the same path on both sides
+                r["%s_over_parent" % k] = round(r[k + "_ms"] / r["parent_%s_ms" % k], 3)
         r["full_over_parent_csr"] = round(r["bsr_full_ms"] / r["parent_csr_ms"], 3)
         if "bsr_upper_ms" in r:
             r["upper_over_parent_csr"] = round(r["bsr_upper_ms"] / r["parent_csr_ms"], 3)
