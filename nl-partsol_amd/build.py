@@ -1,14 +1,12 @@
 """Builds the gfx950 shared library (hipcc cross-compiles without a GPU)."""
+import glob
 import os
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "nlps_gpu.hip")
 IO_SRC = os.path.join(HERE, "csrc", "nlps_io.cpp")  # host-only input formats (GiD meshes, lattice, particles)
-DEPS = [SRC, IO_SRC] + [os.path.join(HERE, "csrc", f) for f in ("nlps_device.hpp", "nlps_tables.hpp", "nlps_tile_kernels.hpp",
-                                                         "nlps_tangent_kernels.hpp", "nlps_tangent_operator.hpp", "nlps_tangent_csr.hpp", "nlps_tangent_bsr.hpp", "nlps_krylov.hpp",
-                                                         "nlps_eigen.hpp", "nlps_newton.hpp", "nlps_record.hpp", "nlps_snapshot.hpp",
-                                                         "nlps_host_mem.hpp")] + \
+DEPS = [SRC, IO_SRC] + sorted(glob.glob(os.path.join(HERE, "csrc", "*.hpp"))) + \
        [os.path.join(HERE, "..", "include", "nlps_gpu.h")]
 # NLPS_GPU_LIB: developer hook, loads another BUILD of this same library (kernel experiments: tools/kbench.py)
 LIB = os.environ.get("NLPS_GPU_LIB") or os.path.join(HERE, "csrc", "libnlps_gpu.so")

@@ -6651,6 +6651,35 @@ static int ksp_wait(nlps_gpu* h) {
   return 0;
 }
 
+// the refusal of the solves whose reductions (what: "dot products", "norms") stay on one rank
+static int single_rank_only(nlps_gpu* h, const char* who, const char* what) {
+  if (!h->halo && !(h->rccl && h->rccl->world > 1)) return 0;
+  h->err = std::string(who) + ": single rank only: this handle exchanges halos (a halo callback or an RCCL world > 1), and " +
+           what + " across ranks would need an owner mask and an allreduce";
+  return 1;
+}
+
+// the pinned word(s) the kernels of a solve report through: allocated and zeroed on first use (without a device alias
+// the kernels write a device copy and the solve's wait brings it over)
+template <class T>
+static int ensure_host_word(nlps_gpu* h, Mirrored<T>& w, size_t n = 1) {
+  if (w.host()) return 0;
+  HIPCHK(w.alloc(n));
+  memset(w.host(), 0, n * sizeof(T));
+  return 0;
+}
+
+// the copies back to the caller's host vectors that close a solve; the caller of a solve on device vectors gets its
+// synchronisation all the same
+static int vec_end(nlps_gpu* h, const char* who, VecIO& io) {
+  if (io.finish()) {
+    h->err = std::string(who) + ": HIP error";
+    return 1;
+  }
+  if (io.back.empty()) HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 // the preconditioner of the current linearisation: built from the diagonal blocks once per successful
 // nlps_gpu_tangent_operator (top_serial) and kind, reused by the solves that follow
 static int ksp_pc_build(nlps_gpu* h, int kind) {
@@ -6686,34 +6715,149 @@ static int ksp_pc_build(nlps_gpu* h, int kind) {
   return 0;
 }
 
-static size_t minres_nbn(size_t nA) { return (nA + KSP_NT - 1) / KSP_NT; }
+// ---- what the Krylov drivers share ("One scaffold under the Krylov drivers") ----
+static int ksp_tiles(size_t n) { return (int)((n + KSP_TILE - 1) / KSP_TILE); }
 
-// nlps_gpu_tangent_solve with NLPS_KSP_TYPE_MINRES (nlps_minres.hpp), after the checks the two solvers share: the
-// algorithm of include/nlps_gpu.h, one host wait per step (|eta| and the flags) and one per confirmation
-static int minres_solve(nlps_gpu* h, VecIO& io, const double* b, double* x, nlps_ksp* ksp) {
+// where the two-pass Gram-Schmidt keeps its scalars in a driver's small state (KspSmall and EigSmall name them alike)
+struct GsSmall {
+  int h1, h2, wn2, refine;
+};
+
+// classical Gram-Schmidt of w against the first ncol columns of V (leading dimension n): pass 1 (with w.w for DGKS),
+// then pass 2 when the refine word says so; eight launches, no wait
+static void krylov_orthogonalise(nlps_gpu* h, size_t n, const double* V, int ncol, double* w, const GsSmall o, double* part,
+                                 int nb, double* s) {
+  const dim3 gs(nb), bs(KSP_NT);
+  const double* const nul = nullptr;
+  double* const nulw = nullptr;
+  const double* const refine = s + o.refine;
+  hipLaunchKernelGGL(k_ksp_mdot, gs, bs, 0, h->stream, (int)n, V, n, ncol, 1, (const double*)w, part, nb, nul);
+  hipLaunchKernelGGL(k_ksp_finish, dim3(ncol + 1), bs, 0, h->stream, (const double*)part, nb, s + o.h1, nulw, nul, nulw, nul);
+  hipLaunchKernelGGL(k_ksp_maxpy, gs, bs, 0, h->stream, (int)n, V, n, ncol, (const double*)(s + o.h1), w, part, nul);
+  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, s + o.wn2, nulw, nul, s + o.refine,
+                     (const double*)(s + o.h1 + ncol));
+  hipLaunchKernelGGL(k_ksp_mdot, gs, bs, 0, h->stream, (int)n, V, n, ncol, 0, (const double*)w, part, nb, refine);
+  hipLaunchKernelGGL(k_ksp_finish, dim3(ncol), bs, 0, h->stream, (const double*)part, nb, s + o.h2, nulw, refine, nulw, nul);
+  hipLaunchKernelGGL(k_ksp_maxpy, gs, bs, 0, h->stream, (int)n, V, n, ncol, (const double*)(s + o.h2), w, part, refine);
+  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, s + o.wn2, nulw, refine, nulw, nul);
+}
+
+// the workspace of one linear solver: vectors of n in ksp_v, partial sums, small state, what reserve() calls the first
+// and the last, and the columns of ksp_v that r0 = b - K x0 goes to (r0) and K x0 goes through (scratch)
+struct KspSpace {
+  size_t nvec, npart, nsmall;
+  const char *vectors, *small;
+  int r0, scratch;
+};
+
+// what ksp_begin leaves to the recurrence; rnorm and reason move with the solve
+struct KspRun {
+  size_t n;
+  int nb;
+  const double* bd;
+  double* xd;
+  double bnorm, rnorm, tol;
+  int reason;  // NLPS_KSP_CONVERGED_BZERO when the opening decided, else 0
+};
+
+// the opening of a linear solve: the footprint, the workspace, the preconditioner, ||b|| and r0 = b - K x0 with its
+// norm (one wait).  n == 0 is decided here, ahead of every allocation (the caller returns 0); b == 0 is run.reason
+static int ksp_begin(nlps_gpu* h, VecIO& io, const double* b, double* x, nlps_ksp* ksp, const KspSpace& sp, KspRun& run) {
   const char* who = "nlps_gpu_tangent_solve";
   const size_t n = io.n;
-  const int ND = h->nd, nA = h->nactive, kind = ksp->pc, max_it = ksp->max_it;
-  const int nb = (int)((n + KSP_TILE - 1) / KSP_TILE), nbn = (int)minres_nbn((size_t)nA);
-  ksp->bytes = sizeof(double) * ((size_t)7 * n + (size_t)nb + (size_t)nbn + MINRES_SMALL +
-                                 (kind != NLPS_PC_NONE ? (size_t)nA * ND * ND : 0));
+  const int ND = h->nd, nA = h->nactive, kind = ksp->pc, nb = ksp_tiles(n);
+  ksp->bytes = sizeof(double) * (sp.nvec * n + sp.npart + sp.nsmall + (kind != NLPS_PC_NONE ? (size_t)nA * ND * ND : 0));
   double* hist = ksp->history;
+  run = KspRun{n, nb, nullptr, nullptr, 0.0, 0.0, 0.0, 0};
   if (n == 0) {
     ksp->reason = NLPS_KSP_CONVERGED_BZERO;
     if (hist) hist[0] = 0.0;
     return 0;
   }
-  if (reserve(h, who, h->ksp_v, (size_t)7 * n, "the MINRES vectors") ||
-      reserve(h, who, h->ksp_part, (size_t)nb + nbn, "the partial sums") ||
-      reserve(h, who, h->ksp_s, (size_t)MINRES_SMALL, "the rotation state"))
+  if (reserve(h, who, h->ksp_v, sp.nvec * n, sp.vectors) || reserve(h, who, h->ksp_part, sp.npart, "the partial sums") ||
+      reserve(h, who, h->ksp_s, sp.nsmall, sp.small))
     return 1;
-  if (!h->ksp_h.host()) {
-    HIPCHK(h->ksp_h.alloc());
-    memset(h->ksp_h.host(), 0, sizeof(KspHost));
-  }
+  if (ensure_host_word(h, h->ksp_h)) return 1;
   if (ksp_pc_build(h, kind)) return 1;
-  const double* bd = io.in(b);
-  double* xd = io.out(x, ksp->x_is_guess != 0);
+  const double* bd = run.bd = io.in(b);
+  double* xd = run.xd = io.out(x, ksp->x_is_guess != 0);
+  double* const r0 = h->ksp_v + (size_t)sp.r0 * n;
+  double* const t = h->ksp_v + (size_t)sp.scratch * n;
+  double* const part = h->ksp_part;
+  KspHost* const hw = h->ksp_h.target();
+  const dim3 gs(nb), bs(KSP_NT);
+  const double* const nul = nullptr;
+  double* const nulw = nullptr;
+  hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, nul, nulw, part);
+  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, nulw, &hw->bn2, nul, nulw, nul);
+  if (ksp->x_is_guess) {
+    if (tanop_product(h, xd, t, nullptr)) return 1;
+  } else {
+    HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(double), h->stream));
+  }
+  hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, ksp->x_is_guess ? (const double*)t : nul, r0, part);
+  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, nulw, &hw->rn2, nul, nulw, nul);
+  HIPCHK(hipGetLastError());
+  if (ksp_wait(h)) return 1;
+  run.bnorm = sqrt(h->ksp_h.host()->bn2);
+  run.rnorm = sqrt(h->ksp_h.host()->rn2);
+  run.tol = std::max(ksp->rtol * run.bnorm, ksp->atol);
+  if (hist) hist[0] = run.rnorm;
+  if (run.bnorm == 0.0) {  // x = 0 (also over a guess), as KSPSolve
+    HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(double), h->stream));
+    run.rnorm = 0.0;
+    if (hist) hist[0] = 0.0;
+    run.reason = NLPS_KSP_CONVERGED_BZERO;
+  }
+  return 0;
+}
+
+// the stopping rule of a true residual after its iterations, in KSPSolve's order; broke: the recurrence cannot go on
+static int ksp_stop(const KspRun& run, const nlps_ksp* ksp, int its, bool broke) {
+  if (!std::isfinite(run.rnorm) || !std::isfinite(run.bnorm)) return NLPS_KSP_DIVERGED_NANORINF;
+  if (run.rnorm <= run.tol) return run.rnorm < ksp->atol ? NLPS_KSP_CONVERGED_ATOL : NLPS_KSP_CONVERGED_RTOL;
+  if (run.rnorm > ksp->dtol * run.bnorm) return NLPS_KSP_DIVERGED_DTOL;
+  if (its >= ksp->max_it) return NLPS_KSP_DIVERGED_ITS;
+  return broke ? NLPS_KSP_DIVERGED_BREAKDOWN : 0;
+}
+
+// run.rnorm = ||b - K x|| of the current x, the product through scratch, the residual into r_out (or nowhere): one wait
+static int ksp_true_residual(nlps_gpu* h, KspRun& run, double* scratch, double* r_out) {
+  const dim3 gs(run.nb), bs(KSP_NT);
+  const double* const nul = nullptr;
+  double* const nulw = nullptr;
+  double* const part = h->ksp_part;
+  if (tanop_product(h, run.xd, scratch, nullptr)) return 1;
+  hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)run.n, run.bd, (const double*)scratch, r_out, part);
+  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, run.nb, nulw, &h->ksp_h.target()->rn2, nul,
+                     nulw, nul);
+  HIPCHK(hipGetLastError());
+  if (ksp_wait(h)) return 1;
+  run.rnorm = sqrt(h->ksp_h.host()->rn2);
+  return 0;
+}
+
+// the close of a linear solve: the results, the copies back to host vectors, the synchronisation
+static int ksp_end(nlps_gpu* h, VecIO& io, nlps_ksp* ksp, const KspRun& run, int its) {
+  ksp->reason = run.reason;
+  ksp->iterations = its;
+  ksp->rnorm = run.rnorm;
+  ksp->bnorm = run.bnorm;
+  return vec_end(h, "nlps_gpu_tangent_solve", io);
+}
+
+static size_t minres_nbn(size_t nA) { return (nA + KSP_NT - 1) / KSP_NT; }
+
+// nlps_gpu_tangent_solve with NLPS_KSP_TYPE_MINRES (nlps_minres.hpp), after the checks the two solvers share: the
+// algorithm of include/nlps_gpu.h, one host wait per step (|eta| and the flags) and one per confirmation
+static int minres_solve(nlps_gpu* h, VecIO& io, const double* b, double* x, nlps_ksp* ksp) {
+  const size_t n = io.n;
+  const int nA = h->nactive, kind = ksp->pc, max_it = ksp->max_it, nb = ksp_tiles(n), nbn = (int)minres_nbn((size_t)nA);
+  const KspSpace sp{7, (size_t)nb + (size_t)nbn, MINRES_SMALL, "the MINRES vectors", "the rotation state", 1, 6};
+  KspRun run;  // (r0 into v, K x through p)
+  if (ksp_begin(h, io, b, x, ksp, sp, run)) return 1;
+  if (n == 0) return 0;
+  double* const hist = ksp->history;
   double* const base = h->ksp_v;
   double *vp = base, *v = base + n, *wp = base + 2 * n, *w = base + 3 * n;  // (the pairs that rotate)
   double *const z = base + 4 * n, *const q = base + 5 * n, *const p = base + 6 * n;
@@ -6722,79 +6866,41 @@ static int minres_solve(nlps_gpu* h, VecIO& io, const double* b, double* x, nlps
   double* const s = h->ksp_s;
   const double* const Minv = h->ksp_pc;
   KspHost* const hw = h->ksp_h.target();
-  const dim3 gs(nb), gn(nbn), bs(KSP_NT);
-  const double* const nul = nullptr;
-  double* const nulw = nullptr;
-  // rn2 of the host word = ||b - K x||^2 of the current x, through p
-  auto true_residual = [&](double* rnorm) -> int {
-    if (tanop_product(h, xd, p, nullptr)) return 1;
-    hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, (const double*)p, nulw, part);
-    hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, nulw, &hw->rn2, nul, nulw, nul);
+  const dim3 gs(nb), bs(KSP_NT);
+  // one step from src (r0 on the first, p = K q after it): v_new, z, the rotation and the update of w and x; the
+  // wait brings |eta| and the flags
+  auto step = [&](int first, const double* src) -> int {
+    if (!first) hipLaunchKernelGGL(k_minres_dot, gs, bs, 0, h->stream, (int)n, (const double*)p, (const double*)q, part);
+    LAUNCH_ND_BLK((k_minres_lanczos<2>), (k_minres_lanczos<3>), nbn, KSP_NT, nA, kind, Minv, first, src, (const double*)v,
+                  vp, z, (const double*)part, nb, s, partn);
+    hipLaunchKernelGGL(k_minres_rotate, dim3(1), dim3(64), 0, h->stream, first, (const double*)partn, nbn, s, hw);
+    hipLaunchKernelGGL(k_minres_update, gs, bs, 0, h->stream, (int)n, first, (const double*)s, (const double*)z, q, wp,
+                       (const double*)w, run.xd);
     HIPCHK(hipGetLastError());
-    if (ksp_wait(h)) return 1;
-    *rnorm = sqrt(h->ksp_h.host()->rn2);
-    return 0;
+    return ksp_wait(h);
   };
-  // ||b|| and r0 = b - K x0 into v
-  hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, nul, nulw, part);
-  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, nulw, &hw->bn2, nul, nulw, nul);
-  if (ksp->x_is_guess) {
-    if (tanop_product(h, xd, p, nullptr)) return 1;
-    hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, (const double*)p, v, part);
-  } else {
-    HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(double), h->stream));
-    hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, nul, v, part);
-  }
-  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, nulw, &hw->rn2, nul, nulw, nul);
-  HIPCHK(hipGetLastError());
-  if (ksp_wait(h)) return 1;
-  const double bnorm = sqrt(h->ksp_h.host()->bn2);
-  double rnorm = sqrt(h->ksp_h.host()->rn2);
-  const double tol = std::max(ksp->rtol * bnorm, ksp->atol);
-  if (hist) hist[0] = rnorm;
-  int its = 0, reason = 0;
-  if (bnorm == 0.0) {  // x = 0 (also over a guess), as KSPSolve
-    HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(double), h->stream));
-    rnorm = 0.0;
-    if (hist) hist[0] = 0.0;
-    reason = NLPS_KSP_CONVERGED_BZERO;
-  } else if (!std::isfinite(rnorm) || !std::isfinite(bnorm)) reason = NLPS_KSP_DIVERGED_NANORINF;
-  else if (rnorm <= tol) reason = rnorm < ksp->atol ? NLPS_KSP_CONVERGED_ATOL : NLPS_KSP_CONVERGED_RTOL;
-  else if (rnorm > ksp->dtol * bnorm) reason = NLPS_KSP_DIVERGED_DTOL;
-  else if (max_it == 0) reason = NLPS_KSP_DIVERGED_ITS;
+  int its = 0;
+  if (!run.reason) run.reason = ksp_stop(run, ksp, its, false);
   double scale = 0.0;
-  if (!reason) {  // z = M^-1 r0, g = sqrt(r0 . z), q = z / g; v_prev = w_prev = w = 0
+  if (!run.reason) {  // z = M^-1 r0, g = sqrt(r0 . z), q = z / g; v_prev = w_prev = w = 0
     HIPCHK(hipMemsetAsync(vp, 0, n * sizeof(double), h->stream));
     HIPCHK(hipMemsetAsync(wp, 0, 2 * n * sizeof(double), h->stream));
-    LAUNCH_ND_BLK((k_minres_lanczos<2>), (k_minres_lanczos<3>), nbn, KSP_NT, nA, kind, Minv, 1, (const double*)v,
-                  (const double*)v, vp, z, (const double*)part, nb, s, partn);
-    hipLaunchKernelGGL(k_minres_rotate, dim3(1), dim3(64), 0, h->stream, 1, (const double*)partn, nbn, s, hw);
-    hipLaunchKernelGGL(k_minres_update, gs, bs, 0, h->stream, (int)n, 1, (const double*)s, (const double*)z, q, wp,
-                       (const double*)w, xd);
-    HIPCHK(hipGetLastError());
-    if (ksp_wait(h)) return 1;
+    if (step(1, v)) return 1;
     const int flags = h->ksp_h.host()->flags;
-    if (flags & MINRES_FLAG_INDEFINITE) reason = NLPS_KSP_DIVERGED_INDEFINITE_PC;
-    else if (flags & KSP_FLAG_NONFINITE) reason = NLPS_KSP_DIVERGED_NANORINF;
-    else scale = rnorm / h->ksp_h.host()->est;
+    if (flags & MINRES_FLAG_INDEFINITE) run.reason = NLPS_KSP_DIVERGED_INDEFINITE_PC;
+    else if (flags & KSP_FLAG_NONFINITE) run.reason = NLPS_KSP_DIVERGED_NANORINF;
+    else scale = run.rnorm / h->ksp_h.host()->est;
   }
-  while (!reason) {
+  while (!run.reason) {
     if (tanop_product(h, q, p, nullptr)) return 1;
-    hipLaunchKernelGGL(k_minres_dot, gs, bs, 0, h->stream, (int)n, (const double*)p, (const double*)q, part);
-    LAUNCH_ND_BLK((k_minres_lanczos<2>), (k_minres_lanczos<3>), nbn, KSP_NT, nA, kind, Minv, 0, (const double*)p,
-                  (const double*)v, vp, z, (const double*)part, nb, s, partn);
-    hipLaunchKernelGGL(k_minres_rotate, dim3(1), dim3(64), 0, h->stream, 0, (const double*)partn, nbn, s, hw);
-    hipLaunchKernelGGL(k_minres_update, gs, bs, 0, h->stream, (int)n, 0, (const double*)s, (const double*)z, q, wp,
-                       (const double*)w, xd);
-    HIPCHK(hipGetLastError());
-    if (ksp_wait(h)) return 1;
+    if (step(0, p)) return 1;
     const int flags = h->ksp_h.host()->flags;
     const double eta = h->ksp_h.host()->est;  // (|eta|: the estimate is scale |eta|)
     if (flags & (MINRES_FLAG_INDEFINITE | KSP_FLAG_NONFINITE | KSP_FLAG_SINGULAR)) {  // (x is the one of step its)
-      reason = (flags & MINRES_FLAG_INDEFINITE) ? NLPS_KSP_DIVERGED_INDEFINITE_PC
-               : (flags & KSP_FLAG_NONFINITE)   ? NLPS_KSP_DIVERGED_NANORINF
-                                                : NLPS_KSP_DIVERGED_BREAKDOWN;
-      if (true_residual(&rnorm)) return 1;
+      run.reason = (flags & MINRES_FLAG_INDEFINITE) ? NLPS_KSP_DIVERGED_INDEFINITE_PC
+                   : (flags & KSP_FLAG_NONFINITE)   ? NLPS_KSP_DIVERGED_NANORINF
+                                                    : NLPS_KSP_DIVERGED_BREAKDOWN;
+      if (ksp_true_residual(h, run, p, nullptr)) return 1;
       break;
     }
     std::swap(vp, v);  // (v_new and w_new were written over v_prev and w_prev)
@@ -6803,31 +6909,18 @@ static int minres_solve(nlps_gpu* h, VecIO& io, const double* b, double* x, nlps
     const double est = scale * eta;
     if (hist) hist[its] = est;
     if (!std::isfinite(est)) {
-      reason = NLPS_KSP_DIVERGED_NANORINF;
-      if (true_residual(&rnorm)) return 1;
+      run.reason = NLPS_KSP_DIVERGED_NANORINF;
+      if (ksp_true_residual(h, run, p, nullptr)) return 1;
       break;
     }
     const bool gzero = (flags & MINRES_FLAG_GZERO) != 0;
-    if (est <= tol || its >= max_it || gzero) {  // the confirmation: read-only for the recurrence
-      if (true_residual(&rnorm)) return 1;
-      if (!std::isfinite(rnorm)) reason = NLPS_KSP_DIVERGED_NANORINF;
-      else if (rnorm <= tol) reason = rnorm < ksp->atol ? NLPS_KSP_CONVERGED_ATOL : NLPS_KSP_CONVERGED_RTOL;
-      else if (rnorm > ksp->dtol * bnorm) reason = NLPS_KSP_DIVERGED_DTOL;
-      else if (its >= max_it) reason = NLPS_KSP_DIVERGED_ITS;
-      else if (gzero) reason = NLPS_KSP_DIVERGED_BREAKDOWN;
-      else scale = rnorm / eta;
+    if (est <= run.tol || its >= max_it || gzero) {  // the confirmation: read-only for the recurrence
+      if (ksp_true_residual(h, run, p, nullptr)) return 1;
+      run.reason = ksp_stop(run, ksp, its, gzero);
+      if (!run.reason) scale = run.rnorm / eta;
     }
   }
-  ksp->reason = reason;
-  ksp->iterations = its;
-  ksp->rnorm = rnorm;
-  ksp->bnorm = bnorm;
-  if (io.finish()) {
-    h->err = "nlps_gpu_tangent_solve: HIP error";
-    return 1;
-  }
-  if (io.back.empty()) HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
+  return ksp_end(h, io, ksp, run, its);
 }
 
 extern "C" int nlps_gpu_set_linear_solver(nlps_gpu* h, int type) {
@@ -6861,11 +6954,7 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
   ksp->rnorm = ksp->bnorm = 0.0;
   ksp->bytes = 0;
   if (tanop_valid(h, who)) return 1;
-  if (h->halo || (h->rccl && h->rccl->world > 1)) {
-    h->err = "nlps_gpu_tangent_solve: single rank only: this handle exchanges halos (a halo callback or an RCCL world > 1), "
-             "and dot products across ranks would need an owner mask and an allreduce";
-    return 1;
-  }
+  if (single_rank_only(h, who, "dot products")) return 1;
   if (!b || !x) {
     h->err = "nlps_gpu_tangent_solve: b and x are required";
     return 1;
@@ -6888,27 +6977,13 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
   if (vec_begin(h, who, io)) return 1;
   if (minres) return minres_solve(h, io, b, x, ksp);
   const size_t n = io.n;
-  const int ND = h->nd, nA = h->nactive, nb = (int)((n + KSP_TILE - 1) / KSP_TILE);
+  const int nA = h->nactive, nb = ksp_tiles(n);
   const KspSmall L{m};
-  ksp->bytes = sizeof(double) * ((size_t)(m + 3) * n + (size_t)(m + 2) * nb + L.size() +
-                                 (kind != NLPS_PC_NONE ? (size_t)nA * ND * ND : 0));
-  double* hist = ksp->history;
-  if (n == 0) {
-    ksp->reason = NLPS_KSP_CONVERGED_BZERO;
-    if (hist) hist[0] = 0.0;
-    return 0;
-  }
-  if (reserve(h, who, h->ksp_v, (size_t)(m + 3) * n, "the Krylov basis") ||
-      reserve(h, who, h->ksp_part, (size_t)(m + 2) * nb, "the partial sums") ||
-      reserve(h, who, h->ksp_s, L.size(), "the Hessenberg state"))
-    return 1;
-  if (!h->ksp_h.host()) {  // (without a device alias the kernels write a device copy and ksp_wait brings it over)
-    HIPCHK(h->ksp_h.alloc());
-    memset(h->ksp_h.host(), 0, sizeof(KspHost));
-  }
-  if (ksp_pc_build(h, kind)) return 1;
-  const double* bd = io.in(b);
-  double* xd = io.out(x, ksp->x_is_guess != 0);
+  const KspSpace sp{(size_t)m + 3, (size_t)(m + 2) * nb, L.size(), "the Krylov basis", "the Hessenberg state", 0, m + 2};
+  KspRun run;  // (r0 into V[0], K x through t)
+  if (ksp_begin(h, io, b, x, ksp, sp, run)) return 1;
+  if (n == 0) return 0;
+  double* const hist = ksp->history;
   double* const V = h->ksp_v;  // V[c] at V + c n
   double* const z = V + (size_t)(m + 1) * n;
   double* const t = z + n;
@@ -6916,68 +6991,22 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
   double* const s = h->ksp_s;
   KspHost* const hw = h->ksp_h.target();
   const KspPc pcd{kind, h->ksp_pc, z};
+  const GsSmall gso{L.h1(), L.h2(), L.wn2(), L.refine()};
   const dim3 gs(nb), bs(KSP_NT);
-  // ||b|| and r0 = b - K x0 into V[0]
-  hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, (const double*)nullptr, (double*)nullptr, part);
-  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, (double*)nullptr, &hw->bn2,
-                     (const double*)nullptr, (double*)nullptr, (const double*)nullptr);
-  if (ksp->x_is_guess) {
-    if (tanop_product(h, xd, t, nullptr)) return 1;
-    hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, (const double*)t, V, part);
-  } else {
-    HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(double), h->stream));
-    hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, (const double*)nullptr, V, part);
-  }
-  hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, (double*)nullptr, &hw->rn2,
-                     (const double*)nullptr, (double*)nullptr, (const double*)nullptr);
-  HIPCHK(hipGetLastError());
-  if (ksp_wait(h)) return 1;
-  const double bnorm = sqrt(h->ksp_h.host()->bn2);
-  double rnorm = sqrt(h->ksp_h.host()->rn2);
-  const double tol = std::max(ksp->rtol * bnorm, ksp->atol);
-  if (hist) hist[0] = rnorm;
-  int its = 0, reason = 0;
+  int its = 0;
   bool broke = false;
-  if (bnorm == 0.0) {  // x = 0 (also over a guess), as KSPSolve
-    HIPCHK(hipMemsetAsync(xd, 0, n * sizeof(double), h->stream));
-    rnorm = 0.0;
-    if (hist) hist[0] = 0.0;
-    reason = NLPS_KSP_CONVERGED_BZERO;
-  }
-  while (!reason) {
-    if (!std::isfinite(rnorm) || !std::isfinite(bnorm)) reason = NLPS_KSP_DIVERGED_NANORINF;
-    else if (rnorm <= tol) reason = rnorm < ksp->atol ? NLPS_KSP_CONVERGED_ATOL : NLPS_KSP_CONVERGED_RTOL;
-    else if (rnorm > ksp->dtol * bnorm) reason = NLPS_KSP_DIVERGED_DTOL;
-    else if (its >= max_it) reason = NLPS_KSP_DIVERGED_ITS;
-    else if (broke) reason = NLPS_KSP_DIVERGED_BREAKDOWN;
-    if (reason) break;
+  while (!run.reason) {
+    if ((run.reason = ksp_stop(run, ksp, its, broke))) break;
     // one cycle: V[0] = r / ||r||, Arnoldi steps on K M^-1 until the estimate converges, the cycle is full, max_it or
     // a breakdown; one host synchronisation per step (the estimate and the flags)
-    hipLaunchKernelGGL(k_ksp_scale, gs, bs, 0, h->stream, (int)n, (const double*)V, V, 1.0 / rnorm, (const double*)nullptr);
+    hipLaunchKernelGGL(k_ksp_scale, gs, bs, 0, h->stream, (int)n, (const double*)V, V, 1.0 / run.rnorm, (const double*)nullptr);
     int k = 0;
     bool nonfinite = false;
     for (int j = 0; j < m; j++) {
       double* const w = V + (size_t)(j + 1) * n;
       if (tanop_product(h, V + (size_t)j * n, w, &pcd)) return 1;
-      double* const refine = s + L.refine();
-      // classical Gram-Schmidt, pass 1 (with w.w for DGKS), then pass 2 when the refine word says so
-      hipLaunchKernelGGL(k_ksp_mdot, gs, bs, 0, h->stream, (int)n, (const double*)V, n, j + 1, 1, (const double*)w, part, nb,
-                         (const double*)nullptr);
-      hipLaunchKernelGGL(k_ksp_finish, dim3(j + 2), bs, 0, h->stream, (const double*)part, nb, s + L.h1(), (double*)nullptr,
-                         (const double*)nullptr, (double*)nullptr, (const double*)nullptr);
-      hipLaunchKernelGGL(k_ksp_maxpy, gs, bs, 0, h->stream, (int)n, (const double*)V, n, j + 1, (const double*)(s + L.h1()), w,
-                         part, (const double*)nullptr);
-      hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, s + L.wn2(), (double*)nullptr,
-                         (const double*)nullptr, refine, (const double*)(s + L.h1() + j + 1));
-      hipLaunchKernelGGL(k_ksp_mdot, gs, bs, 0, h->stream, (int)n, (const double*)V, n, j + 1, 0, (const double*)w, part, nb,
-                         (const double*)refine);
-      hipLaunchKernelGGL(k_ksp_finish, dim3(j + 1), bs, 0, h->stream, (const double*)part, nb, s + L.h2(), (double*)nullptr,
-                         (const double*)refine, (double*)nullptr, (const double*)nullptr);
-      hipLaunchKernelGGL(k_ksp_maxpy, gs, bs, 0, h->stream, (int)n, (const double*)V, n, j + 1, (const double*)(s + L.h2()), w,
-                         part, (const double*)refine);
-      hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, s + L.wn2(), (double*)nullptr,
-                         (const double*)refine, (double*)nullptr, (const double*)nullptr);
-      hipLaunchKernelGGL(k_ksp_arnoldi, dim3(1), dim3(64), 0, h->stream, L, s, j, rnorm, hw);
+      krylov_orthogonalise(h, n, V, j + 1, w, gso, part, nb, s);
+      hipLaunchKernelGGL(k_ksp_arnoldi, dim3(1), dim3(64), 0, h->stream, L, s, j, run.rnorm, hw);
       hipLaunchKernelGGL(k_ksp_scale, gs, bs, 0, h->stream, (int)n, (const double*)w, w, 1.0, (const double*)(s + L.wn2()));
       HIPCHK(hipGetLastError());
       if (ksp_wait(h)) return 1;
@@ -6994,36 +7023,21 @@ extern "C" int nlps_gpu_tangent_solve(nlps_gpu* h, const double* b, double* x, n
         break;
       }
       k = j + 1;
-      if (est <= tol || (flags & KSP_FLAG_HAPPY) || its >= max_it) break;
+      if (est <= run.tol || (flags & KSP_FLAG_HAPPY) || its >= max_it) break;
     }
     if (nonfinite) {
-      reason = NLPS_KSP_DIVERGED_NANORINF;
+      run.reason = NLPS_KSP_DIVERGED_NANORINF;
       break;
     }
     if (k > 0) {  // x += M^-1 V y, R y = g
       hipLaunchKernelGGL(k_ksp_hsolve, dim3(1), dim3(64), 0, h->stream, L, s, k);
       LAUNCH_ND((k_ksp_update<2>), (k_ksp_update<3>), nblk(nA), nA, kind, (const double*)h->ksp_pc, (const double*)V, n, k,
-                (const double*)(s + L.y()), xd);
+                (const double*)(s + L.y()), run.xd);
     }
     // the true residual of the new x: confirms the estimate, or starts the next cycle from V[0]
-    if (tanop_product(h, xd, t, nullptr)) return 1;
-    hipLaunchKernelGGL(k_ksp_resid, gs, bs, 0, h->stream, (int)n, bd, (const double*)t, V, part);
-    hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, (double*)nullptr, &hw->rn2,
-                       (const double*)nullptr, (double*)nullptr, (const double*)nullptr);
-    HIPCHK(hipGetLastError());
-    if (ksp_wait(h)) return 1;
-    rnorm = sqrt(h->ksp_h.host()->rn2);
+    if (ksp_true_residual(h, run, t, V)) return 1;
   }
-  ksp->reason = reason;
-  ksp->iterations = its;
-  ksp->rnorm = rnorm;
-  ksp->bnorm = bnorm;
-  if (io.finish()) {
-    h->err = "nlps_gpu_tangent_solve: HIP error";
-    return 1;
-  }
-  if (io.back.empty()) HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
+  return ksp_end(h, io, ksp, run, its);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -7072,11 +7086,7 @@ extern "C" int nlps_gpu_tangent_lambda_max(nlps_gpu* h, const double* lumped_mas
   eig->theta = eig->resid = eig->asymmetry = 0.0;
   eig->bytes = 0;
   if (tanop_valid(h, who)) return 1;
-  if (h->halo || (h->rccl && h->rccl->world > 1)) {
-    h->err = "nlps_gpu_tangent_lambda_max: single rank only: this handle exchanges halos (a halo callback or an RCCL world "
-             "> 1), and dot products across ranks would need an owner mask and an allreduce";
-    return 1;
-  }
+  if (single_rank_only(h, who, "dot products")) return 1;
   if (!lumped_mass) {
     h->err = "nlps_gpu_tangent_lambda_max: lumped_mass is required";
     return 1;
@@ -7093,7 +7103,7 @@ extern "C" int nlps_gpu_tangent_lambda_max(nlps_gpu* h, const double* lumped_mas
   VecIO io;
   if (vec_begin(h, who, io)) return 1;
   const size_t n = io.n;
-  const int nA = h->nactive, nn = h->g.nnodes, nb = (int)((n + KSP_TILE - 1) / KSP_TILE), nbg = nblk(nn, KSP_NT);
+  const int nA = h->nactive, nn = h->g.nnodes, nb = ksp_tiles(n), nbg = nblk(nn, KSP_NT);
   const EigSmall L{m};
   eig->bytes = sizeof(double) * ((size_t)(m + 4) * n + (size_t)(m + 2) * nb + nbg + L.size());
   if (n == 0) {
@@ -7105,10 +7115,7 @@ extern "C" int nlps_gpu_tangent_lambda_max(nlps_gpu* h, const double* lumped_mas
       reserve(h, who, h->ksp_s, L.size(), "the tridiagonal state") ||
       reserve(h, who, h->ksp_bad_d, 1, "the mass check"))
     return 1;
-  if (!h->eig_h.host()) {
-    HIPCHK(h->eig_h.alloc());
-    memset(h->eig_h.host(), 0, sizeof(EigHost));
-  }
+  if (ensure_host_word(h, h->eig_h)) return 1;
   const double* md = io.in(lumped_mass);
   const double* v0d = io.in(v0);
   double* moded = io.out(mode, false);
@@ -7121,6 +7128,7 @@ extern "C" int nlps_gpu_tangent_lambda_max(nlps_gpu* h, const double* lumped_mas
   double* const s = h->ksp_s;
   EigHost* const hw = h->eig_h.target();
   EigHost* const hh = h->eig_h.host();
+  const GsSmall gso{L.h1(), L.h2(), L.wn2(), L.refine()};
   const dim3 gs(nb), bs(KSP_NT);
   const double* const nul = nullptr;
   double* const nulw = nullptr;
@@ -7151,24 +7159,9 @@ extern "C" int nlps_gpu_tangent_lambda_max(nlps_gpu* h, const double* lumped_mas
   else if (!std::isfinite(n2)) reason = NLPS_EIG_DIVERGED_NANORINF;
   for (int j = 0; !reason; j++) {
     double* const w = Q + (size_t)(j + 1) * n;
-    double* const refine = s + L.refine();
     if (eig_product(h, ps, Q + (size_t)j * n, xs, w, apart)) return 1;
     hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)apart, nbg, s + L.aj(), nulw, nul, nulw, nul);
-    // classical Gram-Schmidt against q_1 .. q_j, pass 1 (with w.w for DGKS), then pass 2 when the refine word says so
-    hipLaunchKernelGGL(k_ksp_mdot, gs, bs, 0, h->stream, (int)n, (const double*)Q, n, j + 1, 1, (const double*)w, part, nb, nul);
-    hipLaunchKernelGGL(k_ksp_finish, dim3(j + 2), bs, 0, h->stream, (const double*)part, nb, s + L.h1(), nulw, nul, nulw, nul);
-    hipLaunchKernelGGL(k_ksp_maxpy, gs, bs, 0, h->stream, (int)n, (const double*)Q, n, j + 1, (const double*)(s + L.h1()), w,
-                       part, nul);
-    hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, s + L.wn2(), nulw, nul, refine,
-                       (const double*)(s + L.h1() + j + 1));
-    hipLaunchKernelGGL(k_ksp_mdot, gs, bs, 0, h->stream, (int)n, (const double*)Q, n, j + 1, 0, (const double*)w, part, nb,
-                       (const double*)refine);
-    hipLaunchKernelGGL(k_ksp_finish, dim3(j + 1), bs, 0, h->stream, (const double*)part, nb, s + L.h2(), nulw,
-                       (const double*)refine, nulw, nul);
-    hipLaunchKernelGGL(k_ksp_maxpy, gs, bs, 0, h->stream, (int)n, (const double*)Q, n, j + 1, (const double*)(s + L.h2()), w,
-                       part, (const double*)refine);
-    hipLaunchKernelGGL(k_ksp_finish, dim3(1), bs, 0, h->stream, (const double*)part, nb, s + L.wn2(), nulw,
-                       (const double*)refine, nulw, nul);
+    krylov_orthogonalise(h, n, Q, j + 1, w, gso, part, nb, s);  // (against q_1 .. q_j)
     hipLaunchKernelGGL(k_eig_ritz, dim3(1), dim3(64), 0, h->stream, L, s, j, hw);
     hipLaunchKernelGGL(k_ksp_scale, gs, bs, 0, h->stream, (int)n, (const double*)w, w, 1.0, (const double*)(s + L.wn2()));
     HIPCHK(hipGetLastError());
@@ -7200,12 +7193,7 @@ extern "C" int nlps_gpu_tangent_lambda_max(nlps_gpu* h, const double* lumped_mas
     if (moded) HIPCHK(hipMemsetAsync(moded, 0, n * sizeof(double), h->stream));
     if (reason == NLPS_EIG_DIVERGED_NANORINF) eig->resid = NAN;
   }
-  if (io.finish()) {
-    h->err = "nlps_gpu_tangent_lambda_max: HIP error";
-    return 1;
-  }
-  if (io.back.empty()) HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
+  return vec_end(h, who, io);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -7263,11 +7251,7 @@ extern "C" int nlps_gpu_newton_solve(nlps_gpu* h, double* dU, const double* Un_d
   snes->reason = snes->iterations = snes->function_evaluations = snes->linear_iterations = 0;
   snes->fnorm0 = snes->fnorm = snes->snorm = snes->xnorm = 0.0;
   if (need_masks(h, who)) return 1;
-  if (h->halo || (h->rccl && h->rccl->world > 1)) {
-    h->err = "nlps_gpu_newton_solve: single rank only: this handle exchanges halos (a halo callback or an RCCL world > 1), "
-             "and norms across ranks would need an owner mask and an allreduce";
-    return 1;
-  }
+  if (single_rank_only(h, who, "norms")) return 1;
   if (!dU || !Un_dt || !Un_dt2 || !M || !alpha) {
     h->err = "nlps_gpu_newton_solve: dU, Un_dt, Un_dt2, M and alpha are required";
     return 1;
@@ -7292,10 +7276,7 @@ extern "C" int nlps_gpu_newton_solve(nlps_gpu* h, double* dU, const double* Un_d
       reserve(h, who, h->snes_part, (size_t)5 * nb, "the partial sums"))
     return 1;
   h->snes_nb = nb;
-  if (!h->snes_h.host()) {
-    HIPCHK(h->snes_h.alloc(SNES_H_N));
-    memset(h->snes_h.host(), 0, SNES_H_N * sizeof(double));
-  }
+  if (ensure_host_word(h, h->snes_h, SNES_H_N)) return 1;
   volatile double* const hv = h->snes_h.host();
   double* const hw = h->snes_h.target();
   double *X = h->snes_v, *Y = X + n, *W = Y + n, *F = W + n, *T = F + n;
