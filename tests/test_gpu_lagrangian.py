@@ -12,11 +12,13 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-10
 
 
-def _moved_case(ndim, material, nsteps, rng):
-    """The cloud of test_stage_functions: moving, with accelerations, displaced by a third of a cell after the initial
-    search so that the level-B search has work to do."""
+def _moved_case(ndim, material, nsteps, rng, case=None):
+    """The cloud of test_stage_functions (or `case`): moving, with accelerations, displaced by a third of a cell after the
+    initial search so that the level-B search has work to do."""
     vel = [1.0, -2.0] if ndim == 2 else [1.0, -2.0, 0.5]
-    if ndim == 2:
+    if case is not None:
+        case = dict(case, cloud={k: v.copy() if isinstance(v, np.ndarray) else v for k, v in case["cloud"].items()})
+    elif ndim == 2:
         case = make_case(2, [14, 12], [3, 3], [7, 6], material=material, velocity=vel)
     else:
         case = make_case(3, [11, 10, 9], [3, 3, 2], [5, 4, 4], material=material, velocity=vel)

@@ -22,14 +22,17 @@ HISTORY_TOL = 4.2e-7
 STATE = ("DF", "F_n1", "J_n1", "Stress", "b_e_n1")
 
 
-def _problem(ndim, law="neo-hookean", violent=False):
+def _problem(ndim, law="neo-hookean", violent=False, case=None, plane=None):
+    """case: another cloud than the two below; plane: the layer of grid nodes that is fixed, if not theirs."""
     mat = SOFT if law == "neo-hookean" else DP
-    if ndim == 2:
+    if case is None and ndim == 2:
         case = make_case(2, [12, 11], [3, 3], [5, 4], material=mat, velocity=[5.0, -40.0] if violent else [0.5, -1.0])
-    else:
+    elif case is None:
         case = make_case(3, [8, 8, 7], [3, 3, 2], [2, 2, 2], material=mat, velocity=[0.5, 0.2, -1.0])
     nsteps = 3
-    bcs = nlps().BccSet([dirichlet_plane(case, ndim - 1, 3 if ndim == 2 else 2, nsteps)])
+    if plane is None:
+        plane = 3 if ndim == 2 else 2
+    bcs = nlps().BccSet([dirichlet_plane(case, ndim - 1, plane, nsteps)])
     return case, bcs, [0.0] * (ndim - 1) + [-9.81], nsteps
 
 

@@ -21,17 +21,19 @@ def _case(ndim, material, velocity=True):
     return make_case(3, [8, 8, 7], [3, 3, 2], [2, 2, 2], material=material, velocity=vel)
 
 
-def _linearised(ndim, law, seed=13, with_oracle=True):
-    """Device (and oracle) state after one compatibility + constitutive pass at a random dU, masks at step 1."""
+def _linearised(ndim, law, seed=13, with_oracle=True, case=None, plane=3):
+    """Device (and oracle) state after one compatibility + constitutive pass at a random dU, masks at step 1.
+    case: another cloud of the law's material than _case's; plane: the row of grid nodes that is fixed."""
     mat = LAWS[law]
-    case = _case(ndim, mat)
+    if case is None:
+        case = _case(ndim, mat)
     if law == "matsuoka-nakai":
         cl = case["cloud"]
         cl["b_e_n"] = synth.frictional_states(ndim, mat, cl["x"].shape[0], seed=5)
         cl["kappa_n"][:] = mat["kappa_0"]
         cl["eps_n"][:] = mat["eps_0"]
     nsteps = 2
-    bcs_list = [dirichlet_plane(case, ndim - 1, 3, nsteps)]
+    bcs_list = [dirichlet_plane(case, ndim - 1, plane, nsteps)]
     M, P, prm, mats = oracle_setup(case)
     S = gpu_setup(case, nsteps=nsteps)
     n2m, d2m, na = masks(S, M, bcs_list, 1, nsteps)
