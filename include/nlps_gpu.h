@@ -404,10 +404,10 @@ double nlps_host_courant_dt(double CFL, double h, double Cel, const double *row 
  *   for, waits for its copy first).  nlps_host_write_particles_vtk takes them as they are.  A slot may be waited for
  *   more than once.
  * Memory (nlps_gpu_snapshot_bytes): pinned = slots x max(8, np x (8 D + 4 I)) bytes, device = pinned + 4 max(np, 1) (the
- *   inverse permutation), np the particle count at the set, D the doubles per particle of the selected fields (ndim for
- *   x, dis, vel, acc, lambda; 5 | 9 for F_n, Stress, b_e_n; 3 for Back_stress; 1 for the others), I = 1 with
- *   NLPS_SNAP_I0.  A slot's block holds the selected fields one after the other in ascending bit order, the ints of I0
- *   last.
+ *   inverse permutation, shared with the explicit loads and the step record), np the particle count at the set, D the
+ *   doubles per particle of the selected fields (ndim for x, dis, vel, acc, lambda; 5 | 9 for F_n, Stress, b_e_n; 3 for
+ *   Back_stress; 1 for the others), I = 1 with NLPS_SNAP_I0.  A slot's block holds the selected fields one after the
+ *   other in ascending bit order, the ints of I0 last.
  * Returns 1 with the reason in nlps_gpu_last_error, stores and launches nothing, and leaves the handle usable: the setter
  *   for slots outside [1, NLPS_SNAP_MAX_SLOTS], fields == 0 or a bit outside NLPS_SNAP_*, a failed allocation (the
  *   snapshots set before stay), a migrated handle (its rows are by global id); begin / wait / release / bytes with no

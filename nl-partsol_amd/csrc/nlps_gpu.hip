@@ -1749,8 +1749,8 @@ struct nlps_gpu {
   DevBuf<u64> P_mlo, P_mhi;
   std::vector<int> perm;  // sorted slot -> caller's particle index
   NView N;
-  DevBuf<unsigned char> N_active, N_seed, N_fixed;
-  DevBuf<double> N_nm, N_dU, N_force, N_accel, N_reaction;
+  DevBuf<unsigned char> N_seed;  // (active, fixed, nm and force belong to the tile-list set: ListSet)
+  DevBuf<double> N_dU, N_accel, N_reaction;
   DevBuf<double> h_avg_d;
   DevBuf<double4> beta_t2_d;  // NView::beta_t2
   DevBuf<MatD> mats_d;
@@ -1817,8 +1817,6 @@ struct nlps_gpu {
   int nt[3], ntiles;
   DevBuf<int> tile_count_d;
   DevBuf<int> tile_count2_d;  // the counters the search ahead (k5_tile) fills while tile_count_d still sizes the lists in use
-  DevBuf<int> tile_start_d;
-  DevBuf<int2> work1_d;  // compacted work list of the non-empty tiles, see TileD
   // canonical lists from per-node counters (TileTab): node_cnt[nnodes], nrank[npad], layer tables [ntiles][LMAX]
   DevBuf<int> node_cnt_d, nrank_d, tabo_d;
   DevBuf<int> tile_cursor_d;  // [ntiles + 1] list cursors of the deferred ranks (TileCnt::defer, k_fill_orders)
@@ -1835,66 +1833,106 @@ struct nlps_gpu {
   bool rehome = true;
   double adaptive_resort = 0.8, debt = 0.0;  // default budget: about one re-sort's cost
   int adaptive_min_steps = 4;
-  DevBuf<int> nwork_d;      // ranges[3 classes][begin,end] of the work list (tile_scan_block)
-  DevBuf<int> dmg_first_d, dmg_last_d;  // eigenerosion: run of every node in the I0-sorted particle list
-  DevBuf<int> dmg_first0_d, dmg_last0_d, dmg_sorted0_d;  // the same for the snapshot's closest nodes
   bool beps_snapshot = false;  // F_X0 / F_I00 hold the configuration of Initialize_Beps = true
-  // the explicit step with the damage hooks (nlps_gpu_set_explicit_damage): node runs without a sort (k_run_count /
-  // k_run_first / k_run_fill), tables of their own -- the level-B force stage rebuilds dmg_* with its sorts every call.
-  // xrun_*0: the tables of the snapshot's closest nodes, made once and again after a re-sort has renumbered the slots
-  bool explicit_damage = false;
   bool explicit_fluid = false;  // nlps_gpu_set_explicit_fluid: the explicit step of a cloud that holds the fluid law
-  // the Neumann contours of the explicit step (nlps_gpu_set_explicit_loads): one entry per contour particle
+
+  // Feature state.  Each type below is "off" as default-constructed; a setter builds a value and assigns it behind the
+  // synchronise it performs anyway, a drop assigns {}.
+  //
+  // Caller's index -> memory slot, the inverse of perm_d, for whoever addresses particles by the caller's numbering: the
+  // explicit loads, the probes of the step record, the snapshot pack.  Their setters reserve it (reserve_inv_perm: no
+  // step allocates), inv_perm() rebuilds it when a renumbering has made it stale (slots_renumbered) and it lives as long
+  // as the handle: 4 bytes per particle beside a field block of NFD doubles.
+  struct InvPerm {
+    DevBuf<int> d;  // [npad]
+    bool stale = true;
+  } inv;
+  // The Neumann contours of the explicit step (nlps_gpu_set_explicit_loads): one entry per contour particle
   // in the caller's contour order -- caller's index, contour number, A0 (3-D) -- and the traction vector of every
-  // (step, contour) with the carry-over resolved.  xl_inv_d: caller's index -> slot, rebuilt by the first step behind a
-  // re-sort (xl_inv_valid), never per step.  xl_lane_map: developer switch between the two work mappings of the kernel.
-  int xl_n = 0, xl_nloads = 0;
-  double xl_thickness = 1.0;
-  DevBuf<int> xl_ids_d, xl_load_d, xl_inv_d;
-  DevBuf<double> xl_a0_d, xl_T_d;
-  bool xl_inv_valid = false, xl_lane_map = false;
-  hipEvent_t xl_ev[2] = {};  // bracket of the kernel (timing only: slot 7 of nlps_gpu_get_timing)
-  // the step record (nlps_gpu_set_step_record; kernels in nlps_record.hpp).  rec_on is all a step looks at
-  // with no record set.  The ring rec_rows_d holds rec_capacity rows of rec_row doubles; row number g (0-based since the
-  // set) lives in slot g % rec_capacity.  The probes find their particles through xl_inv_d, the map of the explicit loads.
-  int rec_on = 0;
-  int rec_every = 1, rec_capacity = 0, rec_nsets = 0, rec_nprobes = 0, rec_row = 0, rec_probe_doubles = 0;
-  unsigned rec_fields = 0;
-  long long rec_total = 0;
-  double rec_time = 0.0;
-  DevBuf<double> rec_rows_d, rec_part_d;  // [rec_capacity][rec_row], [REC_NQ][blocks of k_rec_particles <= REC_MAX_BLOCKS]
-  DevBuf<int> rec_probes_d;               // [rec_nprobes] caller's indices
-  // the particle snapshot (nlps_gpu_set_snapshots; kernel in nlps_snapshot.hpp).  Per slot one staging block
-  // on the device and its pinned twin, snap_bytes each, made by the setter for snap_cap particles; the pack kernel runs on
-  // the handle's stream, the one copy of a slot on snap_stream -- a stream of the snapshots' own: `side` is joined back
-  // into the handle's stream by every async step, which would then wait for the copy.
+  // (step, contour) with the carry-over resolved.
+  struct Loads {
+    int n = 0, nloads = 0;
+    double thickness = 1.0;
+    DevBuf<int> ids, load;
+    DevBuf<double> a0, T;
+  } loads;
+  // (not part of a set of loads: the developer switch between the two work mappings of the kernel, and the bracket of
+  // the kernel -- timing only, slot 7 of nlps_gpu_get_timing -- which is made once and outlives every set)
+  bool loads_lane_map = false;
+  hipEvent_t loads_ev[2] = {};
+  // The step record (nlps_gpu_set_step_record; kernels in nlps_record.hpp).  `on` is all a step looks at
+  // with no record set.  The ring `rows` holds `capacity` rows of `row` doubles; row number g (0-based since the set)
+  // lives in slot g % capacity.  The probes find their particles through inv_perm().
+  struct StepRecord {
+    int on = 0;
+    int every = 1, capacity = 0, nsets = 0, nprobes = 0, row = 0, probe_doubles = 0;
+    unsigned fields = 0;
+    long long total = 0;
+    double time = 0.0;
+    DevBuf<double> rows, part;  // [capacity][row], [REC_NQ][blocks of k_rec_particles <= REC_MAX_BLOCKS]
+    DevBuf<int> probes;         // [nprobes] caller's indices
+  } rec;
+  // The particle snapshot (nlps_gpu_set_snapshots; kernel in nlps_snapshot.hpp).  Per slot one staging block
+  // on the device and its pinned twin, `bytes` each, made by the setter for `cap` particles; the pack kernel runs on the
+  // handle's stream, the one copy of a slot on `stream` -- a stream of the snapshots' own: `side` is joined back into the
+  // handle's stream by every async step, which would then wait for the copy.
   struct SnapSlot {
     DevBuf<double> dev;
     Pinned<double> pin;
-    hipEvent_t packed = nullptr, copied = nullptr;  // behind the pack on the handle's stream; behind the copy on snap_stream
+    hipEvent_t packed = nullptr, copied = nullptr;  // behind the pack on the handle's stream; behind the copy on the snapshots'
     int state = 0;                                  // 0 free, 1 begun (in flight or waiting for its release)
     int tag = 0, np = 0;
+    SnapSlot() = default;
+    SnapSlot(SnapSlot&& o) noexcept { *this = std::move(o); }
+    SnapSlot& operator=(SnapSlot&& o) noexcept {  // (a swap: what this one held goes with o)
+      dev.swap(o.dev), pin.swap(o.pin), std::swap(packed, o.packed), std::swap(copied, o.copied);
+      std::swap(state, o.state), std::swap(tag, o.tag), std::swap(np, o.np);
+      return *this;
+    }
+    ~SnapSlot() {
+      if (packed) (void)hipEventDestroy(packed);
+      if (copied) (void)hipEventDestroy(copied);
+    }
+    hipError_t create(size_t words) {
+      hipError_t e = dev.reserve(words);
+      if (e == hipSuccess) e = pin.alloc(words);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&packed, hipEventDisableTiming);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&copied, hipEventDisableTiming);
+      return e;
+    }
   };
-  int snap_slots = 0, snap_cap = 0;
-  unsigned snap_fields = 0;
-  size_t snap_bytes = 0;
-  SnapSlot snap[NLPS_SNAP_MAX_SLOTS];
-  SideStream snap_stream;
-  // The pack kernel runs one thread per caller's index through the inverse permutation snap_inv_d (made by the setter,
-  // rebuilt by the first begin behind a re-sort): gathered reads, coalesced writes, 0.33 against 0.40 ms at 1 M particles
-  // for one thread per memory slot, which nlps_gpu_debug_option "snapshot_by_caller" 0 keeps for comparison.
-  bool snap_by_caller = true, snap_inv_valid = false;
-  DevBuf<int> snap_inv_d;
-  // the fused damage residual (nlps_gpu_set_implicit_damage): the same tables; the runs of the current closest nodes are
-  // built at the first evaluation and reused while nothing has moved, reordered or re-listed particles (xrun_gen == tan_gen)
-  bool implicit_damage = false;
-  unsigned long long xrun_gen = 0;
-  int xrun_builds = 0, dmg_fused_evals = 0;  // developer read-out (nlps_gpu_debug_damage_counters)
-  DevBuf<int> xrun_cnt_d, xrun_cursor_d, xrun_rank_d;              // [nnodes], [1], [npad]
-  DevBuf<int> xrun_first_d, xrun_last_d, xrun_sorted_d;            // [nnodes], [nnodes], [npad]
-  DevBuf<int> xrun_first0_d, xrun_last0_d, xrun_sorted0_d;
-  bool xrun_tables0 = false;
-  bool xrun_tables = false;  // the runs of the current closest nodes have been built since the last drop (read-out only)
+  struct Snapshots {
+    SideStream stream;  // (first: assigning or destroying a Snapshots waits for the copies in flight before a slot is freed)
+    int slots = 0, cap = 0;
+    unsigned fields = 0;
+    size_t bytes = 0;
+    SnapSlot slot[NLPS_SNAP_MAX_SLOTS];
+  } snap;
+  // The pack kernel runs one thread per caller's index through inv_perm(): gathered reads, coalesced writes, 0.33 against
+  // 0.40 ms at 1 M particles for one thread per memory slot, which nlps_gpu_debug_option "snapshot_by_caller" 0 keeps for
+  // comparison (a developer switch like loads_lane_map: it outlives every set).
+  bool snap_by_caller = true;
+  // The node runs of the damage hooks.  The explicit step with the hooks (nlps_gpu_set_explicit_damage) builds them without
+  // a sort (k_run_count / k_run_first / k_run_fill) into tables of its own -- the level-B force stage rebuilds its b_* tables
+  // with its sorts every call.  *0: the tables of the snapshot's closest nodes, made once and again after a re-sort has
+  // renumbered the slots.  The fused damage residual (nlps_gpu_set_implicit_damage) uses the same tables; the runs of the
+  // current closest nodes are built at the first evaluation and reused while nothing has moved, reordered or re-listed
+  // particles (gen == tan_gen).
+  struct DamageRuns {
+    DevBuf<int> b_first, b_last;              // level B, eigenerosion: run of every node in the I0-sorted particle list
+    DevBuf<int> b_first0, b_last0, b_sorted0;  // the same for the snapshot's closest nodes
+    unsigned long long gen = 0;
+    int builds = 0, fused_evals = 0;  // developer read-out (nlps_gpu_debug_damage_counters)
+    DevBuf<int> cnt, cursor, rank;    // [nnodes], [1], [npad]
+    DevBuf<int> first, last, sorted;  // [nnodes], [nnodes], [npad]
+    DevBuf<int> first0, last0, sorted0;
+    bool tables0 = false;
+    bool tables = false;  // the runs of the current closest nodes have been built since the last drop (read-out only)
+    // Run tables built in arrival order are never summed over in the deterministic mode, and sorted ones are not kept for
+    // the atomic path either: both switches drop every cached table.  The buffers stay.
+    void drop() { gen = 0, tables0 = tables = false; }
+  } dmg;
+  bool explicit_damage = false, implicit_damage = false;
   // nlps_gpu_set_deterministic_damage: in deterministic mode the runs are sorted behind k_run_fill (k_run_sort), the force
   // half runs one wave per tile into slabs (k3f_wave) and det_implicit admits the damage cloud
   bool det_damage = false;
@@ -1978,26 +2016,31 @@ struct nlps_gpu {
   int snes_nb = 0;
   // implicit time step (nlps_gpu_newmark_step): M, Un_dt, Un_dt2, dU, dU_dt, dU_dt2, masked [N_A d] each
   DevBuf<double> nm_v;
-  DevBuf<int> order_d;
-  // canonical (layer, closest node) order of every tile list each step for the LDS-atomic-bound K2 and K3; the
+  // The tile-list set: what the list stage of a step writes and its tile kernels read.  It exists twice (below).
+  // order2: canonical (layer, closest node) order of every tile list each step for the LDS-atomic-bound K2 and K3; the
   // memory-bound K5 keeps the lists as binned.  13 us per step at 1 M particles.  A freshly sorted cloud has its lists in
   // that order already (0.685 vs 0.677 ms/step), but once particles have changed closest node -- 45 steps into the bench
   // cloud's fall -- K2 runs 0.231 instead of 0.300 ms and K3 0.260 instead of 0.304, and the stirred cloud of DESIGN.md
   // 0.84 instead of 0.95 ms/step
-  DevBuf<int> order2_d;  // canonical tile lists (k_fill_orders; k_tile_order in deterministic mode), allocated on first use
+  struct ListSet {
+    DevBuf<int2> work;   // compacted work list of the non-empty tiles, see TileD
+    DevBuf<int> nwork;   // ranges[3 classes][begin,end] of the work list (tile_scan_block)
+    DevBuf<int> start;   // [ntiles + 1] first list position of every tile
+    DevBuf<int> order;   // tile lists as binned
+    DevBuf<int> order2;  // canonical tile lists (k_fill_orders; k_tile_order in deterministic mode), allocated on first use
+    DevBuf<unsigned char> active, fixed;  // NView::active, fixed
+    DevBuf<double> nm, force;             // NView::nm, force: the nodal accumulators the list stage resets
+  };
   // Async lists (the folded one-rank explicit step, nlps_gpu_explicit_step): the search of the next step runs as a
   // kernel of its own between K3 and K5 (k_search_ahead), and the activation and list kernels of the next step run on
-  // `side` while K5 runs on the handle's stream.  What they write and K5 still reads exists twice: the tile-list set
-  // (work list, its ranges, starts, both orders), the active flags and the nodal accumulators they reset; the step that
-  // finds lists_ready exchanges the sets (and the two closest-node arrays) instead of launching those kernels
-  // (adopt_ready_lists).  The names without a 2 are always the set in use, for every reader.
+  // `side` while K5 runs on the handle's stream.  What they write and K5 still reads exists twice, as two ListSets; the
+  // step that finds lists_ready exchanges the sets (and the two closest-node arrays) instead of launching those kernels
+  // (adopt_ready_lists).  `lists` is always the set in use, for every reader, and h->N views it (bind_lists); `twin` is
+  // made at the first step that builds lists on the side stream (ensure_list_twins).
+  ListSet lists, twin;
   SideStream side;
   bool async_lists = true;   // nlps_gpu_debug_option "async_lists"
   bool lists_ready = false;  // `ahead`, and the twin set holds the lists, flags and reset accumulators made from it
-  DevBuf<int2> work1_2_d;
-  DevBuf<int> nwork2_d, tile_start2_d, order_2_d, order2_2_d;
-  DevBuf<unsigned char> N_active2, N_fixed2;
-  DevBuf<double> N_nm2, N_force2;
   // The deferred move (k_search_ahead): an async step with the step record off whose successor does not start with a
   // re-sort runs K5 without the move x += d_dis, dis += d_dis and has the search mark the particles K5 would have moved.
   // K2 of the next step applies the marks of the particles it lists; while move_pending, everything else that reads or
@@ -2380,14 +2423,14 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
   // nodal arrays
   size_t nn = (size_t)g.nnodes;
   int ND = g.nd;
-  if (dev_alloc(h, h->N_active, nn, &h->N.active)) return 1;
+  if (dev_alloc(h, h->lists.active, nn, &h->N.active)) return 1;
   if (dev_alloc(h, h->N_seed, nn, &h->N.seed)) return 1;
-  if (dev_alloc(h, h->N_nm, nn * (1 + ND), &h->N.nm)) return 1;
+  if (dev_alloc(h, h->lists.nm, nn * (1 + ND), &h->N.nm)) return 1;
   if (dev_alloc(h, h->N_dU, nn * ND, &h->N.dU)) return 1;
-  if (dev_alloc(h, h->N_force, nn * ND, &h->N.force)) return 1;
+  if (dev_alloc(h, h->lists.force, nn * ND, &h->N.force)) return 1;
   if (dev_alloc(h, h->N_accel, nn * ND, &h->N.accel)) return 1;
   if (dev_alloc(h, h->N_reaction, nn * ND, &h->N.reaction)) return 1;
-  if (dev_alloc(h, h->N_fixed, nn * ND, &h->N.fixed)) return 1;
+  if (dev_alloc(h, h->lists.fixed, nn * ND, &h->N.fixed)) return 1;
   if (dev_alloc(h, h->h_avg_d, nn)) return 1;
   if (dev_alloc(h, h->n2m_d, nn)) return 1;
   if (dev_alloc(h, h->d2m_d, nn * ND)) return 1;
@@ -2505,12 +2548,12 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
   if (dev_alloc(h, h->P_mhi, h->P.npad, &h->P.mhi)) return 1;
   if (dev_alloc(h, h->P_tile, h->P.npad, &h->P.tile)) return 1;
   if (dev_alloc(h, h->P_rank, h->P.npad, &h->P.rank)) return 1;
-  if (dev_alloc(h, h->order_d, h->P.npad)) return 1;
+  if (dev_alloc(h, h->lists.order, h->P.npad)) return 1;
   if (dev_alloc(h, h->tile_count_d, (size_t)h->ntiles + 1)) return 1;
   if (dev_alloc(h, h->tile_count2_d, (size_t)h->ntiles + 1)) return 1;
-  if (dev_alloc(h, h->tile_start_d, (size_t)h->ntiles + 1)) return 1;
-  if (dev_alloc(h, h->work1_d, (size_t)h->ntiles)) return 1;
-  if (dev_alloc(h, h->nwork_d, 6)) return 1;
+  if (dev_alloc(h, h->lists.start, (size_t)h->ntiles + 1)) return 1;
+  if (dev_alloc(h, h->lists.work, (size_t)h->ntiles)) return 1;
+  if (dev_alloc(h, h->lists.nwork, 6)) return 1;
 #if NLPS_DEV
   if (const char* e = getenv("NLPS_ADAPTIVE_RESORT")) h->adaptive_resort = atof(e);  // (0 = off)
 #endif
@@ -2604,6 +2647,23 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
   return 0;
 }
 
+// The particles have changed memory slots (the re-sort, and a migration through it).  Whoever caches something per slot
+// registers here; at present:
+//   the host copy of perm_d (refresh_perm) and the inverse permutation (inv_perm: loads, record probes, snapshot pack);
+//   the tile lists, and the per-particle tile / rank of a search done ahead, which belong to the old slots;
+//   the adaptive re-sort: the slots have new owners, the next search records their tiles (TileCnt::home);
+//   the node runs of the damage hooks, which hold slot numbers (tables: read-out only, until the next build).
+static void slots_renumbered(nlps_gpu* h) {
+  h->perm_dirty = true;
+  h->inv.stale = true;
+  h->binned = false;
+  h->ahead = h->lists_ready = false;
+  h->rehome = true;
+  h->debt = 0.0;
+  h->steps_since_sort = 0;
+  h->dmg.tables0 = h->dmg.tables = false;
+}
+
 // Physical re-sort of every particle array by (tile of I0, corner type, I0 in tile).
 // live_only: called at the head of an explicit step -- the fields that step rewrites in full before anything reads them
 // (d_dis, the n+1 slots of F and b_e, DF, tau, J_n+1, W, kappa_n+1, eps_n+1: 43 of the 89 components) are not moved.
@@ -2612,11 +2672,11 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
   const int np = h->P.np;
   if (np == 0) return 0;
   if (materialise_move(h)) return 1;  // (d_dis does not travel with live_only, and the marks are per slot)
-  // The tile lists of the last step in canonical order (order2_d: layer r = the r-th particle of every closest node,
+  // The tile lists of the last step in canonical order (lists.order2: layer r = the r-th particle of every closest node,
   // nodes in lattice order) ARE the memory order the kernels want -- each wave then reads 64 consecutive slots that hit
   // 64 distinct window rows -- so the periodic re-sort of the fused step takes them as its permutation: no keys, no
   // radix sort.  Otherwise (first sort, migration, level-B callers): sort by (tile, corner type, node).
-  const bool from_lists = !leaving && live_only && h->binned && h->order2_d && h->ntw > 0;
+  const bool from_lists = !leaving && live_only && h->binned && h->lists.order2 && h->ntw > 0;
   if (!from_lists) {
     TileCnt tc;
     for (int a = 0; a < 3; a++) tc.nt[a] = h->nt[a];
@@ -2634,12 +2694,12 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
     HIPCHK(hipMemsetAsync(h->mig_cnt_d, 0, sizeof(int), h->stream));
     HIPCHK(hipMemsetAsync(listed, 0, (size_t)np, h->stream));
     const int last = h->tile0 + h->ntw - 1;
-    hipLaunchKernelGGL(k_mark_listed, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, (const int*)h->tile_start_d + last,
-                       (const int*)h->tile_count_d + last, (const int*)h->order2_d, listed);
+    hipLaunchKernelGGL(k_mark_listed, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, (const int*)h->lists.start + last,
+                       (const int*)h->tile_count_d + last, (const int*)h->lists.order2, listed);
     hipLaunchKernelGGL(k_append_unlisted, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, (const unsigned char*)listed,
-                       (const int*)h->tile_start_d + last, (const int*)h->tile_count_d + last, h->mig_cnt_d, h->order2_d);
+                       (const int*)h->lists.start + last, (const int*)h->tile_count_d + last, h->mig_cnt_d, h->lists.order2);
   }
-  const int* idx = from_lists ? h->order2_d : h->sval2_d;  // new slot -> old slot
+  const int* idx = from_lists ? h->lists.order2 : h->sval2_d;  // new slot -> old slot
   const size_t npad = h->P.npad;
   const int nf = h->level_b_fields ? (int)NFD : (int)F_CEP;  // C_ep and the rate tensors only exist for level B
   // the field block moves into its twin in one launch and the two swap roles (no copy back; the twin costs a second
@@ -2685,16 +2745,7 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
                        (const unsigned long long*)su);
   }
   HIPCHK(hipGetLastError());
-  h->perm_dirty = true;
-  h->binned = false;
-  h->ahead = h->lists_ready = false;  // (the per-particle tile / rank of a search done ahead belong to the old slots)
-  h->steps_since_sort = 0;
-  h->rehome = true;  // the slots have new owners: the next search records their tiles
-  h->debt = 0.0;
-  h->xrun_tables0 = false;  // (slot numbers)
-  h->xrun_tables = false;   // (read-out: the runs of the current closest nodes hold the old slot numbers until the next build)
-  h->xl_inv_valid = false;  // (the caller's index -> slot map of the explicit loads)
-  h->snap_inv_valid = false;
+  slots_renumbered(h);
   return 0;
 }
 
@@ -2824,7 +2875,7 @@ extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_option(nlps
   else if (k == "defer_move_min") h->defer_move_min = (int)value;  // deferred move: the smallest cloud that defers (tests: 0)
   else if (k == "async_lists") h->async_lists = value != 0;      // one-rank folded step: next step's lists on the side stream (1) or in front of K2 (0)
   else if (k == "tangent_symmetric") h->tangent_symmetric = value != 0;  // Neo-Hookean clouds: half rows + mirror (1) or every pair (0)
-  else if (k == "loads_lane_map") h->xl_lane_map = value != 0;  // explicit loads: one lane per contour particle (1) or one wave (0)
+  else if (k == "loads_lane_map") h->loads_lane_map = value != 0;  // explicit loads: one lane per contour particle (1) or one wave (0)
   else if (k == "snapshot_by_caller") h->snap_by_caller = value != 0;  // snapshot pack: one thread per caller's index (1) or per slot (0)
   else {
     h->err = "nlps_gpu_debug_option: unknown option " + k;
@@ -2851,14 +2902,14 @@ extern "C" int nlps_gpu_set_law_launch_mode(nlps_gpu* h, int mode) {
 }
 // every table of the node runs (both damage setters), so that neither a step nor a residual evaluation allocates
 static int xrun_alloc(nlps_gpu* h) {
-  if (!h->xrun_cnt_d) {
+  if (!h->dmg.cnt) {
     const size_t nn = (size_t)h->g.nnodes, npad = h->P.npad;
-    if (dev_alloc(h, h->xrun_cnt_d, nn) || dev_alloc(h, h->xrun_cursor_d, 1) || dev_alloc(h, h->xrun_rank_d, npad)) return 1;
-    if (dev_alloc(h, h->xrun_first_d, nn) || dev_alloc(h, h->xrun_last_d, nn) || dev_alloc(h, h->xrun_sorted_d, npad)) return 1;
+    if (dev_alloc(h, h->dmg.cnt, nn) || dev_alloc(h, h->dmg.cursor, 1) || dev_alloc(h, h->dmg.rank, npad)) return 1;
+    if (dev_alloc(h, h->dmg.first, nn) || dev_alloc(h, h->dmg.last, nn) || dev_alloc(h, h->dmg.sorted, npad)) return 1;
     if (!h->P.softening &&
-        (dev_alloc(h, h->xrun_first0_d, nn) || dev_alloc(h, h->xrun_last0_d, nn) || dev_alloc(h, h->xrun_sorted0_d, npad)))
+        (dev_alloc(h, h->dmg.first0, nn) || dev_alloc(h, h->dmg.last0, nn) || dev_alloc(h, h->dmg.sorted0, npad)))
       return 1;
-    HIPCHK(hipMemsetAsync(h->xrun_cnt_d, 0, nn * sizeof(int), h->stream));  // (k_run_first leaves the counters at zero)
+    HIPCHK(hipMemsetAsync(h->dmg.cnt, 0, nn * sizeof(int), h->stream));  // (k_run_first leaves the counters at zero)
   }
   return 0;
 }
@@ -2900,17 +2951,10 @@ extern "C" int nlps_gpu_set_implicit_damage(nlps_gpu* h, int on) {
   }
   if (on && xrun_alloc(h)) return 1;
   h->implicit_damage = on != 0;
-  h->xrun_gen = 0;
+  h->dmg.gen = 0;
   return 0;
 }
 
-// run tables built in arrival order are never summed over in the deterministic mode, and sorted ones are not kept for
-// the atomic path either: both switches drop every cached table
-static void xrun_drop(nlps_gpu* h) {
-  h->xrun_gen = 0;
-  h->xrun_tables0 = false;
-  h->xrun_tables = false;
-}
 static int det_slab_reserve(nlps_gpu* h, const char* who);  // (defined with det_prepare)
 extern "C" int nlps_gpu_set_deterministic_damage(nlps_gpu* h, int on) {
   if (!h->P.erosion) {
@@ -2922,13 +2966,13 @@ extern "C" int nlps_gpu_set_deterministic_damage(nlps_gpu* h, int on) {
   // allocates, whichever switch comes first)
   if (on && (xrun_alloc(h) || det_slab_reserve(h, "nlps_gpu_set_deterministic_damage"))) return 1;
   h->det_damage = on != 0;
-  xrun_drop(h);
+  h->dmg.drop();
   return 0;
 }
 
 extern "C" int nlps_gpu_set_deterministic(nlps_gpu* h, int on) {
   h->deterministic = on != 0;
-  xrun_drop(h);
+  h->dmg.drop();
   h->ahead = h->lists_ready = false;
   h->rehome = true;
   h->debt = 0.0;
@@ -2963,7 +3007,7 @@ extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_displaced(n
 // first / last [nnodes], sorted[np].  Returns 1 when that table has not been built (or was dropped by a mode switch).
 extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_damage_runs(nlps_gpu* h, int snapshot, int* key, int* first,
                                                                                  int* last, int* sorted) {
-  const bool have = snapshot ? (h->xrun_tables0 && h->xrun_sorted0_d) : (h->xrun_tables && h->xrun_sorted_d);
+  const bool have = snapshot ? (h->dmg.tables0 && h->dmg.sorted0) : (h->dmg.tables && h->dmg.sorted);
   if (!have || h->P.np <= 0) {
     h->err = "nlps_gpu_debug_damage_runs: no such run table has been built";
     return 1;
@@ -2976,31 +3020,30 @@ extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_damage_runs
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(key, kd.get(), np * sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(first, snapshot ? h->xrun_first0_d.get() : h->xrun_first_d.get(), nn * sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(last, snapshot ? h->xrun_last0_d.get() : h->xrun_last_d.get(), nn * sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(sorted, snapshot ? h->xrun_sorted0_d.get() : h->xrun_sorted_d.get(), np * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(first, snapshot ? h->dmg.first0.get() : h->dmg.first.get(), nn * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(last, snapshot ? h->dmg.last0.get() : h->dmg.last.get(), nn * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(sorted, snapshot ? h->dmg.sorted0.get() : h->dmg.sorted.get(), np * sizeof(int), hipMemcpyDeviceToHost));
   return 0;
 }
 
 // developer read-out: how often the node runs of the current closest nodes were built, and how many residual evaluations
 // took the fused damage form (tests: the runs are reused inside a solve; NLPS_LAGR_SEPARATE stays on the separate stages)
 extern "C" __attribute__((visibility("default"))) int nlps_gpu_debug_damage_counters(nlps_gpu* h, int* run_builds, int* fused_evaluations) {
-  *run_builds = h->xrun_builds;
-  *fused_evaluations = h->dmg_fused_evals;
+  *run_builds = h->dmg.builds;
+  *fused_evaluations = h->dmg.fused_evals;
   return 0;
 }
 
-static void snap_drop(nlps_gpu* h);  // (defined with nlps_gpu_set_snapshots)
 extern "C" int nlps_gpu_destroy(nlps_gpu* h) {
   if (!h) return 0;
   (void)nlps_gpu_rccl_detach(h);
-  snap_drop(h);  // (waits for the copies in flight)
+  h->snap = {};  // (waits for the copies in flight)
   (void)materialise_move(h);  // (nothing reads it any more; the handle just never dies with a state half written)
   (void)hipStreamSynchronize(h->stream);
   for (int i = 0; i < 8; i++) (void)hipEventDestroy(h->ev[i]);
   for (hipEvent_t e : h->evw)
     if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h->xl_ev)
+  for (hipEvent_t e : h->loads_ev)
     if (e) (void)hipEventDestroy(e);
   // the members free their memory here: after the synchronise above, before the stream they were used on goes
   const hipStream_t owned = h->own_stream ? h->stream : nullptr;
@@ -3866,15 +3909,37 @@ static TileD tile_view(nlps_gpu* h, int cls = 0) {  // cls: 0 all tiles, 1 bound
   td.sig_cnt = nullptr;
   td.sig_flag = nullptr;
   td.sig_seq = 0;
-  td.work = h->work1_d;
-  td.range = h->nwork_d + 2 * cls;
+  td.work = h->lists.work;
+  td.range = h->lists.nwork + 2 * cls;
   td.phase = h->phase_d;
-  td.start = h->tile_start_d;
+  td.start = h->lists.start;
   td.count = h->tile_count_d;
-  td.order_m = h->order_d;
-  td.order = h->order2_d;
+  td.order_m = h->lists.order;
+  td.order = h->lists.order2;
   return td;
 }
+// What the kernels that BUILD a list set take (k_dilate_scan, k_fill_orders): the nodal view with the flags and
+// accumulators of that set (the seeds are the search's, whichever set) and the scan arguments.  count: the tile counters
+// that size the set; cursor: TileScanArgs::cursor.
+struct ListBuild {
+  NView N;
+  TileScanArgs ts;
+};
+static NView list_nview(const nlps_gpu* h, const nlps_gpu::ListSet& s) {
+  NView N = h->N;
+  N.active = s.active;
+  N.fixed = s.fixed;
+  N.nm = s.nm;
+  N.force = s.force;
+  return N;
+}
+static ListBuild list_build(nlps_gpu* h, const nlps_gpu::ListSet& s, const int* count, int* cursor) {
+  const int TB = h->nd == 3 ? TileCfg<3>::TB : TileCfg<2>::TB;
+  return {list_nview(h, s), {count + h->tile0, s.start + h->tile0, h->ntw, h->tile0, h->ntiles / h->nt[h->nd - 1], TB,
+                             h->band_lo, h->band_hi, s.work, s.nwork, cursor}};
+}
+// h->N views the set in use
+static void bind_lists(nlps_gpu* h) { h->N = list_nview(h, h->lists); }
 
 // S1: closest node + activation (+ binning of the particles to I0-tiles when `tiled`), then lists,
 // beta and the Newton iteration (+ predictor and P2G of mass / m*dD when `p2g`, tiled form only)
@@ -3919,12 +3984,12 @@ static bool det_implicit(const nlps_gpu* h) {
 // exact), so no sum ever runs over a non-exact list.  An exact list is a valid canonical list for every other kernel.
 static int det_prepare(nlps_gpu* h, const char* who) {
   if (!h->lists_exact) {
-    if (!h->binned || !h->order2_d) {
+    if (!h->binned || !h->lists.order2) {
       h->err = std::string(who) + ": deterministic mode needs tile lists: call nlps_gpu_local_search() first";
       return 1;
     }
-    LAUNCH_ND_BLK((k_tile_order<2, true>), (k_tile_order<3, true>), h->ntw, 256, h->P, h->g, tile_view(h, 0), (const int*)h->order_d,
-                  h->order2_d);
+    LAUNCH_ND_BLK((k_tile_order<2, true>), (k_tile_order<3, true>), h->ntw, 256, h->P, h->g, tile_view(h, 0), (const int*)h->lists.order,
+                  h->lists.order2);
     HIPCHK(hipGetLastError());
     h->lists_exact = true;
   }
@@ -4086,36 +4151,21 @@ static void launch_k2(nlps_gpu* h, bool p2g, int cls, double dt, double gamma_nm
 
 // Async lists: the twin set (see nlps_gpu::side), made at the first step that builds lists on the side stream
 static int ensure_list_twins(nlps_gpu* h) {
-  if (h->order_2_d) return 0;
+  nlps_gpu::ListSet& t = h->twin;
+  if (t.order) return 0;
   const size_t nn = (size_t)h->g.nnodes, ND = (size_t)h->nd;
-  if (dev_alloc(h, h->work1_2_d, (size_t)h->ntiles)) return 1;
-  if (dev_alloc(h, h->nwork2_d, 6)) return 1;
-  if (dev_alloc(h, h->tile_start2_d, (size_t)h->ntiles + 1)) return 1;
-  if (dev_alloc(h, h->order2_2_d, h->P.npad)) return 1;
-  if (dev_alloc(h, h->N_active2, nn)) return 1;
-  if (dev_alloc(h, h->N_fixed2, nn * ND)) return 1;
-  if (dev_alloc(h, h->N_nm2, nn * (1 + ND))) return 1;
-  if (dev_alloc(h, h->N_force2, nn * ND)) return 1;
-  if (dev_alloc(h, h->order_2_d, h->P.npad)) return 1;
-  return 0;
+  if (dev_alloc(h, t.work, (size_t)h->ntiles) || dev_alloc(h, t.nwork, 6) || dev_alloc(h, t.start, (size_t)h->ntiles + 1)) return 1;
+  if (dev_alloc(h, t.order2, h->P.npad)) return 1;
+  if (dev_alloc(h, t.active, nn) || dev_alloc(h, t.fixed, nn * ND)) return 1;
+  if (dev_alloc(h, t.nm, nn * (1 + ND)) || dev_alloc(h, t.force, nn * ND)) return 1;
+  return dev_alloc(h, t.order, h->P.npad);  // (last: its presence says the twin is complete)
 }
 // The step that finds the lists of its search built (lists_ready): the twin set becomes the set in use.  The closest
 // nodes of that search, I0n, hold a value for every particle (k_search_ahead), so they are adopted by exchanging the
 // two arrays; the tile counters change places as after any search done ahead (search_and_lists).
 static void adopt_ready_lists(nlps_gpu* h) {
-  h->work1_d.swap(h->work1_2_d);
-  h->nwork_d.swap(h->nwork2_d);
-  h->tile_start_d.swap(h->tile_start2_d);
-  h->order_d.swap(h->order_2_d);
-  h->order2_d.swap(h->order2_2_d);
-  h->N_active.swap(h->N_active2);
-  h->N_fixed.swap(h->N_fixed2);
-  h->N_nm.swap(h->N_nm2);
-  h->N_force.swap(h->N_force2);
-  h->N.active = h->N_active;
-  h->N.fixed = h->N_fixed;
-  h->N.nm = h->N_nm;
-  h->N.force = h->N_force;
+  std::swap(h->lists, h->twin);
+  bind_lists(h);
   h->P_I0.swap(h->P_I0n);
   h->P.I0 = h->P_I0;
   h->P.I0n = h->P_I0n;
@@ -4153,9 +4203,7 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
     else LAUNCH_ND((k_search<2>), (k_search<3>), nblk(np), h->P, h->g, h->N, h->rank1_d, tc, searched ? 0 : 1);
   }
   {
-    const int TB = h->nd == 3 ? TileCfg<3>::TB : TileCfg<2>::TB;
-    TileScanArgs ts{h->tile_count_d + h->tile0, h->tile_start_d + h->tile0, h->ntw, h->tile0, h->ntiles / h->nt[h->nd - 1], TB,
-                    h->band_lo, h->band_hi, h->work1_d, h->nwork_d, deferred ? h->tile_cursor_d + h->tile0 : nullptr};
+    const TileScanArgs ts = list_build(h, h->lists, h->tile_count_d, deferred ? h->tile_cursor_d + h->tile0 : nullptr).ts;
     const int nb = 1 + (h->nwn + 1023) / 1024 + (node_lists(h) ? (h->ntw + 15) / 16 : 0);
     int* fo = (h->adaptive_resort > 0.0 && !h->deterministic) ? h->foreign_d : nullptr;
     LAUNCH_ND_BLK(k_dilate_scan<2>, k_dilate_scan<3>, nb, 1024, h->n0, h->nwn, h->g, h->N, ts, fo, h->foreign_h.host(), tile_tab(h),
@@ -4163,20 +4211,20 @@ static int search_and_lists(nlps_gpu* h, bool init, bool p2g, double dt, double 
   }
   HIPCHK(hipGetLastError());
   if (halo(h, h->N.active, 1, 1, 1, overlap ? 1 : 0)) return 1;
-  if (!h->order2_d) {
-    HIPCHK(h->order2_d.reserve(h->P.npad));
-    HIPCHK(hipMemsetAsync(h->order2_d, 0, h->P.npad * sizeof(int), h->stream));
+  if (!h->lists.order2) {
+    HIPCHK(h->lists.order2.reserve(h->P.npad));
+    HIPCHK(hipMemsetAsync(h->lists.order2, 0, h->P.npad * sizeof(int), h->stream));
   }
   if (node_lists(h)) {  // both lists in one pass, the canonical one through the layer tables of this step (TileTab)
     const int* adopt = ahead ? h->P.I0n : nullptr;
-    LAUNCH_ND(k_fill_orders<2>, k_fill_orders<3>, nblk(np), np, h->P.tile, h->P.rank, h->nrank_d, h->P.I0, adopt, h->tile_start_d,
-              h->g, tile_tab(h), h->order_d, h->order2_d, deferred ? h->tile_cursor_d : (int*)nullptr, h->node_cnt_d);
+    LAUNCH_ND(k_fill_orders<2>, k_fill_orders<3>, nblk(np), np, h->P.tile, h->P.rank, h->nrank_d, h->P.I0, adopt, h->lists.start,
+              h->g, tile_tab(h), h->lists.order, h->lists.order2, deferred ? h->tile_cursor_d : (int*)nullptr, h->node_cnt_d);
   } else {  // deterministic mode: the exact per-tile sort
     if (ahead) hipLaunchKernelGGL(k_commit_I0, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, (const int*)h->P.I0n, h->P.I0);
-    hipLaunchKernelGGL(k_fill_order, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, h->P.tile, h->P.rank, h->tile_start_d,
-                       h->order_d);
-    LAUNCH_ND_BLK((k_tile_order<2, true>), (k_tile_order<3, true>), h->ntw, 256, h->P, h->g, tile_view(h, 0), (const int*)h->order_d,
-                  h->order2_d);
+    hipLaunchKernelGGL(k_fill_order, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, h->P.tile, h->P.rank, h->lists.start,
+                       h->lists.order);
+    LAUNCH_ND_BLK((k_tile_order<2, true>), (k_tile_order<3, true>), h->ntw, 256, h->P, h->g, tile_view(h, 0), (const int*)h->lists.order,
+                  h->lists.order2);
   }
   h->lists_exact = !node_lists(h);
   HIPCHK(hipGetLastError());
@@ -4464,44 +4512,44 @@ extern "C" int nlps_gpu_internal_forces(nlps_gpu* h, double* R) {
   if (h->P.erosion && h->P.np > 0) {  // damage of every particle, then its Kirchhoff stress scaled in place (:1313-1331)
     const int np = h->P.np;
     const size_t nn = (size_t)h->g.nnodes;
-    if (!h->dmg_first_d) {
-      HIPCHK(h->dmg_first_d.reserve(nn));
-      HIPCHK(h->dmg_last_d.reserve(nn));
+    if (!h->dmg.b_first) {
+      HIPCHK(h->dmg.b_first.reserve(nn));
+      HIPCHK(h->dmg.b_last.reserve(nn));
     }
-    HIPCHK(hipMemsetAsync(h->dmg_first_d, 0, nn * sizeof(int), h->stream));
-    HIPCHK(hipMemsetAsync(h->dmg_last_d, 0, nn * sizeof(int), h->stream));
+    HIPCHK(hipMemsetAsync(h->dmg.b_first, 0, nn * sizeof(int), h->stream));
+    HIPCHK(hipMemsetAsync(h->dmg.b_last, 0, nn * sizeof(int), h->stream));
     hipLaunchKernelGGL(k_tangent_keys, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->P, h->skey_d, h->sval_d);
     size_t bytes = h->cub_tmp_bytes;
     HIPCHK(hipcub::DeviceRadixSort::SortPairs(h->cub_tmp.get(), bytes, h->skey_d.get(), h->skey2_d.get(), h->sval_d.get(), h->sval2_d.get(), np, 0, 32,
                                               h->stream));
-    hipLaunchKernelGGL(k_node_ranges, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, h->skey2_d, h->dmg_first_d, h->dmg_last_d);
+    hipLaunchKernelGGL(k_node_ranges, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, h->skey2_d, h->dmg.b_first, h->dmg.b_last);
     if (h->P.softening) {
       double* T0 = h->gather_tmp.get();  // [npad] scratch of the re-sort, idle here
       LAUNCH_ND((k_soften_pass1<2>), (k_soften_pass1<3>), nblk(np), h->P, h->mats_d, T0);
-      LAUNCH_ND((k_soften_pass2<2>), (k_soften_pass2<3>), nblk(np), h->P, h->g, h->mats_d, h->dmg_first_d, h->dmg_last_d, h->sval2_d,
+      LAUNCH_ND((k_soften_pass2<2>), (k_soften_pass2<3>), nblk(np), h->P, h->g, h->mats_d, h->dmg.b_first, h->dmg.b_last, h->sval2_d,
                 (const uint8_t*)h->rank1_d, (const int*)h->perm_d, (const double*)T0, h->g.h);
     } else {
       // frozen lists (Beps.c:30-36): the node tables of the snapshot's closest nodes, rebuilt per call like the others
       if (beps_snapshot(h)) return 1;
-      if (!h->dmg_first0_d) {
-        HIPCHK(h->dmg_first0_d.reserve(nn));
-        HIPCHK(h->dmg_last0_d.reserve(nn));
-        HIPCHK(h->dmg_sorted0_d.reserve(h->P.npad));
+      if (!h->dmg.b_first0) {
+        HIPCHK(h->dmg.b_first0.reserve(nn));
+        HIPCHK(h->dmg.b_last0.reserve(nn));
+        HIPCHK(h->dmg.b_sorted0.reserve(h->P.npad));
       }
-      // dmg_sorted0_d: the CURRENT order just sorted; sval2_d: free for the next sort.  (Both blocks hold npad ints, so
+      // dmg.b_sorted0: the CURRENT order just sorted; sval2_d: free for the next sort.  (Both blocks hold npad ints, so
       // an error return between the two swaps leaves either owner with a block of the right size.)
-      h->dmg_sorted0_d.swap(h->sval2_d);
-      HIPCHK(hipMemsetAsync(h->dmg_first0_d, 0, nn * sizeof(int), h->stream));
-      HIPCHK(hipMemsetAsync(h->dmg_last0_d, 0, nn * sizeof(int), h->stream));
+      h->dmg.b_sorted0.swap(h->sval2_d);
+      HIPCHK(hipMemsetAsync(h->dmg.b_first0, 0, nn * sizeof(int), h->stream));
+      HIPCHK(hipMemsetAsync(h->dmg.b_last0, 0, nn * sizeof(int), h->stream));
       hipLaunchKernelGGL(k_beps_keys0, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->P, h->skey_d, h->sval_d);
       bytes = h->cub_tmp_bytes;
       HIPCHK(hipcub::DeviceRadixSort::SortPairs(h->cub_tmp.get(), bytes, h->skey_d.get(), h->skey2_d.get(), h->sval_d.get(), h->sval2_d.get(), np, 0, 32,
                                                 h->stream));
-      hipLaunchKernelGGL(k_node_ranges, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, h->skey2_d, h->dmg_first0_d, h->dmg_last0_d);
-      // (current order in dmg_sorted0_d, snapshot order in sval2_d)
-      LAUNCH_ND((k_damage<2>), (k_damage<3>), nblk(np), h->P, h->g, h->mats_d, h->dmg_first_d, h->dmg_last_d, h->dmg_sorted0_d,
-                h->dmg_first0_d, h->dmg_last0_d, h->sval2_d, h->g.h);
-      h->dmg_sorted0_d.swap(h->sval2_d);  // the sort buffers go back to where the re-sort expects them
+      hipLaunchKernelGGL(k_node_ranges, dim3(nblk(np)), dim3(BLK), 0, h->stream, np, h->skey2_d, h->dmg.b_first0, h->dmg.b_last0);
+      // (current order in dmg.b_sorted0, snapshot order in sval2_d)
+      LAUNCH_ND((k_damage<2>), (k_damage<3>), nblk(np), h->P, h->g, h->mats_d, h->dmg.b_first, h->dmg.b_last, h->dmg.b_sorted0,
+                h->dmg.b_first0, h->dmg.b_last0, h->sval2_d, h->g.h);
+      h->dmg.b_sorted0.swap(h->sval2_d);  // the sort buffers go back to where the re-sort expects them
     }
     HIPCHK(hipGetLastError());
   }
@@ -4521,6 +4569,14 @@ extern "C" int nlps_gpu_internal_forces(nlps_gpu* h, double* R) {
 __global__ void k_inverse_perm(const int* __restrict__ perm, int np, int* __restrict__ inv) {
   int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s < np) inv[perm[s]] = s;
+}
+// nlps_gpu::inv.  The setters of its users reserve it; the users (none of which accepts a migrated handle, where perm_d
+// is no permutation of [0, np) any more) take the pointer from inv_perm(), which rebuilds the map behind a renumbering.
+static hipError_t reserve_inv_perm(nlps_gpu* h) { return h->inv.d.reserve(std::max<size_t>(h->P.npad, 1)); }
+static const int* inv_perm(nlps_gpu* h) {
+  if (h->inv.stale) hipLaunchKernelGGL(k_inverse_perm, dim3(nblk(h->P.np)), dim3(BLK), 0, h->stream, h->perm_d, h->P.np, h->inv.d.get());
+  h->inv.stale = false;
+  return h->inv.d;
 }
 template <int ND>
 __global__ void k_traction(PView P, GridD g, int n, const int* __restrict__ ids, const int* __restrict__ inv,
@@ -4621,6 +4677,7 @@ static int traction_to_grid(nlps_gpu* h, const char* who, double* out, const nlp
   HIPCHK(hipMemcpyAsync(ids_d, ids.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(T_d, T.data(), (size_t)n * ND * sizeof(double), hipMemcpyHostToDevice, h->stream));
   if (ND == 3) HIPCHK(hipMemcpyAsync(A_d, A.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  // (not inv_perm(): this call is open to a migrated handle, whose perm_d holds other ranks' indices too)
   hipLaunchKernelGGL(k_inverse_perm, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->perm_d, np, h->sval_d);
   HIPCHK(hipMemsetAsync(out, 0, (size_t)h->g.nnodes * ND * sizeof(double), h->stream));
   if (det_implicit(h))
@@ -4775,55 +4832,42 @@ extern "C" int nlps_gpu_set_explicit_loads(nlps_gpu* h, const nlps_bcc* loads, i
         for (int i = 0; i < 3; i++) T[((size_t)t * nloads + l) * 3 + i] = Tc[i];
       }
     }
-  DevBuf<int> ids_d, load_d, inv_d;
-  DevBuf<double> a0_d, T_d;
+  nlps_gpu::Loads fresh;
+  fresh.n = (int)n;
+  fresh.nloads = n ? nloads : 0;
+  fresh.thickness = thickness;
   if (n) {
-    HIPCHK(ids_d.reserve(n));
-    HIPCHK(load_d.reserve(n));
-    HIPCHK(T_d.reserve(T.size()));
-    if (ND == 3) HIPCHK(a0_d.reserve(n));
-    HIPCHK(hipMemcpy(ids_d, ids.data(), n * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(load_d, lidx.data(), n * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(T_d, T.data(), T.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (ND == 3) HIPCHK(hipMemcpy(a0_d, A.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    if (h->xl_inv_d) inv_d.swap(h->xl_inv_d);  // (sized by the cloud: kept from one set of loads to the next)
-    else HIPCHK(inv_d.reserve((size_t)std::max(np, 1)));
-  } else if (h->rec_nprobes > 0) {
-    inv_d.swap(h->xl_inv_d);  // (the probes of the step record read the same map: it stays when the loads go)
+    HIPCHK(fresh.ids.reserve(n));
+    HIPCHK(fresh.load.reserve(n));
+    HIPCHK(fresh.T.reserve(T.size()));
+    if (ND == 3) HIPCHK(fresh.a0.reserve(n));
+    HIPCHK(hipMemcpy(fresh.ids, ids.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(fresh.load, lidx.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(fresh.T, T.data(), T.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (ND == 3) HIPCHK(hipMemcpy(fresh.a0, A.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(reserve_inv_perm(h));
   }
   // the copies above are ordered on the default stream only (see ensure_bcs), and a step in flight may still read the
   // tables this call replaces
   HIPCHK(hipDeviceSynchronize());
-  h->xl_ids_d = std::move(ids_d);
-  h->xl_load_d = std::move(load_d);
-  h->xl_a0_d = std::move(a0_d);
-  h->xl_T_d = std::move(T_d);
-  h->xl_inv_d = std::move(inv_d);
-  h->xl_n = (int)n;
-  h->xl_nloads = n ? nloads : 0;
-  h->xl_thickness = thickness;
-  h->xl_inv_valid = false;
+  h->loads = std::move(fresh);
   return 0;
 }
 
-// the contour tractions of `step` into the nodal force of the explicit step (xl_n > 0; the checks are the step's)
+// the contour tractions of `step` into the nodal force of the explicit step (loads.n > 0; the checks are the step's)
 static int explicit_loads_launch(nlps_gpu* h, int step) {
-  if (!h->xl_inv_valid) {  // the first step behind a re-sort (or the setter): caller's index -> slot
-    hipLaunchKernelGGL(k_inverse_perm, dim3(nblk(h->P.np)), dim3(BLK), 0, h->stream, h->perm_d, h->P.np, h->xl_inv_d.get());
-    h->xl_inv_valid = true;
-  }
-  const XlArgs a{h->xl_ids_d, h->xl_load_d, h->xl_inv_d, h->xl_a0_d, h->xl_T_d + (size_t)step * h->xl_nloads * 3, h->xl_thickness,
-                 h->xl_n};
+  const XlArgs a{h->loads.ids, h->loads.load, inv_perm(h), h->loads.a0, h->loads.T + (size_t)step * h->loads.nloads * 3, h->loads.thickness,
+                 h->loads.n};
   if (h->timing) {
-    for (hipEvent_t& e : h->xl_ev)
+    for (hipEvent_t& e : h->loads_ev)
       if (!e) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipEventRecord(h->xl_ev[0], h->stream));
+    HIPCHK(hipEventRecord(h->loads_ev[0], h->stream));
   }
   if (h->deterministic) LAUNCH_ND_BLK((k_explicit_traction<2, 2>), (k_explicit_traction<3, 2>), 1, 64, h->P, h->g, a, h->N.force);
-  else if (h->xl_lane_map) LAUNCH_ND((k_explicit_traction<2, 1>), (k_explicit_traction<3, 1>), nblk(h->xl_n), h->P, h->g, a, h->N.force);
-  else LAUNCH_ND((k_explicit_traction<2, 0>), (k_explicit_traction<3, 0>), nblk(h->xl_n, BLK / 64), h->P, h->g, a, h->N.force);
+  else if (h->loads_lane_map) LAUNCH_ND((k_explicit_traction<2, 1>), (k_explicit_traction<3, 1>), nblk(h->loads.n), h->P, h->g, a, h->N.force);
+  else LAUNCH_ND((k_explicit_traction<2, 0>), (k_explicit_traction<3, 0>), nblk(h->loads.n, BLK / 64), h->P, h->g, a, h->N.force);
   HIPCHK(hipGetLastError());
-  if (h->timing) HIPCHK(hipEventRecord(h->xl_ev[1], h->stream));
+  if (h->timing) HIPCHK(hipEventRecord(h->loads_ev[1], h->stream));
   return 0;
 }
 
@@ -4841,26 +4885,11 @@ static int rec_probe_doubles_of(int nd, unsigned fields) {
     if ((fields >> b) & 1u) n += b < 4 ? nd : (b < 6 ? T : 1);
   return n;
 }
-static void rec_drop(nlps_gpu* h) {
-  h->rec_on = 0;
-  h->rec_capacity = h->rec_nsets = h->rec_nprobes = h->rec_row = h->rec_probe_doubles = 0;
-  h->rec_fields = 0;
-  h->rec_total = 0;
-  h->rec_time = 0.0;
-  h->rec_rows_d.reset();
-  h->rec_part_d.reset();
-  h->rec_probes_d.reset();
-  if (h->xl_n == 0) {  // (the map serves the explicit loads too)
-    h->xl_inv_d.reset();
-    h->xl_inv_valid = false;
-  }
-}
-
 extern "C" int nlps_gpu_set_step_record(nlps_gpu* h, const nlps_record_cfg* cfg) {
   const char* who = "nlps_gpu_set_step_record: ";
   if (!cfg) {
     HIPCHK(hipDeviceSynchronize());  // (a step in flight may still write the ring)
-    rec_drop(h);
+    h->rec = {};
     return 0;
   }
   const int np = h->P.np;
@@ -4885,56 +4914,46 @@ extern "C" int nlps_gpu_set_step_record(nlps_gpu* h, const nlps_record_cfg* cfg)
     h->err = std::string(who) + step_record_halo_msg;
     return 1;
   }
-  const int pd = cfg->nprobes > 0 ? rec_probe_doubles_of(h->nd, cfg->probe_fields) : 0;
-  const size_t row = (size_t)NLPS_REC_NGLOBAL + (size_t)cfg->nsets * 3 + (size_t)cfg->nprobes * pd;
-  DevBuf<double> rows_d, part_d;
-  DevBuf<int> probes_d, inv_d;
-  HIPCHK(rows_d.reserve(row * (size_t)cfg->capacity));
-  HIPCHK(part_d.reserve((size_t)REC_NQ * REC_MAX_BLOCKS));  // (for any particle count: a migration changes it)
+  nlps_gpu::StepRecord fresh;
+  fresh.on = 1;
+  fresh.every = cfg->every;
+  fresh.capacity = cfg->capacity;
+  fresh.nsets = cfg->nsets;
+  fresh.nprobes = cfg->nprobes;
+  fresh.fields = cfg->nprobes > 0 ? cfg->probe_fields : 0u;
+  fresh.probe_doubles = cfg->nprobes > 0 ? rec_probe_doubles_of(h->nd, cfg->probe_fields) : 0;
+  const size_t row = (size_t)NLPS_REC_NGLOBAL + (size_t)cfg->nsets * 3 + (size_t)cfg->nprobes * fresh.probe_doubles;
+  fresh.row = (int)row;
+  HIPCHK(fresh.rows.reserve(row * (size_t)cfg->capacity));
+  HIPCHK(fresh.part.reserve((size_t)REC_NQ * REC_MAX_BLOCKS));  // (for any particle count: a migration changes it)
   if (cfg->nprobes > 0) {
-    HIPCHK(probes_d.reserve((size_t)cfg->nprobes));
-    HIPCHK(hipMemcpy(probes_d, cfg->probes, (size_t)cfg->nprobes * sizeof(int), hipMemcpyHostToDevice));
-    if (!h->xl_inv_d) HIPCHK(inv_d.reserve((size_t)std::max(np, 1)));
+    HIPCHK(fresh.probes.reserve((size_t)cfg->nprobes));
+    HIPCHK(hipMemcpy(fresh.probes, cfg->probes, (size_t)cfg->nprobes * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(reserve_inv_perm(h));
   }
-  HIPCHK(hipMemset(rows_d, 0, row * (size_t)cfg->capacity * sizeof(double)));
+  HIPCHK(hipMemset(fresh.rows, 0, row * (size_t)cfg->capacity * sizeof(double)));
   // the copies above are ordered on the default stream only, and a step in flight may still write the ring this call replaces
   HIPCHK(hipDeviceSynchronize());
-  h->rec_rows_d = std::move(rows_d);
-  h->rec_part_d = std::move(part_d);
-  h->rec_probes_d = std::move(probes_d);
-  if (inv_d) {
-    h->xl_inv_d = std::move(inv_d);
-    h->xl_inv_valid = false;
-  }
-  h->rec_every = cfg->every;
-  h->rec_capacity = cfg->capacity;
-  h->rec_nsets = cfg->nsets;
-  h->rec_nprobes = cfg->nprobes;
-  h->rec_fields = cfg->nprobes > 0 ? cfg->probe_fields : 0u;
-  h->rec_probe_doubles = pd;
-  h->rec_row = (int)row;
-  h->rec_total = 0;
-  h->rec_time = 0.0;
-  h->rec_on = 1;
+  h->rec = std::move(fresh);
   return 0;
 }
 
 extern "C" int nlps_gpu_step_record_layout(nlps_gpu* h, int* row_doubles, int* reaction_offset, int* probe_offset,
                                            int* probe_doubles) {
-  if (!h->rec_on) {
+  if (!h->rec.on) {
     h->err = "nlps_gpu_step_record_layout: no step record is set";
     return 1;
   }
-  if (row_doubles) *row_doubles = h->rec_row;
+  if (row_doubles) *row_doubles = h->rec.row;
   if (reaction_offset) *reaction_offset = NLPS_REC_NGLOBAL;
-  if (probe_offset) *probe_offset = NLPS_REC_NGLOBAL + 3 * h->rec_nsets;
-  if (probe_doubles) *probe_doubles = h->rec_probe_doubles;
+  if (probe_offset) *probe_offset = NLPS_REC_NGLOBAL + 3 * h->rec.nsets;
+  if (probe_doubles) *probe_doubles = h->rec.probe_doubles;
   return 0;
 }
 
 // a record with reaction totals or probes on a handle that has become a slab rank (or migrated) since the set
 static int rec_check(nlps_gpu* h, const char* who) {
-  if ((h->rec_nprobes > 0 || h->rec_nsets > 0) && (h->halo || h->rccl || h->migrated)) {
+  if ((h->rec.nprobes > 0 || h->rec.nsets > 0) && (h->halo || h->rccl || h->migrated)) {
     h->err = std::string(who) + ": the step record is set with reaction totals or probes: " + step_record_halo_msg;
     return 1;
   }
@@ -4946,14 +4965,14 @@ static int rec_check(nlps_gpu* h, const char* who) {
 static int rec_write(nlps_gpu* h, int kind, int step, double dt, const nlps_bcc* bcc, int nbcc) {
   if (materialise_move(h)) return 1;  // (nlps_gpu_record_now between two steps; a step with the record on defers nothing)
   const int np = h->P.np, nb = np > 0 ? std::min(nblk(np, REC_NT), REC_MAX_BLOCKS) : 0;
-  double* row = h->rec_rows_d + (size_t)(h->rec_total % h->rec_capacity) * h->rec_row;
+  double* row = h->rec.rows + (size_t)(h->rec.total % h->rec.capacity) * h->rec.row;
   const int lazy = (h->rolled && !h->rolled_keep) ? 1 : 0;  // tau and W of the hyperelastic laws are not stored
-  if (np > 0) LAUNCH_ND_BLK(k_rec_particles<2>, k_rec_particles<3>, nb, REC_NT, h->P, h->mats_d, lazy, h->rec_part_d.get(), nb);
-  const RecHead hd{(double)step, (double)kind, dt, h->rec_time, (double)np};
-  hipLaunchKernelGGL(k_rec_finish, dim3(REC_NQ), dim3(REC_NT), 0, h->stream, (const double*)h->rec_part_d.get(), nb, hd,
+  if (np > 0) LAUNCH_ND_BLK(k_rec_particles<2>, k_rec_particles<3>, nb, REC_NT, h->P, h->mats_d, lazy, h->rec.part.get(), nb);
+  const RecHead hd{(double)step, (double)kind, dt, h->rec.time, (double)np};
+  hipLaunchKernelGGL(k_rec_finish, dim3(REC_NQ), dim3(REC_NT), 0, h->stream, (const double*)h->rec.part.get(), nb, hd,
                      (const int*)h->gstatus_d.get(), row);
-  for (int s0 = 0; s0 < h->rec_nsets; s0 += REC_SETS_PER_LAUNCH) {
-    const int cnt = std::min(REC_SETS_PER_LAUNCH, h->rec_nsets - s0);
+  for (int s0 = 0; s0 < h->rec.nsets; s0 += REC_SETS_PER_LAUNCH) {
+    const int cnt = std::min(REC_SETS_PER_LAUNCH, h->rec.nsets - s0);
     RecSets rs;
     memset(&rs, 0, sizeof rs);
     rs.nlive = std::max(0, std::min(cnt, nbcc - s0));
@@ -4966,28 +4985,25 @@ static int rec_write(nlps_gpu* h, int kind, int step, double dt, const nlps_bcc*
     }
     LAUNCH_ND_BLK(k_rec_reactions<2>, k_rec_reactions<3>, cnt, REC_NT, h->N, rs, h->n0, h->nwn, row + NLPS_REC_NGLOBAL + (size_t)3 * s0);
   }
-  if (h->rec_nprobes > 0) {
-    if (!h->xl_inv_valid) {  // the first row behind a re-sort (or a setter): caller's index -> slot
-      hipLaunchKernelGGL(k_inverse_perm, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->perm_d, np, h->xl_inv_d.get());
-      h->xl_inv_valid = true;
-    }
-    LAUNCH_ND_BLK(k_rec_probes<2>, k_rec_probes<3>, nblk(h->rec_nprobes * 10, REC_NT), REC_NT, h->P, h->mats_d, lazy,
-                  (const int*)h->rec_probes_d.get(), (const int*)h->xl_inv_d.get(), h->rec_nprobes, h->rec_fields, h->rec_probe_doubles,
-                  row + NLPS_REC_NGLOBAL + (size_t)3 * h->rec_nsets);
+  if (h->rec.nprobes > 0) {
+    const int* inv = inv_perm(h);
+    LAUNCH_ND_BLK(k_rec_probes<2>, k_rec_probes<3>, nblk(h->rec.nprobes * 10, REC_NT), REC_NT, h->P, h->mats_d, lazy,
+                  (const int*)h->rec.probes.get(), inv, h->rec.nprobes, h->rec.fields, h->rec.probe_doubles,
+                  row + NLPS_REC_NGLOBAL + (size_t)3 * h->rec.nsets);
   }
   HIPCHK(hipGetLastError());
-  h->rec_total++;
+  h->rec.total++;
   return 0;
 }
 // the tail of a step (rec_on): the clock runs for every step, a row is written for the steps of the interval
 static int rec_step(nlps_gpu* h, int kind, int step, double dt, const nlps_bcc* bcc, int nbcc) {
-  h->rec_time += dt;
-  if (step % h->rec_every != 0) return 0;
+  h->rec.time += dt;
+  if (step % h->rec.every != 0) return 0;
   return rec_write(h, kind, step, dt, bcc, nbcc);
 }
 
 extern "C" int nlps_gpu_record_now(nlps_gpu* h, int tag) {
-  if (!h->rec_on) {
+  if (!h->rec.on) {
     h->err = "nlps_gpu_record_now: no step record is set";
     return 1;
   }
@@ -4996,7 +5012,7 @@ extern "C" int nlps_gpu_record_now(nlps_gpu* h, int tag) {
 }
 
 extern "C" int nlps_gpu_read_step_records(nlps_gpu* h, long long* total, int* count, double* rows, int max_rows) {
-  if (!h->rec_on) {
+  if (!h->rec.on) {
     h->err = "nlps_gpu_read_step_records: no step record is set";
     return 1;
   }
@@ -5005,15 +5021,15 @@ extern "C" int nlps_gpu_read_step_records(nlps_gpu* h, long long* total, int* co
     return 1;
   }
   HIPCHK(hipStreamSynchronize(h->stream));
-  const long long have = std::min<long long>(h->rec_total, h->rec_capacity);
+  const long long have = std::min<long long>(h->rec.total, h->rec.capacity);
   const int n = (int)std::min<long long>(have, max_rows);
-  if (total) *total = h->rec_total;
+  if (total) *total = h->rec.total;
   if (count) *count = n;
   if (!rows) return 0;
   for (int r = 0; r < n; r++) {  // (row number g lives in slot g % capacity: at most two runs of slots, copied row by row)
-    const long long g = h->rec_total - n + r;
-    HIPCHK(hipMemcpy(rows + (size_t)r * h->rec_row, h->rec_rows_d + (size_t)(g % h->rec_capacity) * h->rec_row,
-                     (size_t)h->rec_row * sizeof(double), hipMemcpyDeviceToHost));
+    const long long g = h->rec.total - n + r;
+    HIPCHK(hipMemcpy(rows + (size_t)r * h->rec.row, h->rec.rows + (size_t)(g % h->rec.capacity) * h->rec.row,
+                     (size_t)h->rec.row * sizeof(double), hipMemcpyDeviceToHost));
   }
   return 0;
 }
@@ -5025,28 +5041,10 @@ extern "C" double nlps_host_courant_dt(double CFL, double hh, double Cel, const 
 // ------------------------------------------------------------------------------------------------
 // the particle snapshot (include/nlps_gpu.h)
 // ------------------------------------------------------------------------------------------------
-// waits for the copies in flight (the reset of the stream synchronises it), then frees
-static void snap_drop(nlps_gpu* h) {
-  h->snap_stream.reset();
-  for (auto& s : h->snap) {
-    if (s.packed) (void)hipEventDestroy(s.packed);
-    if (s.copied) (void)hipEventDestroy(s.copied);
-    s.packed = s.copied = nullptr;
-    s.dev.reset();
-    s.pin.reset();
-    s.state = 0;
-  }
-  h->snap_inv_d.reset();
-  h->snap_inv_valid = false;
-  h->snap_slots = h->snap_cap = 0;
-  h->snap_fields = 0;
-  h->snap_bytes = 0;
-}
-
 extern "C" int nlps_gpu_set_snapshots(nlps_gpu* h, const nlps_snapshot_cfg* cfg) {
   const char* who = "nlps_gpu_set_snapshots: ";
   if (!cfg) {
-    snap_drop(h);
+    h->snap = {};  // (waits for the copies in flight, then frees)
     return 0;
   }
   if (cfg->slots < 1 || cfg->slots > NLPS_SNAP_MAX_SLOTS) {
@@ -5065,55 +5063,32 @@ extern "C" int nlps_gpu_set_snapshots(nlps_gpu* h, const nlps_snapshot_cfg* cfg)
   const size_t per = (size_t)8 * snap_doubles_before(cfg->fields, SNAP_NFIELDS - 1, h->nd) + ((cfg->fields & NLPS_SNAP_I0) ? 4 : 0);
   const size_t bytes = std::max<size_t>(8, (size_t)np * per), words = (bytes + 7) / 8;
   // everything is made first: a failure leaves the snapshots that were set as they are
-  nlps_gpu::SnapSlot fresh[NLPS_SNAP_MAX_SLOTS];
-  SideStream st;
-  auto undo = [&]() {
-    for (auto& s : fresh) {
-      if (s.packed) (void)hipEventDestroy(s.packed);
-      if (s.copied) (void)hipEventDestroy(s.copied);
-    }
-  };
-  DevBuf<int> inv;
-  hipError_t e = st.create();
-  if (e == hipSuccess) e = inv.reserve((size_t)std::max(np, 1));
-  for (int i = 0; i < cfg->slots && e == hipSuccess; i++) {
-    e = fresh[i].dev.reserve(words);
-    if (e == hipSuccess) e = fresh[i].pin.alloc(words);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&fresh[i].packed, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&fresh[i].copied, hipEventDisableTiming);
-  }
+  nlps_gpu::Snapshots fresh;
+  fresh.slots = cfg->slots;
+  fresh.cap = np;
+  fresh.fields = cfg->fields;
+  fresh.bytes = bytes;
+  hipError_t e = fresh.stream.create();
+  for (int i = 0; i < cfg->slots && e == hipSuccess; i++) e = fresh.slot[i].create(words);
+  if (e == hipSuccess) e = reserve_inv_perm(h);  // (last: a refused call leaves nothing on the handle)
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    undo();
     char buf[200];
     snprintf(buf, sizeof buf, "%scannot allocate %d slots of %zu bytes on the device and in pinned memory (%s)", who, cfg->slots,
              bytes, hipGetErrorString(e));
     h->err = buf;
     return 1;
   }
-  snap_drop(h);
-  for (int i = 0; i < cfg->slots; i++) {
-    h->snap[i].dev = std::move(fresh[i].dev);
-    h->snap[i].pin.swap(fresh[i].pin);
-    h->snap[i].packed = fresh[i].packed;
-    h->snap[i].copied = fresh[i].copied;
-  }
-  h->snap_stream.swap(st);
-  h->snap_inv_d = std::move(inv);
-  h->snap_inv_valid = false;
-  h->snap_slots = cfg->slots;
-  h->snap_cap = np;
-  h->snap_fields = cfg->fields;
-  h->snap_bytes = bytes;
+  h->snap = std::move(fresh);  // (waits for the copies in flight of the snapshots that were set, then frees them)
   return 0;
 }
 
 static int snap_check(nlps_gpu* h, const char* who, int slot, bool begun) {
-  if (h->snap_slots == 0) {
+  if (h->snap.slots == 0) {
     h->err = std::string(who) + ": no snapshots are set (nlps_gpu_set_snapshots)";
     return 1;
   }
-  if (begun && (slot < 0 || slot >= h->snap_slots || h->snap[slot].state == 0)) {
+  if (begun && (slot < 0 || slot >= h->snap.slots || h->snap.slot[slot].state == 0)) {
     h->err = std::string(who) + ": that slot was not begun";
     return 1;
   }
@@ -5124,33 +5099,29 @@ extern "C" int nlps_gpu_snapshot_begin(nlps_gpu* h, int tag, int* slot) {
   const char* who = "nlps_gpu_snapshot_begin";
   if (snap_check(h, who, 0, false)) return 1;
   const int np = h->P.np;
-  if (h->migrated || np > h->snap_cap) {
+  if (h->migrated || np > h->snap.cap) {
     h->err = std::string(who) + ": the handle has migrated particles since the snapshots were set: its rows are by global id";
     return 1;
   }
   int i = 0;
-  while (i < h->snap_slots && h->snap[i].state != 0) i++;
-  if (i == h->snap_slots) {
+  while (i < h->snap.slots && h->snap.slot[i].state != 0) i++;
+  if (i == h->snap.slots) {
     h->err = std::string(who) + ": every slot is in flight or unreleased (nlps_gpu_snapshot_release)";
     return 1;
   }
-  nlps_gpu::SnapSlot& s = h->snap[i];
-  const int D = snap_doubles_before(h->snap_fields, SNAP_NFIELDS - 1, h->nd);
-  const size_t bytes = (size_t)np * ((size_t)8 * D + ((h->snap_fields & NLPS_SNAP_I0) ? 4 : 0));
+  nlps_gpu::SnapSlot& s = h->snap.slot[i];
+  const int D = snap_doubles_before(h->snap.fields, SNAP_NFIELDS - 1, h->nd);
+  const size_t bytes = (size_t)np * ((size_t)8 * D + ((h->snap.fields & NLPS_SNAP_I0) ? 4 : 0));
   if (np > 0) {
-    if (h->snap_by_caller && !h->snap_inv_valid) {
-      hipLaunchKernelGGL(k_inverse_perm, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->perm_d, np, h->snap_inv_d.get());
-      h->snap_inv_valid = true;
-    }
-    const SnapArgs a{h->snap_fields, h->rolled ? 1 : 0, (h->rolled && !h->rolled_keep) ? 1 : 0,
-                     h->move_pending ? h->moved_d.get() : nullptr, h->snap_by_caller ? h->snap_inv_d.get() : h->perm_d.get(),
+    const SnapArgs a{h->snap.fields, h->rolled ? 1 : 0, (h->rolled && !h->rolled_keep) ? 1 : 0,
+                     h->move_pending ? h->moved_d.get() : nullptr, h->snap_by_caller ? inv_perm(h) : h->perm_d.get(),
                      s.dev.get()};
     if (h->snap_by_caller) LAUNCH_ND_BLK((k_snap_pack<2, true>), (k_snap_pack<3, true>), nblk(np, SNAP_NT), SNAP_NT, h->P, h->mats_d, a);
     else LAUNCH_ND_BLK(k_snap_pack<2>, k_snap_pack<3>, nblk(np, SNAP_NT), SNAP_NT, h->P, h->mats_d, a);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipEventRecord(s.packed, h->stream));
-  const hipStream_t ss = h->snap_stream.stream();
+  const hipStream_t ss = h->snap.stream.stream();
   HIPCHK(hipStreamWaitEvent(ss, s.packed, 0));
   if (bytes > 0) HIPCHK(hipMemcpyAsync(s.pin.host(), s.dev.get(), bytes, hipMemcpyDeviceToHost, ss));
   HIPCHK(hipEventRecord(s.copied, ss));
@@ -5163,7 +5134,7 @@ extern "C" int nlps_gpu_snapshot_begin(nlps_gpu* h, int tag, int* slot) {
 
 extern "C" int nlps_gpu_snapshot_wait(nlps_gpu* h, int slot, nlps_particles* view, int* tag) {
   if (snap_check(h, "nlps_gpu_snapshot_wait", slot, true)) return 1;
-  nlps_gpu::SnapSlot& s = h->snap[slot];
+  nlps_gpu::SnapSlot& s = h->snap.slot[slot];
   HIPCHK(hipEventSynchronize(s.copied));
   if (tag) *tag = s.tag;
   if (!view) return 0;
@@ -5174,25 +5145,25 @@ extern "C" int nlps_gpu_snapshot_wait(nlps_gpu* h, int slot, nlps_particles* vie
                                        &view->Back_stress, &view->Damage_n, &view->Strain_f_n, &view->lambda, &view->Beta};
   double* o = s.pin.host();
   for (int b = 0; b < SNAP_NFIELDS - 1; b++) {
-    if (!((h->snap_fields >> b) & 1u)) continue;
+    if (!((h->snap.fields >> b) & 1u)) continue;
     *member[b] = o;
     o += (size_t)s.np * snap_ncomp(b, h->nd);
   }
-  if (h->snap_fields & NLPS_SNAP_I0) view->I0 = reinterpret_cast<int*>(o);
+  if (h->snap.fields & NLPS_SNAP_I0) view->I0 = reinterpret_cast<int*>(o);
   return 0;
 }
 
 extern "C" int nlps_gpu_snapshot_release(nlps_gpu* h, int slot) {
   if (snap_check(h, "nlps_gpu_snapshot_release", slot, true)) return 1;
-  HIPCHK(hipEventSynchronize(h->snap[slot].copied));  // (a copy in flight still writes the pinned block the next begin reuses)
-  h->snap[slot].state = 0;
+  HIPCHK(hipEventSynchronize(h->snap.slot[slot].copied));  // (a copy in flight still writes the pinned block the next begin reuses)
+  h->snap.slot[slot].state = 0;
   return 0;
 }
 
 extern "C" int nlps_gpu_snapshot_bytes(nlps_gpu* h, size_t* device, size_t* pinned) {
   if (snap_check(h, "nlps_gpu_snapshot_bytes", 0, false)) return 1;
-  if (device) *device = (size_t)h->snap_slots * h->snap_bytes + h->snap_inv_d.size() * sizeof(int);
-  if (pinned) *pinned = (size_t)h->snap_slots * h->snap_bytes;
+  if (device) *device = (size_t)h->snap.slots * h->snap.bytes + (size_t)std::max(h->snap.cap, 1) * sizeof(int);  // (+ the inverse permutation)
+  if (pinned) *pinned = (size_t)h->snap.slots * h->snap.bytes;
   return 0;
 }
 
@@ -5252,9 +5223,9 @@ template <bool SNAP>  // the runs of the current (false) or the snapshot's (true
 static void build_runs(nlps_gpu* h, int* first, int* last, int* sorted, bool sort_runs) {
   const int np = h->P.np, nn = h->g.nnodes;
   const dim3 gp(nblk(np)), gn(nblk(nn)), blk(BLK);
-  hipLaunchKernelGGL(k_run_count<SNAP>, gp, blk, 0, h->stream, h->P, nn, h->xrun_cnt_d.get(), h->xrun_rank_d.get(), h->xrun_cursor_d.get());
-  hipLaunchKernelGGL(k_run_first, gn, blk, 0, h->stream, nn, h->xrun_cnt_d.get(), h->xrun_cursor_d.get(), first, last);
-  hipLaunchKernelGGL(k_run_fill<SNAP>, gp, blk, 0, h->stream, h->P, nn, (const int*)first, (const int*)h->xrun_rank_d.get(), sorted);
+  hipLaunchKernelGGL(k_run_count<SNAP>, gp, blk, 0, h->stream, h->P, nn, h->dmg.cnt.get(), h->dmg.rank.get(), h->dmg.cursor.get());
+  hipLaunchKernelGGL(k_run_first, gn, blk, 0, h->stream, nn, h->dmg.cnt.get(), h->dmg.cursor.get(), first, last);
+  hipLaunchKernelGGL(k_run_fill<SNAP>, gp, blk, 0, h->stream, h->P, nn, (const int*)first, (const int*)h->dmg.rank.get(), sorted);
   if (sort_runs) hipLaunchKernelGGL(k_run_sort, gn, blk, 0, h->stream, nn, np, (const int*)first, (const int*)last, sorted);
 }
 static int damage_runs_and_hook(nlps_gpu* h, bool rebuild) {
@@ -5263,23 +5234,23 @@ static int damage_runs_and_hook(nlps_gpu* h, bool rebuild) {
   // over a neighbourhood run in an order the particle arrays alone decide.  (Both switches drop the cached tables.)
   const bool sort_runs = h->deterministic && h->det_damage;
   if (rebuild) {
-    build_runs<false>(h, h->xrun_first_d.get(), h->xrun_last_d.get(), h->xrun_sorted_d.get(), sort_runs);
-    h->xrun_builds++;
-    h->xrun_tables = true;
+    build_runs<false>(h, h->dmg.first.get(), h->dmg.last.get(), h->dmg.sorted.get(), sort_runs);
+    h->dmg.builds++;
+    h->dmg.tables = true;
   }
   if (h->P.softening) {
     double* T0 = h->gather_tmp.get();  // [npad] scratch of the re-sort, idle here
     LAUNCH_ND((k_soften_pass1<2>), (k_soften_pass1<3>), nblk(np), h->P, h->mats_d, T0);
     // (orig[] = the caller's index of every slot: perm_d travels with the re-sorts)
-    LAUNCH_ND((k_soften_pass2<2>), (k_soften_pass2<3>), nblk(np), h->P, h->g, h->mats_d, h->xrun_first_d, h->xrun_last_d, h->xrun_sorted_d,
+    LAUNCH_ND((k_soften_pass2<2>), (k_soften_pass2<3>), nblk(np), h->P, h->g, h->mats_d, h->dmg.first, h->dmg.last, h->dmg.sorted,
               (const uint8_t*)h->rank1_d, (const int*)h->perm_d, (const double*)T0, h->g.h);
   } else {
-    if (!h->xrun_tables0) {  // frozen lists (Beps.c:30-36): the runs of the snapshot's closest nodes
-      build_runs<true>(h, h->xrun_first0_d.get(), h->xrun_last0_d.get(), h->xrun_sorted0_d.get(), sort_runs);
-      h->xrun_tables0 = true;
+    if (!h->dmg.tables0) {  // frozen lists (Beps.c:30-36): the runs of the snapshot's closest nodes
+      build_runs<true>(h, h->dmg.first0.get(), h->dmg.last0.get(), h->dmg.sorted0.get(), sort_runs);
+      h->dmg.tables0 = true;
     }
-    LAUNCH_ND((k_damage<2>), (k_damage<3>), nblk(np), h->P, h->g, h->mats_d, h->xrun_first_d, h->xrun_last_d, h->xrun_sorted_d,
-              h->xrun_first0_d, h->xrun_last0_d, h->xrun_sorted0_d, h->g.h);
+    LAUNCH_ND((k_damage<2>), (k_damage<3>), nblk(np), h->P, h->g, h->mats_d, h->dmg.first, h->dmg.last, h->dmg.sorted,
+              h->dmg.first0, h->dmg.last0, h->dmg.sorted0, h->g.h);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -5319,7 +5290,7 @@ static int explicit_step_refuse(nlps_gpu* h, int nbcc, int step) {
              "node runs take ranks and run starts from atomics)";
     return 1;
   }
-  const bool loads = h->xl_n > 0 && h->P.np > 0;
+  const bool loads = h->loads.n > 0 && h->P.np > 0;
   if (loads && (h->halo || h->rccl)) {
     h->err = std::string("nlps_gpu_explicit_step: ") + explicit_loads_halo_msg;
     return 1;
@@ -5329,7 +5300,7 @@ static int explicit_step_refuse(nlps_gpu* h, int nbcc, int step) {
     return 1;
   }
   if ((nbcc > 0 || loads) && check_step(h, step, "nlps_gpu_explicit_step")) return 1;
-  if (h->rec_on && rec_check(h, "nlps_gpu_explicit_step")) return 1;  // (nlps_gpu_set_step_record)
+  if (h->rec.on && rec_check(h, "nlps_gpu_explicit_step")) return 1;  // (nlps_gpu_set_step_record)
   return 0;
 }
 
@@ -5384,7 +5355,7 @@ struct StepForm {
 static StepForm step_form(const nlps_gpu* h, const nlps_bcc* bcc, int nbcc, int step) {
   StepForm f{};
   f.dmg = h->P.erosion != 0;
-  f.loads = h->xl_n > 0 && h->P.np > 0;
+  f.loads = h->loads.n > 0 && h->P.np > 0;
   f.det = h->deterministic;
   f.ov2 = h->rccl && h->overlap == 2 && !h->deterministic;
   f.ov = !f.ov2 && (h->halo || h->rccl) && h->overlap;
@@ -5503,15 +5474,15 @@ struct ExplicitStep {
   // the move, so nothing K5 writes is read by the search, and the fork comes in front of the search: the whole chain
   // k_search_ahead, k_dilate_scan, k_fill_orders runs beside K5.  Who touches what between the fork and the join:
   //   k5_tile_lazy<., ., false, true>  reads   x, lambda, beta, I0, mlo, mhi, vel of the particles of this step's lists
-  //                                            (td.order_m, tile_start / tile_count of the set in use), nm, force, active
+  //                                            (td.order_m, lists.start / tile_count_d of the set in use), nm, force, active
   //                                            and fixed of the set in use, the Dirichlet sets;   writes acc, vel, gstatus (or)
   //   k_search_ahead                   reads   I0, tile, mlo, mhi, x, dis, d_dis, moved, rank1;   writes I0n, tile, rank, nrank,
   //                                            seed, tile_count2, node_cnt, home / foreign, moved, status / gstatus (or), and
   //                                            x, dis of a particle whose mark K2 did not take -- one in no list, which K5
   //                                            never visits
   //   k_dilate_scan<., 256>            reads   seed, tile_count2, node_cnt;   writes active, fixed, nm, force of the TWIN set,
-  //                                            tile_start2, work1_2, nwork2, the layer tables (tile_tab), foreign_h
-  //   k_fill_orders                    reads   tile, rank, nrank, I0n, tile_start2, the layer tables;   writes order_2, order2_2
+  //                                            twin.start, twin.work, twin.nwork, the layer tables (tile_tab), foreign_h
+  //   k_fill_orders                    reads   tile, rank, nrank, I0n, twin.start, the layer tables;   writes twin.order, twin.order2
   // tile_count2, node_cnt and the seeds are reset by K3's workgroups (LazyNodal), so the fork stands behind K3.  With the
   // timing brackets on, the same K5 runs behind the search on the handle's stream and the lists are left to the next step.
   int search_next_and_fork() {
@@ -5520,7 +5491,7 @@ struct ExplicitStep {
     tc.count = h->tile_count2_d;     // (tile_count_d sizes the lists K5 walks)
     h->ranks_deferred = false;
     const bool next_sorts = resort_due(h);
-    deferred = !h->rec_on && !next_sorts && np >= h->defer_move_min;
+    deferred = !h->rec.on && !next_sorts && np >= h->defer_move_min;
     const bool lists = !h->timing && !next_sorts;
     if (deferred && !h->moved_d) {
       HIPCHK(h->moved_d.reserve(h->P.npad));
@@ -5538,25 +5509,18 @@ struct ExplicitStep {
     if (h->moved_d) h->move_pending = deferred;  // (stale marks are gone either way; new ones exist in the deferred form)
     if (!lists) return 0;
     if (!side_search) HIPCHK(h->side.fork(h->stream));
-    const int TB = ND == 3 ? TileCfg<3>::TB : TileCfg<2>::TB;
-    TileScanArgs ts{h->tile_count2_d + h->tile0, h->tile_start2_d + h->tile0, h->ntw, h->tile0, h->ntiles / h->nt[ND - 1], TB,
-                    h->band_lo, h->band_hi, h->work1_2_d, h->nwork2_d, nullptr};
-    NView N2 = h->N;  // (the seeds are the search's; flags and accumulators of the twin set)
-    N2.active = h->N_active2;
-    N2.fixed = h->N_fixed2;
-    N2.nm = h->N_nm2;
-    N2.force = h->N_force2;
+    const ListBuild b2 = list_build(h, h->twin, h->tile_count2_d, nullptr);
     // (workgroups of 256: they are placed beside K5's, which leave one wave per SIMD free -- see k_dilate_scan)
     constexpr int SNT = 256;
     const int nb = 1 + (h->nwn + SNT - 1) / SNT + (h->ntw + SNT / 64 - 1) / (SNT / 64);
     int* fo = h->adaptive_resort > 0.0 ? h->foreign_d : nullptr;
     with_nd(ND, [&](auto D) {
-      hipLaunchKernelGGL((k_dilate_scan<CT(D), SNT>), dim3(nb), dim3(SNT), 0, ss, h->n0, h->nwn, h->g, N2, ts, fo, h->foreign_h.host(),
+      hipLaunchKernelGGL((k_dilate_scan<CT(D), SNT>), dim3(nb), dim3(SNT), 0, ss, h->n0, h->nwn, h->g, b2.N, b2.ts, fo, h->foreign_h.host(),
                          tile_tab(h), 1);
       // (non-deferred: position = start + rank, canonical position from the rank inside the node; the closest node is read
       // from I0n and nothing is committed -- K5 reads I0)
       hipLaunchKernelGGL(k_fill_orders<CT(D)>, dim3(nblk(np)), dim3(BLK), 0, ss, np, h->P.tile, h->P.rank, h->nrank_d, h->P.I0n,
-                         (const int*)nullptr, h->tile_start2_d, h->g, tile_tab(h), h->order_2_d, h->order2_2_d, (int*)nullptr,
+                         (const int*)nullptr, h->twin.start, h->g, tile_tab(h), h->twin.order, h->twin.order2, (int*)nullptr,
                          h->node_cnt_d);
     });
     HIPCHK(hipGetLastError());
@@ -5674,7 +5638,7 @@ static int step_timing_read(nlps_gpu* h, bool loads) {
   h->ms[4] = t[2] + t[4];  // the nodal kernels
   h->ms[5] = t[6];  // the calibration bracket
   h->ms[7] = 0.f;  // the contour-traction kernel (nlps_gpu_set_explicit_loads)
-  if (loads) HIPCHK(hipEventElapsedTime(&h->ms[7], h->xl_ev[0], h->xl_ev[1]));
+  if (loads) HIPCHK(hipEventElapsedTime(&h->ms[7], h->loads_ev[0], h->loads_ev[1]));
   h->ms[6] = 0.f;  // time the handle's stream spent in / waiting for the ghost-layer exchanges of this step
   for (int q = 0; q < h->nwait; q++) {
     float tw = 0.f;
@@ -5763,7 +5727,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
   if (h->timing && step_timing_read(h, f.loads)) return 1;
   // the step record: behind the last particle kernel of the step (and the join of the side stream), outside the timing brackets; N.active, N.nm and
   // N.force of this step are intact in every form (placement table), nothing here writes them
-  if (h->rec_on && rec_step(h, NLPS_REC_KIND_EXPLICIT, step, dt, bcc, nbcc)) return 1;
+  if (h->rec.on && rec_step(h, NLPS_REC_KIND_EXPLICIT, step, dt, bcc, nbcc)) return 1;
   return 0;
 }
 
@@ -5965,7 +5929,7 @@ static int snes_fnorm_launch(nlps_gpu* h, const double* F);  // (defined with nl
 // that make the matrix-free operator stale (tan_stale) changes a closest node --, the hook, which sets Damage_n1
 // (Strain_f_n1) and scales every Kirchhoff stress in place, and the force half with the Lagrangian's sign.  All on the
 // handle's stream, no sort, no synchronisation, no allocation (the setter made the tables).  The level-B stages keep
-// tables of their own (dmg_*, the sort buffers): nothing here touches them.
+// tables of their own (dmg.b_*, the sort buffers): nothing here touches them.
 static int lagrangian_damage_launches(nlps_gpu* h) {
   if (beps_snapshot(h)) return 1;  // (taken by the first search: nothing to do here for a handle that has searched)
   // deterministic mode with nlps_gpu_set_deterministic_damage: the exact lists, sorted runs, the one-wave force half and
@@ -5977,9 +5941,9 @@ static int lagrangian_damage_launches(nlps_gpu* h) {
   if (!det) td.slab = nullptr;
   launch_k3<6>(h, td, K3Launch{});  // (a cloud of several laws: per law present, FILT)
   // (built once per numbering: nothing between two calls that make the matrix-free operator stale changes a closest node)
-  if (damage_runs_and_hook(h, h->xrun_gen != h->tan_gen)) return 1;
-  h->xrun_gen = h->tan_gen;
-  h->dmg_fused_evals++;
+  if (damage_runs_and_hook(h, h->dmg.gen != h->tan_gen)) return 1;
+  h->dmg.gen = h->tan_gen;
+  h->dmg.fused_evals++;
   if (scatter_tiles<2, 3>(h, "nlps_gpu_lagrangian_evaluation", 1, h->N.force, [&](auto NT, TileD) {  // (on this site's td)
         if (CT(NT) == 64) LAUNCH_ND_BLK((k3f_wave<2, true>), (k3f_wave<3, true>), h->ntw, 64, h->P, h->g, h->N, td, h->gstatus_d);
         else LAUNCH_ND_BLK((k3f_tile<2, true>), (k3f_tile<3, true>), h->ntw, K3_BLK, h->P, h->g, h->N, td, h->gstatus_d);
@@ -7448,7 +7412,7 @@ extern "C" int nlps_gpu_newmark_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc,
   if (nlps_gpu_nodal_kinetic_increments(h, dV, dA, dU, V, A, alpha)) return 1;          // :380
   if (nlps_gpu_roll_state(h)) return 1;                                                 // :393
   if (nlps_gpu_update_kinetics(h, nm->alpha_blend, dU, V, dV, dA)) return 1;            // :396
-  if (h->rec_on) {  // the step record (nlps_gpu_set_step_record): a converged step, behind the particle update
+  if (h->rec.on) {  // the step record (nlps_gpu_set_step_record): a converged step, behind the particle update
     if (rec_check(h, who)) return 1;
     return rec_step(h, NLPS_REC_KIND_NEWMARK, step, dt, nullptr, 0);
   }

@@ -65,6 +65,11 @@ class Pinned {
   Pinned() = default;
   Pinned(const Pinned&) = delete;
   Pinned& operator=(const Pinned&) = delete;
+  Pinned(Pinned&& o) noexcept { swap(o); }
+  Pinned& operator=(Pinned&& o) noexcept {
+    if (this != &o) reset(), swap(o);
+    return *this;
+  }
   ~Pinned() { reset(); }
   void reset() {
     if (p_) (void)hipHostFree(p_);
@@ -120,6 +125,11 @@ class SideStream {
   SideStream() = default;
   SideStream(const SideStream&) = delete;
   SideStream& operator=(const SideStream&) = delete;
+  SideStream(SideStream&& o) noexcept { swap(o); }
+  SideStream& operator=(SideStream&& o) noexcept {  // (the reset waits for what the stream still runs)
+    if (this != &o) reset(), swap(o);
+    return *this;
+  }
   ~SideStream() { reset(); }
   void reset() {
     if (s_) (void)hipStreamSynchronize(s_), (void)hipStreamDestroy(s_);

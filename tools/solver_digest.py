@@ -1,18 +1,25 @@
 #!/usr/bin/env python3
-"""Developer tool: what the device GMRES, MINRES, Lanczos, Newton and Newmark calls return, as bits, for a host-side
-refactor that must not move any of them.  Fresh handles on the small clouds of the tests, deterministic mode on ahead of
-the first call; one JSON line per case: {"case": name, "sha256": digest} with the digest over the output vector's bytes,
-the history's bytes and the integer and float result fields, or {"case": name, "error": text} for a refused call.
+"""Developer tool: what the device GMRES, MINRES, Lanczos, Newton and Newmark calls and the explicit step with the
+handle's features on (the steps/ cases) return, as bits, for a host-side refactor that must not move any of them.
+Fresh handles on the small clouds of the tests, deterministic mode on ahead of the first call; one JSON line per case:
+{"case": name, "sha256": digest} with the digest over the output vector's bytes, the history's bytes and the integer
+and float result fields, or {"case": name, "error": text} for a refused call.
 
     python tools/solver_digest.py            every case
     python tools/solver_digest.py --one      one GMRES(5) solve, one MINRES solve and one 8-step Lanczos run on the 3-D
                                              Neo-Hookean cloud (for `rocprofv3 --kernel-trace -- python ...`)
+    python tools/solver_digest.py --steps    the steps/ cases alone
+    python tools/solver_digest.py --steps-trace
+                                             12 shipped-mode steps of the small 3-D cloud with loads, record probes and
+                                             snapshots on, a re-sort every 4 (for `rocprofv3 --kernel-trace -- python ...`)
     python tools/solver_digest.py --compare parent1 parent2 new1 new2
                                              a case counts if the parent's two runs agree; exit 0 if every case counts
                                              and every counted case is equal on the new side, one JSON line either way
-    python tools/solver_digest.py --launches kernel_trace.csv [list.txt]
+    python tools/solver_digest.py --launches kernel_trace.csv [list.txt] [--without KERNEL]
                                              length and SHA-256 of rocprofv3's ordered (kernel, grid, block) list, in
-                                             the order of the launches; the list itself into list.txt
+                                             the order of the launches; the list itself into list.txt.  --without: the
+                                             launches of kernels whose name starts with KERNEL are counted apart and
+                                             left out of the list
 
 Two libraries are compared by running the tool twice, the other build through NLPS_GPU_LIB."""
 import csv
@@ -50,11 +57,19 @@ def _launches(path):
     rows.sort(key=lambda r: int(r["Dispatch_Id"]))  # (the order of the host's launches)
     seq = [(r["Kernel_Name"], r["Grid_Size_X"], r["Grid_Size_Y"], r["Grid_Size_Z"], r["Workgroup_Size_X"],
             r["Workgroup_Size_Y"], r["Workgroup_Size_Z"]) for r in rows]
+    args = sys.argv[sys.argv.index("--launches") + 1:]
+    out = {"tool": "solver_digest --launches"}
+    if "--without" in args:
+        i = args.index("--without")
+        name = args[i + 1]
+        out["without"], out["left_out"] = name, sum(s[0].startswith(name) for s in seq)
+        seq = [s for s in seq if not s[0].startswith(name)]
+        del args[i:i + 2]
     text = "\n".join(" ".join(s) for s in seq)
-    if len(sys.argv) > sys.argv.index("--launches") + 2:
-        open(sys.argv[sys.argv.index("--launches") + 2], "w").write(text + "\n")
-    print(json.dumps({"tool": "solver_digest --launches", "length": len(seq), "kernels": len({s[0] for s in seq}),
-                      "sha256": hashlib.sha256(text.encode()).hexdigest()}))
+    if len(args) > 1:
+        open(args[1], "w").write(text + "\n")
+    out.update(length=len(seq), kernels=len({s[0] for s in seq}), sha256=hashlib.sha256(text.encode()).hexdigest())
+    print(json.dumps(out))
     sys.exit(0)
 
 
@@ -149,6 +164,98 @@ if "--one" in sys.argv:
     S.tangent_operator(0.0, None, True)
     emit("one lanczos(8)", lambda: lanczos(S, s["Mv"], seed=2, max_it=8, rtol=0.0, mode=True, history=True))
     S.close()
+    sys.exit(0)
+
+
+# ------------------------------------------------------------------------------------------------ steps/
+def step_cases():
+    """The explicit step with the handle's features coming, going and sharing the slot map across re-sorts (the scenarios
+    of tests/test_gpu_feature_state.py), the plain step, and the fused damage residual: downloaded state, nodal arrays,
+    record rows and snapshot blocks."""
+    import explicit_damage_ref as xr
+    import explicit_loads_ref as lr
+    import test_gpu_feature_state as fs
+    from test_gpu_implicit_damage import alpha_of, solver as implicit_solver
+
+    def outputs(S, snaps=(), rows=False):
+        nod, st = fs.results(S)
+        info = {f"nodal {k}": v for k, v in nod.items() if isinstance(v, np.ndarray)}
+        info.update({f"state {k}": v for k, v in st.items() if isinstance(v, np.ndarray)})
+        for t, snap in enumerate(snaps):
+            info.update({f"snapshot {t:02d} {k}": v for k, v in snap.items()})
+        if rows:
+            info["rows"] = S.read_step_records()["rows"]
+        S.close()
+        return None, info
+
+    def stepped(handle, rows):
+        S, bset = handle
+        fs.run(S, bset)
+        return outputs(S, rows=rows)
+
+    def together(case, probes, by_caller):
+        S, bset = fs.carrying(case, probes, ("record", "snapshots"), by_caller)
+        return outputs(S, fs.run_with_downloads(S, bset, True, "digest"), rows=True)
+
+    def damage(case):
+        S = fs.damage_handle(case)
+        fs.damage_steps(S, True)
+        return outputs(S)
+
+    def fused_damage_residual(ndim):
+        case, dU, _, _ = sx.erosion_case(ndim, 0, "part")
+        S = implicit_solver(case, "erosion", True, 2)
+        S.set_deterministic(True)
+        S.set_deterministic_damage(True)
+        info, z = {}, None
+        for k, scale in enumerate((1.0, 0.5, 0.25)):  # the runs are built, reused, dropped by a mode switch and built again
+            if k == 2:
+                S.set_deterministic(False)
+                S.set_deterministic(True)
+            if k != 1:
+                S.local_search()
+                S.active_masks(N.BccSet([]), 0)
+                Mv, z = S.compute_nodal_lumped_mass(), np.zeros(S.nactive * ndim)
+            info[f"residual {k}"] = np.array(S.lagrangian_evaluation(scale * dU, z, z, Mv, alpha_of(1.0e-3)[1]))
+        info.update({f"state {k}": v for k, v in S.download_state().items() if isinstance(v, np.ndarray)})
+        S.close()
+        return None, info
+
+    for ndim in (2, 3):
+        case = lr.loaded_case(ndim)
+        probes = fs.probe_ids(case["cloud"]["x"].shape[0])
+        emit(f"steps/{ndim}-D plain", lambda: stepped(fs.loaded_solver(case, None, fs.prepare(case)), False))
+        emit(f"steps/{ndim}-D record, loads set and removed", lambda: stepped(fs.had_loads(case, probes), True))
+        emit(f"steps/{ndim}-D loads, record set and dropped", lambda: stepped(fs.had_record(case, probes), False))
+        emit(f"steps/{ndim}-D loads, probes and snapshots", lambda: together(case, probes, 1))
+        emit(f"steps/{ndim}-D loads, probes and snapshots, pack by slot", lambda: together(case, probes, 0))
+        emit(f"steps/{ndim}-D fused damage residual", lambda: fused_damage_residual(ndim))
+    emit("steps/3-D damage hooks, mode switches", lambda: damage(xr.erosion_case(3, 0, Gf=xr.erosion_Gf(3, 0))))
+
+
+def traced_steps():
+    """what `--steps-trace` runs under rocprofv3: the shipped (async, non-deterministic) step of one small 3-D Neo-Hookean
+    cloud with loads, record probes and snapshots on, 12 steps, a re-sort every 4"""
+    import explicit_loads_ref as lr
+    import test_gpu_feature_state as fs
+    case = lr.loaded_case(3)
+    S, bset = fs.loaded_solver(case)
+    S.set_resort_interval(4)
+    fs.record(S, fs.probe_ids(S.np))
+    S.set_snapshots(N.SNAP_ALL, 2)
+    for t in range(12):
+        fs.step(S, bset, fs.TABLE_STEP[t % fs.NSTEPS])
+        slot = S.snapshot_begin(t)
+        S.snapshot_wait(slot, copy=False)
+        S.snapshot_release(slot)
+    S.close()
+
+
+if "--steps" in sys.argv:
+    step_cases()
+    sys.exit(0)
+if "--steps-trace" in sys.argv:
+    traced_steps()
     sys.exit(0)
 
 
@@ -371,3 +478,5 @@ emit("refusal newton: halo callback", lambda: newton(dev, z.copy(), ksp=TIGHT))
 S.set_halo_exchange(None)
 emit("newton after the refusals", lambda: newton(dev, z.copy(), linesearch="basic", ksp=TIGHT, max_it=12, rtol=1e-10, atol=0.0, stol=0.0))
 S.close()
+
+step_cases()
