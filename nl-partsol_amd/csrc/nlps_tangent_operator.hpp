@@ -203,10 +203,9 @@ __global__ __launch_bounds__(NT) void k_tanop_apply(PView P, GridD g, TileD td, 
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN, E = ND * ND;
   __shared__ double win[NW * ND];  // x of the window, node-major
   __shared__ double acc[ND * NW];  // (K x) of the window, field-major (kb_fint_tile's layout)
-  const int wb = td.range[0] + (int)blockIdx.x;
-  if (wb >= td.range[1]) return;
-  const int tile = td.work[wb].x;
-  const int cnt = td.count[tile];
+  TileWork tw;
+  if (!tile_work_item(td, tw)) return;
+  const int tile = tw.tile, cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
   for (int idx = threadIdx.x; idx < NW; idx += NT) {
@@ -221,7 +220,7 @@ __global__ __launch_bounds__(NT) void k_tanop_apply(PView P, GridD g, TileD td, 
   __syncthreads();
   const int start = td.start[tile];
   for (int s = threadIdx.x; s < cnt; s += NT) {
-    const int p = (NT == 64) ? td.order[start + s] : td.order_m[start + s];
+    const int p = tile_list<NT>(td)[start + s];
     Lme<ND> c;
     double lam[ND], beta;
     if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
@@ -326,19 +325,7 @@ __global__ __launch_bounds__(NT) void k_tanop_apply(PView P, GridD g, TileD td, 
     }
   }
   __syncthreads();
-  if constexpr (NT == 64) {
-    window_to_slab<ND, ND, NT>(td, tile, acc);
-    return;
-  }
-  for (int q = threadIdx.x; q < NW * ND; q += NT) {
-    const int f = q % ND, idx = q / ND;
-    const double v = acc[f * NW + idx];
-    if (v != 0.0) {
-      bool in;
-      const int node = window_node<ND>(g, w0, idx, in);
-      if (in) atomic_add_f64(y + (size_t)node * ND + f, v);
-    }
-  }
+  window_leave<ND, ND, NT>(g, td, tile, w0, acc, y);
 }
 
 // out_grid[A][i][j] += sum_p sum_mn gn_A[m] gn_A[n] Dh_p[m][n][i][j]: the diagonal blocks, d^2 accumulator fields per node
@@ -347,17 +334,16 @@ __global__ __launch_bounds__(NT) void k_tanop_bdiag(PView P, GridD g, TileD td, 
                                                      double* __restrict__ out) {
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN, E = ND * ND;
   __shared__ double acc[E * NW];
-  const int wb = td.range[0] + (int)blockIdx.x;
-  if (wb >= td.range[1]) return;
-  const int tile = td.work[wb].x;
-  const int cnt = td.count[tile];
+  TileWork tw;
+  if (!tile_work_item(td, tw)) return;
+  const int tile = tw.tile, cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
   for (int idx = threadIdx.x; idx < NW * E; idx += NT) acc[idx] = 0.0;
   __syncthreads();
   const int start = td.start[tile];
   for (int s = threadIdx.x; s < cnt; s += NT) {
-    const int p = (NT == 64) ? td.order[start + s] : td.order_m[start + s];
+    const int p = tile_list<NT>(td)[start + s];
     Lme<ND> c;
     double lam[ND], beta;
     if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
@@ -432,19 +418,7 @@ __global__ __launch_bounds__(NT) void k_tanop_bdiag(PView P, GridD g, TileD td, 
     }
   }
   __syncthreads();
-  if constexpr (NT == 64) {
-    window_to_slab<ND, E, NT>(td, tile, acc);
-    return;
-  }
-  for (int q = threadIdx.x; q < NW * E; q += NT) {
-    const int f = q % E, idx = q / E;
-    const double v = acc[f * NW + idx];
-    if (v != 0.0) {
-      bool in;
-      const int node = window_node<ND>(g, w0, idx, in);
-      if (in) atomic_add_f64(out + (size_t)node * E + f, v);
-    }
-  }
+  window_leave<ND, E, NT>(g, td, tile, w0, acc, out);
 }
 
 // x (masked) -> grid numbering, the dofs fixed at the step of nlps_gpu_active_masks zeroed when d2m is given

@@ -316,10 +316,9 @@ __global__ __launch_bounds__(256) void k_tile_order(PView P, GridD g, TileD td, 
   __shared__ int lsize[LMAX + 1];
   __shared__ int keys[CAP], pp[CAP];
   __shared__ int maxc;
-  const int wb = td.range[0] + (int)blockIdx.x;
-  if (wb >= td.range[1]) return;
-  const int tile = td.work[wb].x;
-  const int n = td.count[tile];
+  TileWork tw;
+  if (!tile_work_item(td, tw)) return;
+  const int tile = tw.tile, n = td.count[tile];
   const int start = td.start[tile];
   if (n > CAP || n <= 1) {
     if (EXACT && n > 1) {
@@ -473,6 +472,30 @@ __device__ __forceinline__ void window_flush3(const GridD& g, const int* w0, con
       if (in) atomic_add_f64(out + (size_t)node * NF + f, v);
     }
   }
+}
+// How an accumulator window in the padded layout (WA / PSA; acc: [NF][NWA], field-major) leaves its workgroup, called by
+// all threads behind the barrier that ends the scatter (K2, K3, the force half k3f_*).
+// window_flush: global atomics into out[node][NF], zeros and cells outside the grid skipped
+template <int ND, int NF, int NT>
+__device__ __forceinline__ void window_flush(const GridD& g, const int* w0, const double* acc, double* out) {
+  constexpr int NWA = TileCfg<ND>::NWA;
+  if (ND == 3) return window_flush3<NF, NT>(g, w0, acc, out);
+  for (int q = threadIdx.x; q < NWA * NF; q += NT) {
+    const int f = q % NF, idx = q / NF;
+    const double v = acc[f * NWA + idx];
+    if (v != 0.0) {
+      bool in;
+      const int node = window_node_a<ND>(g, w0, idx, in);
+      if (in) atomic_add_f64(out + (size_t)node * NF + f, v);
+    }
+  }
+}
+// window_slab_copy: deterministic mode (TileD::slab), the window as it is into the slot of this launch in the tile's slab
+template <int ND, int NF, int NT>
+__device__ __forceinline__ void window_slab_copy(const TileD& td, int tile, const double* acc) {
+  constexpr int NWA = TileCfg<ND>::NWA;
+  double* out = td.slab + ((size_t)tile * td.slab_n + td.slab_slot) * (NF * NWA);
+  for (int q = threadIdx.x; q < NWA * NF; q += NT) out[q] = acc[q];
 }
 
 // membership bits of row (j,k) into the 125-bit mask
@@ -834,23 +857,10 @@ __device__ __forceinline__ void k2_body(const PView& P, const GridD& g, const NV
   __syncthreads();
   PH(4)
   if (td.slab) {
-    double* out = td.slab + ((size_t)tile * td.slab_n + td.slab_slot) * (NF * NWA);
-    for (int q = threadIdx.x; q < NWA * NF; q += NT) out[q] = acc[q];
+    window_slab_copy<ND, NF, NT>(td, tile, acc);
     return;
   }
-  if (ND == 3) {
-    window_flush3<NF, NT>(g, w0, acc, N.nm);
-  } else {
-    for (int q = threadIdx.x; q < NWA * NF; q += NT) {
-      int f = q % NF, idx = q / NF;
-      double v = acc[f * NWA + idx];
-      if (v != 0.0) {
-        bool in;
-        int node = window_node_a<ND>(g, w0, idx, in);
-        if (in) atomic_add_f64(N.nm + (size_t)node * NF + f, v);
-      }
-    }
-  }
+  window_flush<ND, NF, NT>(g, w0, acc, N.nm);
   PH(5)
   tile_signal(td, wb, nbnd);
 }
@@ -1510,6 +1520,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
       const double hx = c.lx[2] - c.lx[3];
       const double al[3] = {c.lx[2], c.ly[2], (ND == 3) ? c.lz[2 % KN] : 0.0};
       // pass 2: -f_A = p_A * (B l_A) with l = a - h u:  B l = B a - h (B[.][x] u_i + B[.][y] v_j + B[.][z] w_k)
+      // (k3f_body holds the same scatter, kept as a second copy: as one helper it costs K3 registers and scratch)
       double Ba[ND], hB[ND * ND];
 #pragma unroll
       for (int a = 0; a < ND; a++) {
@@ -1564,23 +1575,10 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
   // flush is not part of their code
   constexpr bool SLAB_ONLY = NT == 64 && (MODE == 3 || MODE == 4);
   if (SLAB_ONLY || td.slab) {
-    double* out = td.slab + ((size_t)tile * td.slab_n + td.slab_slot) * (ND * NWA);
-    for (int qq = threadIdx.x; qq < NWA * ND; qq += NT) out[qq] = fac[qq];
+    window_slab_copy<ND, ND, NT>(td, tile, fac);
     return;
   }
-  if (ND == 3) {
-    window_flush3<ND, NT>(g, w0, fac, N.force);
-  } else {
-    for (int qq = threadIdx.x; qq < NWA * ND; qq += NT) {
-      int f = qq % ND, idx = qq / ND;
-      double v = fac[f * NWA + idx];
-      if (v != 0.0) {
-        bool in;
-        int node = window_node_a<ND>(g, w0, idx, in);
-        if (in) atomic_add_f64(N.force + (size_t)node * ND + f, v);
-      }
-    }
-  }
+  window_flush<ND, ND, NT>(g, w0, fac, N.force);
   PH(14)
   tile_signal(td, wb, nbnd);
 }
@@ -1670,180 +1668,109 @@ __global__ __launch_bounds__(K3_BLK, (K3Waves<ND, LAW, 1>::value)) void k3_tile_
 // from the STORED Kirchhoff stress -- scaled by the damage hook since k3_tile<., ., 5> wrote it -- and DF, into the
 // nodal forces.  K3's scatter in K3's shape: the padded accumulator window (NWA, rows of 12), lds_add, the canonical
 // lists, force_operator with sign -1, one flush per tile; the LME factors are rebuilt from the particle's stored x,
-// lambda, beta and masks (load_lme, as K3's RELOAD path does), J^-1 and Z^-1 from their moments.  One rank, atomic
-// flush: no slabs, no boundary signal.
+// lambda, beta and masks (load_lme, as K3's RELOAD path does), J^-1 and Z^-1 from their moments.  One rank: no boundary
+// signal.
 // PLUS (nlps_gpu_set_implicit_damage): +f_int, what the Lagrangian of the implicit driver accumulates (MODE 3's sign);
 // the default is the explicit step's kernel, whose code the argument does not change.
+// k3f_body: accumulator reset, the particle loop, closing barrier; two kernels around it differ in how the window leaves.
+// k3f_tile: K3_BLK threads, atomic flush into the nodal forces (window_flush), no slabs.
+// k3f_wave, the deterministic sibling (nlps_gpu_set_deterministic_damage): ONE wave per tile walks the exact canonical
+// list (k_tile_order<., true>) in list order, accumulates into the same window with the same arithmetic and leaves it as
+// the tile's one slab (window_slab_copy); k_slab_gather<ND, ND> then sums the slabs per node in a fixed order.  No global
+// atomics on the forces.
+// Every thread of a workgroup arrives at both barriers of the body (the work item is uniform, the barriers stand outside
+// the particle loop): a lane without a particle of the list -- or a list of zero particles -- passes them like every
+// other lane.
+template <int ND, bool PLUS, int NT>
+__device__ __forceinline__ void k3f_body(const PView& P, const GridD& g, const TileD& td, int* __restrict__ gstatus, int tile,
+                                         const int* w0, double* fac) {
+  NLPS_FP_CONTRACT
+  constexpr int KN = Lme<ND>::KN, WA = TileCfg<ND>::WA, PSA = TileCfg<ND>::PSA, NWA = TileCfg<ND>::NWA;
+  const int cnt = td.count[tile];
+  for (int idx = threadIdx.x; idx < ND * NWA; idx += NT) fac[idx] = 0.0;
+  __syncthreads();
+  const int start = td.start[tile];
+  for (int s = threadIdx.x; s < cnt; s += NT) {
+    const int p = td.order[start + s];
+    Lme<ND> c;
+    double lam[ND], beta;
+    if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
+    double Zinv, r[ND], J[ND * ND], Jm1[ND * ND], tau[ND * ND], DF[ND * ND], B[ND * ND], z;
+    lme_moments_h<ND>(c, Zinv, r, J);
+    load_block<ND>(P, F_TAU, p, tau, z);
+    load_block<ND>(P, F_DF, p, DF, z);
+    if (!(inverse<ND>(Jm1, J) && force_operator<ND>(B, tau, DF, Jm1, PF(P, F_VOL0, p), PLUS ? 1.0 : -1.0))) {
+      atomicOr(&P.status[p], ST_JACOBIAN);
+      atomicOr(gstatus, ST_JACOBIAN);
+      continue;
+    }
+    NLPS_YZ_LOCALS(c);
+    (void)ly5;
+    (void)lz5;
+    // -f_A = p_A * (B l_A) with l = a - h u:  B l = B a - h (B[.][x] u_i + B[.][y] v_j + B[.][z] w_k)
+    // (k3_body's pass 2, kept as a second copy: as one helper it costs K3 registers and scratch)
+    const double hx = c.lx[2] - c.lx[3];
+    const double al[3] = {c.lx[2], c.ly[2], (ND == 3) ? c.lz[2 % KN] : 0.0};
+    double Ba[ND], hB[ND * ND];
+#pragma unroll
+    for (int a = 0; a < ND; a++) {
+      double v = 0.0;
+#pragma unroll
+      for (int mm = 0; mm < ND; mm++) {
+        v = fma(B[a * ND + mm], al[mm], v);
+        hB[a * ND + mm] = -hx * B[a * ND + mm];
+      }
+      Ba[a] = v;
+    }
+    const int basea = window_base_a<ND>(c.ijk, w0);
+#pragma unroll 1
+    for (int k = 0; k < KN; k++) {
+      const unsigned pb = plane_bits<ND>(c, k);
+      const int basek = basea + (ND == 3 ? PSA * (k - 2) : 0);
+      const double wz = Zinv * ez5[k];
+      const double ck = (double)(k - 2);
+      double cz[ND];
+#pragma unroll
+      for (int a = 0; a < ND; a++) cz[a] = (ND == 3) ? fma(hB[a * ND + (2 % ND)], ck, Ba[a]) : Ba[a];
+      unsigned pbs = pb << 7;  // pop_member: bit 24 (j = 4, i = 4) first
+#pragma unroll
+      for (int j = 4; j >= 0; j--) {
+        const double w = wz * ey5[j];
+        double cr[ND];
+#pragma unroll
+        for (int a = 0; a < ND; a++) cr[a] = fma(hB[a * ND + 1], (double)(j - 2), cz[a]);
+#pragma unroll
+        for (int i = 4; i >= 0; i--)
+          if (pop_member(pbs)) {
+            const int li = basek + (i - 2) + WA * (j - 2);
+            const double we = w * c.ex[i];
+#pragma unroll
+            for (int a = 0; a < ND; a++) lds_add(&fac[a * NWA + li], we * fma(hB[a * ND + 0], (double)(i - 2), cr[a]));
+          }
+      }
+    }
+  }
+  __syncthreads();
+}
 template <int ND, bool PLUS = false>
 __global__ __launch_bounds__(K3_BLK, 2) void k3f_tile(PView P, GridD g, NView N, TileD td, int* __restrict__ gstatus) {
-  NLPS_FP_CONTRACT
-  constexpr int KN = Lme<ND>::KN, WA = TileCfg<ND>::WA, PSA = TileCfg<ND>::PSA, NWA = TileCfg<ND>::NWA;
-  __shared__ double fac[ND * NWA];
+  __shared__ double fac[ND * TileCfg<ND>::NWA];
   TileWork tw;
   if (!tile_work_item(td, tw)) return;
-  const int tile = tw.tile, cnt = td.count[tile];
   int w0[3];
-  tile_origin<ND>(td, tile, w0);
-  for (int idx = threadIdx.x; idx < ND * NWA; idx += K3_BLK) fac[idx] = 0.0;
-  __syncthreads();
-  const int start = td.start[tile];
-  for (int s = threadIdx.x; s < cnt; s += K3_BLK) {
-    const int p = td.order[start + s];
-    Lme<ND> c;
-    double lam[ND], beta;
-    if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
-    double Zinv, r[ND], J[ND * ND], Jm1[ND * ND], tau[ND * ND], DF[ND * ND], B[ND * ND], z;
-    lme_moments_h<ND>(c, Zinv, r, J);
-    load_block<ND>(P, F_TAU, p, tau, z);
-    load_block<ND>(P, F_DF, p, DF, z);
-    if (!(inverse<ND>(Jm1, J) && force_operator<ND>(B, tau, DF, Jm1, PF(P, F_VOL0, p), PLUS ? 1.0 : -1.0))) {
-      atomicOr(&P.status[p], ST_JACOBIAN);
-      atomicOr(gstatus, ST_JACOBIAN);
-      continue;
-    }
-    NLPS_YZ_LOCALS(c);
-    (void)ly5;
-    (void)lz5;
-    // -f_A = p_A * (B l_A) with l = a - h u:  B l = B a - h (B[.][x] u_i + B[.][y] v_j + B[.][z] w_k)   (as k3_body)
-    const double hx = c.lx[2] - c.lx[3];
-    const double al[3] = {c.lx[2], c.ly[2], (ND == 3) ? c.lz[2 % KN] : 0.0};
-    double Ba[ND], hB[ND * ND];
-#pragma unroll
-    for (int a = 0; a < ND; a++) {
-      double v = 0.0;
-#pragma unroll
-      for (int mm = 0; mm < ND; mm++) {
-        v = fma(B[a * ND + mm], al[mm], v);
-        hB[a * ND + mm] = -hx * B[a * ND + mm];
-      }
-      Ba[a] = v;
-    }
-    const int basea = window_base_a<ND>(c.ijk, w0);
-#pragma unroll 1
-    for (int k = 0; k < KN; k++) {
-      const unsigned pb = plane_bits<ND>(c, k);
-      const int basek = basea + (ND == 3 ? PSA * (k - 2) : 0);
-      const double wz = Zinv * ez5[k];
-      const double ck = (double)(k - 2);
-      double cz[ND];
-#pragma unroll
-      for (int a = 0; a < ND; a++) cz[a] = (ND == 3) ? fma(hB[a * ND + (2 % ND)], ck, Ba[a]) : Ba[a];
-      unsigned pbs = pb << 7;  // pop_member: bit 24 (j = 4, i = 4) first
-#pragma unroll
-      for (int j = 4; j >= 0; j--) {
-        const double w = wz * ey5[j];
-        double cr[ND];
-#pragma unroll
-        for (int a = 0; a < ND; a++) cr[a] = fma(hB[a * ND + 1], (double)(j - 2), cz[a]);
-#pragma unroll
-        for (int i = 4; i >= 0; i--)
-          if (pop_member(pbs)) {
-            const int li = basek + (i - 2) + WA * (j - 2);
-            const double we = w * c.ex[i];
-#pragma unroll
-            for (int a = 0; a < ND; a++) lds_add(&fac[a * NWA + li], we * fma(hB[a * ND + 0], (double)(i - 2), cr[a]));
-          }
-      }
-    }
-  }
-  __syncthreads();
-  if (ND == 3) {
-    window_flush3<ND, K3_BLK>(g, w0, fac, N.force);
-  } else {
-    for (int qq = threadIdx.x; qq < NWA * ND; qq += K3_BLK) {
-      const int f = qq % ND, idx = qq / ND;
-      const double v = fac[f * NWA + idx];
-      if (v != 0.0) {
-        bool in;
-        const int node = window_node_a<ND>(g, w0, idx, in);
-        if (in) atomic_add_f64(N.force + (size_t)node * ND + f, v);
-      }
-    }
-  }
+  tile_origin<ND>(td, tw.tile, w0);
+  k3f_body<ND, PLUS, K3_BLK>(P, g, td, gstatus, tw.tile, w0, fac);
+  window_flush<ND, ND, K3_BLK>(g, w0, fac, N.force);
 }
-
-// The deterministic sibling (nlps_gpu_set_deterministic_damage): ONE wave per tile walks the exact canonical list
-// (k_tile_order<., true>) in list order, accumulates into the same window with the same arithmetic and leaves it as the
-// tile's one slab; k_slab_gather<ND, ND> then sums the slabs per node in a fixed order.  No global atomics on the forces.
-// A kernel of its own rather than a template form of k3f_tile, whose compiled code stays what it was.  Every thread of the
-// wave arrives at both barriers (the work item is uniform, the barriers stand outside the particle loop): a lane without a
-// particle of the list -- or a list of zero particles -- passes them like every other lane.  PLUS: as k3f_tile.
 template <int ND, bool PLUS>
 __global__ __launch_bounds__(64) void k3f_wave(PView P, GridD g, NView N, TileD td, int* __restrict__ gstatus) {
-  NLPS_FP_CONTRACT
-  constexpr int KN = Lme<ND>::KN, WA = TileCfg<ND>::WA, PSA = TileCfg<ND>::PSA, NWA = TileCfg<ND>::NWA;
-  __shared__ double fac[ND * NWA];
+  __shared__ double fac[ND * TileCfg<ND>::NWA];
   TileWork tw;
   if (!tile_work_item(td, tw)) return;
-  const int tile = tw.tile, cnt = td.count[tile];
   int w0[3];
-  tile_origin<ND>(td, tile, w0);
-  for (int idx = threadIdx.x; idx < ND * NWA; idx += 64) fac[idx] = 0.0;
-  __syncthreads();
-  const int start = td.start[tile];
-  for (int s = threadIdx.x; s < cnt; s += 64) {
-    const int p = td.order[start + s];
-    Lme<ND> c;
-    double lam[ND], beta;
-    if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
-    double Zinv, r[ND], J[ND * ND], Jm1[ND * ND], tau[ND * ND], DF[ND * ND], B[ND * ND], z;
-    lme_moments_h<ND>(c, Zinv, r, J);
-    load_block<ND>(P, F_TAU, p, tau, z);
-    load_block<ND>(P, F_DF, p, DF, z);
-    if (!(inverse<ND>(Jm1, J) && force_operator<ND>(B, tau, DF, Jm1, PF(P, F_VOL0, p), PLUS ? 1.0 : -1.0))) {
-      atomicOr(&P.status[p], ST_JACOBIAN);
-      atomicOr(gstatus, ST_JACOBIAN);
-      continue;
-    }
-    NLPS_YZ_LOCALS(c);
-    (void)ly5;
-    (void)lz5;
-    // -f_A = p_A * (B l_A) with l = a - h u:  B l = B a - h (B[.][x] u_i + B[.][y] v_j + B[.][z] w_k)   (as k3_body)
-    const double hx = c.lx[2] - c.lx[3];
-    const double al[3] = {c.lx[2], c.ly[2], (ND == 3) ? c.lz[2 % KN] : 0.0};
-    double Ba[ND], hB[ND * ND];
-#pragma unroll
-    for (int a = 0; a < ND; a++) {
-      double v = 0.0;
-#pragma unroll
-      for (int mm = 0; mm < ND; mm++) {
-        v = fma(B[a * ND + mm], al[mm], v);
-        hB[a * ND + mm] = -hx * B[a * ND + mm];
-      }
-      Ba[a] = v;
-    }
-    const int basea = window_base_a<ND>(c.ijk, w0);
-#pragma unroll 1
-    for (int k = 0; k < KN; k++) {
-      const unsigned pb = plane_bits<ND>(c, k);
-      const int basek = basea + (ND == 3 ? PSA * (k - 2) : 0);
-      const double wz = Zinv * ez5[k];
-      const double ck = (double)(k - 2);
-      double cz[ND];
-#pragma unroll
-      for (int a = 0; a < ND; a++) cz[a] = (ND == 3) ? fma(hB[a * ND + (2 % ND)], ck, Ba[a]) : Ba[a];
-      unsigned pbs = pb << 7;  // pop_member: bit 24 (j = 4, i = 4) first
-#pragma unroll
-      for (int j = 4; j >= 0; j--) {
-        const double w = wz * ey5[j];
-        double cr[ND];
-#pragma unroll
-        for (int a = 0; a < ND; a++) cr[a] = fma(hB[a * ND + 1], (double)(j - 2), cz[a]);
-#pragma unroll
-        for (int i = 4; i >= 0; i--)
-          if (pop_member(pbs)) {
-            const int li = basek + (i - 2) + WA * (j - 2);
-            const double we = w * c.ex[i];
-#pragma unroll
-            for (int a = 0; a < ND; a++) lds_add(&fac[a * NWA + li], we * fma(hB[a * ND + 0], (double)(i - 2), cr[a]));
-          }
-      }
-    }
-  }
-  __syncthreads();
-  // (fac has the slab's layout already -- rows of WA, planes of PSA --: a plain copy, as k3_body's)
-  double* __restrict__ out = td.slab + ((size_t)tile * td.slab_n + td.slab_slot) * (ND * NWA);
-  for (int qq = threadIdx.x; qq < NWA * ND; qq += 64) out[qq] = fac[qq];
+  tile_origin<ND>(td, tw.tile, w0);
+  k3f_body<ND, PLUS, 64>(P, g, td, gstatus, tw.tile, w0, fac);
+  window_slab_copy<ND, ND, 64>(td, tw.tile, fac);
 }
 
 // Sums, for every node of two node ranges, the window slabs of the tiles whose window holds the node (<= 2 per axis)
@@ -1907,8 +1834,7 @@ __device__ __forceinline__ void k5_body(const PView& P, const GridD& g, const NV
                                         const NodalFold* fs, int* __restrict__ gstatus) {
   static_assert(!(SEARCH && DEFER), "the riding search needs the position this kernel writes");
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN;
-  const int tile = tw.tile;
-  const int cnt = td.count[tile];
+  const int tile = tw.tile, cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
   for (int idx0 = threadIdx.x; idx0 < ((ND == 3) ? 512 : NW); idx0 += K5_BLK) {
@@ -2079,6 +2005,29 @@ __device__ __forceinline__ void window_to_slab(const TileD& td, int tile, const 
     for (int q = threadIdx.x; q < NF * NW; q += NT) out[q] = acc[q];
   }
 }
+// How a level-B accumulator window (gather layout; acc: [NF][NW], field-major) leaves its workgroup, called by all
+// threads behind the barrier that ends the scatter: NT = 64 is the deterministic form and knows the slab only
+// (window_to_slab, out unused), every other NT flushes by global atomics into out[node][NF]
+template <int ND, int NF, int NT>
+__device__ __forceinline__ void window_leave(const GridD& g, const TileD& td, int tile, const int* w0, const double* acc,
+                                             double* __restrict__ out) {
+  constexpr int NW = TileCfg<ND>::NW;
+  if constexpr (NT == 64) return window_to_slab<ND, NF, NT>(td, tile, acc);
+  for (int q = threadIdx.x; q < NW * NF; q += NT) {
+    const int f = q % NF, idx = q / NF;
+    const double v = acc[f * NW + idx];
+    if (v != 0.0) {
+      bool in;
+      const int node = window_node<ND>(g, w0, idx, in);
+      if (in) atomic_add_f64(out + (size_t)node * NF + f, v);
+    }
+  }
+}
+// the tile lists a level-B kernel walks: canonical (exact) order for the one wave of the deterministic form, as binned otherwise
+template <int NT>
+__device__ __forceinline__ const int* tile_list(const TileD& td) {
+  return (NT == 64) ? td.order : td.order_m;
+}
 
 // Z^-1 alone (rows of masked ex, then ey, ez)
 template <int ND>
@@ -2112,17 +2061,16 @@ __global__ __launch_bounds__(NT) void kb_p2g_tile(PView P, GridD g, TileD td, do
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN;
   constexpr int NF = MODE == 0 ? 1 : 2 * ND;
   __shared__ double acc[NF * NW];
-  const int wb = td.range[0] + (int)blockIdx.x;
-  if (wb >= td.range[1]) return;
-  const int tile = td.work[wb].x;
-  const int cnt = td.count[tile];
+  TileWork tw;
+  if (!tile_work_item(td, tw)) return;
+  const int tile = tw.tile, cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
   for (int idx = threadIdx.x; idx < NW * NF; idx += NT) acc[idx] = 0.0;
   __syncthreads();
   const int start = td.start[tile];
   for (int s = threadIdx.x; s < cnt; s += NT) {
-    const int p = (NT == 64) ? td.order[start + s] : td.order_m[start + s];
+    const int p = tile_list<NT>(td)[start + s];
     Lme<ND> c;
     double lam[ND], beta;
     if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
@@ -2161,19 +2109,7 @@ __global__ __launch_bounds__(NT) void kb_p2g_tile(PView P, GridD g, TileD td, do
     }
   }
   __syncthreads();
-  if constexpr (NT == 64) {
-    window_to_slab<ND, NF, NT>(td, tile, acc);
-    return;
-  }
-  for (int q = threadIdx.x; q < NW * NF; q += NT) {
-    int f = q % NF, idx = q / NF;
-    double v = acc[f * NW + idx];
-    if (v != 0.0) {
-      bool in;
-      int node = window_node<ND>(g, w0, idx, in);
-      if (in) atomic_add_f64(out + (size_t)node * NF + f, v);
-    }
-  }
+  window_leave<ND, NF, NT>(g, td, tile, w0, acc, out);
 }
 
 // __nodal_internal_forces (U-Newmark-beta.c:1257-1374): +V0 tau (DF^-T grad N) from the stored tau, DF
@@ -2183,17 +2119,16 @@ __global__ __launch_bounds__(NT) void kb_fint_tile(PView P, GridD g, TileD td, d
                                                     int* __restrict__ gstatus) {
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN;
   __shared__ double fac[ND * NW];
-  const int wb = td.range[0] + (int)blockIdx.x;
-  if (wb >= td.range[1]) return;
-  const int tile = td.work[wb].x;
-  const int cnt = td.count[tile];
+  TileWork tw;
+  if (!tile_work_item(td, tw)) return;
+  const int tile = tw.tile, cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
   for (int idx = threadIdx.x; idx < NW * ND; idx += NT) fac[idx] = 0.0;
   __syncthreads();
   const int start = td.start[tile];
   for (int s = threadIdx.x; s < cnt; s += NT) {
-    const int p = (NT == 64) ? td.order[start + s] : td.order_m[start + s];
+    const int p = tile_list<NT>(td)[start + s];
     Lme<ND> c;
     double lam[ND], beta;
     if (!load_lme<ND>(P, g, p, c, lam, beta)) continue;
@@ -2234,19 +2169,7 @@ __global__ __launch_bounds__(NT) void kb_fint_tile(PView P, GridD g, TileD td, d
     }
   }
   __syncthreads();
-  if constexpr (NT == 64) {
-    window_to_slab<ND, ND, NT>(td, tile, fac);
-    return;
-  }
-  for (int qq = threadIdx.x; qq < NW * ND; qq += NT) {
-    int f = qq % ND, idx = qq / ND;
-    double v = fac[f * NW + idx];
-    if (v != 0.0) {
-      bool in;
-      int node = window_node<ND>(g, w0, idx, in);
-      if (in) atomic_add_f64(force + (size_t)node * ND + f, v);
-    }
-  }
+  window_leave<ND, ND, NT>(g, td, tile, w0, fac, force);
 }
 
 // __update_particles_kinetics_FLIP_PIC (U-Newmark-beta.c:1993-2072): gathers 4 nodal vectors
@@ -2259,10 +2182,9 @@ __global__ __launch_bounds__(BLK) void kb_kinetics_tile(PView P, GridD g, TileD 
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN;
   constexpr int NV = 4 * ND, NP = NV / 2;
   __shared__ __attribute__((aligned(16))) double win[NW * NV];
-  const int wb = td.range[0] + (int)blockIdx.x;
-  if (wb >= td.range[1]) return;
-  const int tile = td.work[wb].x;
-  const int cnt = td.count[tile];
+  TileWork tw;
+  if (!tile_work_item(td, tw)) return;
+  const int tile = tw.tile, cnt = td.count[tile];
   int w0[3];
   tile_origin<ND>(td, tile, w0);
   for (int idx = threadIdx.x; idx < NW; idx += BLK) {
