@@ -290,6 +290,58 @@ int nlps_gpu_set_explicit_fluid(nlps_gpu *h, int on);
  * fluid law (as above).
  * The setter returns 1 for a cloud created without either driver. */
 int nlps_gpu_set_explicit_damage(nlps_gpu *h, int on);
+/* F-bar, the reference's volumetric-locking control, inside the explicit step, on patches of background-lattice cells.
+ * Upstream: Neo-Hookean-Wriggers and Newtonian-Fluid-Compressible carry Fbar / Fbar-alpha
+ * (InOutFun/Material/Hyperelastic/Neo-Hookean.c:133-146, Fluid/Compressible-Newtonian-Fluid.c:107-118); the compatibility
+ * stage sums J Vol_0 over patches of elements (U-Newmark-beta.c:1146-1193);
+ * get_locking_free_Deformation_Gradient_n1__Particles__ (compute-Strains.c:109-172) turns the patch ratio into Fbar; the
+ * law reads (Fbar, Jbar) in place of (F_n1, J_n1) (Constitutive.c:32-38, 66-72, 89-95).  Upstream defines its patches on
+ * T6 / T10 meshes only, overwrites Fbar_n in place at every residual evaluation and starts Phi.Fbar from zeros, so the
+ * definition is stated here and only the formulas are upstream's.
+ *
+ * Off by default: a step then launches exactly what it launches without this call.  With a configuration set, a step is
+ * the explicit composition above with one insertion between the compatibility and the constitutive update:
+ *   - The patch of a particle.  Its cell is c_k = clamp(floor((x_k - origin_k) / h), 0, n_k - 2) per axis k, with x the
+ *     position nlps_gpu_download_state would return in front of the step and n_k the nodes of the lattice along k; its
+ *     patch is c_k / block[k] (integer division) per axis.
+ *   - Patch sums, behind the step's compatibility (DF, F_n1 = DF F_n, J_n1 as always), over ALL particles of a patch
+ *     whatever their material, as upstream does: Vn = sum J_n Vol_0, Vn1 = sum J_n1 Vol_0, J_patch = Vn1 / Vn.
+ *   - Per particle, with alpha the entry of its material (a material with alpha < 0 forms its values with alpha = 0):
+ *       DJ = det DF (2-D: of the in-plane 2 x 2 block),   c = (J_patch / DJ)^(1 / ndim),
+ *       Fbar_n1 = alpha F_n1 + (1 - alpha) c DF Fbar_n    (2-D: the in-plane block; the zz entry is F_n1's),
+ *       Jbar_n1 = Jbar_n J_patch.
+ *     Both are formed for every particle.
+ *   - The law.  A material with alpha >= 0 receives (Fbar_n1, Jbar_n1) where it would receive (F_n1, J_n1).  The rate of
+ *     the fluid law stays the unbarred dt_F_n1 of nlps_gpu_set_explicit_fluid (Constitutive.c:87).  Everything else in the
+ *     step is unchanged -- for a material with alpha < 0 the whole step: density, internal force in the Kirchhoff form
+ *     with the step's own gradients (DF, not a barred one), gravity, Dirichlet sets, contour loads, equilibrium, G2P,
+ *     corrector.
+ *   - The roll adds Fbar_n <- Fbar_n1, Jbar_n <- Jbar_n1.  F_n, J_n, rho and the rates stay unbarred; Stress and W of a
+ *     download behind the step are the law's values at the state it received.
+ * Fbar_n / Jbar_n belong to the particles: they move with them in nlps_gpu_resort, the periodic and the adaptive re-sort,
+ * and nlps_gpu_download_fbar returns them in the caller's order ([np][5 | 9] like every tensor, [np]).  A run is restarted
+ * from (the downloaded state, Fbar_n, Jbar_n).  Inside a step F-bar adds kernels on the handle's stream and nothing else:
+ * no allocation, no synchronisation, no copy (the setter makes the patch array, 2 doubles per patch of the lattice).
+ * Patch sums are taken by floating-point atomics: their summation order is not fixed.
+ *
+ * cfg == NULL switches F-bar off and frees everything it made.  The setter returns 1, with the reason in
+ * nlps_gpu_last_error, stores nothing and leaves the handle as it was for: a block entry < 1; an alpha > 1; alpha >= 0 on a
+ * material that is neither Neo-Hookean nor Newtonian-Fluid-Compressible; every alpha < 0; a cloud created with
+ * driver_eigenerosion / driver_eigensoftening; a handle with a halo callback or an RCCL exchange attached; a migrated
+ * handle.  A step returns 1 in the same way, launching nothing, when an exchange has been attached since, after a
+ * migration, in deterministic mode (fixed-order patch sums are not built), and -- as without F-bar -- for a fluid material
+ * without nlps_gpu_set_explicit_fluid.  While F-bar is set, the calls whose law would have to read it return 1:
+ * nlps_gpu_compatibility, _constitutive, _lagrangian_evaluation, _newton_solve, _newmark_step, _tangent_assemble,
+ * _tangent_operator, _tangent_csr_pattern, _tangent_bsr_pattern, _tangent_lambda_max (the consistent F-bar tangent couples
+ * all particles of a patch).  The step runs the non-folded form on one rank. */
+typedef struct {
+  int block[3];         /* cells per patch along each axis, >= 1 (block[2] not read in 2-D) */
+  const double *alpha;  /* [nmats] alpha_Fbar in [0,1] for materials whose law reads F-bar; < 0: the material does not */
+  const double *Fbar_n; /* [np][T], caller's order, or NULL: F_n as it stands on the device */
+  const double *Jbar_n; /* [np], caller's order, or NULL: J_n as it stands */
+} nlps_fbar_cfg;
+int nlps_gpu_set_explicit_fbar(nlps_gpu *h, const nlps_fbar_cfg *cfg);   /* NULL: off, frees everything */
+int nlps_gpu_download_fbar(nlps_gpu *h, double *Fbar_n, double *Jbar_n); /* caller's order; either may be NULL */
 /* The Neumann contours inside the explicit step: compute_Nodal_Nominal_traction_Forces (U-Verlet.c:805-902), which
  * compute_Nodal_Forces calls directly behind the internal forces (:680-699), Forces[A] += N_pA T A0_p over the particles
  * of MPM_Mesh.Neumann_Contours.  The arguments mean what they mean in nlps_gpu_nodal_traction_forces: loads[l].nodes are

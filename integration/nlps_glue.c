@@ -329,6 +329,30 @@ int nlps_glue_set_explicit_loads(const nlps_glue *G, Particle MPM_Mesh, const nl
   return STATUS;
 }
 
+/* F-bar of the explicit drivers on patches of block[] cells of the GramsBox lattice (the reference's own patches exist on
+ * T6 / T10 meshes only): call once behind nlps_glue_create.  The flags come from the materials --
+ * Mat[m].Locking_Control_Fbar switches a material in, Mat[m].alpha_Fbar is its alpha (Neo-Hookean.c:133-146,
+ * Compressible-Newtonian-Fluid.c:107-118) -- and travel as the alpha array of nlps_fbar_cfg; Fbar_n / Jbar_n start as
+ * F_n / J_n on the device.  No material with the flag: nothing is set (EXIT_SUCCESS). */
+int nlps_glue_set_explicit_fbar(const nlps_glue *G, Particle MPM_Mesh, const int block[3]) {
+  const int Nmat = MPM_Mesh.NumberMaterials;
+  double *alpha = (double *)malloc((size_t)(Nmat > 0 ? Nmat : 1) * sizeof(double));
+  if (alpha == NULL) return EXIT_FAILURE;
+  int any = 0;
+  for (int m = 0; m < Nmat; m++) {
+    alpha[m] = MPM_Mesh.Mat[m].Locking_Control_Fbar ? MPM_Mesh.Mat[m].alpha_Fbar : -1.0;
+    any |= MPM_Mesh.Mat[m].Locking_Control_Fbar ? 1 : 0;
+  }
+  int STATUS = EXIT_SUCCESS;
+  if (any) {
+    nlps_fbar_cfg cfg = {{block[0], block[1], block[2]}, alpha, NULL, NULL};
+    STATUS = nlps_gpu_set_explicit_fbar(G->gpu, &cfg);
+    if (STATUS != EXIT_SUCCESS) fprintf(stderr, "" RED "%s" RESET "\n", nlps_gpu_last_error(G->gpu));
+  }
+  free(alpha);
+  return STATUS;
+}
+
 /* __jacobian_evaluation (U-Newmark-beta.c:1646-1830) as a MatShell instead of an assembled MATAIJ: the matrix-free
  * counterpart of nlps_gpu_tangent_assemble + nlps_gpu_tangent_coo.  Call it where the driver assembles the Jacobian
  * (the SNES Jacobian callback): it linearises at the state the last residual evaluation left, with alpha_1 M on the

@@ -1755,6 +1755,7 @@ struct nlps_gpu {
   DevBuf<double4> beta_t2_d;  // NView::beta_t2
   DevBuf<MatD> mats_d;
   int nmats;
+  std::vector<int> mat_klaw;  // kernel law of every material (what nlps_gpu_set_explicit_fbar checks its flags against)
   int uniform_law;  // material law shared by every particle, or -1
   int law_present;  // bit l set: some material follows law l
   bool k3_per_law = true;  // several laws: one K3 launch per law (few mixed tiles) or one run-time-dispatch kernel
@@ -1932,6 +1933,16 @@ struct nlps_gpu {
     // the atomic path either: both switches drop every cached table.  The buffers stay.
     void drop() { gen = 0, tables0 = tables = false; }
   } dmg;
+  // F-bar on lattice-cell patches inside the explicit step (nlps_gpu_set_explicit_fbar).  F / J: Fbar_n
+  // [T][npad] and Jbar_n [npad] of every particle, by memory slot: they travel with every re-sort (resort gathers them
+  // into the twins and swaps).  sums / pid: the patch sums and the patch of every particle of the step in flight.
+  struct Fbar {
+    bool on = false;
+    int block[3] = {1, 1, 1}, np[3] = {1, 1, 1};
+    size_t npatch = 0;
+    DevBuf<double> F, J, F_alt, J_alt, sums, alpha;
+    DevBuf<int> pid;
+  } fbar;
   bool explicit_damage = false, implicit_damage = false;
   // nlps_gpu_set_deterministic_damage: in deterministic mode the runs are sorted behind k_run_fill (k_run_sort), the force
   // half runs one wave per tile into slabs (k3f_wave) and det_implicit admits the damage cloud
@@ -2463,6 +2474,7 @@ extern "C" int nlps_gpu_create(nlps_gpu** out, const nlps_grid* grid, const nlps
       return 1;
     }
     if (klaw_of(mats[i].type) != klaw_of(mats[0].type)) h->uniform_law = -1;
+    h->mat_klaw.push_back(klaw_of(mats[i].type));
     h->law_present |= 1 << klaw_of(mats[i].type);
   }
   {
@@ -2729,6 +2741,14 @@ static int resort(nlps_gpu* h, const unsigned char* leaving = nullptr, bool live
   }
   h->Pd.swap(h->Pd_alt);
   h->P.d = h->Pd;  // (the view is passed by value: it must follow the owner)
+  if (h->fbar.on) {  // Fbar_n / Jbar_n travel with the particles, into their twins (nlps_gpu_set_explicit_fbar made them)
+    hipLaunchKernelGGL(k_gather_fields, dim3(nblk(np), (h->T + GATHER_FIELDS - 1) / GATHER_FIELDS), dim3(BLK), 0, h->stream,
+                       h->fbar.F_alt.get(), (const double*)h->fbar.F.get(), idx, np, npad, h->T);
+    hipLaunchKernelGGL(k_gather<double>, dim3(nblk(np)), dim3(BLK), 0, h->stream, h->fbar.J_alt.get(), (const double*)h->fbar.J.get(),
+                       idx, np);
+    h->fbar.F.swap(h->fbar.F_alt);
+    h->fbar.J.swap(h->fbar.J_alt);
+  }
   {
     // (the twin block now holds the OLD field values, which nothing reads any more: its head is the scratch of the
     // integer arrays -- 2 x npad doubles for the mask words, then 7 x npad ints)
@@ -2931,6 +2951,133 @@ extern "C" int nlps_gpu_set_explicit_damage(nlps_gpu* h, int on) {
   h->explicit_damage = on != 0;
   return 0;
 }
+static int refresh_perm(nlps_gpu* h);
+// F-bar on lattice-cell patches (include/nlps_gpu.h).  The setter checks, builds a fresh nlps_gpu::Fbar
+// -- the patch array, the patch of every particle, the flags, Fbar_n / Jbar_n with their re-sort twins -- and assigns
+// it behind a synchronise; nothing is stored when it refuses.
+extern "C" int nlps_gpu_set_explicit_fbar(nlps_gpu* h, const nlps_fbar_cfg* cfg) {
+  const std::string who = "nlps_gpu_set_explicit_fbar: ";
+  if (!cfg) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->fbar = {};
+    return 0;
+  }
+  const int ND = h->nd, T = h->T, np = h->P.np;
+  for (int a = 0; a < ND; a++)
+    if (cfg->block[a] < 1) {
+      h->err = who + "a block entry is < 1 (cells per patch along each axis)";
+      return 1;
+    }
+  if (!cfg->alpha) {
+    h->err = who + "alpha is NULL (one entry per material)";
+    return 1;
+  }
+  bool any = false;
+  for (int m = 0; m < h->nmats; m++) {
+    const double al = cfg->alpha[m];
+    if (al > 1.0) {
+      h->err = who + "an alpha is > 1 (alpha_Fbar lies in [0, 1]; < 0: the material does not read F-bar)";
+      return 1;
+    }
+    if (!(al < 0.0)) {
+      const int law = h->mat_klaw[m];
+      if (!(al >= 0.0) || (law != NLPS_MAT_NEO_HOOKEAN && law != NLPS_KLAW_FLUID)) {
+        h->err = who + "alpha >= 0 on a material that is neither Neo-Hookean nor Newtonian-Fluid-Compressible (the laws that "
+                       "carry Fbar upstream)";
+        return 1;
+      }
+      any = true;
+    }
+  }
+  if (!any) {
+    h->err = who + "every alpha is < 0: no material reads F-bar (pass NULL to switch it off)";
+    return 1;
+  }
+  if (h->P.erosion) {
+    h->err = who + "the cloud was created with driver_eigenerosion / driver_eigensoftening; the step with the damage hooks has "
+                   "its own split of K3";
+    return 1;
+  }
+  if (h->halo || h->rccl) {
+    h->err = who + "built for one rank: not with a halo callback or an RCCL exchange attached (a patch across a slab face "
+                   "would need its sums exchanged)";
+    return 1;
+  }
+  if (h->migrated) {
+    h->err = who + "not available after a migration (particle order is by global id)";
+    return 1;
+  }
+  nlps_gpu::Fbar fresh;
+  fresh.on = true;
+  fresh.npatch = 1;
+  for (int a = 0; a < 3; a++) {
+    fresh.block[a] = a < ND ? cfg->block[a] : 1;
+    fresh.np[a] = a < ND ? (std::max(1, h->g.n[a] - 1) + fresh.block[a] - 1) / fresh.block[a] : 1;
+    fresh.npatch *= (size_t)fresh.np[a];
+  }
+  if (fresh.npatch >= ((size_t)1 << 30)) {
+    h->err = who + "more than 2^30 patches";
+    return 1;
+  }
+  const size_t npad = h->P.npad;
+  HIPCHK(fresh.sums.alloc_zeroed(2 * fresh.npatch));
+  HIPCHK(fresh.pid.alloc_zeroed(npad));
+  HIPCHK(fresh.alpha.alloc_zeroed((size_t)std::max(1, h->nmats)));
+  HIPCHK(fresh.F.alloc_zeroed((size_t)T * npad));
+  HIPCHK(fresh.J.alloc_zeroed(npad));
+  HIPCHK(fresh.F_alt.alloc_zeroed((size_t)T * npad));
+  HIPCHK(fresh.J_alt.alloc_zeroed(npad));
+  HIPCHK(hipMemcpy(fresh.alpha, cfg->alpha, (size_t)h->nmats * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if ((cfg->Fbar_n || cfg->Jbar_n) && refresh_perm(h)) return 1;
+  std::vector<double> tmp(npad, 0.0);
+  if (cfg->Fbar_n) {
+    for (int c = 0; c < T; c++) {
+      for (int s = 0; s < np; s++) tmp[s] = cfg->Fbar_n[(size_t)h->perm[s] * T + c];
+      HIPCHK(hipMemcpy(fresh.F + (size_t)c * npad, tmp.data(), npad * sizeof(double), hipMemcpyHostToDevice));
+    }
+  } else {  // F_n as it stands on the device
+    HIPCHK(hipMemcpy(fresh.F, h->P.d + (size_t)fFN(h->P) * npad, (size_t)T * npad * sizeof(double), hipMemcpyDeviceToDevice));
+  }
+  if (cfg->Jbar_n) {
+    for (int s = 0; s < np; s++) tmp[s] = cfg->Jbar_n[h->perm[s]];
+    HIPCHK(hipMemcpy(fresh.J, tmp.data(), npad * sizeof(double), hipMemcpyHostToDevice));
+  } else {
+    HIPCHK(hipMemcpy(fresh.J, h->P.d + (size_t)F_JN * npad, npad * sizeof(double), hipMemcpyDeviceToDevice));
+  }
+  HIPCHK(hipDeviceSynchronize());  // (the copies above are ordered on the default stream only, see ensure_bcs)
+  h->fbar = std::move(fresh);
+  return 0;
+}
+extern "C" int nlps_gpu_download_fbar(nlps_gpu* h, double* Fbar_n, double* Jbar_n) {
+  if (!h->fbar.on) {
+    h->err = "nlps_gpu_download_fbar: F-bar is not set on this handle (nlps_gpu_set_explicit_fbar)";
+    return 1;
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (refresh_perm(h)) return 1;
+  const int T = h->T, np = h->P.np;
+  const size_t npad = h->P.npad;
+  std::vector<double> tmp(npad);
+  for (int c = 0; Fbar_n && c < T; c++) {
+    HIPCHK(hipMemcpy(tmp.data(), h->fbar.F + (size_t)c * npad, (size_t)np * sizeof(double), hipMemcpyDeviceToHost));
+    for (int s = 0; s < np; s++) Fbar_n[(size_t)h->perm[s] * T + c] = tmp[s];
+  }
+  if (Jbar_n) {
+    HIPCHK(hipMemcpy(tmp.data(), h->fbar.J.get(), (size_t)np * sizeof(double), hipMemcpyDeviceToHost));
+    for (int s = 0; s < np; s++) Jbar_n[h->perm[s]] = tmp[s];
+  }
+  return 0;
+}
+// the level-B stages and the implicit path while F-bar is set: their law would have to read it, and its consistent
+// tangent couples all particles of a patch
+static int fbar_refuse(nlps_gpu* h, const char* who) {
+  if (!h->fbar.on) return 0;
+  h->err = std::string(who) + ": F-bar is set on this handle (nlps_gpu_set_explicit_fbar), which only the explicit step reads; "
+                              "pass NULL to it first";
+  return 1;
+}
+
 static const char* implicit_damage_halo_msg =
     "the fused damage residual is built for one rank: with a halo callback or an RCCL exchange attached, an "
     "epsilon-neighbourhood across a slab face would need ghost particles";
@@ -4023,6 +4170,9 @@ static void arm_signal(nlps_gpu* h, TileD& td, int stage) {
 //   MODE 6  the state half of MODE 3 (damage hooks)    nothing else (tests/test_isa_implicit_damage.py)
 //   MODE 7  MODE 1 with the step's mean rate (dt)      the fluid law only: plain, FILT, one wave per tile
 //                                                      (nlps_gpu_set_explicit_fluid; MODE 1 hands the law's particles to it)
+//   MODE 8  the kinematic half of the F-bar step       no law at all: LAW = -1, plain, one form per dimension.  Its kernel
+//           (MODE 5 up to the law, the patch sums)     is k3_kin_tile<ND> -- dt and the patch arrays as arguments -- and its
+//                                                      one launch site is launch_k3_fbar_kin below, not launch_k3
 template <int MODE>
 struct K3Forms {
   static constexpr bool dispatch = MODE == 1 || MODE == 5;  // LAW = -1: the law of every particle looked up at run time
@@ -4092,6 +4242,42 @@ static void launch_k3(nlps_gpu* h, TileD td, const K3Launch& a) {
   } else {
     launch_k3_law<MODE, false, K3_BLK>(h, td, law, a);
   }
+}
+// The step with F-bar (nlps_gpu_set_explicit_fbar): the clear of the patch array and of the patch per particle, then the
+// kinematic half (k3_tile's MODE 8); fluid_dt > 0: the cloud holds the fluid law, whose particles get their rate.
+static void launch_k3_fbar_kin(nlps_gpu* h, const TileD& td, double fluid_dt) {
+  nlps_gpu::Fbar& fb = h->fbar;
+  const int n = std::max((int)(2 * fb.npatch), h->P.np);
+  hipLaunchKernelGGL(k_fbar_clear, dim3(nblk(n)), dim3(BLK), 0, h->stream, fb.sums.get(), (int)(2 * fb.npatch), fb.pid.get(), h->P.np);
+  FbarKin k{fb.sums.get(), fb.pid.get(), {fb.block[0], fb.block[1], fb.block[2]}, {fb.np[0], fb.np[1], fb.np[2]}};
+  with_nd(h->nd, [&](auto D) {
+    hipLaunchKernelGGL(k3_kin_tile<CT(D)>, dim3(h->ntw), dim3(K3_BLK), 0, h->stream, h->P, h->g, h->N, td, h->mats_d.get(), h->prm,
+                       h->gstatus_d.get(), fluid_dt, k);
+  });
+}
+// ... and behind it the stress kernel, in the launch form of the cloud (one law; one launch per law present; the
+// run-time dispatch where nlps_gpu_set_law_launch_mode allows it), and the force half of the damage step, k3f_tile
+static void launch_fbar_stress(nlps_gpu* h) {
+  const nlps_gpu::Fbar& fb = h->fbar;
+  const FbarD d{fb.sums.get(), fb.pid.get(), fb.F.get(), fb.J.get(), fb.alpha.get()};
+  const dim3 grid(nblk(h->P.np)), blk(BLK);
+  with_nd(h->nd, [&](auto D) {
+    auto one = [&](int l, auto FILT) {
+      if (l == NLPS_KLAW_FLUID)
+        hipLaunchKernelGGL((k_fbar_stress<CT(D), NLPS_KLAW_FLUID, CT(FILT)>), grid, blk, 0, h->stream, h->P, h->mats_d.get(), h->prm,
+                           h->gstatus_d.get(), d);
+      else
+        with_law(l, [&](auto L) {
+          hipLaunchKernelGGL((k_fbar_stress<CT(D), CT(L), CT(FILT)>), grid, blk, 0, h->stream, h->P, h->mats_d.get(), h->prm,
+                             h->gstatus_d.get(), d);
+        });
+    };
+    if (h->uniform_law >= 0) one(h->uniform_law, std::false_type{});
+    else if (!h->k3_per_law)
+      hipLaunchKernelGGL((k_fbar_stress<CT(D), -1, false>), grid, blk, 0, h->stream, h->P, h->mats_d.get(), h->prm, h->gstatus_d.get(), d);
+    else for_each_law_present(h->law_present, [&](int l, bool) { one(l, std::true_type{}); });
+  });
+  LAUNCH_ND(k3f_tile<2>, k3f_tile<3>, h->ntw, h->P, h->g, h->N, tile_view(h, 0), h->gstatus_d);
 }
 // The folded form of the explicit step (one law, 0 .. NLPS_KLAW_FRICTIONAL): k3_tile_lazy, plain or one-material
 static void launch_k3_lazy(nlps_gpu* h, TileD td, bool signal, const LazyNodal& ln) {
@@ -4471,6 +4657,7 @@ extern "C" int nlps_gpu_nodal_field_n(nlps_gpu* h, double* V, double* A, const d
 }
 
 extern "C" int nlps_gpu_compatibility(nlps_gpu* h, const double* dU, const double* dU_dt) {
+  if (fbar_refuse(h, "nlps_gpu_compatibility")) return 1;
   if (need_masks(h, "nlps_gpu_compatibility")) return 1;
   if (!dU_dt && (h->law_present & (1 << NLPS_KLAW_FLUID))) {
     h->err = "nlps_gpu_compatibility: the cloud holds the Newtonian-Fluid-Compressible law, whose stress reads dt_F_n1: "
@@ -4495,6 +4682,7 @@ extern "C" int nlps_gpu_compatibility(nlps_gpu* h, const double* dU, const doubl
 }
 
 extern "C" int nlps_gpu_constitutive(nlps_gpu* h) {
+  if (fbar_refuse(h, "nlps_gpu_constitutive")) return 1;
   if (materialise_roll(h)) return 1;
   h->level_b_fields = true;
   if (h->law_present & (1 << NLPS_KLAW_FRICTIONAL))
@@ -5290,6 +5478,21 @@ static int explicit_step_refuse(nlps_gpu* h, int nbcc, int step) {
              "node runs take ranks and run starts from atomics)";
     return 1;
   }
+  if (h->fbar.on) {  // (nlps_gpu_set_explicit_fbar; the setter has refused what it could see)
+    if (h->halo || h->rccl) {
+      h->err = "nlps_gpu_explicit_step: F-bar is built for one rank: not with a halo callback or an RCCL exchange attached (a "
+               "patch across a slab face would need its sums exchanged)";
+      return 1;
+    }
+    if (h->deterministic) {
+      h->err = "nlps_gpu_explicit_step: F-bar is not built for the deterministic mode (its patch sums are taken by atomics)";
+      return 1;
+    }
+    if (h->migrated) {
+      h->err = "nlps_gpu_explicit_step: F-bar is not available after a migration (particle order is by global id)";
+      return 1;
+    }
+  }
   const bool loads = h->loads.n > 0 && h->P.np > 0;
   if (loads && (h->halo || h->rccl)) {
     h->err = std::string("nlps_gpu_explicit_step: ") + explicit_loads_halo_msg;
@@ -5320,6 +5523,7 @@ static bool resort_due(const nlps_gpu* h) {
 // What one step runs, decided once in front of its first launch.  (Which K3 kernel: launch_k3 / launch_k3_lazy.)
 struct StepForm {
   bool dmg;    // the step with the damage hooks (nlps_gpu_set_explicit_damage)
+  bool fbar;   // the step with F-bar (nlps_gpu_set_explicit_fbar): K3 split like the damage step's
   bool loads;  // the Neumann contours (nlps_gpu_set_explicit_loads)
   bool det;    // nlps_gpu_set_deterministic: one wave per tile, slabs, k_slab_gather
   // With a halo callback and ghost bands set, every exchange is started right after the tiles that touch a
@@ -5355,13 +5559,14 @@ struct StepForm {
 static StepForm step_form(const nlps_gpu* h, const nlps_bcc* bcc, int nbcc, int step) {
   StepForm f{};
   f.dmg = h->P.erosion != 0;
+  f.fbar = h->fbar.on && h->P.np > 0;
   f.loads = h->loads.n > 0 && h->P.np > 0;
   f.det = h->deterministic;
   f.ov2 = h->rccl && h->overlap == 2 && !h->deterministic;
   f.ov = !f.ov2 && (h->halo || h->rccl) && h->overlap;
   f.ride = h->P.np > 0;
   f.lazy = (h->lazy_nodal == 2 || (h->lazy_nodal == 1 && h->P.np <= 2000000)) && f.ride && !f.det && h->uniform_law >= 0 &&
-           h->uniform_law <= NLPS_KLAW_FRICTIONAL && nbcc <= NLPS_MAX_BC_INLINE && !f.dmg;
+           h->uniform_law <= NLPS_KLAW_FRICTIONAL && nbcc <= NLPS_MAX_BC_INLINE && !f.dmg && !f.fbar;
   f.async_form = f.lazy && h->async_lists && !h->halo && !h->rccl && node_lists(h) && h->nwn == h->g.nnodes;
   f.inline_bc = nbcc <= NLPS_MAX_BC_INLINE;
   f.law = h->uniform_law;
@@ -5430,6 +5635,7 @@ struct ExplicitStep {
   void k3(int cls, bool signal = false) {
     const TileD td = tile_view(h, cls);
     if (f.lazy) return launch_k3_lazy(h, td, signal, ln);
+    if (f.fbar) return launch_k3_fbar_kin(h, td, (h->law_present & (1 << NLPS_KLAW_FLUID)) ? dt : 0.0);
     const K3Launch a{signal, f.det && !f.dmg, nullptr, dt};
     if (f.dmg) launch_k3<5>(h, td, a);
     else launch_k3<1>(h, td, a);
@@ -5600,6 +5806,7 @@ struct ExplicitStep {
     if (h->timing) HIPCHK(hipEventRecord(h->ev[3], h->stream));
     k3(0);
     if (f.dmg && np > 0 && damage_hook_and_forces()) return 1;
+    if (f.fbar) launch_fbar_stress(h);  // (between the kinematic half of K3, launched by k3 above, and the nodal accelerations)
     HIPCHK(hipGetLastError());
     if (h->timing) HIPCHK(hipEventRecord(h->ev[4], h->stream));
     gather_force(0);
@@ -5719,7 +5926,7 @@ extern "C" int nlps_gpu_explicit_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc
 
   h->P.flip ^= 1;  // F_n <- F_n+1, b_e,n <- b_e,n+1 by renaming
   h->rolled = true;
-  h->rolled_keep = f.dmg;  // (tau and W of this step are stored: k_copy_n_to_n1 must not re-make them)
+  h->rolled_keep = f.dmg || f.fbar;  // (tau and W of this step are stored: k_copy_n_to_n1 must not re-make them)
   h->rolled_rate = (h->law_present & (1 << NLPS_KLAW_FLUID)) != 0;  // (K3 wrote the step's rate into dt_F_n: k_roll_rate)
   h->searched = f.ride;    // K5 has updated the closest nodes for the positions it wrote ...
   h->ahead = f.ride;       // ... and binned the particles for the next step
@@ -5957,6 +6164,7 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
                                               const double* Un_dt2, const double* M, const double* alpha,
                                               const double* gravity, const nlps_bcc* loads, int nloads, int step,
                                               double thickness, const double* area0, int flags) {
+  if (fbar_refuse(h, "nlps_gpu_lagrangian_evaluation")) return 1;
   if (need_masks(h, "nlps_gpu_lagrangian_evaluation")) return 1;
   if (materialise_move(h)) return 1;
   if (!R || !dU || !Un_dt || !Un_dt2 || !M || !alpha) {
@@ -6080,6 +6288,7 @@ extern "C" int nlps_gpu_lagrangian_evaluation(nlps_gpu* h, double* R, const doub
 // tangent assembly
 // ------------------------------------------------------------------------------------------------
 extern "C" int nlps_gpu_tangent_assemble(nlps_gpu* h, long long* nnz) {
+  if (fbar_refuse(h, "nlps_gpu_tangent_assemble")) return 1;
   if (need_masks(h, "nlps_gpu_tangent_assemble")) return 1;
   if (materialise_roll(h)) return 1;
   const int ND = h->nd, S = ND == 3 ? TanCfg<3>::S : TanCfg<2>::S;
@@ -6213,6 +6422,7 @@ static int tanop_valid(nlps_gpu* h, const char* who) {
 
 extern "C" int nlps_gpu_tangent_operator(nlps_gpu* h, double alpha_1, const double* lumped_mass, int apply_dirichlet,
                                          size_t* bytes) {
+  if (fbar_refuse(h, "nlps_gpu_tangent_operator")) return 1;
   if (need_masks(h, "nlps_gpu_tangent_operator")) return 1;
   if (materialise_roll(h)) return 1;
   h->top_gen = 0;  // (no operator until this call succeeds)
@@ -6428,6 +6638,7 @@ static int tancsr_records(nlps_gpu* h, const char* who) {
 }
 
 extern "C" int nlps_gpu_tangent_csr_pattern(nlps_gpu* h, long long* nnz, size_t* bytes) {
+  if (fbar_refuse(h, "nlps_gpu_tangent_csr_pattern")) return 1;
   const char* who = "nlps_gpu_tangent_csr_pattern";
   if (tanop_valid(h, who)) return 1;
   if (tancsr_one_rank(h, who)) return 1;
@@ -6533,6 +6744,7 @@ static size_t tanbsr_bytes(int nd, size_t np, size_t nnodes, size_t nactive) {
 }
 
 extern "C" int nlps_gpu_tangent_bsr_pattern(nlps_gpu* h, int kind, long long* nblocks, size_t* bytes) {
+  if (fbar_refuse(h, "nlps_gpu_tangent_bsr_pattern")) return 1;
   const char* who = "nlps_gpu_tangent_bsr_pattern";
   if (tanop_valid(h, who)) return 1;
   if (tancsr_one_rank(h, who)) return 1;
@@ -7040,6 +7252,7 @@ static int eig_wait(nlps_gpu* h) {
 
 extern "C" int nlps_gpu_tangent_lambda_max(nlps_gpu* h, const double* lumped_mass, const double* v0, nlps_eig* eig,
                                            double* mode) {
+  if (fbar_refuse(h, "nlps_gpu_tangent_lambda_max")) return 1;
   const char* who = "nlps_gpu_tangent_lambda_max";
   if (!eig) {
     h->err = "nlps_gpu_tangent_lambda_max: eig is required";
@@ -7207,6 +7420,7 @@ static int snes_residual(nlps_gpu* h, const SnesResidual& r, const double* x, do
 extern "C" int nlps_gpu_newton_solve(nlps_gpu* h, double* dU, const double* Un_dt, const double* Un_dt2, const double* M,
                                      const double* alpha, const double* gravity, const nlps_bcc* loads, int nloads, int step,
                                      double thickness, const double* area0, nlps_snes* snes) {
+  if (fbar_refuse(h, "nlps_gpu_newton_solve")) return 1;
   const char* who = "nlps_gpu_newton_solve";
   if (!snes) {
     h->err = "nlps_gpu_newton_solve: snes is required";
@@ -7380,6 +7594,7 @@ extern "C" int nlps_gpu_newton_solve(nlps_gpu* h, double* dU, const double* Un_d
 extern "C" int nlps_gpu_newmark_step(nlps_gpu* h, const nlps_bcc* bcc, int nbcc, int step, const nlps_newmark* nm,
                                      const double* gravity, const nlps_bcc* loads, int nloads, double thickness,
                                      const double* area0, nlps_snes* snes, int* nactive, double* dU_out) {
+  if (fbar_refuse(h, "nlps_gpu_newmark_step")) return 1;
   const char* who = "nlps_gpu_newmark_step";
   if (!nm || !snes) {
     h->err = "nlps_gpu_newmark_step: nm and snes are required";

@@ -905,6 +905,12 @@ __global__ __launch_bounds__(NT, NT == 64 ? 1 : (ND == 2 ? K2_WAVES_2D : K2_WAVE
 // without the carried term DF dt_F_n of MODE 2 / 4: no second window, no load of dt_F_n.  The fluid stress from F_n1,
 // dt_F_n1, J_n1 in registers; stores what MODE 1 stores (F_n+1, J to its n slot, d_dis; DF stays in registers), tau, and
 // dt_F_n1 once, into the slot that is dt_F_n after the step.  dt is the kernel's last argument (the k3_tile overload below).
+// MODE 8 (LAW = -1 only): the kinematic half of the explicit step with F-bar (nlps_gpu_set_explicit_fbar).
+// MODE 5 up to the law and without it: the gather of dU, DF, F_n1, J_n1 (both slots), d_dis, the fluid particles' rate as
+// MODE 7 makes it (dt > 0) -- and the two patch terms J_n Vol_0, J_n1 Vol_0 of every particle, summed per patch in LDS
+// (the accumulator `fac`, PCAP patches around the tile) and flushed once per patch and tile by global_atomic_add_f64.
+// It stores the patch of every particle it has visited (FbarKin::pid), which is how the stress kernel k_fbar_stress
+// knows them.  dt and the patch arrays are the kernel's last arguments (the k3_tile overload below).
 // FILT (clouds with several laws): the launch handles only the tile's particles whose material follows LAW; they are
 // compacted into an LDS list first, so every lane works and the kernel is the single-law specialisation (one launch per
 // law present; the run-time dispatch over all laws in one kernel needed 436 B of scratch per lane and 0.51 ms).
@@ -922,6 +928,31 @@ struct K3Waves {
                                : ((MODE == 1 || MODE == 3 || MODE == 5 || MODE == 6) && LAW == NLPS_MAT_DRUCKER_PRAGER) ? K3_WAVES_DP
                                                                                : K3_WAVES;
 };
+// The lattice-cell patches of F-bar as the kinematic half sees them.  A tile's particles have their closest node in the
+// tile, so their cells lie in tile * TB - 1 .. tile * TB + TB - 1 per axis while the closest nodes are current; PCAP
+// leaves one more on either side, and a patch outside that box (a closest node several cells stale) takes the two global
+// atomics itself.
+struct FbarKin {
+  double* sums;  // [npatches][2]: sum J_n Vol_0, sum J_n1 Vol_0
+  int* pid;      // [npad] patch of every particle this step has visited, -1 otherwise (k_fbar_clear)
+  int block[3];  // cells per patch
+  int np[3];     // patches per axis
+};
+template <int ND>
+struct FbarCfg {
+  static constexpr int R = TileCfg<ND>::TB + 3;  // local patches per axis
+  static constexpr int PCAP = ND == 3 ? R * R * R : R * R;
+};
+// patch of the cell that holds x (include/nlps_gpu.h): per axis clamp(floor((x - o) / h), 0, n - 2) / block
+template <int ND>
+__device__ __forceinline__ void fbar_patch(const GridD& g, const FbarKin& fb, const double* x, int* pk) {
+#pragma unroll
+  for (int a = 0; a < ND; a++) {
+    int c = (int)floor((x[a] - g.o[a]) / g.h);
+    c = c < 0 ? 0 : (c > g.n[a] - 2 ? g.n[a] - 2 : c);
+    pk[a] = c / fb.block[a];
+  }
+}
 // the LDS of k3_tile, owned by the caller of k3_body (the kernels below)
 template <int ND, int MODE, bool FILT>
 struct K3Lds {
@@ -929,7 +960,8 @@ struct K3Lds {
   static constexpr bool RATES = (MODE == 2 || MODE == 4);
   static constexpr int SELCAP = FILT ? 4096 : 1;
   static constexpr int N_DVXY = RATES ? 2 * NW : 2, N_DVZ = (RATES && ND == 3) ? NW : 1, N_DUZ = (ND == 3) ? NW : 1;
-  static constexpr int N_FAC = (MODE == 6) ? 1 : ND * NWA;  // (MODE 6 scatters nothing: no force accumulator)
+  // (MODE 6 scatters nothing: no force accumulator; MODE 8 keeps its patch sums there)
+  static constexpr int N_FAC = (MODE == 6) ? 1 : (MODE == 8) ? 2 * FbarCfg<ND>::PCAP : ND * NWA;
   double* dvxy;  // [N_DVXY], 16-byte aligned
   double* dvz;   // [N_DVZ]
   double* duxy;  // [2 NW], 16-byte aligned
@@ -948,7 +980,8 @@ template <int ND, int LAW, int MODE, bool FILT, int NT, bool UMAT = false>
 __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NView& N, const TileD& td,
                                         const MatD* __restrict__ mats, const ParamsD& prm, int* __restrict__ gstatus,
                                         const double* __restrict__ dVgrid, const TileWork& tw, int nbnd,
-                                        const K3Lds<ND, MODE, FILT>& lds, const NodalFold* fs, double dt = 0.0) {
+                                        const K3Lds<ND, MODE, FILT>& lds, const NodalFold* fs, double dt = 0.0,
+                                        const FbarKin* fb = nullptr) {
   NLPS_FP_CONTRACT
   constexpr int W = TileCfg<ND>::W, PS = TileCfg<ND>::PS, NW = TileCfg<ND>::NW, KN = Lme<ND>::KN;
   constexpr bool RATES = (MODE == 2 || MODE == 4);
@@ -966,6 +999,8 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
   // residual is evaluated many times from it.  A failed particle (Damage_n == 1) gets W = 0 and nothing else (k_stress).
   constexpr bool STATE_N1 = (MODE == 6);
   constexpr bool STRESS = SCATTER || STATE || STATE_N1;
+  constexpr bool KIN = (MODE == 8);  // the kinematic half of the step with F-bar: no law, the patch sums
+  static_assert(!KIN || (LAW == -1 && !FILT), "the kinematic half runs no law: one form");
   static_assert(FLUID == (LAW == NLPS_KLAW_FLUID), "the rate-carrying modes are the fluid law's, and only its");
   // gather window of dU: {x,y} as one 16-B double2 per node (ds_read_b128) + z as a separate 8-B array
   // (ds_read_b64): with node strides of 16 B and 8 B the tile's 64 I0 positions hit distinct banks; a
@@ -1059,7 +1094,15 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     }
   }
   if (!STATE_N1)
-    for (int idx = threadIdx.x; idx < ND * NWA; idx += NT) fac[idx] = 0.0;
+    for (int idx = threadIdx.x; idx < (KIN ? 2 * FbarCfg<ND>::PCAP : ND * NWA); idx += NT) fac[idx] = 0.0;
+  int pk0[3] = {0, 0, 0};  // KIN: the first patch of the local box, per axis
+  if constexpr (KIN) {
+#pragma unroll
+    for (int a = 0; a < ND; a++) {
+      const int c0 = w0[a];  // (the window's first node = the tile's first node less two cells: one for the closest node's reach, one spare)
+      pk0[a] = (c0 < 0 ? 0 : c0) / fb->block[a];
+    }
+  }
   __syncthreads();
   const double2* du2 = reinterpret_cast<const double2*>(duxy);
   const double2* dv2 = reinterpret_cast<const double2*>(dvxy);
@@ -1355,7 +1398,7 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     if (!inverse<ND>(Jm1, J)) st |= ST_NEWTON;
     // DF = I + sum_A dU_A (x) grad N_A = I - (G/Z) J^-T            (compute-Strains.c:20-44)
     double DF[ND * ND], Fn1[ND * ND];
-    constexpr int NK = FLUID ? ND * ND : 1;
+    constexpr int NK = (FLUID || KIN) ? ND * ND : 1;
     double dFk[NK];  // dt_F_n1, kept for the fluid stress (MODE 4, 7); MODE 7: dt_DF until F_n is here
 #pragma unroll
     for (int i = 0; i < ND; i++)
@@ -1366,8 +1409,24 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
         for (int m = 0; m < ND; m++) v = fma(G[i * ND + m] * Zinv, Jm1[j * ND + m], v);
         DF[i * ND + j] = ((i == j) ? 1.0 : 0.0) - v;
         if (MODE == 7) dFk[(i * ND + j) % NK] = -v / dt;  // dt_DF = sum (dU_A / dt) (x) grad N_A
+        if (KIN) dFk[(i * ND + j) % NK] = -v;             // (divided by dt where a fluid particle asks for it)
       }
     load_block<ND>(P, fFN(P), pl, Fn, fzz);
+    if constexpr (KIN) {  // the rate of a fluid particle, as MODE 7 makes and stores it
+      if (dt > 0.0 && mats[P.mat[pl]].type == NLPS_KLAW_FLUID) {
+        double dFn1[ND * ND];
+#pragma unroll
+        for (int i = 0; i < ND; i++)
+#pragma unroll
+          for (int j = 0; j < ND; j++) {
+            double a2 = 0.0;
+#pragma unroll
+            for (int k2 = 0; k2 < ND; k2++) a2 += (dFk[(i * ND + k2) % NK] / dt) * Fn[k2 * ND + j];
+            dFn1[i * ND + j] = a2;
+          }
+        store_block<ND>(P, F_DTFN, pl, dFn1, 0.0, false);
+      }
+    }
 #pragma unroll
     for (int i = 0; i < ND; i++)
 #pragma unroll
@@ -1395,8 +1454,10 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     double Jn1 = det<ND>(Fn1);
     if (Jn1 <= 0.0) {
       st |= ST_JACOBIAN;  // fatal in the explicit scheme (U-Verlet.c:608-613), clamped in the implicit one
-      if (!XSTEP && !STATE) Jn1 = 0.0;
+      if (!XSTEP && !STATE && !KIN) Jn1 = 0.0;
     }
+    double Jn_old = 0.0;
+    if (KIN) Jn_old = PF(P, F_JN, pl);  // (the patch term of the n state, read in front of the store below)
     // the fused explicit step (MODE 1) keeps DF in registers: nothing reads it before the next step rewrites it, and a
     // level-B stage or a download gets it back as F_n+1 F_n^-1 from the two slots of F (k_copy_n_to_n1): 72 B per
     // particle less to store (K3 0.260 -> 0.251 ms at 1 M particles)
@@ -1405,7 +1466,35 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     // fused step: J goes straight to its n slot (nothing reads J_n inside the step; J_n+1 = J_n is restored with the
     // roll, k_copy_n_to_n1), so K5 has no copy to make
     PF(P, XSTEP ? F_JN : F_JN1, pl) = Jn1;
-    if (STATE) PF(P, F_JN, pl) = Jn1;  // (K5 makes no copy: the n slot as in MODE 1, the n+1 slot for the hook's volumes)
+    if (STATE || KIN) PF(P, F_JN, pl) = Jn1;  // (K5 makes no copy: the n slot as in MODE 1, the n+1 slot for the hook's volumes)
+    if constexpr (KIN) {
+      // d_dis as MODE 1 / 5; the patch of the particle's cell and its two terms: into the tile's LDS box, or -- a patch
+      // outside the box -- straight into the patch array
+#pragma unroll
+      for (int a = 0; a < ND; a++) PF(P, F_DDIS + a, pl) = U[a] * Zinv;
+      constexpr int R = FbarCfg<ND>::R;
+      double xp[ND];
+#pragma unroll
+      for (int a = 0; a < ND; a++) xp[a] = PF(P, F_X + a, pl);
+      int pk[3] = {0, 0, 0};
+      fbar_patch<ND>(g, *fb, xp, pk);
+      const int id = pk[0] + fb->np[0] * (pk[1] + fb->np[1] * pk[2]);
+      fb->pid[pl] = id;
+      const double V0 = PF(P, F_VOL0, pl);
+      const int l0 = pk[0] - pk0[0], l1 = pk[1] - pk0[1], l2 = (ND == 3) ? pk[2] - pk0[2] : 0;
+      if (l0 >= 0 && l0 < R && l1 >= 0 && l1 < R && l2 >= 0 && l2 < R) {
+        // (the two branches name their address spaces: merged into one atomic on a generic pointer they do not compile)
+        typedef __attribute__((address_space(3))) double lds_double;
+        lds_double* acc = (lds_double*)(fac + 2 * (l0 + R * (l1 + R * l2)));
+        __hip_atomic_fetch_add(acc, Jn_old * V0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(acc + 1, Jn1 * V0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      } else {
+        typedef __attribute__((address_space(1))) double global_double;
+        global_double* out = (global_double*)(fb->sums + 2 * (size_t)id);
+        __hip_atomic_fetch_add(out, Jn_old * V0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(out + 1, Jn1 * V0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
     if (RATES) {
       double dDF[ND * ND], dFn[ND * ND], dFn1[ND * ND], zz;
 #pragma unroll
@@ -1568,6 +1657,20 @@ __device__ __forceinline__ void k3_body(const PView& P, const GridD& g, const NV
     }
     PH(12)
   }
+  if constexpr (KIN) {
+    // one flush per patch and tile: every thread arrives (the loop above leaves by `continue` alone); a patch no particle
+    // of the tile lies in holds zeros and is passed over (J_n Vol_0 > 0 for every particle)
+    __syncthreads();
+    constexpr int R = FbarCfg<ND>::R;
+    for (int slot = threadIdx.x; slot < FbarCfg<ND>::PCAP; slot += NT) {
+      const double a = fac[2 * slot], b = fac[2 * slot + 1];
+      if (a == 0.0 && b == 0.0) continue;
+      const int q0 = pk0[0] + slot % R, q1 = pk0[1] + (slot / R) % R, q2 = (ND == 3) ? pk0[2] + slot / (R * R) : 0;
+      const size_t id = (size_t)q0 + (size_t)fb->np[0] * ((size_t)q1 + (size_t)fb->np[1] * (size_t)q2);
+      atomic_add_f64(&fb->sums[2 * id], a);
+      atomic_add_f64(&fb->sums[2 * id + 1], b);
+    }
+  }
   if (!SCATTER) return;
   __syncthreads();
   PH(13)
@@ -1622,6 +1725,103 @@ __global__ __launch_bounds__(NT, (NT == 64 ? 1 : (K3Waves<ND, LAW, MODE>::value)
   if (!tile_work_item(td, tw)) return;
   const L lds{dvxy, dvz, duxy, duz, fac, sel, &nsel, wcnt};
   k3_body<ND, LAW, MODE, FILT, NT, UMAT>(P, g, N, td, mats, prm, gstatus, nullptr, tw, nbnd, lds, nullptr, dt);
+}
+// MODE 8, the kinematic half of the step with F-bar: one form per dimension (no law, one rank: no boundary signal)
+template <int ND>
+__global__ __launch_bounds__(K3_BLK, (K3Waves<ND, -1, 8>::value)) void k3_kin_tile(PView P, GridD g, NView N, TileD td, const MatD* __restrict__ mats,
+                                                                                ParamsD prm, int* __restrict__ gstatus, double dt, FbarKin fb) {
+  using L = K3Lds<ND, 8, false>;
+  __shared__ __attribute__((aligned(16))) double dvxy[L::N_DVXY];
+  __shared__ double dvz[L::N_DVZ];
+  __shared__ __attribute__((aligned(16))) double duxy[2 * L::NW];
+  __shared__ double duz[L::N_DUZ];
+  __shared__ double fac[L::N_FAC];
+  __shared__ int sel[L::SELCAP];
+  __shared__ int nsel;
+  __shared__ int wcnt[K3_BLK / 64];
+  TileWork tw;
+  if (!tile_work_item(td, tw)) return;
+  const L lds{dvxy, dvz, duxy, duz, fac, sel, &nsel, wcnt};
+  k3_body<ND, -1, 8, false, K3_BLK>(P, g, N, td, mats, prm, gstatus, nullptr, tw, 0, lds, nullptr, dt, &fb);
+}
+
+// The stress kernel of the step with F-bar, one thread per particle, between k3_kin_tile and the force half k3f_tile.
+// From the patch sums: J_patch = Vn1 / Vn, c = (J_patch / det DF)^(1/d), Fbar_n1 = alpha F_n1 + (1 - alpha) c DF Fbar_n
+// (compute-Strains.c:109-172; the 2-D zz entry is F_n1's), Jbar_n1 = Jbar_n J_patch -- both for every particle, written
+// over Fbar_n / Jbar_n (each thread reads only its own: that store is the roll).  Then the law, at (Fbar_n1, Jbar_n1) for
+// a material with alpha >= 0 (Constitutive.c:32-38, 66-72, 89-95) and at (F_n1, J_n1) otherwise, storing tau and W as the
+// state half of the damage step does (stress_update KEEP); the fluid law with the unbarred rate k3_kin_tile left in
+// dt_F_n (Constitutive.c:87).  A material with alpha < 0 forms its Fbar_n1 with alpha = 0.
+// FILT: the launch of law LAW in a cloud of several (one per law present); LAW = -1: the run-time dispatch.
+struct FbarD {
+  const double* sums;
+  const int* pid;
+  double* F;            // [T][npad] Fbar_n
+  double* J;            // [npad] Jbar_n
+  const double* alpha;  // [nmats]
+};
+template <int ND, int LAW, bool FILT>
+__global__ __launch_bounds__(BLK) void k_fbar_stress(PView P, const MatD* __restrict__ mats, ParamsD prm, int* __restrict__ gstatus, FbarD fb) {
+  NLPS_FP_CONTRACT
+  const int p = blockIdx.x * BLK + threadIdx.x;
+  if (p >= P.np) return;
+  const int id = fb.pid[p];
+  if (id < 0) return;  // (in no list, or without a neighbourhood: the kinematic half has passed it over)
+  const int mi = P.mat[p];
+  if (FILT && mats[mi].type != LAW) return;
+  double DF[ND * ND], Fn1[ND * ND], Fb[ND * ND], Fb1[ND * ND], z, fzz;
+  load_block<ND>(P, F_DF, p, DF, z);
+  load_block<ND>(P, fFN1(P), p, Fn1, fzz);
+  const double Jn1 = PF(P, F_JN1, p);
+#pragma unroll
+  for (int s = 0; s < ND * ND; s++) Fb[s] = fb.F[(size_t)s * P.npad + p];
+  const double Jp = fb.sums[2 * (size_t)id + 1] / fb.sums[2 * (size_t)id];
+  const double q = Jp / det<ND>(DF);
+  const double c = (ND == 2) ? sqrt(q) : cbrt(q);
+  const double al = fb.alpha[mi], a = al < 0.0 ? 0.0 : al;
+#pragma unroll
+  for (int i = 0; i < ND; i++)
+#pragma unroll
+    for (int j = 0; j < ND; j++) {
+      double v = 0.0;
+#pragma unroll
+      for (int k = 0; k < ND; k++) v += DF[i * ND + k] * Fb[k * ND + j];
+      Fb1[i * ND + j] = a * Fn1[i * ND + j] + (1.0 - a) * (c * v);
+    }
+  const double Jb1 = fb.J[p] * Jp;
+#pragma unroll
+  for (int s = 0; s < ND * ND; s++) fb.F[(size_t)s * P.npad + p] = Fb1[s];
+  if (ND == 2) fb.F[(size_t)4 * P.npad + p] = fzz;
+  fb.J[p] = Jb1;
+  const bool barred = al >= 0.0;
+  double Fl[ND * ND], tau[ND * ND];
+#pragma unroll
+  for (int s = 0; s < ND * ND; s++) Fl[s] = barred ? Fb1[s] : Fn1[s];
+  const double Jl = barred ? Jb1 : Jn1;
+  int st = 0;
+  if constexpr (LAW == NLPS_KLAW_FLUID) {
+    double dF[ND * ND], tzz = 0.0;
+    load_block<ND>(P, F_DTFN, p, dF, z);
+    if (!law_newtonian_fluid<ND>(mats[mi], Fl, dF, Jl, tau, tzz)) {  // no stress, no force of this particle (as MODE 7)
+      st |= ST_CONSTITUTIVE;
+#pragma unroll
+      for (int s = 0; s < ND * ND; s++) tau[s] = 0.0;
+      tzz = 0.0;
+    }
+    store_block<ND>(P, F_TAU, p, tau, tzz, true);
+  } else {
+    st |= stress_update<ND, LAW, false, (LAW == NLPS_KLAW_FRICTIONAL), true, true>(P, p, mats, prm, Fl, DF, Jl, tau, mi);
+  }
+  if (st) {
+    atomicOr(&P.status[p], st);
+    atomicOr(gstatus, st);
+  }
+}
+// in front of the kinematic half: the patch sums to zero, no particle visited
+__global__ void k_fbar_clear(double* __restrict__ sums, int npatch2, int* __restrict__ pid, int np) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < npatch2) sums[t] = 0.0;
+  if (t < np) pid[t] = -1;
 }
 
 // The explicit step of one GPU without a ghost exchange, "folded" form: the nodal kernels between the stages are gone.

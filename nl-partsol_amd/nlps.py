@@ -101,6 +101,10 @@ class Bcc(C.Structure):
     _fields_ = [("nnodes", C.c_int), ("nodes", _ip), ("dim", C.c_int), ("dir", _ip), ("value", _dp)]
 
 
+class FbarCfg(C.Structure):  # nlps_fbar_cfg
+    _fields_ = [("block", C.c_int * 3), ("alpha", _dp), ("Fbar_n", _dp), ("Jbar_n", _dp)]
+
+
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int)
 
 _LIB = None
@@ -114,7 +118,7 @@ SYMBOLS = ["nlps_gpu_lagrangian_evaluation", "nlps_gpu_create", "nlps_gpu_destro
            "nlps_gpu_internal_forces", "nlps_gpu_nodal_traction_forces", "nlps_gpu_roll_state", "nlps_gpu_update_kinetics",
            "nlps_gpu_explicit_step", "nlps_gpu_num_active", "nlps_gpu_explicit_nodal", "nlps_gpu_set_halo_exchange",
            "nlps_gpu_resort", "nlps_gpu_set_resort_interval", "nlps_gpu_set_adaptive_resort", "nlps_gpu_set_law_launch_mode", "nlps_gpu_set_deterministic", "nlps_gpu_set_explicit_damage",
-           "nlps_gpu_set_explicit_fluid",
+           "nlps_gpu_set_explicit_fluid", "nlps_gpu_set_explicit_fbar", "nlps_gpu_download_fbar",
            "nlps_gpu_set_explicit_loads",
            "nlps_gpu_set_step_record", "nlps_gpu_step_record_layout", "nlps_gpu_record_now", "nlps_gpu_read_step_records",
            "nlps_host_courant_dt",
@@ -385,6 +389,7 @@ class Solver:
         self._h_avg = None if h_avg is None else np.ascontiguousarray(h_avg, dtype=np.float64)
         g = Grid(self.ndim, (C.c_int * 3)(*n3), (C.c_double * 3)(*o3), float(h), _d(self._h_avg))
         self.params = params or default_params()
+        self.nmats = len(materials)
         mats = (Material * len(materials))()
         for k, m in enumerate(materials):
             mats[k] = Material(int(m["type"]), float(m.get("E", 0.0)), float(m.get("nu", 0.0)), float(m.get("phi_deg", 0.0)),
@@ -674,6 +679,31 @@ class Solver:
         """explicit_step for a cloud that holds the compressible Newtonian fluid (off by default: the step refuses such a
         cloud); the rate of such a step, dt_F_n1 = (F_n1 - F_n) / dt, is defined in include/nlps_gpu.h."""
         self._chk(self.L.nlps_gpu_set_explicit_fluid(self.h, 1 if on else 0))
+
+    def set_explicit_fbar(self, alpha, block=1, Fbar_n=None, Jbar_n=None):
+        """F-bar on lattice-cell patches inside explicit_step.  alpha: one entry per material, alpha_Fbar in [0, 1] for a
+        material whose law reads F-bar, < 0 for one that does not; alpha=None switches it off.  block: cells per patch, one
+        number or one per axis.  Fbar_n [np][T] / Jbar_n [np] in the caller's order, None: F_n / J_n as they stand on the
+        device.  The definition is in include/nlps_gpu.h."""
+        self.L.nlps_gpu_set_explicit_fbar.argtypes = [C.c_void_p, C.POINTER(FbarCfg)]
+        if alpha is None:
+            self._chk(self.L.nlps_gpu_set_explicit_fbar(self.h, None))
+            return
+        b = [int(block)] * 3 if np.isscalar(block) else (list(int(v) for v in block) + [1, 1, 1])[:3]
+        al = np.ascontiguousarray(alpha, dtype=np.float64)
+        F = None if Fbar_n is None else np.ascontiguousarray(Fbar_n, dtype=np.float64)
+        J = None if Jbar_n is None else np.ascontiguousarray(Jbar_n, dtype=np.float64)
+        if al.size != self.nmats or (F is not None and F.shape != (self.np, self.T)) or (J is not None and J.shape != (self.np,)):
+            raise NlpsError("set_explicit_fbar: alpha is [nmats], Fbar_n [np][T], Jbar_n [np]")
+        cfg = FbarCfg((C.c_int * 3)(*b), _d(al), _d(F), _d(J))
+        self._chk(self.L.nlps_gpu_set_explicit_fbar(self.h, C.byref(cfg)))
+
+    def download_fbar(self):
+        """-> (Fbar_n [np][T], Jbar_n [np]) in the caller's order"""
+        F, J = np.zeros((self.np, self.T)), np.zeros(self.np)
+        self.L.nlps_gpu_download_fbar.argtypes = [C.c_void_p, _dp, _dp]
+        self._chk(self.L.nlps_gpu_download_fbar(self.h, _d(F), _d(J)))
+        return F, J
 
     def set_explicit_loads(self, loads, thickness=1.0, area0=None):
         """The Neumann contours of explicit_step (compute_Nodal_Nominal_traction_Forces): a BccSet whose nodes are particle
